@@ -16,6 +16,8 @@ Prints ONE JSON line on rank 0 (driver contract).  Besides the headline it carri
                     without and with the final score gather -- the curve the north star asks for
     cpu_baseline    the reference algorithm on the host cores: the factored C/OpenMP port on the full workload
                     and the literal dense A*(W*W) (numpy / OpenBLAS dgemm, what SimSpread.jl executes) down-scaled
+--dump-outputs DIR writes the scores of the last timed step (rank 0) to DIR/scores.npy; the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -31,6 +33,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 HBM_ACHIEVABLE_GBS = 6300.0 # ibid.: what streaming kernels reach (SURVEY.md 8d asks for the fraction of this too)
 FP32_PEAK_TFLOPS = 157.3    # fp32 vector == fp32-input MFMA peak
+DUMP_BYTES = 60_000_000     # --dump-outputs: budget of the written arrays (a seeded row sample of larger outputs)
+DUMP_SEED = 20250222 + 7
 
 
 def synth_c2(nq, ns, nf, nt, dx, dy, seed, rank, weighted=True):
@@ -73,6 +77,28 @@ def pmc_entry(kernel_substr):
     except Exception as e:  # missing / unreadable profile: no traffic figure
         return None, "no profile (%s)" % type(e).__name__
     return None, "kernel not in profiles/pmc_latest.json"
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write what the timed path handed back in its last step as <path>/<name>.npy.  An output larger than
+    the budget is reduced to a fixed, seeded sample of its rows (sorted), the same rows on every run with the same
+    arguments; returns {name: {"shape": full shape, "rows_written": ...}} for the result line."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_BYTES // max(1, len(arrays))
+    info = {}
+    for name, a in arrays.items():
+        assert a.dtype in (torch.float32, torch.float64), (name, a.dtype)
+        n = a.shape[0]
+        k = min(n, budget // max(1, a[0].numel() * a.element_size())) if n else 0
+        sampled = k < n
+        if sampled:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+            a = a[torch.as_tensor(rows, device=a.device)]
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy())
+        info[name] = {"shape": [int(x) for x in arrays[name].shape], "rows_written": int(k),
+                      "row_sample_seed": DUMP_SEED if sampled else None}
+    return info
 
 
 def csr_bytes(nnz, rows, vb=4):
@@ -182,12 +208,13 @@ def lib_gather_check(ss, torch, out, world, rank):
     return same_all and same_root, counts
 
 
-def c3_loo_curve(args, ss, torch, dist, world, rank, backend, agree=None, state=None):
+def c3_loo_curve(args, ss, torch, dist, world, rank, backend, agree=None, state=None, dump=None):
     """BASELINE configs[2] on this run's ranks: 100k x 100k, 1 %, leave-one-out; the 10^5 folds are block-sharded
     (ss.shard_range), every rank scores `--folds` consecutive folds of its shard per step (same per-rank work at every
     N: weak scaling in the step, i.e. the full 10^5-fold job gets N times faster).  Reported without any exchange, with
     the direct all-to-all gather of the score blocks (torch.distributed AND, on RCCL, the library's own communicator),
-    with a gather to rank 0 only, and with the reduced gather of the top-L predictions per fold."""
+    with a gather to rank 0 only, and with the reduced gather of the top-L predictions per fold.  dump(out), if given,
+    is called on rank 0 with the scores of the last step of the leg without exchange."""
     agree = agree or make_agree(torch, dist, world, backend)
     state = state if state is not None else {}
     steps = args.c3_steps
@@ -260,6 +287,7 @@ def c3_loo_curve(args, ss, torch, dist, world, rank, backend, agree=None, state=
     if r0 is None:
         return {"error": "the leg without exchange failed", "errors": state.get("errors")}
     el0, t = r0
+    dumped = dump(out) if dump is not None and rank == 0 else None
     res = {"workload": "BASELINE configs[2]: 100k x 100k, 1%% density, leave-one-out, folds block-sharded over ranks; %d folds "
                        "per rank and step, %d steps" % (folds, steps),
            "nnz_X": g.nnz_xs, "nnz_Y": g.nnz_ys, "folds_per_rank_step": folds,
@@ -267,6 +295,8 @@ def c3_loo_curve(args, ss, torch, dist, world, rank, backend, agree=None, state=
            "ms_per_step": el0 / steps * 1e3,
            "stage1_ms": t["transfer_ms"] / max(1, t["transfer_launches"]), "stage2_ms": t["spmm_ms"] / max(1, t["spmm_launches"]),
            "full_loo_seconds_at_this_rate": n / (folds * world * steps / el0)}
+    if dumped is not None:
+        res["dumped_outputs"] = dumped
 
     def put(key, r, extra=None):
         if r is None:
@@ -417,7 +447,8 @@ def c5_loo_leg(args, ss, torch, dist, world, rank, backend, agree=None, state=No
 
 def bench_c3loo(args, ss, torch, dist, world, rank, backend):
     """--workload c3loo: the configs[2] curve as the headline line (the default line carries it as `c3_loo`)."""
-    res = c3_loo_curve(args, ss, torch, dist, world, rank, backend)
+    dump = (lambda out: dump_outputs(args.dump_outputs, {"scores": out})) if args.dump_outputs else None
+    res = c3_loo_curve(args, ss, torch, dist, world, rank, backend, dump=dump)
     if rank == 0:
         n = 100_000
         flops = 2.0 * res["nnz_Y"] * res["folds_per_rank_step"]
@@ -520,9 +551,14 @@ def main():
     ap.add_argument("--aux-timeout", type=int, default=300,
                     help="N > 1: seconds the auxiliary legs (configs[2] curve) may take before the headline line is printed without them")
     ap.add_argument("--gather", action="store_true", help="also time the final gather of the C2 score blocks (outside `value`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the scores of the last step as DIR/<name>.npy (rank 0; a fixed, "
+                         "seeded row sample when they exceed ~60 MB)")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start the ranks, all-reduce one number over gloo on the CPU, print it and exit (tests the launch path without a GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.c3_steps < 1:
+        ap.error("--steps and --c3-steps must be >= 1, --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves.  Nothing in this process has touched the GPU
@@ -587,6 +623,7 @@ def main():
     t = ss.timing_last()
     ss.timing_hold(False)
     path = ss.path_last()
+    dumped = dump_outputs(args.dump_outputs, {"scores": scores}) if args.dump_outputs and rank == 0 else None
     # average duration of one launch of each kernel over the timed region (one launch per stage and step here)
     transfer_ms = t["transfer_ms"] / max(1, t["transfer_launches"])
     spmm_ms = t["spmm_ms"] / max(1, t["spmm_launches"])
@@ -696,6 +733,8 @@ def main():
         }
         if gather_ms is not None:
             result["score_gather_ms"] = gather_ms
+        if dumped is not None:
+            result["dumped_outputs"] = dumped
 
     # ---- auxiliary legs, after the headline numbers are final and under a watchdog (never lose the headline line)
     timer = None
