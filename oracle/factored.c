@@ -62,6 +62,7 @@ typedef struct {
   int64_t nq, ns, nf, nt;
   csr_t XsT, YsT;
   double *inv_kf, *inv_ks;
+  int64_t* ks; /* source degrees as counts (the leave-one-out form corrects them per fold) */
 } oracle_graph;
 
 void oracle_release(oracle_graph* g) {
@@ -70,6 +71,7 @@ void oracle_release(oracle_graph* g) {
   csr_free(&g->YsT);
   free(g->inv_kf);
   free(g->inv_ks);
+  free(g->ks);
   free(g);
 }
 
@@ -85,12 +87,14 @@ oracle_graph* oracle_prepare(int64_t nq, int64_t ns, int64_t nf, int64_t nt, con
   }
   g->inv_kf = (double*)malloc((size_t)(nf ? nf : 1) * sizeof(double));
   g->inv_ks = (double*)malloc((size_t)(ns ? ns : 1) * sizeof(double));
-  if (!g->inv_kf || !g->inv_ks) { oracle_release(g); return NULL; }
+  g->ks = (int64_t*)malloc((size_t)(ns ? ns : 1) * sizeof(int64_t));
+  if (!g->inv_kf || !g->inv_ks || !g->ks) { oracle_release(g); return NULL; }
   for (int64_t f = 0; f < nf; ++f) g->inv_kf[f] = inv_count(g->XsT.ptr[f + 1] - g->XsT.ptr[f]);
   for (int64_t s = 0; s < ns; ++s) {
     int64_t d = 0;
     for (int64_t x = xs_ptr[s]; x < xs_ptr[s + 1]; ++x) d += xs_val[x] != 0.0;
     for (int64_t x = ys_ptr[s]; x < ys_ptr[s + 1]; ++x) d += ys_val[x] != 0.0;
+    g->ks[s] = d;
     g->inv_ks[s] = inv_count(d);
   }
   return g;
@@ -133,6 +137,115 @@ int oracle_predict_rows(const oracle_graph* g, const int64_t* xq_ptr, const int3
       }
     }
     free(v);
+  }
+  return failed ? -1 : 0;
+}
+
+/* Leave-one-out scores of source rows [i0, i1) of a square featurized X (column j = the feature named after source j)
+ * with labels Y; out is row-major (i1-i0) x nt.  g comes from oracle_prepare(0, n, n, nt, X, Y): the query-free graph.
+ * Row i is predict(construct(y, X, [source_i]), y[[source_i], :]) (src/core.jl:148-201 drops row i and feature column i,
+ * :365-371 spread, :402-423 predict), restated with the rank-1 degree corrections of predict_loo_factored:
+ *     u[f] = X[i,f] / (kf[f] - 1)   for f != i        (row i leaves every feature column it touched)
+ *     v    = X u
+ *     z[s] = v[s] / (ks[s] - [X[s,i] != 0]),  z[i] = 0 (feature column i leaves every source row that had it)
+ *     out  = Y' z,  1/0 -> 0 throughout (:367-368)
+ * and with clean != 0 the -99 of clean! (:478-484) where kt[t] - [Y[i,t] != 0] == 0.
+ * Each thread takes FB folds at a time and keeps their z interleaved (z[s*FB + j]), so Y' is streamed once per batch.
+ * Returns 0 on success. */
+#define LOO_FB 16
+int oracle_predict_loo_rows(const oracle_graph* g, const int64_t* x_ptr, const int32_t* x_idx, const double* x_val,
+                            const int64_t* y_ptr, const int32_t* y_idx, const double* y_val, int64_t i0, int64_t i1,
+                            int clean, double* out, int threads) {
+  const int64_t n = g->ns, nt = g->nt;
+  if (g->nf != n || g->nq != 0 || i0 < 0 || i1 > n || i0 > i1) return -2;
+  const csr_t XT = g->XsT, YT = g->YsT;
+  const int64_t* ks = g->ks;
+  int failed = 0;
+#ifdef _OPENMP
+  if (threads > 0) omp_set_num_threads(threads);
+  const int nth = omp_get_max_threads();
+#else
+  const int nth = 1;
+#endif
+  /* enough batches to occupy every thread, never more than LOO_FB folds in one */
+  int64_t fb = (i1 - i0 + nth - 1) / (nth > 0 ? nth : 1);
+  if (fb < 1) fb = 1;
+  if (fb > LOO_FB) fb = LOO_FB;
+  const int64_t nb = (i1 - i0 + fb - 1) / fb;
+#pragma omp parallel
+  {
+    double* z = (double*)malloc((size_t)(n ? n : 1) * fb * sizeof(double));
+    double* fix = NULL;
+    int64_t cap = 0;
+    if (!z) {
+#pragma omp atomic write
+      failed = 1;
+    }
+#pragma omp for schedule(dynamic, 1)
+    for (int64_t b = 0; b < nb; ++b) {
+      if (!z) continue;
+      const int64_t q0 = i0 + b * fb, q1 = (q0 + fb < i1) ? q0 + fb : i1, w = q1 - q0;
+      memset(z, 0, (size_t)n * fb * sizeof(double));
+      for (int64_t j = 0; j < w; ++j) {
+        const int64_t i = q0 + j;
+        for (int64_t x = x_ptr[i]; x < x_ptr[i + 1]; ++x) {   /* v = X u, as a sum of the columns of X that row i touches */
+          const int32_t f = x_idx[x];
+          if (f == i || x_val[x] == 0.0) continue;
+          const double c = x_val[x] * inv_count(XT.ptr[f + 1] - XT.ptr[f] - 1);
+          if (c == 0.0) continue;
+          for (int64_t e = XT.ptr[f]; e < XT.ptr[f + 1]; ++e) z[(int64_t)XT.idx[e] * fb + j] += c * XT.val[e];
+        }
+      }
+      /* z = v / ks, except where source s had feature i_j: there v / (ks - 1), taken from the raw v (kept aside) */
+      int64_t nfix = 0;
+      for (int64_t j = 0; j < w; ++j) nfix += XT.ptr[q0 + j + 1] - XT.ptr[q0 + j];
+      if (nfix > cap) {
+        free(fix);
+        cap = nfix;
+        fix = (double*)malloc((size_t)cap * sizeof(double));
+        if (!fix) {
+#pragma omp atomic write
+          failed = 1;
+          cap = 0;
+          continue;
+        }
+      }
+      for (int64_t j = 0, o = 0; j < w; ++j)
+        for (int64_t e = XT.ptr[q0 + j]; e < XT.ptr[q0 + j + 1]; ++e, ++o) {
+          const int64_t s = XT.idx[e];
+          fix[o] = z[s * fb + j] * inv_count(ks[s] - 1);
+        }
+      for (int64_t s = 0; s < n; ++s) {
+        const double r = inv_count(ks[s]);
+        for (int64_t j = 0; j < w; ++j) z[s * fb + j] *= r;
+      }
+      for (int64_t j = 0, o = 0; j < w; ++j) {
+        for (int64_t e = XT.ptr[q0 + j]; e < XT.ptr[q0 + j + 1]; ++e, ++o) z[(int64_t)XT.idx[e] * fb + j] = fix[o];
+        z[(q0 + j) * fb + j] = 0.0;   /* the query is not a source of its own fold */
+      }
+      double acc[LOO_FB];
+      for (int64_t t = 0; t < nt; ++t) {
+        for (int64_t j = 0; j < w; ++j) acc[j] = 0.0;
+        for (int64_t e = YT.ptr[t]; e < YT.ptr[t + 1]; ++e) {
+          const double yv = YT.val[e];
+          const double* zs = z + (int64_t)YT.idx[e] * fb;
+          for (int64_t j = 0; j < w; ++j) acc[j] += yv * zs[j];
+        }
+        for (int64_t j = 0; j < w; ++j) out[(q0 - i0 + j) * nt + t] = acc[j];
+      }
+      if (clean) {   /* kt[t] - [Y[i,t] != 0] == 0 -> -99 */
+        for (int64_t j = 0; j < w; ++j) {
+          const int64_t i = q0 + j;
+          double* o = out + (q0 - i0 + j) * nt;
+          for (int64_t t = 0; t < nt; ++t)
+            if (YT.ptr[t + 1] == YT.ptr[t]) o[t] = -99.0;
+          for (int64_t x = y_ptr[i]; x < y_ptr[i + 1]; ++x)
+            if (y_val[x] != 0.0 && YT.ptr[y_idx[x] + 1] - YT.ptr[y_idx[x]] == 1) o[y_idx[x]] = -99.0;
+        }
+      }
+    }
+    free(z);
+    free(fix);
   }
   return failed ? -1 : 0;
 }

@@ -353,6 +353,45 @@ def predict_loo_dense(X, Y, clean_flag: bool = False, queries: Iterable[int] | N
     return out
 
 
+def predict_loo_dense_blocked(X, Y, clean_flag: bool = False, queries: Iterable[int] | None = None,
+                              block: int = 512) -> np.ndarray:
+    """predict_loo_dense with the folds taken ``block`` at a time as matrix products (BLAS), for checking every fold of
+    a production-size dense block: per block Q, ``U = X[Q] / (kf - [X[Q] != 0])`` with ``U[j, Q_j] = 0``,
+    ``V = U X'``, ``Z = V / (ks - [X[:, Q] != 0]')`` with ``Z[j, Q_j] = 0``, rows ``= Z Y``.  Same identity, same
+    1/0 -> 0; tests/test_oracle.py pins it against predict_loo_dense.  An fp64 ``X`` is not copied."""
+    X = np.asarray(X, dtype=np.float64)
+    Y = sp.csr_matrix(Y, dtype=np.float64)
+    Y.eliminate_zeros()
+    n = X.shape[0]
+    assert X.shape == (n, n)
+    kf = np.zeros(n)
+    ks = np.asarray((Y != 0).sum(axis=1)).ravel().astype(np.float64)
+    for a in range(0, n, 2048):                 # degree counts without an n x n boolean temporary
+        nz = X[a:a + 2048] != 0
+        kf += nz.sum(axis=0)
+        ks[a:a + 2048] += nz.sum(axis=1)
+    kt = np.asarray((Y != 0).sum(axis=0)).ravel().astype(np.float64)
+    qs = np.arange(n) if queries is None else np.asarray(list(queries), dtype=np.int64)
+    out = np.zeros((len(qs), Y.shape[1]))
+    YT = Y.T.tocsr()
+    for a in range(0, len(qs), block):
+        q = qs[a:a + block]
+        r = np.arange(len(q))
+        Xq = X[q]
+        U = Xq * _inv_count(kf[None, :] - (Xq != 0))
+        U[r, q] = 0.0
+        V = U @ X.T
+        del U
+        V *= _inv_count(ks[None, :] - (X[:, q] != 0).T)
+        V[r, q] = 0.0
+        rows = np.asarray(YT @ V.T).T
+        if clean_flag:
+            yq = (Y[q] != 0).toarray()
+            rows = np.where((kt[None, :] - yq) == 0, -99.0, rows)
+        out[a:a + len(q)] = rows
+    return out
+
+
 # --------------------------------------------------------------------------- synthetic inputs shared by tests / bench
 def synth_bipartite(nq: int, ns: int, nf: int, nt: int, dx: float, dy: float, seed: int,
                     weighted: bool = True, alpha: float = 0.5, dtype=np.float32):

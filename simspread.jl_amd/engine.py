@@ -330,6 +330,26 @@ class DeviceSpMat:
         fn = getattr(lib, f"ss_spmat_create_csr_{self._suf}")
         L.check(fn(W.shape[0], W.shape[1], _ptr(p), _ptr(i), _ptr(v), 0, L.SS_MEM_HOST, C.byref(self._h)))
 
+    @classmethod
+    def from_device_csr(cls, rows: int, cols: int, ptr, idx, val, dtype=np.float32):
+        """W given as CSR torch CUDA tensors (ptr int64, idx int32, val of the precision; val None means all ones)."""
+        import torch
+        self = cls.__new__(cls)
+        self.shape = (int(rows), int(cols))
+        self.dtype = np.dtype(dtype)
+        self._suf = _suffix(dtype)
+        want = torch.float32 if self.dtype == np.float32 else torch.float64
+        _is_torch(ptr)
+        if ptr.dtype != torch.int64 or idx.dtype != torch.int32 or (val is not None and val.dtype != want):
+            raise TypeError("device CSR needs int64 pointers, int32 indices and values of the matrix precision")
+        self.nnz = int(idx.numel())
+        self._keep = (ptr, idx, val)
+        self._h = C.c_void_p()
+        fn = getattr(L.lib(), f"ss_spmat_create_csr_{self._suf}")
+        L.check(fn(rows, cols, ptr.data_ptr(), idx.data_ptr(), None if val is None else val.data_ptr(), 0,
+                   L.SS_MEM_DEVICE, C.byref(self._h)))
+        return self
+
     def cost(self, B: int):
         b, f = C.c_double(), C.c_double()
         L.check(L.load().ss_spmat_cost(self._h, B, C.byref(b), C.byref(f)))

@@ -230,3 +230,146 @@ def test_c_oracle_equals_python_oracle():
     assert np.array_equal(prep.predict(3, 40), got[3:40])       # prepared form == one-shot form, any row block
     assert np.array_equal(prep.predict(threads=1), got)
     prep.close()
+
+
+def _loo_edge_graph(seed, n=240, nt=70):
+    """A square weighted X and labels Y with the corner cases of the leave-one-out identity: a feature of degree 1
+    (kf - 1 = 0 for its one query), a source whose only edge is to itself, a target whose only edge is one query
+    (clean!), an empty label row, an all-zero target, and an explicitly stored zero in X."""
+    import scipy.sparse as sp
+    rng = np.random.default_rng(seed)
+    X = sp.random(n, n, density=0.05, format="lil", random_state=rng)
+    X.setdiag(1.0)
+    X[:, 17] = 0.0; X[40, 17] = 0.8             # feature 17 has degree 1: its only source is 40
+    X[23, :] = 0.0; X[:, 23] = 0.0; X[23, 23] = 1.0   # source 23: only edge is to itself
+    X = X.tocsr()
+    X.data = 0.5 + 0.5 * rng.random(X.nnz)
+    X.data[X.indptr[5] + 1] = 0.0                # an explicitly stored zero is no edge
+    Y = sp.random(n, nt, density=0.06, format="lil", random_state=rng)
+    Y[:, 4] = 0.0; Y[71, 4] = 1.0                # target 4: only edge is source 71
+    Y[:, 6] = 0.0                                # target 6: no edge at all
+    Y[23, :] = 0.0; Y[100, :] = 0.0              # empty label rows
+    Y = Y.tocsr()
+    Y.data[:] = 1.0
+    return X, Y
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+def test_c_loo_equals_python_loo(seed):
+    """oracle_predict_loo_rows (the checker of the at-size leave-one-out GPU tests) against predict_loo_factored, with
+    and without clean!, and the same rows from any block split as from one whole-range call."""
+    from oracle import c_oracle
+    X, Y = _loo_edge_graph(seed)
+    n = X.shape[0]
+    prep = c_oracle.PreparedLoo(X, Y)
+    for clean in (False, True):
+        want = O.predict_loo_factored(X, Y, clean_flag=clean)
+        got = prep.predict(clean=clean)
+        np.testing.assert_allclose(got, want, rtol=1e-14, atol=0)
+        assert np.array_equal(got == 0, want == 0)
+        if clean:
+            assert got[71, 4] == -99.0 and (got[:, 6] == -99.0).all() and (got[:, 4] == -99).sum() == 1
+        # blocks starting and ending mid-range, a single row, an empty block, one thread
+        for i0, i1 in ((0, 1), (3, 97), (40, 41), (97, 203), (203, n), (17, 17)):
+            assert np.array_equal(prep.predict(i0, i1, clean=clean), got[i0:i1]), (i0, i1)
+        assert np.array_equal(prep.predict(5, 150, clean=clean, threads=1), got[5:150])
+    assert (got[23] == np.where(got[23] == -99, -99, 0)).all()     # a source linked to nothing else scores 0
+    prep.close()
+    np.testing.assert_array_equal(c_oracle.predict_loo(X, Y, 10, 30, clean=True), got[10:30])
+
+
+def test_c_loo_missing_symbol_is_a_rebuild_error(monkeypatch):
+    from oracle import c_oracle
+
+    class Old:                               # a liboracle.so built before the leave-one-out form existed
+        pass
+    monkeypatch.setattr(c_oracle, "_lib", Old())
+    X, Y = _loo_edge_graph(1, n=120, nt=10)
+    with pytest.raises(RuntimeError, match="rebuild the oracle"):
+        c_oracle.PreparedLoo(X, Y)
+
+
+def test_blocked_dense_loo_equals_per_fold_dense_loo():
+    """predict_loo_dense_blocked (the checker of every C4 fold at 20k) against predict_loo_dense, at block sizes that do
+    and do not divide the fold list, on a 90 % full and a sparse cutoff, weighted and not, with an isolated target."""
+    rng = np.random.default_rng(9)
+    n, nt = 150, 31
+    S = rng.random((n, n)); S = np.triu(S, 1); S = S + S.T; np.fill_diagonal(S, 1.0)
+    Y = (rng.random((n, nt)) < 0.1).astype(np.float64)
+    Y[:, 3] = 0.0
+    Y[:, 4] = 0.0; Y[33, 4] = 1.0
+    Y[50] = 0.0
+    qs = list(range(7, 140))
+    for alpha, weighted in ((0.1, True), (0.1, False), (0.9, True)):
+        X = O.cutoff(S, alpha, weighted)
+        want = O.predict_loo_dense(X, Y, clean_flag=True, queries=qs)
+        for block in (1, 16, 50, 512):
+            got = O.predict_loo_dense_blocked(X, Y, clean_flag=True, queries=qs, block=block)
+            np.testing.assert_allclose(got, want, rtol=1e-13, atol=0)
+            assert np.array_equal(got == -99, want == -99) and np.array_equal(got == 0, want == 0)
+        assert (want[33 - 7, 4] == -99)
+        np.testing.assert_allclose(O.predict_loo_dense_blocked(X, Y, block=64), O.predict_loo_dense(X, Y),
+                                   rtol=1e-13, atol=0)
+
+
+def test_kfold_query_form_equals_the_literal_fold_loop():
+    """c_oracle.predict_kfold (the checker of k-fold at 10k sources) against the reference's literal fold loop
+    (construct(y, X, members) -> predict -> clean!) on the dense block graph, with a target whose edges all sit in one
+    fold and an empty fold."""
+    from oracle import c_oracle
+    rng = np.random.default_rng(13)
+    n, nt, k = 70, 19, 6
+    S = rng.random((n, n)); S = (S + S.T) / 2; np.fill_diagonal(S, 1.0)
+    names = [f"d{i:02d}" for i in range(n)]; tn = [f"t{i}" for i in range(nt)]
+    Xn = O.featurize(Named(S, names, names), 0.7, True)
+    Yarr = (rng.random((n, nt)) < 0.15).astype(float)
+    Yarr[:, 2] = 0; Yarr[8, 2] = 1; Yarr[11, 2] = 1
+    Yn = Named(Yarr, names, tn)
+    fold = rng.integers(0, k - 1, size=n); fold[8] = fold[11] = 1        # fold k-1 stays empty
+    want = np.zeros((n, nt))
+    for phi in range(k):
+        idx = [i for i in range(n) if fold[i] == phi]
+        if not idx:
+            continue
+        members = [names[i] for i in idx]
+        A, B = O.construct_queries(Yn, Xn, members)
+        yq = Yn.sub(members, tn)
+        yh = O.predict(A, B, yq); O.clean(yh, A, yq)
+        want[idx] = yh.array
+    got = c_oracle.predict_kfold(Xn.array, Yarr, fold, k, clean=True)
+    np.testing.assert_allclose(got, want, rtol=1e-12, atol=1e-15)
+    assert np.array_equal(got == -99, want == -99) and (got[8, 2] == -99) and (got[11, 2] == -99)
+    np.testing.assert_allclose(c_oracle.predict_kfold(Xn.array, Yarr, fold, k), want * (want != -99), rtol=1e-12, atol=1e-15)
+
+
+def _helper_block():
+    rng = np.random.default_rng(3)
+    want = rng.random((40, 300)) * (rng.random((40, 300)) < 0.3)
+    want[:, 7] = -99.0
+    return want
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_compare_block_accepts_rounding_and_catches_subtle_errors(dtype):
+    """The shared comparison of the at-size tests passes a block rounded to the result precision, and fails on each
+    subtle error a kernel could make: one entry off by 1e-3 of itself, one contribution-carrying entry lost, two
+    neighbouring rows exchanged, one clean! marker lost."""
+    from block_compare import compare_block
+    want = _helper_block()
+    ok = want.astype(dtype)
+    m = compare_block(ok, want, dtype, "rounded")
+    assert m["elem"] <= (6e-8 if dtype == np.float32 else 1.2e-16)
+    r, c = np.argwhere(want > 0)[5]
+
+    def bad(f):
+        g = ok.astype(np.float64).copy()
+        f(g)
+        with pytest.raises(AssertionError):
+            compare_block(g, want, dtype, "perturbed")
+
+    bad(lambda g: g.__setitem__((r, c), g[r, c] * (1 + 1e-3)))
+    bad(lambda g: g.__setitem__((r, c), 0.0))
+    bad(lambda g: g.__setitem__(slice(10, 12), g[[11, 10]]))
+    bad(lambda g: g.__setitem__((3, 7), 0.0))
+    bad(lambda g: g.__setitem__((r, c), np.nan))
+    bad(lambda g: g.__setitem__(tuple(np.argwhere(want == 0)[0]), 1e-30))
