@@ -84,8 +84,8 @@ int ss_synchronize(void);
  * (stage 2), [3] epilogues/transposes, [4] host->device, [5] device->host,
  * [6] number of SpMM launches, [7] number of stage-1 launches.  Writes min(n,8) values. */
 int ss_timing_last(double* ms, int n);
-/* Which kernels the last predict / spmm call of this host thread went through: a comma-separated list of tags
- * ("transfer", "transfer_loo", "transfer_dense_bf16_ring", "transfer_dense_bf16_128", "transfer_dense_f32_mfma",
+/* Which kernels the last predict / spmm / fingerprint call of this host thread went through: a comma-separated list of tags
+ * ("tanimoto_csr_sym", "tanimoto_csr_cross", "transfer", "transfer_loo", "transfer_dense_bf16_ring", "transfer_dense_bf16_128", "transfer_dense_f32_mfma",
  * "spmm_sell", "spmm_sell_sorted", "spmm_csell", "spmm_colgroup", "spmm_chunked_narrow", ...), NUL-terminated, truncated
  * to n - 1 characters.  Lets a caller (and the parity tests) assert that a size-dependent routing decision was the one
  * expected.  Has no counterpart in the reference (its only switch is GPU::Bool, src/core.jl:402,404). */
@@ -120,6 +120,27 @@ int ss_gather_rows_f64(const double* local, int64_t ncols, const int64_t* counts
  * unit diagonal; two all-zero rows have similarity 1 (Distances.jl: distance 0). */
 int ss_similarity_jaccard_f32(const float* F, int64_t n, int64_t d, int64_t ld, float* S, int64_t lds, int mem);
 int ss_similarity_jaccard_f64(const double* F, int64_t n, int64_t d, int64_t ld, double* S, int64_t lds, int mem);
+
+/* featurize(1 .- pairwise(Jaccard(), F, dims=1), alpha, weighted) for binary fingerprints, as CSR
+ * (src/core.jl:106-112; docs/src/tutorial/fishers-flowers.jl:66).  On 0/1 rows that similarity is Tanimoto:
+ *     c = popcount(a & b), u = popcount(a) + popcount(b) - c, s = u == 0 ? 1 : T(c) / T(u)   (T = float / double)
+ *     entry (i, j) is kept iff s >= alpha and v != 0, v = weighted ? s : 1
+ * which is bitwise what ss_similarity_jaccard_* on the unpacked 0/1 rows followed by the cutoff assembly gives; the
+ * dense n x n similarity never exists.
+ * Layout: a fingerprint of d bits is nwords = ceil(d/64) little-endian uint64 words, bit k = bit k % 64 of word k / 64;
+ * bits past d MUST be zero (the caller's contract).  Rows are contiguous: Fa is na x nwords row-major.  This is Julia's
+ * BitVector.chunks layout: pass an nwords x n Matrix{UInt64} whose column i is fps[i].chunks.
+ * Output: ptr[na + 1] (int64), idx[nnz] (int32, ascending within each row), val[nnz] (s when weighted, 1 otherwise;
+ * val == NULL: not written), all in `mem`; deterministic run to run.
+ * Fb == NULL: Fb = Fa, nb = na (symmetric; the Xs block, diagonal included).  idx == NULL: size query -- writes ptr and
+ * *nnz only.  capacity < nnz: SS_EINVAL with *nnz set.  nnz >= 2^31: SS_EUNSUPPORTED with *nnz set, nothing else
+ * written (use the dense-similarity graph). */
+int ss_similarity_tanimoto_csr_f32(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords,
+                                   float alpha, int weighted, int64_t* ptr, int32_t* idx, float* val,
+                                   int64_t capacity, int64_t* nnz, int mem);
+int ss_similarity_tanimoto_csr_f64(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords,
+                                   double alpha, int weighted, int64_t* ptr, int32_t* idx, double* val,
+                                   int64_t capacity, int64_t* nnz, int mem);
 
 /* ------------------------------------------------------- cutoff / k / spread -- */
 /* cutoff(X, alpha, weighted): out = x >= alpha ? (weighted ? x : 1) : 0, element-wise
@@ -182,6 +203,19 @@ int ss_graph_create_similarity_f64(int64_t nq, int64_t ns, int64_t nt,
                                    const double* Sq, int64_t ldq, const double* Ss, int64_t lds,
                                    const int64_t* y_ptr, const int32_t* y_idx, const double* y_val,
                                    int index_base, double alpha, int weighted, int mem, ss_graph** out);
+/* construct(y, X, ...) with X = featurize(Tanimoto(F), alpha, weighted) for binary fingerprints (layout as in
+ * ss_similarity_tanimoto_csr_*): Xq = cut(T(Fq, Fs)) (nq x ns), Xs = cut(T(Fs, Fs)) (ns x ns), the features named after
+ * the sources (nf = ns); Y (ns x nt CSR) as in ss_graph_create_similarity_*.  The CSR blocks are produced on the device
+ * (ss_path_last: "tanimoto_csr_sym", "tanimoto_csr_cross").  nq may be 0 (Fq may then be NULL).  Serves ss_predict_* (query
+ * and source rows), ss_predict_loo_* and ss_predict_kfold_*. */
+int ss_graph_create_fingerprint_f32(int64_t nq, int64_t ns, int64_t nt, int64_t nwords,
+                                    const uint64_t* Fq, const uint64_t* Fs,
+                                    const int64_t* y_ptr, const int32_t* y_idx, const float* y_val,
+                                    int index_base, float alpha, int weighted, int mem, ss_graph** out);
+int ss_graph_create_fingerprint_f64(int64_t nq, int64_t ns, int64_t nt, int64_t nwords,
+                                    const uint64_t* Fq, const uint64_t* Fs,
+                                    const int64_t* y_ptr, const int32_t* y_idx, const double* y_val,
+                                    int index_base, double alpha, int weighted, int mem, ss_graph** out);
 /* General form for caller-built adjacency matrices: predict accepts ANY named A, B
  * (src/core.jl:402-425; the reference's own test passes hand-written 9 x 9 matrices,
  * test/runtests.jl:120-158).  With n nodes, the caller passes

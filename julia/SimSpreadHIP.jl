@@ -158,6 +158,42 @@ function jaccard_similarity(X::Matrix{Float32})
     return S
 end
 
+"""
+    tanimoto_csr(Fa::Matrix{UInt64}, Fb=nothing; alpha, weighted=true, T=Float32)
+
+`featurize(1 .- pairwise(Jaccard(), F, dims=1), alpha, weighted)` for binary fingerprints, produced as CSR on the device
+without the dense similarity.  `Fa` is `nwords x na` with column `i` = `fps[i].chunks` of a `BitVector` (bits past the
+fingerprint length zero, as `BitVector` keeps them); `Fb === nothing`: the symmetric block of `Fa` against itself.
+Returns the `na x nb` matrix as a `SparseMatrixCSC` (the library's row-major CSR read as the CSC of the transpose).
+"""
+function tanimoto_csr(Fa::Matrix{UInt64}, Fb::Union{Nothing,Matrix{UInt64}}=nothing; alpha::Real, weighted::Bool=true,
+                      T::Type=Float32)
+    nwords, na = size(Fa)
+    nb = Fb === nothing ? na : size(Fb, 2)
+    Fb === nothing || size(Fb, 1) == nwords || throw(ArgumentError("Fa and Fb have different fingerprint widths"))
+    pb = Fb === nothing ? Ptr{UInt64}(C_NULL) : pointer(Fb)
+    ptr = Vector{Int64}(undef, na + 1)
+    nnz = Ref{Int64}(0)
+    call(idx, val, cap) = if T === Float32
+        ccall((:ss_similarity_tanimoto_csr_f32, LIB), Cint,
+              (Ptr{UInt64}, Int64, Ptr{UInt64}, Int64, Int64, Float32, Cint, Ptr{Int64}, Ptr{Int32}, Ptr{Float32},
+               Int64, Ptr{Int64}, Cint),
+              Fa, na, pb, nb, nwords, Float32(alpha), weighted ? 1 : 0, ptr, idx, val, cap, nnz, SS_MEM_HOST)
+    else
+        ccall((:ss_similarity_tanimoto_csr_f64, LIB), Cint,
+              (Ptr{UInt64}, Int64, Ptr{UInt64}, Int64, Int64, Float64, Cint, Ptr{Int64}, Ptr{Int32}, Ptr{Float64},
+               Int64, Ptr{Int64}, Cint),
+              Fa, na, pb, nb, nwords, Float64(alpha), weighted ? 1 : 0, ptr, idx, val, cap, nnz, SS_MEM_HOST)
+    end
+    GC.@preserve Fa Fb begin
+        check(call(Ptr{Int32}(C_NULL), Ptr{T}(C_NULL), 0))             # size query
+        idx, val = Vector{Int32}(undef, nnz[]), Vector{T}(undef, nnz[])
+        check(call(idx, val, nnz[]))
+    end
+    # row-major CSR of (na x nb) == CSC of its (nb x na) transpose, 1-based
+    return permutedims(SparseMatrixCSC(nb, na, ptr .+ 1, Vector{Int}(idx) .+ 1, val))
+end
+
 # ------------------------------------------------------------------------------------------------ graph handles
 mutable struct Graph{T<:Union{Float32,Float64}}
     handle::Ptr{Cvoid}
@@ -261,6 +297,38 @@ function graph_similarity(Sq::Union{Nothing,AbstractMatrix}, Ss::AbstractMatrix,
               (Int64, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Float64},
                Cint, Float64, Cint, Cint, Ref{Ptr{Cvoid}}),
               nq, ns, nt, q, max(nq, 1), s, max(ns, 1), yp, yi, yv, 1, Float64(alpha), weighted ? 1 : 0, SS_MEM_HOST, h)
+    end
+    check(rc)
+    return Graph{T}(h[], nq, ns, ns, nt)
+end
+
+"""
+    graph_fingerprint(Fq, Fs::Matrix{UInt64}, Y::SparseMatrixCSC; alpha, weighted=true, T=Float32)
+
+`construct(y, X)` with `X = featurize(Tanimoto(F), alpha, weighted)` for binary fingerprints (`nwords x n` matrices,
+column `i` = `fps[i].chunks`): the thresholded similarity blocks are produced as CSR on the device.  `Fq === nothing`:
+the 3-layer graph of `construct(y, X)` (leave-one-out / k-fold).
+"""
+function graph_fingerprint(Fq::Union{Nothing,Matrix{UInt64}}, Fs::Matrix{UInt64}, Y::SparseMatrixCSC;
+                           alpha::Real, weighted::Bool=true, T::Type=Float32)
+    nwords, ns = size(Fs)
+    nq = Fq === nothing ? 0 : size(Fq, 2)
+    Fq === nothing || size(Fq, 1) == nwords || throw(ArgumentError("Fq and Fs have different fingerprint widths"))
+    size(Y, 1) == ns || throw(AssertionError("Labels and features have different number of source nodes"))
+    pq = Fq === nothing ? Ptr{UInt64}(C_NULL) : pointer(Fq)
+    yp, yi, yv = _csr(Y, T)
+    nt = size(Y, 2)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = GC.@preserve Fq if T === Float32
+        ccall((:ss_graph_create_fingerprint_f32, LIB), Cint,
+              (Int64, Int64, Int64, Int64, Ptr{UInt64}, Ptr{UInt64}, Ptr{Int64}, Ptr{Int32}, Ptr{Float32},
+               Cint, Float32, Cint, Cint, Ref{Ptr{Cvoid}}),
+              nq, ns, nt, nwords, pq, Fs, yp, yi, yv, 1, Float32(alpha), weighted ? 1 : 0, SS_MEM_HOST, h)
+    else
+        ccall((:ss_graph_create_fingerprint_f64, LIB), Cint,
+              (Int64, Int64, Int64, Int64, Ptr{UInt64}, Ptr{UInt64}, Ptr{Int64}, Ptr{Int32}, Ptr{Float64},
+               Cint, Float64, Cint, Cint, Ref{Ptr{Cvoid}}),
+              nq, ns, nt, nwords, pq, Fs, yp, yi, yv, 1, Float64(alpha), weighted ? 1 : 0, SS_MEM_HOST, h)
     end
     check(rc)
     return Graph{T}(h[], nq, ns, ns, nt)

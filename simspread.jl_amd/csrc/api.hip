@@ -357,6 +357,124 @@ static int graph_create_similarity_impl(int64_t nq, int64_t ns, int64_t nt, cons
   return SS_OK;
 }
 
+// ------------------------------------------------------------------ binary fingerprints -> thresholded Tanimoto CSR
+static int check_fingerprints(const char* what, const uint64_t* F, int64_t n, int64_t nwords) {
+  if (n < 0) return fail(SS_EINVAL, "%s: negative fingerprint count", what);
+  if (n >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "%s: %lld fingerprints (>= 2^31)", what, (long long)n);
+  if (n > 0 && !F) return fail(SS_EINVAL, "%s is NULL", what);
+  return SS_OK;
+}
+static int check_nwords(int64_t nwords) {
+  if (nwords < 1) return fail(SS_EINVAL, "nwords must be >= 1");
+  // popcounts stay exact in fp32 (and fit the int accumulators) for d < 2^24 bits
+  if (nwords > (1LL << 18)) return fail(SS_EUNSUPPORTED, "nwords > 2^18 (fingerprints of 2^24 bits or more)");
+  return SS_OK;
+}
+// fingerprints on the device: the caller's buffer (SS_MEM_DEVICE) or a staged copy
+static int stage_fingerprints(const uint64_t* F, int64_t n, int64_t nwords, int mem, DevBuf<uint64_t>& buf,
+                              const uint64_t** dev) {
+  if (mem == SS_MEM_DEVICE || n == 0) {
+    *dev = F;
+    return SS_OK;
+  }
+  SS_TRY(buf.alloc((size_t)n * (size_t)nwords));
+  SS_TRY(upload(buf.p, F, (size_t)n * (size_t)nwords, mem));
+  *dev = buf.p;
+  return SS_OK;
+}
+
+template <class T>
+static int tanimoto_csr_impl(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords, T alpha,
+                             int weighted, int64_t* ptr, int32_t* idx, T* val, int64_t capacity, int64_t* nnz,
+                             int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  path_note().clear();
+  const bool sym = (Fb == nullptr);
+  if (sym) nb = na;
+  SS_TRY(check_nwords(nwords));
+  SS_TRY(check_fingerprints("Fa", Fa, na, nwords));
+  if (!sym) SS_TRY(check_fingerprints("Fb", Fb, nb, nwords));
+  if (!ptr || !nnz) return fail(SS_EINVAL, "tanimoto: ptr and nnz must not be NULL");
+  DevBuf<uint64_t> ba, bb;
+  const uint64_t *da = nullptr, *db = nullptr;
+  SS_TRY(stage_fingerprints(Fa, na, nwords, mem, ba, &da));
+  if (!sym) SS_TRY(stage_fingerprints(Fb, nb, nwords, mem, bb, &db));
+  TanimotoCsr<T> tc;
+  SS_TRY(tc.count(da, na, sym ? nullptr : db, nb, nwords, alpha, weighted != 0));
+  path_add(sym ? "tanimoto_csr_sym" : "tanimoto_csr_cross");
+  *nnz = tc.nnz;
+  if (tc.nnz >= (1LL << 31))
+    return fail(SS_EUNSUPPORTED, "tanimoto: nnz = %lld >= 2^31 (use the dense-similarity graph)", (long long)tc.nnz);
+  if (idx && capacity < tc.nnz)
+    return fail(SS_EINVAL, "tanimoto: capacity %lld < nnz %lld", (long long)capacity, (long long)tc.nnz);
+  hipStream_t st = ctx().stream;
+  const hipMemcpyKind back = mem == SS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  SS_HIP(hipMemcpyAsync(ptr, tc.ptr.p, (size_t)(na + 1) * sizeof(int64_t), back, st));
+  if (idx && tc.nnz > 0) {
+    if (mem == SS_MEM_DEVICE) {
+      SS_TRY(tc.fill(idx, val, nullptr));
+    } else {
+      DevBuf<int> di;
+      DevBuf<T> dv;
+      SS_TRY(di.alloc(tc.nnz));
+      if (val) SS_TRY(dv.alloc(tc.nnz));
+      SS_TRY(tc.fill(di.p, val ? dv.p : nullptr, nullptr));
+      SS_HIP(hipMemcpyAsync(idx, di.p, (size_t)tc.nnz * sizeof(int), back, st));
+      if (val) SS_HIP(hipMemcpyAsync(val, dv.p, (size_t)tc.nnz * sizeof(T), back, st));
+      SS_HIP(hipStreamSynchronize(st));
+    }
+  }
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
+}
+
+// construct(y, X, ...) with X = featurize(Tanimoto(F), alpha, weighted): Xs = cut(T(Fs, Fs)), Xq = cut(T(Fq, Fs)),
+// features named after the sources; the CSR blocks are produced on the device and finalised like the other graphs
+template <class T>
+static int graph_create_fingerprint_impl(int64_t nq, int64_t ns, int64_t nt, int64_t nwords, const uint64_t* Fq,
+                                         const uint64_t* Fs, const int64_t* y_ptr, const int32_t* y_idx,
+                                         const T* y_val, int index_base, T alpha, int weighted, int mem,
+                                         ss_graph** out) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  if (!out) return fail(SS_EINVAL, "out handle pointer is NULL");
+  *out = nullptr;
+  path_note().clear();
+  if (nt < 0) return fail(SS_EINVAL, "negative node count");
+  if (nt >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "dimension >= 2^31");
+  SS_TRY(check_nwords(nwords));
+  SS_TRY(check_fingerprints("Fq", Fq, nq, nwords));
+  SS_TRY(check_fingerprints("Fs", Fs, ns, nwords));
+  DevBuf<uint64_t> bq, bs;
+  const uint64_t *dq = nullptr, *ds = nullptr;
+  SS_TRY(stage_fingerprints(Fs, ns, nwords, mem, bs, &ds));
+  SS_TRY(stage_fingerprints(Fq, nq, nwords, mem, bq, &dq));
+  GraphBox<T>* box = new (std::nothrow) GraphBox<T>();
+  if (!box) return fail(SS_ENOMEM, "host allocation failed");
+  box->dtype = (int)sizeof(T);
+  Graph<T>& g = box->g;
+  g.nq = nq; g.ns = ns; g.nf = ns; g.nt = nt;
+  int rc = SS_OK;
+  {
+    TanimotoCsr<T> ts;
+    rc = ts.count(ds, ns, nullptr, ns, nwords, alpha, weighted != 0);
+    if (rc == SS_OK) rc = ts.to_dev_csr(g.Xs);
+    path_add("tanimoto_csr_sym");
+  }
+  if (rc == SS_OK) {
+    TanimotoCsr<T> tq;
+    rc = tq.count(dq, nq, ds, ns, nwords, alpha, weighted != 0);
+    if (rc == SS_OK) rc = tq.to_dev_csr(g.Xq);
+    if (nq > 0) path_add("tanimoto_csr_cross");
+  }
+  if (rc == SS_OK) rc = csr_from_user<T>(ns, nt, y_ptr, y_idx, y_val, index_base, mem, g.Ys);
+  if (rc == SS_OK) rc = graph_finalize<T>(g);
+  if (rc != SS_OK) { delete box; return rc; }
+  *out = reinterpret_cast<ss_graph*>(box);
+  return SS_OK;
+}
+
 // stage-2 operand of a graph: W = Ys' cut for the tile width of this precision
 template <class T>
 static int graph_sell(Graph<T>& g) {
@@ -1269,6 +1387,33 @@ int ss_graph_create_similarity_f64(int64_t nq, int64_t ns, int64_t nt, const dou
   SS_API_LOCK();
   return graph_create_similarity_impl<double>(nq, ns, nt, Sq, ldq, Ss, lds, y_ptr, y_idx, y_val, index_base, alpha,
                                               weighted, mem, out);
+}
+
+int ss_similarity_tanimoto_csr_f32(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords,
+                                   float alpha, int weighted, int64_t* ptr, int32_t* idx, float* val, int64_t capacity,
+                                   int64_t* nnz, int mem) {
+  SS_API_LOCK();
+  return tanimoto_csr_impl<float>(Fa, na, Fb, nb, nwords, alpha, weighted, ptr, idx, val, capacity, nnz, mem);
+}
+int ss_similarity_tanimoto_csr_f64(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords,
+                                   double alpha, int weighted, int64_t* ptr, int32_t* idx, double* val, int64_t capacity,
+                                   int64_t* nnz, int mem) {
+  SS_API_LOCK();
+  return tanimoto_csr_impl<double>(Fa, na, Fb, nb, nwords, alpha, weighted, ptr, idx, val, capacity, nnz, mem);
+}
+int ss_graph_create_fingerprint_f32(int64_t nq, int64_t ns, int64_t nt, int64_t nwords, const uint64_t* Fq,
+                                    const uint64_t* Fs, const int64_t* y_ptr, const int32_t* y_idx, const float* y_val,
+                                    int index_base, float alpha, int weighted, int mem, ss_graph** out) {
+  SS_API_LOCK();
+  return graph_create_fingerprint_impl<float>(nq, ns, nt, nwords, Fq, Fs, y_ptr, y_idx, y_val, index_base, alpha,
+                                              weighted, mem, out);
+}
+int ss_graph_create_fingerprint_f64(int64_t nq, int64_t ns, int64_t nt, int64_t nwords, const uint64_t* Fq,
+                                    const uint64_t* Fs, const int64_t* y_ptr, const int32_t* y_idx, const double* y_val,
+                                    int index_base, double alpha, int weighted, int mem, ss_graph** out) {
+  SS_API_LOCK();
+  return graph_create_fingerprint_impl<double>(nq, ns, nt, nwords, Fq, Fs, y_ptr, y_idx, y_val, index_base, alpha,
+                                               weighted, mem, out);
 }
 
 int ss_graph_destroy(ss_graph* h) {

@@ -261,6 +261,25 @@ int launch_unpermute(const T* in, int64_t ldin, int64_t nrows, int64_t nt, const
 template <class T>
 int launch_loo_clean_fix(const DevCsr<T>& YsT, const int* kt, int64_t i_begin, int64_t nrows, T* out, int64_t ld);
 
+// ---- fingerprint.hip: thresholded Tanimoto similarity of packed binary fingerprints as CSR (two passes: count, fill).
+// Fa (na x nwords) against Fb (nb x nwords), both device-resident uint64 rows; Fb == nullptr: Fb = Fa (symmetric).
+template <class T>
+struct TanimotoCsr {
+  const uint64_t* Fa = nullptr;
+  const uint64_t* Fb = nullptr;
+  int64_t na = 0, nb = 0, nwords = 0;
+  int64_t ntj = 0;      // column tiles
+  int64_t nnz = 0;      // set by count(), summed in 64 bits (may be >= 2^31: the caller refuses it)
+  T alpha = T(0);
+  bool weighted = true, sym = false;
+  DevBuf<int> pop_a, pop_b;  // popcount of every row
+  DevBuf<int> counts;        // [ntj][na] in-row offset of every (column tile, row) slot
+  DevBuf<int64_t> ptr;       // [na + 1] row pointers
+  int count(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords, T alpha, bool weighted);
+  int fill(int* idx, T* val, bool* binary);  // device idx[nnz], val[nnz] (val may be null); binary: every value == 1
+  int to_dev_csr(DevCsr<T>& out);            // fill a DevCsr (SS_EUNSUPPORTED when nnz >= 2^31)
+};
+
 // ---- comm.hip: in-library score gather over RCCL (dlopen'ed), one process per GPU
 int comm_unique_id(char* id128);
 int comm_init(const char* id128, int rank, int nranks);

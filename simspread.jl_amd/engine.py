@@ -229,6 +229,53 @@ class DeviceGraph:
         return cls(h, dt)
 
     @classmethod
+    def from_fingerprints(cls, Fq, Fs, Y, alpha: float, weighted: bool = True, dtype=np.float32):
+        """``construct(y, X)`` with ``X = featurize(Tanimoto(F), alpha, weighted)`` for packed binary fingerprints (see
+        ``pack_fingerprints``): Xq = cut(T(Fq, Fs)), Xs = cut(T(Fs, Fs)), features named after the sources, produced as
+        CSR on the device (the dense similarity never exists).  Fq may be None (3-layer graph: predict_loo /
+        predict_kfold).  Fq, Fs: uint64 numpy arrays (n, nwords) with Y a scipy matrix (ns x nt), or int64 torch CUDA
+        tensors with Y = (ptr, idx, val, nt) device CSR."""
+        import scipy.sparse as sp
+        lib = L.lib()
+        dt = np.dtype(dtype).type
+        if dt not in (np.float32, np.float64):
+            raise TypeError("dtype must be float32 or float64")
+        dev = _is_torch(Fs)
+        keep = []
+        fq, nq, nwq = _fingerprints(Fq, dev, keep)
+        fs, ns, nwords = _fingerprints(Fs, dev, keep)
+        if Fq is not None and nwq != nwords:
+            raise ValueError("Fq and Fs have different fingerprint widths")
+        if dev:
+            import torch
+            want = torch.float32 if dt == np.float32 else torch.float64
+            yp, yi, yv, nt = Y[0].to(torch.int64).contiguous(), Y[1].to(torch.int32).contiguous(), Y[2], int(Y[3])
+            yv = None if yv is None else yv.to(want).contiguous()
+            if yp.numel() != ns + 1:
+                raise AssertionError("Labels and features have different number of source nodes")
+            keep.extend([yp, yi, yv])
+            yptr, yidx, yval = yp.data_ptr(), yi.data_ptr(), (None if yv is None else yv.data_ptr())
+            mem = L.SS_MEM_DEVICE
+        else:
+            Y = sp.csr_matrix(Y)
+            if Y.shape[0] != ns:
+                raise AssertionError("Labels and features have different number of source nodes")
+            nt = Y.shape[1]
+            parts = _csr_parts(Y, dt)
+            keep.append(parts)
+            yptr, yidx, yval = _ptr(parts[0]), _ptr(parts[1]), _ptr(parts[2])
+            mem = L.SS_MEM_HOST
+        h = C.c_void_p()
+        ctype = C.c_float if dt == np.float32 else C.c_double
+        fn = getattr(lib, f"ss_graph_create_fingerprint_{_suffix(dt)}")
+        L.check(fn(nq, ns, nt, nwords, fq, fs, yptr, yidx, yval, 0, ctype(alpha), 1 if weighted else 0, mem,
+                   C.byref(h)))
+        if dev:
+            L.check(lib.ss_synchronize())
+        del keep
+        return cls(h, dt)
+
+    @classmethod
     def general(cls, A_rows, B, B_cols_T, dtype=np.float64):
         """predict for caller-built A, B (src/core.jl:402-425): A_rows = A[rows, :], B, B_cols_T = B[:, cols]'."""
         import scipy.sparse as sp
@@ -468,3 +515,79 @@ def jaccard_similarity(X, dtype=np.float64):
     S = np.empty((n, n), dtype=dt, order="F")
     L_.check(getattr(lib, f"ss_similarity_jaccard_{suf}")(Xf.ctypes.data, n, d, max(n, 1), S.ctypes.data, max(n, 1), L_.SS_MEM_HOST))
     return np.ascontiguousarray(S)
+
+
+def pack_fingerprints(bits):
+    """Pack binary fingerprints (bool or 0/1 array of shape (n, d)) into the library's layout: (n, ceil(d/64)) uint64,
+    bit k of a fingerprint = bit k % 64 of word k // 64 (little-endian), bits past d zero.  This is Julia's
+    ``BitVector.chunks`` layout, one fingerprint per row."""
+    b = np.asarray(bits)
+    if b.ndim != 2:
+        raise ValueError("bits must be an (n, d) matrix")
+    n, d = b.shape
+    nwords = max((d + 63) // 64, 1)
+    packed = np.packbits(b != 0, axis=1, bitorder="little")          # (n, ceil(d/8)) bytes
+    out = np.zeros((n, nwords * 8), dtype=np.uint8)
+    out[:, :packed.shape[1]] = packed
+    return out.view("<u8").astype(np.uint64, copy=False).reshape(n, nwords)
+
+
+def _fingerprints(F, dev, keep):
+    """(pointer, rows, nwords) of packed fingerprints: uint64 numpy rows or an int64 torch CUDA tensor."""
+    if F is None:
+        return None, 0, 0
+    if dev:
+        import torch
+        if not (type(F).__module__.startswith("torch") and F.is_cuda and F.dtype == torch.int64 and F.ndim == 2):
+            raise TypeError("device fingerprints must be (n, nwords) int64 CUDA tensors")
+        t = F.contiguous()
+        keep.append(t)
+        return t.data_ptr(), t.shape[0], t.shape[1]
+    a = np.asarray(F)
+    if a.ndim != 2 or a.dtype.kind not in "ui" or a.dtype.itemsize != 8:
+        raise TypeError("fingerprints must be an (n, nwords) uint64 array (see pack_fingerprints)")
+    a = np.ascontiguousarray(a).view(np.uint64)
+    keep.append(a)
+    return a.ctypes.data, a.shape[0], a.shape[1]
+
+
+def tanimoto_csr(Fa, Fb=None, alpha=None, weighted: bool = True, dtype=np.float32):
+    """``featurize(1 .- pairwise(Jaccard(), F, dims=1), alpha, weighted)`` for packed binary fingerprints (see
+    ``pack_fingerprints``), produced as CSR on the device without the dense similarity: entry (i, j) = Tanimoto(Fa[i],
+    Fb[j]) when it is >= alpha (1 when not weighted).  Fb None: Fb = Fa.  Host input (uint64 numpy) returns a
+    scipy.sparse.csr_matrix; device input (int64 torch CUDA tensors) returns (ptr int64, idx int32, val) tensors."""
+    if alpha is None:
+        raise TypeError("tanimoto_csr needs alpha")
+    lib = L_.lib()
+    dt = np.dtype(dtype).type
+    suf = _suffix(dt)
+    fn = getattr(lib, f"ss_similarity_tanimoto_csr_{suf}")
+    ctype = C.c_float if dt == np.float32 else C.c_double
+    dev = _is_torch(Fa)
+    keep = []
+    pa, na, nw = _fingerprints(Fa, dev, keep)
+    pb, nb, nwb = _fingerprints(Fb, dev, keep)
+    if Fb is None:
+        nb, nwb = na, nw
+    if nwb != nw:
+        raise ValueError("Fa and Fb have different fingerprint widths")
+    nnz = C.c_int64(0)
+    w = 1 if weighted else 0
+    if dev:
+        import torch
+        ptr = torch.empty(na + 1, dtype=torch.int64, device=Fa.device)
+        L_.check(fn(pa, na, pb, nb, nw, ctype(alpha), w, ptr.data_ptr(), None, None, 0, C.byref(nnz), L_.SS_MEM_DEVICE))
+        idx = torch.empty(max(nnz.value, 1), dtype=torch.int32, device=Fa.device)
+        val = torch.empty(max(nnz.value, 1), dtype=torch.float32 if dt == np.float32 else torch.float64, device=Fa.device)
+        L_.check(fn(pa, na, pb, nb, nw, ctype(alpha), w, ptr.data_ptr(), idx.data_ptr(), val.data_ptr(), nnz.value,
+                    C.byref(nnz), L_.SS_MEM_DEVICE))
+        return ptr, idx[:nnz.value], val[:nnz.value]
+    import scipy.sparse as sp
+    ptr = np.zeros(na + 1, np.int64)
+    L_.check(fn(pa, na, pb, nb, nw, ctype(alpha), w, ptr.ctypes.data, None, None, 0, C.byref(nnz), L_.SS_MEM_HOST))
+    idx = np.empty(max(nnz.value, 1), np.int32)
+    val = np.empty(max(nnz.value, 1), dt)
+    L_.check(fn(pa, na, pb, nb, nw, ctype(alpha), w, ptr.ctypes.data, idx.ctypes.data, val.ctypes.data, nnz.value,
+                C.byref(nnz), L_.SS_MEM_HOST))
+    del keep
+    return sp.csr_matrix((val[:nnz.value], idx[:nnz.value], ptr), shape=(na, nb))
