@@ -296,6 +296,35 @@ int ss_topl_f32(const float* scores, int64_t nrows, int64_t ncols, int64_t ld, i
  * AuROC/AuPRC are NaN when a class is missing, as in the reference. */
 int ss_rank_metrics_f32(const uint8_t* y, const float* yhat, int64_t n, double alpha, double out[4], int mem);
 
+/* Ranking metrics of every row of a score block, on the device (one vector per row, as src/performance.jl evaluates
+ * one vector): out[r*6 + 0..5] = AuROC, AuPRC, BEDROC(alpha), validity ratio (src/performance.jl:22-89,558-560),
+ * recall@L, precision@L (src/performance.jl:308-385).  Row r's scores are yhat[r*ld .. r*ld + ncols) (row-major,
+ * ld >= ncols); its positives are the CSR column indices yidx[yptr[r] - index_base .. yptr[r+1] - index_base)
+ * (pattern only: every stored entry is a positive; sorted, unique and in range, otherwise SS_EINVAL and nothing is
+ * written; yptr[0] may exceed index_base, so a slice of a larger CSR can be passed as it is).  Each row follows
+ * ss_rank_metrics_f32's conventions: order sortperm(yhat, rev=true) (score descending, ties by ascending column), a
+ * confusion matrix at every unique score, trapezoid without a (0,0) point, AuROC/AuPRC NaN when a class is missing
+ * and the row has two or more distinct scores, clean!'s -99 an ordinary score; recall@L / precision@L count the
+ * positives of rank <= L, recall NaN without positives.  Scores must not be NaN.  out (nrows x 6 doubles, row-major)
+ * lives in `mem` like the inputs and is complete on return.  nrows == 0: no-op.  ncols < 2, ncols >= 2^31, L < 1 or
+ * L >= ncols ("Number of labels is less than length", src/performance.jl:311): SS_EINVAL.  Bitwise repeatable;
+ * scratch O(nrows + nnz(labels)).  ss_path_last: "rank_rows_lds" (rows of at most 2048 positives) and/or
+ * "rank_rows_large". */
+int ss_rank_metrics_rows_f32(const int64_t* yptr, const int32_t* yidx, int index_base, const float* yhat, int64_t nrows,
+                             int64_t ncols, int64_t ld, double alpha, int L, double* out, int mem);
+int ss_rank_metrics_rows_f64(const int64_t* yptr, const int32_t* yidx, int index_base, const double* yhat, int64_t nrows,
+                             int64_t ncols, int64_t ld, double alpha, int L, double* out, int mem);
+/* A leave-one-out sweep evaluated in place: row i - i_begin of out (6 doubles as in ss_rank_metrics_rows_*) is fold i of
+ * ss_predict_loo_*(g, i_begin, i_end, clean) ranked against the graph's own labels Ys[i, :] -- bitwise what
+ * ss_predict_loo_* into a device buffer followed by ss_rank_metrics_rows_* gives, for every block_rows.  The library
+ * streams blocks of block_rows folds through a score buffer of its own (0: its choice, about 1 GiB of scores); no
+ * score leaves the device.  Same preconditions as ss_predict_loo_* (CSR, dense-similarity and fingerprint graphs).
+ * out (n x 6 doubles) lives in `mem` and is complete on return. */
+int ss_evaluate_loo_f32(ss_graph* g, int64_t i_begin, int64_t i_end, int clean, double alpha, int L, int64_t block_rows,
+                        double* out, int mem);
+int ss_evaluate_loo_f64(ss_graph* g, int64_t i_begin, int64_t i_end, int clean, double alpha, int L, int64_t block_rows,
+                        double* out, int mem);
+
 /* -------------------------------------------------------------- raw W*R SpMM --- */
 /* The resource-spreading product F = W * R on its own (kernel unit tests and the
  * roofline benchmark; inside predict W = Ys' and R = the transfer block, src/core.jl:413).

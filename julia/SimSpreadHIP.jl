@@ -473,6 +473,58 @@ function rank_metrics(y::AbstractVector, yhat::AbstractVector; alpha::Float64=20
     return (AuROC=out[1], AuPRC=out[2], BEDROC=out[3], validity_ratio=out[4])
 end
 
+"""
+    rank_metrics_rows(y, yhat; alpha=20.0, L=20) -> Matrix{Float64} (rows x 6)
+
+The ranking metrics of every row of a `rows x targets` score matrix against the 0/1 label matrix `y` of the same
+size, on the device: columns AuROC, AuPRC, BEDROC(alpha), validity ratio (src/performance.jl:22-89,558-560),
+recall@L and precision@L (src/performance.jl:308-385).  The labels go over as host CSR (the transpose of `y` as a
+SparseMatrixCSC is the CSR of `y`), the scores row-contiguous (the transpose of the Julia matrix as it lies in memory).
+"""
+function rank_metrics_rows(y::AbstractMatrix, yhat::AbstractMatrix{T}; alpha::Float64=20.0, L::Integer=20) where {T<:Union{Float32,Float64}}
+    size(y) == size(yhat) || throw(AssertionError("Number of predictions and labels don't match"))
+    nrows, ncols = size(yhat)
+    ncols > L || throw(AssertionError("Number of labels is less than length (L > y)"))
+    yt = SparseMatrixCSC{Float64,Int64}(sparse(transpose(y .!= 0)))   # columns of yt = rows of y
+    dropzeros!(yt)
+    ptr = Vector{Int64}(yt.colptr)        # 1-based
+    idx = Vector{Int32}(yt.rowval)        # 1-based
+    rowmajor = Matrix{T}(transpose(yhat))
+    out = Matrix{Float64}(undef, 6, nrows)
+    rc = if T === Float32
+        ccall((:ss_rank_metrics_rows_f32, LIB), Cint,
+              (Ptr{Int64}, Ptr{Int32}, Cint, Ptr{Float32}, Int64, Int64, Int64, Float64, Cint, Ptr{Float64}, Cint),
+              ptr, idx, 1, rowmajor, nrows, ncols, ncols, alpha, L, out, SS_MEM_HOST)
+    else
+        ccall((:ss_rank_metrics_rows_f64, LIB), Cint,
+              (Ptr{Int64}, Ptr{Int32}, Cint, Ptr{Float64}, Int64, Int64, Int64, Float64, Cint, Ptr{Float64}, Cint),
+              ptr, idx, 1, rowmajor, nrows, ncols, ncols, alpha, L, out, SS_MEM_HOST)
+    end
+    check(rc)
+    return Matrix{Float64}(out')
+end
+
+"""
+    evaluate_loo(g, i_begin, i_end; clean=true, alpha=20.0, L=20, block_rows=0) -> Matrix{Float64} (n x 6)
+
+The leave-one-out folds `i_begin:i_end` (1-based, inclusive) of `predict_loo` ranked against the graph's own labels,
+without the scores leaving the device: one row of `rank_metrics_rows` per fold.
+"""
+function evaluate_loo(g::Graph{T}, i_begin::Integer, i_end::Integer; clean::Bool=true, alpha::Float64=20.0,
+                      L::Integer=20, block_rows::Integer=0) where {T}
+    lo, hi = i_begin - 1, i_end
+    out = Matrix{Float64}(undef, 6, max(hi - lo, 0))
+    rc = if T === Float32
+        ccall((:ss_evaluate_loo_f32, LIB), Cint, (Ptr{Cvoid}, Int64, Int64, Cint, Float64, Cint, Int64, Ptr{Float64}, Cint),
+              g.handle, lo, hi, clean ? 1 : 0, alpha, L, block_rows, out, SS_MEM_HOST)
+    else
+        ccall((:ss_evaluate_loo_f64, LIB), Cint, (Ptr{Cvoid}, Int64, Int64, Cint, Float64, Cint, Int64, Ptr{Float64}, Cint),
+              g.handle, lo, hi, clean ? 1 : 0, alpha, L, block_rows, out, SS_MEM_HOST)
+    end
+    check(rc)
+    return Matrix{Float64}(out')
+end
+
 # ------------------------------------------------------------------------------------------------ raw W*R SpMM
 mutable struct SpMat{T<:Union{Float32,Float64}}
     handle::Ptr{Cvoid}

@@ -234,6 +234,14 @@ int launch_topl(const float* scores, int64_t nrows, int64_t ncols, int64_t ld, i
 // metrics.hip: AuROC, AuPRC, BEDROC(alpha), validity ratio of one score vector (device inputs, host outputs)
 int launch_rank_metrics(const unsigned char* y, const float* yhat, int64_t n, double alpha, double* out4);
 
+// rank_rows.hip: the six per-row ranking metrics of a row-major score block against CSR positives (device inputs and
+// out, enqueued on the stream).  Row r's positives are yidx[yptr[r] - shift .. yptr[r+1] - shift), values - base;
+// host_ptr is a host copy of yptr[0..nrows].  validate: sorted, unique, in range (syncs; SS_EINVAL otherwise).
+template <class PtrT>
+int launch_rank_rows_validate(const PtrT* yptr, int64_t shift, const int* yidx, int base, int64_t nrows, int64_t ncols);
+template <class T, class PtrT>
+int launch_rank_rows(const PtrT* yptr, int64_t shift, const int* yidx, int base, const PtrT* host_ptr, const T* yhat,
+                     int64_t nrows, int64_t ncols, int64_t ld, double alpha, int L, double* out);
 // ---- dense.hip (fp32 only: fp32-input MFMA)
 int launch_transfer_dense(const DenseSim<float>& d, bool loo, const float* inv_k, const float* inv_n, const int* ks,
                           int64_t row_begin, int64_t nrows, float* out, int64_t ldo, bool source_rows = false);

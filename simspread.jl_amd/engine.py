@@ -349,6 +349,20 @@ class DeviceGraph:
                    L.SS_LAYOUT_ROWMAJOR, L.SS_MEM_HOST))
         return out
 
+    def evaluate_loo(self, i_begin: int = 0, i_end: Optional[int] = None, clean: bool = False, alpha: float = 20.0,
+                     L: int = 20, block_rows: int = 0):
+        """The leave-one-out folds [i_begin, i_end) ranked against the graph's own labels without the scores leaving the
+        device: row i - i_begin = rank_metrics_rows(Ys[i, :], predict_loo(i)).  Returns (n, 6) float64 numpy, columns
+        RANK_ROWS_FIELDS.  block_rows: folds per device block (0: the library's choice, about 1 GiB of scores)."""
+        i_end = self.ns if i_end is None else i_end
+        n = max(i_end - i_begin, 0)
+        _check_L(self.nt, L)
+        out = np.empty((n, len(RANK_ROWS_FIELDS)), np.float64)
+        fn = getattr(L_.lib(), f"ss_evaluate_loo_{self._suf}")
+        L_.check(fn(self._h, i_begin, i_end, 1 if clean else 0, float(alpha), int(L), int(block_rows), out.ctypes.data,
+                    L_.SS_MEM_HOST))
+        return out
+
     def close(self):
         if self._h is not None and self._h.value:
             L.load().ss_graph_destroy(self._h)
@@ -491,6 +505,117 @@ def rank_metrics(y, yhat, alpha: float = 20.0) -> dict:
             raise AssertionError("The number of scores must be equal to the number of labels")
         L_.check(lib.ss_rank_metrics_f32(yl.ctypes.data, sc.ctypes.data, sc.size, float(alpha), out, L_.SS_MEM_HOST))
     return {"AuROC": out[0], "AuPRC": out[1], "BEDROC": out[2], "validity_ratio": out[3]}
+
+
+RANK_ROWS_FIELDS = ("AuROC", "AuPRC", "BEDROC", "validity_ratio", "recallatL", "precisionatL")
+
+
+def _check_L(ncols: int, L: int):
+    # the reference's assertions (src/performance.jl:309-312)
+    if L < 1:
+        raise AssertionError("Please use a list length greater than 0 (L > 0)")
+    if ncols <= L:
+        raise AssertionError("Number of labels is less than length (L > y)")
+
+
+def _label_csr(y, nrows: int, ncols: int):
+    """(ptr int64, idx int32) host arrays of a label matrix: scipy sparse (stored zeros dropped), a dense 0/1 array or a
+    host (ptr, idx) pair.  Every remaining entry is a positive; the order of the indices is kept as given."""
+    import scipy.sparse as sp
+    if isinstance(y, tuple):
+        ptr, idx = (np.ascontiguousarray(np.asarray(v), dtype=t) for v, t in zip(y, (np.int64, np.int32)))
+        if ptr.shape != (nrows + 1,):
+            raise ValueError(f"label row pointers have shape {ptr.shape}, expected {(nrows + 1,)}")
+        return ptr, idx
+    if sp.issparse(y):
+        m = sp.csr_matrix(y, copy=True)
+        if m.shape != (nrows, ncols):
+            raise ValueError(f"labels have shape {m.shape}, scores {(nrows, ncols)}")
+        m.eliminate_zeros()
+        return np.ascontiguousarray(m.indptr, dtype=np.int64), np.ascontiguousarray(m.indices, dtype=np.int32)
+    a = np.asarray(y)
+    if a.shape != (nrows, ncols):
+        raise ValueError(f"labels have shape {a.shape}, scores {(nrows, ncols)}")
+    nzr, nzc = np.nonzero(a)
+    ptr = np.zeros(nrows + 1, np.int64)
+    np.cumsum(np.bincount(nzr, minlength=nrows), out=ptr[1:])
+    return ptr, np.ascontiguousarray(nzc, dtype=np.int32)
+
+
+def _check_label_order(ptr, idx, ncols: int):
+    """Column indices sorted, unique and in range within every row (the library checks it again on the device)."""
+    ptr = np.asarray(ptr, dtype=np.int64)
+    if ptr[0] < 0 or np.any(np.diff(ptr) < 0) or ptr[-1] > np.size(idx):
+        raise ValueError("label row pointers are not a 0-based CSR row pointer array")
+    idx = np.asarray(idx, dtype=np.int64)[ptr[0]:ptr[-1]]    # rows of a larger CSR may start past its first entry
+    ptr = ptr - ptr[0]
+    if idx.size == 0:
+        return
+    if idx.min() < 0 or idx.max() >= ncols:
+        raise ValueError("label column index out of range")
+    starts = np.zeros(idx.size, bool)
+    starts[ptr[:-1][np.diff(ptr) > 0]] = True
+    if np.any(np.diff(idx)[~starts[1:]] <= 0):
+        raise ValueError("label column indices must be sorted and unique within every row")
+
+
+def rank_metrics_rows(y, yhat, alpha: float = 20.0, L: int = 20):
+    """Ranking metrics of every row of a score block on the device: AuROC, AuPRC, BEDROC(alpha), validity ratio
+    (src/performance.jl:22-89,558-560), recall@L and precision@L (src/performance.jl:308-385), one row each, columns in
+    RANK_ROWS_FIELDS.  `yhat`: (nrows, ncols) float32/float64, a C-order numpy array or a contiguous CUDA tensor.
+    `y`: the positives -- a scipy sparse matrix or dense 0/1 array of the same shape, or a 0-based CSR (ptr int64,
+    idx int32) pair, host arrays or CUDA tensors, indices sorted and unique in every row; ptr may be a slice of a larger
+    CSR's row pointers (ptr[0] > 0).  Returns (nrows, 6) float64
+    of the same kind as `yhat`.  Bad shapes, L >= ncols and bad label indices raise before the device is touched."""
+    torch_in = type(yhat).__module__.startswith("torch")
+    if torch_in:
+        import torch
+        if yhat.dim() != 2 or not yhat.is_contiguous() or not yhat.is_cuda:
+            raise ValueError("yhat must be a contiguous 2-D CUDA tensor")
+        suf = {torch.float32: "f32", torch.float64: "f64"}.get(yhat.dtype)
+        if suf is None:
+            raise TypeError("yhat must be float32 or float64")
+        nrows, ncols = (int(v) for v in yhat.shape)
+    else:
+        a = np.asarray(yhat)
+        if a.ndim != 2:
+            raise ValueError("yhat must be 2-D (rows x columns)")
+        suf = _suffix(a.dtype)
+        a = np.ascontiguousarray(a)
+        nrows, ncols = a.shape
+    _check_L(ncols, L)
+    dev_labels = isinstance(y, tuple) and type(y[0]).__module__.startswith("torch")
+    if dev_labels:
+        import torch
+        ptr_t, idx_t = y
+        if ptr_t.dtype != torch.int64 or idx_t.dtype != torch.int32 or not (ptr_t.is_cuda and idx_t.is_cuda):
+            raise TypeError("device labels are a (ptr int64, idx int32) pair of CUDA tensors")
+        if ptr_t.numel() != nrows + 1:
+            raise ValueError(f"label row pointers have {ptr_t.numel()} entries, expected {nrows + 1}")
+        # the indices stay on the device: the library checks them there before it writes anything
+    else:
+        hp, hi = _label_csr(y, nrows, ncols)
+        _check_label_order(hp, hi, ncols)
+    lib = L_.lib()
+    fn = getattr(lib, f"ss_rank_metrics_rows_{suf}")
+    if torch_in:
+        import torch
+        _is_torch(yhat)  # order the library after the kernels that produced the scores
+        if dev_labels:
+            ptr_d, idx_d = ptr_t.contiguous(), idx_t.contiguous()
+        else:
+            ptr_d = torch.from_numpy(hp).to(yhat.device)
+            idx_d = torch.from_numpy(hi if hi.size else np.zeros(1, np.int32)).to(yhat.device)
+        out = torch.empty((nrows, 6), dtype=torch.float64, device=yhat.device)
+        L_.check(fn(ptr_d.data_ptr(), idx_d.data_ptr(), 0, yhat.data_ptr(), nrows, ncols, ncols, float(alpha), int(L),
+                    out.data_ptr(), L_.SS_MEM_DEVICE))
+        return out
+    if dev_labels:
+        raise TypeError("device labels need device scores (a CUDA tensor yhat)")
+    out = np.empty((nrows, 6), np.float64)
+    L_.check(fn(hp.ctypes.data, hi.ctypes.data, 0, a.ctypes.data, nrows, ncols, ncols, float(alpha), int(L),
+                out.ctypes.data, L_.SS_MEM_HOST))
+    return out
 
 
 def jaccard_similarity(X, dtype=np.float64):
