@@ -85,7 +85,7 @@ int ss_synchronize(void);
  * [6] number of SpMM launches, [7] number of stage-1 launches.  Writes min(n,8) values. */
 int ss_timing_last(double* ms, int n);
 /* Which kernels the last predict / spmm / fingerprint call of this host thread went through: a comma-separated list of tags
- * ("tanimoto_csr_sym", "tanimoto_csr_cross", "transfer", "transfer_loo", "transfer_dense_bf16_ring", "transfer_dense_bf16_128", "transfer_dense_f32_mfma",
+ * ("tanimoto_csr_sym", "tanimoto_csr_cross", "jaccard_csr_sym", "jaccard_csr_cross", "transfer", "transfer_loo", "transfer_dense_bf16_ring", "transfer_dense_bf16_128", "transfer_dense_f32_mfma",
  * "spmm_sell", "spmm_sell_sorted", "spmm_csell", "spmm_colgroup", "spmm_chunked_narrow", ...), NUL-terminated, truncated
  * to n - 1 characters.  Lets a caller (and the parity tests) assert that a size-dependent routing decision was the one
  * expected.  Has no counterpart in the reference (its only switch is GPU::Bool, src/core.jl:402,404). */
@@ -141,6 +141,28 @@ int ss_similarity_tanimoto_csr_f32(const uint64_t* Fa, int64_t na, const uint64_
 int ss_similarity_tanimoto_csr_f64(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords,
                                    double alpha, int weighted, int64_t* ptr, int32_t* idx, double* val,
                                    int64_t capacity, int64_t* nnz, int mem);
+
+/* featurize(1 .- pairwise(Jaccard(), X, dims=1), alpha, weighted) for real-valued feature rows, as CSR
+ * (src/core.jl:106-112; docs/src/tutorial/fishers-flowers.jl:66,95-96).  On non-negative rows that similarity is the
+ * weighted Jaccard (Ruzicka) Σmin / Σmax:
+ *     smin = smax = +0; for k = 0 .. d-1 in order, in T: smin += min(a_k, b_k), smax += max(a_k, b_k)
+ *     s = smax == 0 ? 1 : smin / smax                    (T = float / double, one correctly rounded division)
+ *     entry (i, j) is kept iff s >= alpha and v != 0, v = weighted ? s : 1
+ * which is bitwise what ss_similarity_jaccard_* on the stacked rows followed by the cutoff assembly gives; the dense
+ * n x n similarity never exists.  Negative and infinite features give what that route gives; a NaN feature or a NaN
+ * alpha is SS_EINVAL, checked before anything is written.  d = 0: every pair has s = 1.
+ * Layout: as ss_similarity_jaccard_*: Fa is na x d column-major with lda >= na (Fb likewise), i.e. a Julia Matrix with
+ * one sample per row, or X.t().contiguous() of a torch (n, d) tensor.
+ * Output and size protocol as ss_similarity_tanimoto_csr_*: ptr[na + 1] (int64), idx[nnz] (int32, ascending within each
+ * row), val[nnz] (val == NULL: not written), all in `mem`; deterministic run to run.  Fb == NULL: Fb = Fa, nb = na
+ * (symmetric).  idx == NULL: size query -- writes ptr and *nnz only.  capacity < nnz: SS_EINVAL with *nnz set.
+ * nnz >= 2^31: SS_EUNSUPPORTED with *nnz set, nothing else written. */
+int ss_similarity_jaccard_csr_f32(const float* Fa, int64_t na, int64_t lda, const float* Fb, int64_t nb, int64_t ldb,
+                                  int64_t d, float alpha, int weighted, int64_t* ptr, int32_t* idx, float* val,
+                                  int64_t capacity, int64_t* nnz, int mem);
+int ss_similarity_jaccard_csr_f64(const double* Fa, int64_t na, int64_t lda, const double* Fb, int64_t nb, int64_t ldb,
+                                  int64_t d, double alpha, int weighted, int64_t* ptr, int32_t* idx, double* val,
+                                  int64_t capacity, int64_t* nnz, int mem);
 
 /* ------------------------------------------------------- cutoff / k / spread -- */
 /* cutoff(X, alpha, weighted): out = x >= alpha ? (weighted ? x : 1) : 0, element-wise
@@ -216,6 +238,20 @@ int ss_graph_create_fingerprint_f64(int64_t nq, int64_t ns, int64_t nt, int64_t 
                                     const uint64_t* Fq, const uint64_t* Fs,
                                     const int64_t* y_ptr, const int32_t* y_idx, const double* y_val,
                                     int index_base, double alpha, int weighted, int mem, ss_graph** out);
+/* construct(y, X, ...) with X = featurize(J(F), alpha, weighted), J the weighted Jaccard similarity of real-valued
+ * feature rows (layout and rule as in ss_similarity_jaccard_csr_*; src/core.jl:106-112,148-201;
+ * docs/src/tutorial/fishers-flowers.jl:66,95-96): Xq = cut(J(Fq, Fs)) (nq x ns), Xs = cut(J(Fs, Fs)) (ns x ns), the
+ * features named after the sources (nf = ns); Y (ns x nt CSR) as in ss_graph_create_similarity_*.  The CSR blocks are
+ * produced on the device (ss_path_last: "jaccard_csr_sym", "jaccard_csr_cross").  nq may be 0 (Fq may then be NULL).
+ * Serves ss_predict_* (query and source rows), ss_predict_loo_*, ss_predict_kfold_* and ss_evaluate_loo_*. */
+int ss_graph_create_features_f32(int64_t nq, int64_t ns, int64_t nt, int64_t d,
+                                 const float* Fq, int64_t ldq, const float* Fs, int64_t lds,
+                                 const int64_t* y_ptr, const int32_t* y_idx, const float* y_val,
+                                 int index_base, float alpha, int weighted, int mem, ss_graph** out);
+int ss_graph_create_features_f64(int64_t nq, int64_t ns, int64_t nt, int64_t d,
+                                 const double* Fq, int64_t ldq, const double* Fs, int64_t lds,
+                                 const int64_t* y_ptr, const int32_t* y_idx, const double* y_val,
+                                 int index_base, double alpha, int weighted, int mem, ss_graph** out);
 /* General form for caller-built adjacency matrices: predict accepts ANY named A, B
  * (src/core.jl:402-425; the reference's own test passes hand-written 9 x 9 matrices,
  * test/runtests.jl:120-158).  With n nodes, the caller passes

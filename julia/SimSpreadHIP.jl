@@ -194,6 +194,44 @@ function tanimoto_csr(Fa::Matrix{UInt64}, Fb::Union{Nothing,Matrix{UInt64}}=noth
     return permutedims(SparseMatrixCSC(nb, na, ptr .+ 1, Vector{Int}(idx) .+ 1, val))
 end
 
+"""
+    jaccard_csr(Fa::Matrix{T}, Fb=nothing; alpha, weighted=true) where T<:Union{Float32,Float64}
+
+`featurize(1 .- pairwise(Jaccard(), X, dims=1), alpha, weighted)` for real-valued feature rows
+(docs/src/tutorial/fishers-flowers.jl:66,95-96), produced as CSR on the device without the dense similarity: the
+weighted Jaccard Σmin / Σmax of every pair of rows, bitwise what `jaccard_similarity` followed by the cutoff gives.
+`Fa` is `na x d` with one sample per row (a plain Julia `Matrix`, column-major); `Fb === nothing`: the symmetric block of
+`Fa` against itself.  Returns the `na x nb` matrix as a `SparseMatrixCSC`.
+"""
+function jaccard_csr(Fa::Matrix{T}, Fb::Union{Nothing,Matrix{T}}=nothing; alpha::Real,
+                     weighted::Bool=true) where {T<:Union{Float32,Float64}}
+    na, d = size(Fa)
+    nb = Fb === nothing ? na : size(Fb, 1)
+    Fb === nothing || size(Fb, 2) == d || throw(ArgumentError("Fa and Fb have different numbers of features"))
+    pb = Fb === nothing ? Ptr{T}(C_NULL) : pointer(Fb)
+    ptr = Vector{Int64}(undef, na + 1)
+    nnz = Ref{Int64}(0)
+    call(idx, val, cap) = if T === Float32
+        ccall((:ss_similarity_jaccard_csr_f32, LIB), Cint,
+              (Ptr{Float32}, Int64, Int64, Ptr{Float32}, Int64, Int64, Int64, Float32, Cint, Ptr{Int64}, Ptr{Int32},
+               Ptr{Float32}, Int64, Ptr{Int64}, Cint),
+              Fa, na, max(na, 1), pb, nb, max(nb, 1), d, Float32(alpha), weighted ? 1 : 0, ptr, idx, val, cap, nnz,
+              SS_MEM_HOST)
+    else
+        ccall((:ss_similarity_jaccard_csr_f64, LIB), Cint,
+              (Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Int64, Float64, Cint, Ptr{Int64}, Ptr{Int32},
+               Ptr{Float64}, Int64, Ptr{Int64}, Cint),
+              Fa, na, max(na, 1), pb, nb, max(nb, 1), d, Float64(alpha), weighted ? 1 : 0, ptr, idx, val, cap, nnz,
+              SS_MEM_HOST)
+    end
+    GC.@preserve Fa Fb begin
+        check(call(Ptr{Int32}(C_NULL), Ptr{T}(C_NULL), 0))             # size query
+        idx, val = Vector{Int32}(undef, nnz[]), Vector{T}(undef, nnz[])
+        check(call(idx, val, nnz[]))
+    end
+    return permutedims(SparseMatrixCSC(nb, na, ptr .+ 1, Vector{Int}(idx) .+ 1, val))
+end
+
 # ------------------------------------------------------------------------------------------------ graph handles
 mutable struct Graph{T<:Union{Float32,Float64}}
     handle::Ptr{Cvoid}
@@ -329,6 +367,41 @@ function graph_fingerprint(Fq::Union{Nothing,Matrix{UInt64}}, Fs::Matrix{UInt64}
               (Int64, Int64, Int64, Int64, Ptr{UInt64}, Ptr{UInt64}, Ptr{Int64}, Ptr{Int32}, Ptr{Float64},
                Cint, Float64, Cint, Cint, Ref{Ptr{Cvoid}}),
               nq, ns, nt, nwords, pq, Fs, yp, yi, yv, 1, Float64(alpha), weighted ? 1 : 0, SS_MEM_HOST, h)
+    end
+    check(rc)
+    return Graph{T}(h[], nq, ns, ns, nt)
+end
+
+"""
+    graph_features(Fq, Fs::Matrix{T}, Y::SparseMatrixCSC; alpha, weighted=true) where T<:Union{Float32,Float64}
+
+`construct(y, X)` with `X = featurize(1 .- pairwise(Jaccard(), F, dims=1), alpha, weighted)` for real-valued feature
+rows (`n x d` matrices, one sample per row; docs/src/tutorial/fishers-flowers.jl:66,95-96): the thresholded weighted
+Jaccard blocks are produced as CSR on the device.  `Fq === nothing`: the 3-layer graph of `construct(y, X)`
+(leave-one-out / k-fold).
+"""
+function graph_features(Fq::Union{Nothing,Matrix{T}}, Fs::Matrix{T}, Y::SparseMatrixCSC; alpha::Real,
+                        weighted::Bool=true) where {T<:Union{Float32,Float64}}
+    ns, d = size(Fs)
+    nq = Fq === nothing ? 0 : size(Fq, 1)
+    Fq === nothing || size(Fq, 2) == d || throw(ArgumentError("Fq and Fs have different numbers of features"))
+    size(Y, 1) == ns || throw(AssertionError("Labels and features have different number of source nodes"))
+    pq = Fq === nothing ? Ptr{T}(C_NULL) : pointer(Fq)
+    yp, yi, yv = _csr(Y, T)
+    nt = size(Y, 2)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = GC.@preserve Fq if T === Float32
+        ccall((:ss_graph_create_features_f32, LIB), Cint,
+              (Int64, Int64, Int64, Int64, Ptr{Float32}, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Ptr{Int32},
+               Ptr{Float32}, Cint, Float32, Cint, Cint, Ref{Ptr{Cvoid}}),
+              nq, ns, nt, d, pq, max(nq, 1), Fs, max(ns, 1), yp, yi, yv, 1, Float32(alpha), weighted ? 1 : 0,
+              SS_MEM_HOST, h)
+    else
+        ccall((:ss_graph_create_features_f64, LIB), Cint,
+              (Int64, Int64, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int32},
+               Ptr{Float64}, Cint, Float64, Cint, Cint, Ref{Ptr{Cvoid}}),
+              nq, ns, nt, d, pq, max(nq, 1), Fs, max(ns, 1), yp, yi, yv, 1, Float64(alpha), weighted ? 1 : 0,
+              SS_MEM_HOST, h)
     end
     check(rc)
     return Graph{T}(h[], nq, ns, ns, nt)

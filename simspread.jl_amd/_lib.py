@@ -72,6 +72,10 @@ def _sigs():
     for suf, ft in (("f32", f32), ("f64", f64)):
         s[f"ss_similarity_tanimoto_csr_{suf}"] = ([_vp, _i64, _vp, _i64, _i64, ft, _int, _vp, _vp, _vp, _i64, _vp, _int], _int)
         s[f"ss_graph_create_fingerprint_{suf}"] = ([_i64] * 4 + [_vp] * 5 + [_int, ft, _int, _int, _vp], _int)
+        s[f"ss_similarity_jaccard_csr_{suf}"] = ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, ft, _int, _vp, _vp, _vp, _i64, _vp,
+                                                   _int], _int)
+        s[f"ss_graph_create_features_{suf}"] = ([_i64] * 4 + [_vp, _i64, _vp, _i64] + [_vp] * 3 + [_int, ft, _int, _int, _vp],
+                                                _int)
 
         s[f"ss_cutoff_{suf}"] = ([_vp, _i64, _i64, _i64, ft, _int, _vp, _i64, _int], _int)
         s[f"ss_similarity_jaccard_{suf}"] = ([_vp, _i64, _i64, _i64, _vp, _i64, _int], _int)

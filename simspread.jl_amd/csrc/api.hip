@@ -383,6 +383,69 @@ static int stage_fingerprints(const uint64_t* F, int64_t n, int64_t nwords, int 
   return SS_OK;
 }
 
+// the size protocol of the fused producers, after their count pass: *nnz always; nnz >= 2^31 refused and capacity
+// checked before anything is written; ptr, then (idx != NULL) idx and val (val may be NULL) in `mem`
+template <class T>
+static int emit_pair_csr(PairCsr<T>& pc, int64_t na, int64_t* ptr, int32_t* idx, T* val, int64_t capacity,
+                         int64_t* nnz, int mem) {
+  *nnz = pc.nnz;
+  if (pc.nnz >= (1LL << 31))
+    return fail(SS_EUNSUPPORTED, "%s: nnz = %lld >= 2^31 (use the dense-similarity graph)", pc.what,
+                (long long)pc.nnz);
+  if (idx && capacity < pc.nnz)
+    return fail(SS_EINVAL, "%s: capacity %lld < nnz %lld", pc.what, (long long)capacity, (long long)pc.nnz);
+  hipStream_t st = ctx().stream;
+  const hipMemcpyKind back = mem == SS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  SS_HIP(hipMemcpyAsync(ptr, pc.ptr.p, (size_t)(na + 1) * sizeof(int64_t), back, st));
+  if (idx && pc.nnz > 0) {
+    if (mem == SS_MEM_DEVICE) {
+      SS_TRY(pc.fill(idx, val, nullptr));
+    } else {
+      DevBuf<int> di;
+      DevBuf<T> dv;
+      SS_TRY(di.alloc(pc.nnz));
+      if (val) SS_TRY(dv.alloc(pc.nnz));
+      SS_TRY(pc.fill(di.p, val ? dv.p : nullptr, nullptr));
+      SS_HIP(hipMemcpyAsync(idx, di.p, (size_t)pc.nnz * sizeof(int), back, st));
+      if (val) SS_HIP(hipMemcpyAsync(val, dv.p, (size_t)pc.nnz * sizeof(T), back, st));
+      SS_HIP(hipStreamSynchronize(st));
+    }
+  }
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
+}
+
+// construct(y, X, ...) from two fused producers: Xs = count_s() (ns x ns, tag_s), Xq = count_q() (nq x ns, tag_q, noted
+// when nq > 0), features named after the sources; Y and the finalisation as for the other graphs
+template <class T, class Prod, class CountS, class CountQ>
+static int graph_from_producers(int64_t nq, int64_t ns, int64_t nt, CountS count_s, CountQ count_q, const char* tag_s,
+                                const char* tag_q, const int64_t* y_ptr, const int32_t* y_idx, const T* y_val,
+                                int index_base, int mem, ss_graph** out) {
+  GraphBox<T>* box = new (std::nothrow) GraphBox<T>();
+  if (!box) return fail(SS_ENOMEM, "host allocation failed");
+  box->dtype = (int)sizeof(T);
+  Graph<T>& g = box->g;
+  g.nq = nq; g.ns = ns; g.nf = ns; g.nt = nt;
+  int rc = SS_OK;
+  {
+    Prod ps;
+    rc = count_s(ps);
+    if (rc == SS_OK) rc = ps.to_dev_csr(g.Xs);
+    path_add(tag_s);
+  }
+  if (rc == SS_OK) {
+    Prod pq;
+    rc = count_q(pq);
+    if (rc == SS_OK) rc = pq.to_dev_csr(g.Xq);
+    if (nq > 0) path_add(tag_q);
+  }
+  if (rc == SS_OK) rc = csr_from_user<T>(ns, nt, y_ptr, y_idx, y_val, index_base, mem, g.Ys);
+  if (rc == SS_OK) rc = graph_finalize<T>(g);
+  if (rc != SS_OK) { delete box; return rc; }
+  *out = reinterpret_cast<ss_graph*>(box);
+  return SS_OK;
+}
+
 template <class T>
 static int tanimoto_csr_impl(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords, T alpha,
                              int weighted, int64_t* ptr, int32_t* idx, T* val, int64_t capacity, int64_t* nnz,
@@ -403,30 +466,7 @@ static int tanimoto_csr_impl(const uint64_t* Fa, int64_t na, const uint64_t* Fb,
   TanimotoCsr<T> tc;
   SS_TRY(tc.count(da, na, sym ? nullptr : db, nb, nwords, alpha, weighted != 0));
   path_add(sym ? "tanimoto_csr_sym" : "tanimoto_csr_cross");
-  *nnz = tc.nnz;
-  if (tc.nnz >= (1LL << 31))
-    return fail(SS_EUNSUPPORTED, "tanimoto: nnz = %lld >= 2^31 (use the dense-similarity graph)", (long long)tc.nnz);
-  if (idx && capacity < tc.nnz)
-    return fail(SS_EINVAL, "tanimoto: capacity %lld < nnz %lld", (long long)capacity, (long long)tc.nnz);
-  hipStream_t st = ctx().stream;
-  const hipMemcpyKind back = mem == SS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  SS_HIP(hipMemcpyAsync(ptr, tc.ptr.p, (size_t)(na + 1) * sizeof(int64_t), back, st));
-  if (idx && tc.nnz > 0) {
-    if (mem == SS_MEM_DEVICE) {
-      SS_TRY(tc.fill(idx, val, nullptr));
-    } else {
-      DevBuf<int> di;
-      DevBuf<T> dv;
-      SS_TRY(di.alloc(tc.nnz));
-      if (val) SS_TRY(dv.alloc(tc.nnz));
-      SS_TRY(tc.fill(di.p, val ? dv.p : nullptr, nullptr));
-      SS_HIP(hipMemcpyAsync(idx, di.p, (size_t)tc.nnz * sizeof(int), back, st));
-      if (val) SS_HIP(hipMemcpyAsync(val, dv.p, (size_t)tc.nnz * sizeof(T), back, st));
-      SS_HIP(hipStreamSynchronize(st));
-    }
-  }
-  SS_HIP(hipStreamSynchronize(st));
-  return SS_OK;
+  return emit_pair_csr<T>(tc, na, ptr, idx, val, capacity, nnz, mem);
 }
 
 // construct(y, X, ...) with X = featurize(Tanimoto(F), alpha, weighted): Xs = cut(T(Fs, Fs)), Xq = cut(T(Fq, Fs)),
@@ -450,29 +490,93 @@ static int graph_create_fingerprint_impl(int64_t nq, int64_t ns, int64_t nt, int
   const uint64_t *dq = nullptr, *ds = nullptr;
   SS_TRY(stage_fingerprints(Fs, ns, nwords, mem, bs, &ds));
   SS_TRY(stage_fingerprints(Fq, nq, nwords, mem, bq, &dq));
-  GraphBox<T>* box = new (std::nothrow) GraphBox<T>();
-  if (!box) return fail(SS_ENOMEM, "host allocation failed");
-  box->dtype = (int)sizeof(T);
-  Graph<T>& g = box->g;
-  g.nq = nq; g.ns = ns; g.nf = ns; g.nt = nt;
-  int rc = SS_OK;
-  {
-    TanimotoCsr<T> ts;
-    rc = ts.count(ds, ns, nullptr, ns, nwords, alpha, weighted != 0);
-    if (rc == SS_OK) rc = ts.to_dev_csr(g.Xs);
-    path_add("tanimoto_csr_sym");
-  }
-  if (rc == SS_OK) {
-    TanimotoCsr<T> tq;
-    rc = tq.count(dq, nq, ds, ns, nwords, alpha, weighted != 0);
-    if (rc == SS_OK) rc = tq.to_dev_csr(g.Xq);
-    if (nq > 0) path_add("tanimoto_csr_cross");
-  }
-  if (rc == SS_OK) rc = csr_from_user<T>(ns, nt, y_ptr, y_idx, y_val, index_base, mem, g.Ys);
-  if (rc == SS_OK) rc = graph_finalize<T>(g);
-  if (rc != SS_OK) { delete box; return rc; }
-  *out = reinterpret_cast<ss_graph*>(box);
+  const bool wgt = weighted != 0;
+  return graph_from_producers<T, TanimotoCsr<T>>(
+      nq, ns, nt, [&](TanimotoCsr<T>& p) { return p.count(ds, ns, nullptr, ns, nwords, alpha, wgt); },
+      [&](TanimotoCsr<T>& p) { return p.count(dq, nq, ds, ns, nwords, alpha, wgt); }, "tanimoto_csr_sym",
+      "tanimoto_csr_cross", y_ptr, y_idx, y_val, index_base, mem, out);
+}
+
+// ------------------------------------------------------- real-valued features -> thresholded weighted Jaccard CSR
+static int check_features(const char* what, const void* F, int64_t n, int64_t ld, int64_t d) {
+  if (n < 0) return fail(SS_EINVAL, "%s: negative row count", what);
+  if (n >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "%s: %lld rows (>= 2^31)", what, (long long)n);
+  if (ld < n) return fail(SS_EINVAL, "%s: leading dimension %lld < %lld rows", what, (long long)ld, (long long)n);
+  if (n > 0 && d > 0 && !F) return fail(SS_EINVAL, "%s is NULL", what);
   return SS_OK;
+}
+// features on the device: the caller's buffer (SS_MEM_DEVICE) or a staged copy with ld = n
+template <class T>
+static int stage_features(const T* F, int64_t n, int64_t ld, int64_t d, int mem, DevBuf<T>& buf, const T** dev,
+                          int64_t* dev_ld) {
+  if (mem == SS_MEM_DEVICE || n == 0 || d == 0) {
+    *dev = F;
+    *dev_ld = ld;
+    return SS_OK;
+  }
+  SS_TRY(buf.alloc((size_t)n * (size_t)d));
+  SS_HIP(hipMemcpy2DAsync(buf.p, n * sizeof(T), F, ld * sizeof(T), n * sizeof(T), d, hipMemcpyHostToDevice,
+                          ctx().stream));
+  *dev = buf.p;
+  *dev_ld = n;
+  return SS_OK;
+}
+
+template <class T>
+static int jaccard_csr_impl(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d,
+                            T alpha, int weighted, int64_t* ptr, int32_t* idx, T* val, int64_t capacity, int64_t* nnz,
+                            int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  path_note().clear();
+  const bool sym = (Fb == nullptr);
+  if (sym) {
+    nb = na;
+    ldb = lda;
+  }
+  if (d < 0) return fail(SS_EINVAL, "jaccard: negative feature count");
+  if (alpha != alpha) return fail(SS_EINVAL, "jaccard: alpha is NaN");
+  SS_TRY(check_features("Fa", Fa, na, lda, d));
+  if (!sym) SS_TRY(check_features("Fb", Fb, nb, ldb, d));
+  if (!ptr || !nnz) return fail(SS_EINVAL, "jaccard: ptr and nnz must not be NULL");
+  DevBuf<T> ba, bb;
+  const T *da = nullptr, *db = nullptr;
+  int64_t la = 0, lb = 0;
+  SS_TRY(stage_features(Fa, na, lda, d, mem, ba, &da, &la));
+  if (!sym) SS_TRY(stage_features(Fb, nb, ldb, d, mem, bb, &db, &lb));
+  JaccardCsr<T> jc;
+  SS_TRY(jc.count(da, na, la, sym ? nullptr : db, nb, lb, d, alpha, weighted != 0));
+  path_add(sym ? "jaccard_csr_sym" : "jaccard_csr_cross");
+  return emit_pair_csr<T>(jc, na, ptr, idx, val, capacity, nnz, mem);
+}
+
+// construct(y, X, ...) with X = featurize(J(F), alpha, weighted), J the weighted Jaccard similarity of the feature
+// rows: Xs = cut(J(Fs, Fs)), Xq = cut(J(Fq, Fs)), features named after the sources
+template <class T>
+static int graph_create_features_impl(int64_t nq, int64_t ns, int64_t nt, int64_t d, const T* Fq, int64_t ldq,
+                                      const T* Fs, int64_t lds_, const int64_t* y_ptr, const int32_t* y_idx,
+                                      const T* y_val, int index_base, T alpha, int weighted, int mem, ss_graph** out) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  if (!out) return fail(SS_EINVAL, "out handle pointer is NULL");
+  *out = nullptr;
+  path_note().clear();
+  if (nt < 0) return fail(SS_EINVAL, "negative node count");
+  if (nt >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "dimension >= 2^31");
+  if (d < 0) return fail(SS_EINVAL, "jaccard: negative feature count");
+  if (alpha != alpha) return fail(SS_EINVAL, "jaccard: alpha is NaN");
+  SS_TRY(check_features("Fq", Fq, nq, ldq, d));
+  SS_TRY(check_features("Fs", Fs, ns, lds_, d));
+  DevBuf<T> bq, bs;
+  const T *dq = nullptr, *ds = nullptr;
+  int64_t lq = 0, ls = 0;
+  SS_TRY(stage_features(Fs, ns, lds_, d, mem, bs, &ds, &ls));
+  SS_TRY(stage_features(Fq, nq, ldq, d, mem, bq, &dq, &lq));
+  const bool wgt = weighted != 0;
+  return graph_from_producers<T, JaccardCsr<T>>(
+      nq, ns, nt, [&](JaccardCsr<T>& p) { return p.count(ds, ns, ls, nullptr, ns, ls, d, alpha, wgt); },
+      [&](JaccardCsr<T>& p) { return p.count(dq, nq, lq, ds, ns, ls, d, alpha, wgt); }, "jaccard_csr_sym",
+      "jaccard_csr_cross", y_ptr, y_idx, y_val, index_base, mem, out);
 }
 
 // stage-2 operand of a graph: W = Ys' cut for the tile width of this precision
@@ -1545,6 +1649,34 @@ int ss_graph_create_fingerprint_f64(int64_t nq, int64_t ns, int64_t nt, int64_t 
   SS_API_LOCK();
   return graph_create_fingerprint_impl<double>(nq, ns, nt, nwords, Fq, Fs, y_ptr, y_idx, y_val, index_base, alpha,
                                                weighted, mem, out);
+}
+
+int ss_similarity_jaccard_csr_f32(const float* Fa, int64_t na, int64_t lda, const float* Fb, int64_t nb, int64_t ldb,
+                                  int64_t d, float alpha, int weighted, int64_t* ptr, int32_t* idx, float* val,
+                                  int64_t capacity, int64_t* nnz, int mem) {
+  SS_API_LOCK();
+  return jaccard_csr_impl<float>(Fa, na, lda, Fb, nb, ldb, d, alpha, weighted, ptr, idx, val, capacity, nnz, mem);
+}
+int ss_similarity_jaccard_csr_f64(const double* Fa, int64_t na, int64_t lda, const double* Fb, int64_t nb, int64_t ldb,
+                                  int64_t d, double alpha, int weighted, int64_t* ptr, int32_t* idx, double* val,
+                                  int64_t capacity, int64_t* nnz, int mem) {
+  SS_API_LOCK();
+  return jaccard_csr_impl<double>(Fa, na, lda, Fb, nb, ldb, d, alpha, weighted, ptr, idx, val, capacity, nnz, mem);
+}
+int ss_graph_create_features_f32(int64_t nq, int64_t ns, int64_t nt, int64_t d, const float* Fq, int64_t ldq,
+                                 const float* Fs, int64_t lds, const int64_t* y_ptr, const int32_t* y_idx,
+                                 const float* y_val, int index_base, float alpha, int weighted, int mem, ss_graph** out) {
+  SS_API_LOCK();
+  return graph_create_features_impl<float>(nq, ns, nt, d, Fq, ldq, Fs, lds, y_ptr, y_idx, y_val, index_base, alpha,
+                                           weighted, mem, out);
+}
+int ss_graph_create_features_f64(int64_t nq, int64_t ns, int64_t nt, int64_t d, const double* Fq, int64_t ldq,
+                                 const double* Fs, int64_t lds, const int64_t* y_ptr, const int32_t* y_idx,
+                                 const double* y_val, int index_base, double alpha, int weighted, int mem,
+                                 ss_graph** out) {
+  SS_API_LOCK();
+  return graph_create_features_impl<double>(nq, ns, nt, d, Fq, ldq, Fs, lds, y_ptr, y_idx, y_val, index_base, alpha,
+                                            weighted, mem, out);
 }
 
 int ss_graph_destroy(ss_graph* h) {

@@ -224,50 +224,22 @@ __global__ void __launch_bounds__(256) tanimoto_tile_kernel(
   if (nb_flag) *not_binary = 1;
 }
 
-// per row: the per-tile counts become exclusive in-row offsets; the row total goes to rowcnt
-__global__ void tanimoto_row_offsets_kernel(int* __restrict__ counts, int64_t rows, int64_t ntj, int* __restrict__ rowcnt) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= rows) return;
-  int run = 0;
-#pragma unroll 8
-  for (int64_t t = 0; t < ntj; ++t) {
-    const int c = counts[t * rows + r];
-    counts[t * rows + r] = run;
-    run += c;
-  }
-  rowcnt[r] = run;
-}
-
-__global__ void ptr_tail_kernel(const int* in, int64_t* out, int64_t n) { out[n] = n ? out[n - 1] + in[n - 1] : 0; }
-
-__global__ void ptr_narrow_kernel(const int64_t* __restrict__ in, int64_t n, int* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i <= n) out[i] = (int)in[i];
-}
-
 }  // namespace
 
 template <class T>
 int TanimotoCsr<T>::count(const uint64_t* Fa_, int64_t na_, const uint64_t* Fb_, int64_t nb_, int64_t nwords_, T alpha_,
                           bool weighted_) {
   hipStream_t st = ctx().stream;
+  what = "tanimoto";
   sym = (Fb_ == nullptr);
   Fa = Fa_;
   Fb = sym ? Fa_ : Fb_;
-  na = na_;
-  nb = sym ? na_ : nb_;
   nwords = nwords_;
   alpha = alpha_;
   weighted = weighted_;
-  nnz = 0;
-  ntj = ceil_div(nb, TILE);
+  SS_TRY(this->begin(na_, sym ? na_ : nb_, TILE));
+  if (na == 0 || nb == 0) return SS_OK;
   const int64_t nti = ceil_div(na, TILE);
-  SS_TRY(ptr.alloc(na + 1));
-  if (na == 0 || nb == 0) {
-    SS_HIP(hipMemsetAsync(ptr.p, 0, (na + 1) * sizeof(int64_t), st));
-    SS_HIP(hipStreamSynchronize(st));
-    return SS_OK;
-  }
   const int64_t nblocks = sym ? nti * (nti + 1) / 2 : nti * ntj;
   if (sym ? nblocks >= (1LL << 31) : (ntj >= (1LL << 31) || nti > 65535))
     return fail(SS_EUNSUPPORTED, "tanimoto: %lld x %lld pairs need more tiles than one launch holds", (long long)na,
@@ -292,22 +264,7 @@ int TanimotoCsr<T>::count(const uint64_t* Fa_, int64_t na_, const uint64_t* Fb_,
                        (const int64_t*)nullptr, (int*)nullptr, (T*)nullptr, (int*)nullptr);
   }
   SS_LAUNCH_CHECK();
-  DevBuf<int> rowcnt;
-  SS_TRY(rowcnt.alloc(na));
-  hipLaunchKernelGGL(tanimoto_row_offsets_kernel, dim3((unsigned)ceil_div(na, 256)), dim3(256), 0, st, counts.p, na, ntj,
-                     rowcnt.p);
-  SS_LAUNCH_CHECK();
-  // row totals are < 2^31 each; their sum is taken in 64 bits so that nnz >= 2^31 is seen rather than wrapped
-  size_t bytes = 0;
-  SS_HIP(rocprim::exclusive_scan(nullptr, bytes, rowcnt.p, ptr.p, (int64_t)0, (size_t)na, rocprim::plus<int64_t>(), st));
-  DevBuf<unsigned char> tmp;
-  SS_TRY(tmp.alloc(bytes));
-  SS_HIP(rocprim::exclusive_scan(tmp.p, bytes, rowcnt.p, ptr.p, (int64_t)0, (size_t)na, rocprim::plus<int64_t>(), st));
-  hipLaunchKernelGGL(ptr_tail_kernel, dim3(1), dim3(1), 0, st, rowcnt.p, ptr.p, na);
-  SS_LAUNCH_CHECK();
-  SS_HIP(hipMemcpyAsync(&nnz, ptr.p + na, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  SS_HIP(hipStreamSynchronize(st));  // tmp, rowcnt are freed on return
-  return SS_OK;
+  return this->scan();
 }
 
 template <class T>
@@ -333,24 +290,6 @@ int TanimotoCsr<T>::fill(int* idx, T* val, bool* binary) {
   SS_HIP(hipMemcpyAsync(&notbin, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
   SS_HIP(hipStreamSynchronize(st));
   if (binary) *binary = (notbin == 0);
-  return SS_OK;
-}
-
-template <class T>
-int TanimotoCsr<T>::to_dev_csr(DevCsr<T>& out) {
-  hipStream_t st = ctx().stream;
-  if (nnz >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "tanimoto: nnz = %lld >= 2^31", (long long)nnz);
-  out.rows = na;
-  out.cols = nb;
-  out.nnz = nnz;
-  SS_TRY(out.ptr.alloc(na + 1));
-  SS_TRY(out.idx.alloc(nnz));
-  SS_TRY(out.val.alloc(nnz));
-  hipLaunchKernelGGL(ptr_narrow_kernel, dim3((unsigned)ceil_div(na + 1, 256)), dim3(256), 0, st, ptr.p, na, out.ptr.p);
-  SS_LAUNCH_CHECK();
-  bool bin = true;
-  SS_TRY(fill(out.idx.p, out.val.p, &bin));
-  out.binary = bin;
   return SS_OK;
 }
 

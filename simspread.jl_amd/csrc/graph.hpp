@@ -269,23 +269,57 @@ int launch_unpermute(const T* in, int64_t ldin, int64_t nrows, int64_t nt, const
 template <class T>
 int launch_loo_clean_fix(const DevCsr<T>& YsT, const int* kt, int64_t i_begin, int64_t nrows, T* out, int64_t ld);
 
-// ---- fingerprint.hip: thresholded Tanimoto similarity of packed binary fingerprints as CSR (two passes: count, fill).
-// Fa (na x nwords) against Fb (nb x nwords), both device-resident uint64 rows; Fb == nullptr: Fb = Fa (symmetric).
+// ---- pair_csr.hip: the host skeleton shared by the fused thresholded-similarity producers (fingerprint.hip,
+// jaccard_csr.hip).  A producer's count pass writes the kept entries of every (column tile, row) slot into counts;
+// scan() turns them into in-row offsets and a 64-bit scan of the row totals into ptr and nnz; the producer's fill pass
+// writes every slot at ptr[i] + its offset in column order.
 template <class T>
-struct TanimotoCsr {
-  const uint64_t* Fa = nullptr;
-  const uint64_t* Fb = nullptr;
-  int64_t na = 0, nb = 0, nwords = 0;
+struct PairCsr {
+  const char* what = "";  // producer name for messages
+  int64_t na = 0, nb = 0;
   int64_t ntj = 0;      // column tiles
   int64_t nnz = 0;      // set by count(), summed in 64 bits (may be >= 2^31: the caller refuses it)
   T alpha = T(0);
   bool weighted = true, sym = false;
+  DevBuf<int> counts;   // [ntj][na] in-row offset of every (column tile, row) slot
+  DevBuf<int64_t> ptr;  // [na + 1] row pointers
+  virtual ~PairCsr() = default;
+  int begin(int64_t na, int64_t nb, int64_t tile);     // sizes, ptr (zeroed and synchronised when na or nb is 0)
+  int scan();                                          // counts -> offsets, row totals -> ptr, nnz (synchronises)
+  virtual int fill(int* idx, T* val, bool* binary) = 0;  // device idx[nnz], val[nnz] (val may be null);
+                                                         // binary: every value == 1
+  int to_dev_csr(DevCsr<T>& out);                      // fill a DevCsr (SS_EUNSUPPORTED when nnz >= 2^31)
+};
+
+// ---- fingerprint.hip: thresholded Tanimoto similarity of packed binary fingerprints as CSR (two passes: count, fill).
+// Fa (na x nwords) against Fb (nb x nwords), both device-resident uint64 rows; Fb == nullptr: Fb = Fa (symmetric).
+template <class T>
+struct TanimotoCsr : PairCsr<T> {
+  using PairCsr<T>::what, PairCsr<T>::na, PairCsr<T>::nb, PairCsr<T>::ntj, PairCsr<T>::nnz, PairCsr<T>::alpha,
+      PairCsr<T>::weighted, PairCsr<T>::sym, PairCsr<T>::counts, PairCsr<T>::ptr;
+  const uint64_t* Fa = nullptr;
+  const uint64_t* Fb = nullptr;
+  int64_t nwords = 0;
   DevBuf<int> pop_a, pop_b;  // popcount of every row
-  DevBuf<int> counts;        // [ntj][na] in-row offset of every (column tile, row) slot
-  DevBuf<int64_t> ptr;       // [na + 1] row pointers
   int count(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords, T alpha, bool weighted);
-  int fill(int* idx, T* val, bool* binary);  // device idx[nnz], val[nnz] (val may be null); binary: every value == 1
-  int to_dev_csr(DevCsr<T>& out);            // fill a DevCsr (SS_EUNSUPPORTED when nnz >= 2^31)
+  int fill(int* idx, T* val, bool* binary) override;
+};
+
+// ---- jaccard_csr.hip: thresholded weighted Jaccard (Ruzicka) similarity of real-valued feature rows as CSR, bitwise
+// what jaccard_kernel followed by the dense cutoff assembly gives.  Fa (na x d, column-major, lda >= na) against Fb
+// (nb x d, ldb >= nb), both device-resident; Fb == nullptr: Fb = Fa (symmetric).  count() refuses NaN features with
+// SS_EINVAL before anything is written.
+template <class T>
+struct JaccardCsr : PairCsr<T> {
+  using PairCsr<T>::what, PairCsr<T>::na, PairCsr<T>::nb, PairCsr<T>::ntj, PairCsr<T>::nnz, PairCsr<T>::alpha,
+      PairCsr<T>::weighted, PairCsr<T>::sym, PairCsr<T>::counts, PairCsr<T>::ptr;
+  const T* Fa = nullptr;
+  const T* Fb = nullptr;
+  int64_t lda = 0, ldb = 0, d = 0;
+  DevBuf<int> tile_nz;  // per launched tile: 1 when the count pass kept a pair in it (the fill pass skips the others)
+  int count(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d, T alpha,
+            bool weighted);
+  int fill(int* idx, T* val, bool* binary) override;
 };
 
 // ---- comm.hip: in-library score gather over RCCL (dlopen'ed), one process per GPU

@@ -1,0 +1,102 @@
+// Host skeleton of the fused thresholded-similarity producers (fingerprint.hip, jaccard_csr.hip): a producer's count
+// pass leaves the kept entries of every (column tile, row) slot in counts[jt * rows + i]; scan() turns them into
+// exclusive in-row offsets and takes a 64-bit scan of the row totals into ptr, so that nnz >= 2^31 is seen (and
+// refused by the caller) before any output exists.  Positions come from scans, never from atomics.
+#include <cstring>
+#include <hip/hip_runtime.h>
+#include <rocprim/rocprim.hpp>
+
+#include "graph.hpp"
+
+namespace ss {
+
+#define SS_LAUNCH_CHECK()                                                                              \
+  do {                                                                                                 \
+    hipError_t _e = hipGetLastError();                                                                 \
+    if (_e != hipSuccess)                                                                              \
+      return fail(SS_EHIP, "%s:%d kernel launch: %s", __FILE__, __LINE__, hipGetErrorString(_e));      \
+  } while (0)
+
+namespace {
+
+// per row: the per-tile counts become exclusive in-row offsets; the row total goes to rowcnt
+__global__ void pair_row_offsets_kernel(int* __restrict__ counts, int64_t rows, int64_t ntj, int* __restrict__ rowcnt) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= rows) return;
+  int run = 0;
+#pragma unroll 8
+  for (int64_t t = 0; t < ntj; ++t) {
+    const int c = counts[t * rows + r];
+    counts[t * rows + r] = run;
+    run += c;
+  }
+  rowcnt[r] = run;
+}
+
+__global__ void ptr_tail_kernel(const int* in, int64_t* out, int64_t n) { out[n] = n ? out[n - 1] + in[n - 1] : 0; }
+
+__global__ void ptr_narrow_kernel(const int64_t* __restrict__ in, int64_t n, int* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i <= n) out[i] = (int)in[i];
+}
+
+}  // namespace
+
+template <class T>
+int PairCsr<T>::begin(int64_t na_, int64_t nb_, int64_t tile) {
+  na = na_;
+  nb = nb_;
+  nnz = 0;
+  ntj = ceil_div(nb, tile);
+  SS_TRY(ptr.alloc(na + 1));
+  if (na == 0 || nb == 0) {
+    hipStream_t st = ctx().stream;
+    SS_HIP(hipMemsetAsync(ptr.p, 0, (na + 1) * sizeof(int64_t), st));
+    SS_HIP(hipStreamSynchronize(st));
+  }
+  return SS_OK;
+}
+
+template <class T>
+int PairCsr<T>::scan() {
+  hipStream_t st = ctx().stream;
+  DevBuf<int> rowcnt;
+  SS_TRY(rowcnt.alloc(na));
+  hipLaunchKernelGGL(pair_row_offsets_kernel, dim3((unsigned)ceil_div(na, 256)), dim3(256), 0, st, counts.p, na, ntj,
+                     rowcnt.p);
+  SS_LAUNCH_CHECK();
+  // row totals are < 2^31 each; their sum is taken in 64 bits so that nnz >= 2^31 is seen rather than wrapped
+  size_t bytes = 0;
+  SS_HIP(rocprim::exclusive_scan(nullptr, bytes, rowcnt.p, ptr.p, (int64_t)0, (size_t)na, rocprim::plus<int64_t>(), st));
+  DevBuf<unsigned char> tmp;
+  SS_TRY(tmp.alloc(bytes));
+  SS_HIP(rocprim::exclusive_scan(tmp.p, bytes, rowcnt.p, ptr.p, (int64_t)0, (size_t)na, rocprim::plus<int64_t>(), st));
+  hipLaunchKernelGGL(ptr_tail_kernel, dim3(1), dim3(1), 0, st, rowcnt.p, ptr.p, na);
+  SS_LAUNCH_CHECK();
+  SS_HIP(hipMemcpyAsync(&nnz, ptr.p + na, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));  // tmp, rowcnt are freed on return
+  return SS_OK;
+}
+
+template <class T>
+int PairCsr<T>::to_dev_csr(DevCsr<T>& out) {
+  hipStream_t st = ctx().stream;
+  if (nnz >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "%s: nnz = %lld >= 2^31", what, (long long)nnz);
+  out.rows = na;
+  out.cols = nb;
+  out.nnz = nnz;
+  SS_TRY(out.ptr.alloc(na + 1));
+  SS_TRY(out.idx.alloc(nnz));
+  SS_TRY(out.val.alloc(nnz));
+  hipLaunchKernelGGL(ptr_narrow_kernel, dim3((unsigned)ceil_div(na + 1, 256)), dim3(256), 0, st, ptr.p, na, out.ptr.p);
+  SS_LAUNCH_CHECK();
+  bool bin = true;
+  SS_TRY(fill(out.idx.p, out.val.p, &bin));
+  out.binary = bin;
+  return SS_OK;
+}
+
+template struct PairCsr<float>;
+template struct PairCsr<double>;
+
+}  // namespace ss

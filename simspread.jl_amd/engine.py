@@ -235,7 +235,6 @@ class DeviceGraph:
         CSR on the device (the dense similarity never exists).  Fq may be None (3-layer graph: predict_loo /
         predict_kfold).  Fq, Fs: uint64 numpy arrays (n, nwords) with Y a scipy matrix (ns x nt), or int64 torch CUDA
         tensors with Y = (ptr, idx, val, nt) device CSR."""
-        import scipy.sparse as sp
         lib = L.lib()
         dt = np.dtype(dtype).type
         if dt not in (np.float32, np.float64):
@@ -246,29 +245,38 @@ class DeviceGraph:
         fs, ns, nwords = _fingerprints(Fs, dev, keep)
         if Fq is not None and nwq != nwords:
             raise ValueError("Fq and Fs have different fingerprint widths")
-        if dev:
-            import torch
-            want = torch.float32 if dt == np.float32 else torch.float64
-            yp, yi, yv, nt = Y[0].to(torch.int64).contiguous(), Y[1].to(torch.int32).contiguous(), Y[2], int(Y[3])
-            yv = None if yv is None else yv.to(want).contiguous()
-            if yp.numel() != ns + 1:
-                raise AssertionError("Labels and features have different number of source nodes")
-            keep.extend([yp, yi, yv])
-            yptr, yidx, yval = yp.data_ptr(), yi.data_ptr(), (None if yv is None else yv.data_ptr())
-            mem = L.SS_MEM_DEVICE
-        else:
-            Y = sp.csr_matrix(Y)
-            if Y.shape[0] != ns:
-                raise AssertionError("Labels and features have different number of source nodes")
-            nt = Y.shape[1]
-            parts = _csr_parts(Y, dt)
-            keep.append(parts)
-            yptr, yidx, yval = _ptr(parts[0]), _ptr(parts[1]), _ptr(parts[2])
-            mem = L.SS_MEM_HOST
+        yptr, yidx, yval, nt, mem = _source_labels(Y, ns, dt, dev, keep)
         h = C.c_void_p()
         ctype = C.c_float if dt == np.float32 else C.c_double
         fn = getattr(lib, f"ss_graph_create_fingerprint_{_suffix(dt)}")
         L.check(fn(nq, ns, nt, nwords, fq, fs, yptr, yidx, yval, 0, ctype(alpha), 1 if weighted else 0, mem,
+                   C.byref(h)))
+        if dev:
+            L.check(lib.ss_synchronize())
+        del keep
+        return cls(h, dt)
+
+    @classmethod
+    def from_features(cls, Fq, Fs, Y, alpha: float, weighted: bool = True, dtype=np.float32):
+        """``construct(y, X)`` with ``X = featurize(1 .- pairwise(Jaccard(), F, dims=1), alpha, weighted)`` for
+        real-valued feature rows (the reference's tutorial, docs/src/tutorial/fishers-flowers.jl:66,95-96): Xq =
+        cut(J(Fq, Fs)), Xs = cut(J(Fs, Fs)) with J the weighted Jaccard similarity of ``jaccard_csr``, features named
+        after the sources, produced as CSR on the device (the dense similarity never exists).  Fq may be None (3-layer
+        graph: predict_loo / predict_kfold / evaluate_loo).  Fq, Fs: (n, d) numpy arrays with Y a scipy matrix (ns x
+        nt), or float CUDA tensors of the graph's dtype with Y = (ptr, idx, val, nt) device CSR."""
+        dt = _feature_dtype(dtype)
+        dev = _is_torch(Fs)
+        keep = []
+        fq, nq, dq, ldq = _features(Fq, dt, dev, keep)
+        fs, ns, d, lds = _features(Fs, dt, dev, keep)
+        if Fq is not None and dq != d:
+            raise ValueError("Fq and Fs have different numbers of features")
+        yptr, yidx, yval, nt, mem = _source_labels(Y, ns, dt, dev, keep)
+        lib = L.lib()
+        h = C.c_void_p()
+        ctype = C.c_float if dt == np.float32 else C.c_double
+        fn = getattr(lib, f"ss_graph_create_features_{_suffix(dt)}")
+        L.check(fn(nq, ns, nt, d, fq, ldq, fs, lds, yptr, yidx, yval, 0, ctype(alpha), 1 if weighted else 0, mem,
                    C.byref(h)))
         if dev:
             L.check(lib.ss_synchronize())
@@ -373,6 +381,27 @@ class DeviceGraph:
             self.close()
         except Exception:
             pass
+
+
+def _source_labels(Y, ns, dt, dev, keep):
+    """(ptr, idx, val, nt, mem) of the source labels of a graph built from raw data: a scipy matrix (ns x nt) on the
+    host, or (ptr, idx, val, nt) device CSR tensors (converted to the ABI's types and kept alive in ``keep``)."""
+    if dev:
+        import torch
+        want = torch.float32 if dt == np.float32 else torch.float64
+        yp, yi, yv, nt = Y[0].to(torch.int64).contiguous(), Y[1].to(torch.int32).contiguous(), Y[2], int(Y[3])
+        yv = None if yv is None else yv.to(want).contiguous()
+        if yp.numel() != ns + 1:
+            raise AssertionError("Labels and features have different number of source nodes")
+        keep.extend([yp, yi, yv])
+        return yp.data_ptr(), yi.data_ptr(), (None if yv is None else yv.data_ptr()), nt, L.SS_MEM_DEVICE
+    import scipy.sparse as sp
+    Y = sp.csr_matrix(Y)
+    if Y.shape[0] != ns:
+        raise AssertionError("Labels and features have different number of source nodes")
+    parts = _csr_parts(Y, dt)
+    keep.append(parts)
+    return _ptr(parts[0]), _ptr(parts[1]), _ptr(parts[2]), Y.shape[1], L.SS_MEM_HOST
 
 
 class DeviceSpMat:
@@ -714,5 +743,84 @@ def tanimoto_csr(Fa, Fb=None, alpha=None, weighted: bool = True, dtype=np.float3
     val = np.empty(max(nnz.value, 1), dt)
     L_.check(fn(pa, na, pb, nb, nw, ctype(alpha), w, ptr.ctypes.data, idx.ctypes.data, val.ctypes.data, nnz.value,
                 C.byref(nnz), L_.SS_MEM_HOST))
+    del keep
+    return sp.csr_matrix((val[:nnz.value], idx[:nnz.value], ptr), shape=(na, nb))
+
+
+def _feature_dtype(dtype):
+    dt = np.dtype(dtype).type
+    if dt not in (np.float32, np.float64):
+        raise TypeError("dtype must be float32 or float64")
+    return dt
+
+
+def _features(F, dt, dev, keep):
+    """(pointer, rows, d, ld) of real-valued feature rows in the library's column-major layout: an (n, d) numpy array
+    (any real dtype, converted to dt) or an (n, d) CUDA tensor of dtype dt (X.t().contiguous(), no copy when X is
+    already column-major)."""
+    if F is None:
+        return None, 0, 0, 1
+    if dev:
+        import torch
+        want = torch.float32 if dt == np.float32 else torch.float64
+        if not (type(F).__module__.startswith("torch") and F.is_cuda and F.ndim == 2):
+            raise TypeError("device features must be (n, d) CUDA tensors")
+        if F.dtype != want:
+            raise TypeError(f"device features must be {want} (the graph's dtype), got {F.dtype}")
+        t = F.t().contiguous()                    # column-major n x d
+        keep.append(t)
+        return t.data_ptr(), F.shape[0], F.shape[1], max(F.shape[0], 1)
+    if type(F).__module__.startswith("torch"):
+        raise TypeError("features must all live on the host (numpy) or all on the device (CUDA tensors)")
+    a = np.asarray(F)
+    if a.ndim != 2:
+        raise ValueError("features must be an (n, d) matrix")
+    if a.dtype.kind not in "fiu":
+        raise TypeError(f"features must be real numbers, got {a.dtype}")
+    a = np.asfortranarray(a, dtype=dt)
+    keep.append(a)
+    return a.ctypes.data, a.shape[0], a.shape[1], max(a.shape[0], 1)
+
+
+def jaccard_csr(Fa, Fb=None, alpha=None, weighted: bool = True, dtype=np.float32):
+    """``featurize(1 .- pairwise(Jaccard(), X, dims=1), alpha, weighted)`` for real-valued feature rows, produced as CSR
+    on the device without the dense similarity: entry (i, j) = J(Fa[i], Fb[j]) = sum(min) / sum(max) (1 when both rows
+    are all zero) when it is >= alpha (1 when not weighted), bitwise what ``jaccard_similarity`` followed by the cutoff
+    gives.  Fb None: Fb = Fa.  Host input ((n, d) numpy) returns a scipy.sparse.csr_matrix; device input ((n, d) CUDA
+    tensors of dtype) returns (ptr int64, idx int32, val) tensors.  A NaN feature or alpha raises SimSpreadError."""
+    if alpha is None:
+        raise TypeError("jaccard_csr needs alpha")
+    dt = _feature_dtype(dtype)
+    dev = _is_torch(Fa)
+    keep = []
+    pa, na, d, lda = _features(Fa, dt, dev, keep)
+    pb, nb, db, ldb = _features(Fb, dt, dev, keep)
+    if Fb is None:
+        nb, db, ldb = na, d, lda
+    if db != d:
+        raise ValueError("Fa and Fb have different numbers of features")
+    fn = getattr(L_.lib(), f"ss_similarity_jaccard_csr_{_suffix(dt)}")
+    ctype = C.c_float if dt == np.float32 else C.c_double
+    nnz = C.c_int64(0)
+    w = 1 if weighted else 0
+    if dev:
+        import torch
+        ptr = torch.empty(na + 1, dtype=torch.int64, device=Fa.device)
+        L_.check(fn(pa, na, lda, pb, nb, ldb, d, ctype(alpha), w, ptr.data_ptr(), None, None, 0, C.byref(nnz),
+                    L_.SS_MEM_DEVICE))
+        idx = torch.empty(max(nnz.value, 1), dtype=torch.int32, device=Fa.device)
+        val = torch.empty(max(nnz.value, 1), dtype=torch.float32 if dt == np.float32 else torch.float64, device=Fa.device)
+        L_.check(fn(pa, na, lda, pb, nb, ldb, d, ctype(alpha), w, ptr.data_ptr(), idx.data_ptr(), val.data_ptr(),
+                    nnz.value, C.byref(nnz), L_.SS_MEM_DEVICE))
+        del keep
+        return ptr, idx[:nnz.value], val[:nnz.value]
+    import scipy.sparse as sp
+    ptr = np.zeros(na + 1, np.int64)
+    L_.check(fn(pa, na, lda, pb, nb, ldb, d, ctype(alpha), w, ptr.ctypes.data, None, None, 0, C.byref(nnz),
+                L_.SS_MEM_HOST))
+    idx = np.empty(max(nnz.value, 1), np.int32)
+    val = np.empty(max(nnz.value, 1), dt)
+    L_.check(fn(pa, na, lda, pb, nb, ldb, d, ctype(alpha), w, ptr.ctypes.data, idx.ctypes.data, val.ctypes.data,
+                nnz.value, C.byref(nnz), L_.SS_MEM_HOST))
     del keep
     return sp.csr_matrix((val[:nnz.value], idx[:nnz.value], ptr), shape=(na, nb))
