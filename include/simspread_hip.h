@@ -361,6 +361,42 @@ int ss_evaluate_loo_f32(ss_graph* g, int64_t i_begin, int64_t i_end, int clean, 
 int ss_evaluate_loo_f64(ss_graph* g, int64_t i_begin, int64_t i_end, int clean, double alpha, int L, int64_t block_rows,
                         double* out, int mem);
 
+/* Binary prediction metrics of every row of a score block over all thresholds, on the device: for each of f1score, mcc,
+ * accuracy, balancedaccuracy, recall, precision (m = 0..5, src/performance.jl:102-296) the max, mean and corrected std
+ * (s = 0..2) of its value over the row's thresholds, as maxperformance / meanperformance / meanstdperformance
+ * (src/performance.jl:420-520) give them: out[r*18 + 3*m + s].  Scores and labels are passed as for
+ * ss_rank_metrics_rows_* (row-major yhat with ld >= ncols; CSR positives sorted, unique and in range, otherwise
+ * SS_EINVAL and nothing is written; yptr[0] may exceed index_base).  Definition, row by row (n = ncols, P positives,
+ * N = n - P):
+ *   - the thresholds are the row's U distinct scores, sort(unique(yhat)); at threshold v a column is predicted positive
+ *     iff score >= v, compared in the row's own type.  clean!'s -99 is an ordinary score; -0.0 equals +0.0; scores
+ *     must not be NaN.
+ *   - each metric is evaluated in double on the integer counts (tp, fp, tn, fn) exactly as the host mirror
+ *     (simspread.jl_amd/metrics.py) writes it, mcc's four limit forms with eps = floatmin(Float64) included (they
+ *     can reach +-Inf, as on the host).  mcc's numerator tp*tn - fp*fn is formed in int64 and converted once, its
+ *     denominator as double(p_pred*n_pred) * double(p_act*n_act): bitwise the mirror's value for ncols < 1.9e8.  The
+ *     mirror (Python integers) is the definition here: Julia's own Int64 products overflow above about 110k balanced
+ *     columns.
+ *   - max; mean = sum / U; std = sqrt(sum((m - mean)^2) / (U - 1)) (StatsBase mean_and_std), NaN when U == 1.  A NaN
+ *     at any threshold makes all three NaN (recall and balancedaccuracy when P == 0, balancedaccuracy when N == 0).
+ * out (nrows x 18 doubles, row-major) lives in `mem` like the inputs and is complete on return.  nrows == 0: no-op.
+ * ncols < 1 or ncols >= 2^31: SS_EINVAL.  Bitwise repeatable, and a row's values do not depend on the path that served
+ * it.  ss_path_last: "binary_rows_lds" (ncols <= 16384: one workgroup sorts and reduces a row in LDS) or
+ * "binary_rows_large" (segmented radix sort in device scratch of at most 2^25 elements per batch). */
+int ss_binary_metrics_rows_f32(const int64_t* yptr, const int32_t* yidx, int index_base, const float* yhat,
+                               int64_t nrows, int64_t ncols, int64_t ld, double* out, int mem);
+int ss_binary_metrics_rows_f64(const int64_t* yptr, const int32_t* yidx, int index_base, const double* yhat,
+                               int64_t nrows, int64_t ncols, int64_t ld, double* out, int mem);
+/* A leave-one-out sweep judged by the binary metrics in place: row i - i_begin of out (18 doubles as in
+ * ss_binary_metrics_rows_*) is fold i of ss_predict_loo_*(g, i_begin, i_end, clean) against the graph's own labels
+ * Ys[i, :] -- bitwise what ss_predict_loo_* into a device buffer followed by ss_binary_metrics_rows_* gives, for every
+ * block_rows (0: the library's choice, about 1 GiB of scores).  Same graphs and preconditions as ss_evaluate_loo_*.
+ * out (n x 18 doubles) lives in `mem` and is complete on return. */
+int ss_evaluate_loo_binary_f32(ss_graph* g, int64_t i_begin, int64_t i_end, int clean, int64_t block_rows, double* out,
+                               int mem);
+int ss_evaluate_loo_binary_f64(ss_graph* g, int64_t i_begin, int64_t i_end, int clean, int64_t block_rows, double* out,
+                               int mem);
+
 /* -------------------------------------------------------------- raw W*R SpMM --- */
 /* The resource-spreading product F = W * R on its own (kernel unit tests and the
  * roofline benchmark; inside predict W = Ys' and R = the transfer block, src/core.jl:413).

@@ -598,6 +598,59 @@ function evaluate_loo(g::Graph{T}, i_begin::Integer, i_end::Integer; clean::Bool
     return Matrix{Float64}(out')
 end
 
+"""
+    binary_metrics_rows(y, yhat) -> Matrix{Float64} (rows x 18)
+
+Binary prediction metrics of every row of a `rows x targets` score matrix over all of the row's thresholds, on the
+device: for f1score, mcc, accuracy, balancedaccuracy, recall and precision (src/performance.jl:102-296) the max, mean
+and std over the row's distinct scores, as maxperformance / meanperformance / meanstdperformance
+(src/performance.jl:420-520) give them; column 3m + s (1-based: 3(m-1) + s) with s = max, mean, std.  A vector pair is
+one row.
+"""
+function binary_metrics_rows(y::AbstractMatrix, yhat::AbstractMatrix{T}) where {T<:Union{Float32,Float64}}
+    size(y) == size(yhat) || throw(AssertionError("Number of predictions and labels don't match"))
+    nrows, ncols = size(yhat)
+    yt = SparseMatrixCSC{Float64,Int64}(sparse(transpose(y .!= 0)))   # columns of yt = rows of y
+    dropzeros!(yt)
+    ptr = Vector{Int64}(yt.colptr)        # 1-based
+    idx = Vector{Int32}(yt.rowval)        # 1-based
+    rowmajor = Matrix{T}(transpose(yhat))
+    out = Matrix{Float64}(undef, 18, nrows)
+    rc = if T === Float32
+        ccall((:ss_binary_metrics_rows_f32, LIB), Cint,
+              (Ptr{Int64}, Ptr{Int32}, Cint, Ptr{Float32}, Int64, Int64, Int64, Ptr{Float64}, Cint),
+              ptr, idx, 1, rowmajor, nrows, ncols, ncols, out, SS_MEM_HOST)
+    else
+        ccall((:ss_binary_metrics_rows_f64, LIB), Cint,
+              (Ptr{Int64}, Ptr{Int32}, Cint, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Cint),
+              ptr, idx, 1, rowmajor, nrows, ncols, ncols, out, SS_MEM_HOST)
+    end
+    check(rc)
+    return Matrix{Float64}(out')
+end
+binary_metrics_rows(y::AbstractVector, yhat::AbstractVector) = binary_metrics_rows(reshape(y, 1, :), reshape(yhat, 1, :))
+
+"""
+    evaluate_loo_binary(g, i_begin, i_end; clean=true, block_rows=0) -> Matrix{Float64} (n x 18)
+
+The leave-one-out folds `i_begin:i_end` (1-based, inclusive) of `predict_loo` judged by the binary prediction metrics
+against the graph's own labels, without the scores leaving the device: one row of `binary_metrics_rows` per fold.
+"""
+function evaluate_loo_binary(g::Graph{T}, i_begin::Integer, i_end::Integer; clean::Bool=true,
+                             block_rows::Integer=0) where {T}
+    lo, hi = i_begin - 1, i_end
+    out = Matrix{Float64}(undef, 18, max(hi - lo, 0))
+    rc = if T === Float32
+        ccall((:ss_evaluate_loo_binary_f32, LIB), Cint, (Ptr{Cvoid}, Int64, Int64, Cint, Int64, Ptr{Float64}, Cint),
+              g.handle, lo, hi, clean ? 1 : 0, block_rows, out, SS_MEM_HOST)
+    else
+        ccall((:ss_evaluate_loo_binary_f64, LIB), Cint, (Ptr{Cvoid}, Int64, Int64, Cint, Int64, Ptr{Float64}, Cint),
+              g.handle, lo, hi, clean ? 1 : 0, block_rows, out, SS_MEM_HOST)
+    end
+    check(rc)
+    return Matrix{Float64}(out')
+end
+
 # ------------------------------------------------------------------------------------------------ raw W*R SpMM
 mutable struct SpMat{T<:Union{Float32,Float64}}
     handle::Ptr{Cvoid}

@@ -67,6 +67,8 @@ def _sigs():
     for suf in ("f32", "f64"):
         s[f"ss_rank_metrics_rows_{suf}"] = ([_vp, _vp, _int, _vp, _i64, _i64, _i64, f64, _int, _vp, _int], _int)
         s[f"ss_evaluate_loo_{suf}"] = ([_vp, _i64, _i64, _int, f64, _int, _i64, _vp, _int], _int)
+        s[f"ss_binary_metrics_rows_{suf}"] = ([_vp, _vp, _int, _vp, _i64, _i64, _i64, _vp, _int], _int)
+        s[f"ss_evaluate_loo_binary_{suf}"] = ([_vp, _i64, _i64, _int, _i64, _vp, _int], _int)
     s["ss_graph_create_similarity_f32"] = ([_i64] * 3 + [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _int, f32, _int, _int, _vp], _int)
     s["ss_graph_create_similarity_f64"] = ([_i64] * 3 + [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _int, f64, _int, _int, _vp], _int)
     for suf, ft in (("f32", f32), ("f64", f64)):

@@ -956,6 +956,132 @@ static int evaluate_loo_impl(ss_graph* h, int64_t i_begin, int64_t i_end, int cl
   return SS_OK;
 }
 
+// per-row binary prediction metrics (binary_rows.hip): 18 doubles per row
+static int check_binary_rows_shape(int64_t ncols) {
+  if (ncols < 1 || ncols >= (1LL << 31))
+    return fail(SS_EINVAL, "binary metrics rows: ncols = %lld outside [1, 2^31)", (long long)ncols);
+  return SS_OK;
+}
+
+template <class T>
+static int binary_rows_impl(const int64_t* yptr, const int32_t* yidx, int base, const T* yhat, int64_t nrows,
+                            int64_t ncols, int64_t ld, double* out, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  if (base != 0 && base != 1) return fail(SS_EINVAL, "index_base must be 0 or 1");
+  if (nrows < 0) return fail(SS_EINVAL, "binary metrics rows: negative row count");
+  if (nrows == 0) return SS_OK;
+  SS_TRY(check_binary_rows_shape(ncols));
+  if (ld < ncols)
+    return fail(SS_EINVAL, "binary metrics rows: leading dimension %lld < %lld", (long long)ld, (long long)ncols);
+  if (!yptr || !yhat || !out) return fail(SS_EINVAL, "binary metrics rows: NULL buffer");
+  hipStream_t st = ctx().stream;
+  std::vector<int64_t> hp((size_t)nrows + 1);
+  if (mem == SS_MEM_HOST) memcpy(hp.data(), yptr, hp.size() * sizeof(int64_t));
+  else {
+    SS_HIP(hipMemcpyAsync(hp.data(), yptr, hp.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    SS_HIP(hipStreamSynchronize(st));
+  }
+  if (hp[0] < base) return fail(SS_EINVAL, "binary metrics rows: yptr[0] = %lld < index_base", (long long)hp[0]);
+  for (int64_t r = 0; r < nrows; ++r)
+    if (hp[r + 1] < hp[r] || hp[r + 1] - hp[r] > ncols)
+      return fail(SS_EINVAL, "binary metrics rows: row %lld has %lld labels (ncols %lld)", (long long)r,
+                  (long long)(hp[r + 1] - hp[r]), (long long)ncols);
+  const int64_t nnz = hp[nrows] - hp[0];
+  if (nnz > 0 && !yidx) return fail(SS_EINVAL, "binary metrics rows: NULL label index buffer");
+  timing_begin_call();
+  const int64_t* dptr = yptr;
+  const int* didx = yidx;
+  const T* dyhat = yhat;
+  int64_t dld = ld, shift = base;
+  double* dout = out;
+  DevBuf<int64_t> bptr;
+  DevBuf<int> bidx;
+  DevBuf<T> bhat;
+  DevBuf<double> bout;
+  if (mem == SS_MEM_HOST) {
+    // the label slice this call reads, rebased to its first entry
+    SS_TRY(bptr.alloc((size_t)nrows + 1));
+    SS_TRY(bidx.alloc((size_t)nnz));
+    SS_TRY(bhat.alloc((size_t)nrows * ncols));
+    SS_TRY(bout.alloc((size_t)nrows * 18));
+    SS_TRY(upload<int64_t>(bptr.p, hp.data(), (size_t)nrows + 1, SS_MEM_HOST));
+    SS_TRY(upload<int>(bidx.p, yidx + (hp[0] - base), (size_t)nnz, SS_MEM_HOST));
+    SS_HIP(hipMemcpy2DAsync(bhat.p, ncols * sizeof(T), yhat, ld * sizeof(T), ncols * sizeof(T), nrows,
+                            hipMemcpyHostToDevice, st));
+    dptr = bptr.p;
+    didx = bidx.p;
+    dyhat = bhat.p;
+    dld = ncols;
+    shift = hp[0];
+    dout = bout.p;
+  }
+  // nothing is written before the labels have passed the check
+  SS_TRY(launch_rank_rows_validate<int64_t>(dptr, shift, didx, base, nrows, ncols));
+  hipEvent_t e_begin, e_end;
+  SS_TRY(timing_mark(&e_begin));
+  SS_TRY((launch_binary_rows<T, int64_t>(dptr, shift, didx, base, dyhat, nrows, ncols, dld, dout)));
+  SS_TRY(timing_mark(&e_end));
+  timing_span(ST_TOTAL, e_begin, e_end);
+  if (mem == SS_MEM_HOST)
+    SS_HIP(hipMemcpyAsync(out, bout.p, (size_t)nrows * 18 * sizeof(double), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
+}
+
+// leave-one-out folds judged by the binary metrics where they are produced (as evaluate_loo_impl)
+template <class T>
+static int evaluate_loo_binary_impl(ss_graph* h, int64_t i_begin, int64_t i_end, int clean, int64_t block_rows,
+                                    double* out, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  Graph<T>* gp = nullptr;
+  SS_TRY(graph_check<T>(h, &gp));
+  Graph<T>& g = *gp;
+  if (g.general || (!g.dense.on && g.nq != 0) || g.ns != g.nf)
+    return fail(SS_EINVAL, "leave-one-out needs a graph with nq == 0 and ns == nf (feature j named after source j)");
+  if (i_begin < 0 || i_end < i_begin || i_end > g.ns)
+    return fail(SS_EINVAL, "row range [%lld,%lld) outside 0..%lld", (long long)i_begin, (long long)i_end,
+                (long long)g.ns);
+  if (block_rows < 0) return fail(SS_EINVAL, "evaluate_loo_binary: block_rows must be >= 0");
+  const int64_t nrows = i_end - i_begin, nt = g.nt;
+  if (nrows == 0) return SS_OK;
+  SS_TRY(check_binary_rows_shape(nt));
+  if (!out) return fail(SS_EINVAL, "output buffer is NULL");
+  hipStream_t st = ctx().stream;
+  int64_t rb = block_rows;
+  if (rb == 0) {
+    rb = (1LL << 30) / (nt * (int64_t)sizeof(T));  // about 1 GiB of scores
+    if (rb < 1) rb = 1;
+  }
+  if (rb > nrows) rb = nrows;
+  // the labels are the graph's own Ys rows (checked sorted and unique when the graph was built)
+  DevBuf<T> scores;
+  DevBuf<double> bout;
+  SS_TRY(scores.alloc((size_t)rb * nt));
+  double* dout = out;
+  if (mem == SS_MEM_HOST) {
+    SS_TRY(bout.alloc((size_t)nrows * 18));
+    dout = bout.p;
+  }
+  timing_begin_call();
+  hipEvent_t e_begin, e_end;
+  SS_TRY(timing_mark(&e_begin));
+  for (int64_t r0 = 0; r0 < nrows; r0 += rb) {
+    const int64_t nb = nrows - r0 < rb ? nrows - r0 : rb;
+    SS_TRY(predict_rows_device<T>(g, 2, i_begin + r0, i_begin + r0 + nb, clean, scores.p, nt));
+    StageTimer t3(ST_EPILOGUE);
+    SS_TRY((launch_binary_rows<T, int>(g.Ys.ptr.p + i_begin + r0, 0, g.Ys.idx.p, 0, scores.p, nb, nt, nt,
+                                       dout + r0 * 18)));
+  }
+  SS_TRY(timing_mark(&e_end));
+  timing_span(ST_TOTAL, e_begin, e_end);
+  if (mem == SS_MEM_HOST)
+    SS_HIP(hipMemcpyAsync(out, bout.p, (size_t)nrows * 18 * sizeof(double), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
+}
+
 // k-fold: all folds of construct(y, X, members) + predict (+ clean!) from the resident graph
 template <class T>
 static int predict_kfold_impl(ss_graph* h, const int32_t* fold_of_source, int nfolds, int clean, T* out, int64_t ld,
@@ -1400,6 +1526,9 @@ int ss_init(int device) {
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return fail(SS_ENODEV, "device %d is %s; this library carries gfx950 code objects only", device, prop.gcnArchName);
   c.num_cu = prop.multiProcessorCount;
+  // binary_rows.hip's LDS-path row limit, lowered only (tests drive both paths over the same rows with it)
+  c.binary_lds_cols = -1;
+  if (const char* e = getenv("SS_BINARY_LDS_COLS")) c.binary_lds_cols = atoi(e) < 0 ? 0 : atoi(e);
   SS_HIP(hipStreamCreateWithFlags(&c.own_stream, hipStreamNonBlocking));
   c.stream = c.own_stream;
   c.device = device;
@@ -1847,6 +1976,31 @@ int ss_evaluate_loo_f64(ss_graph* g, int64_t i_begin, int64_t i_end, int clean, 
   if (!g) return fail(SS_EINVAL, "handle is NULL");
   SS_HANDLE_LOCK(g);
   return evaluate_loo_impl<double>(g, i_begin, i_end, clean, alpha, L, block_rows, out, mem);
+}
+
+int ss_binary_metrics_rows_f32(const int64_t* yptr, const int32_t* yidx, int index_base, const float* yhat,
+                               int64_t nrows, int64_t ncols, int64_t ld, double* out, int mem) {
+  SS_API_LOCK();
+  return binary_rows_impl<float>(yptr, yidx, index_base, yhat, nrows, ncols, ld, out, mem);
+}
+int ss_binary_metrics_rows_f64(const int64_t* yptr, const int32_t* yidx, int index_base, const double* yhat,
+                               int64_t nrows, int64_t ncols, int64_t ld, double* out, int mem) {
+  SS_API_LOCK();
+  return binary_rows_impl<double>(yptr, yidx, index_base, yhat, nrows, ncols, ld, out, mem);
+}
+int ss_evaluate_loo_binary_f32(ss_graph* g, int64_t i_begin, int64_t i_end, int clean, int64_t block_rows, double* out,
+                               int mem) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  return evaluate_loo_binary_impl<float>(g, i_begin, i_end, clean, block_rows, out, mem);
+}
+int ss_evaluate_loo_binary_f64(ss_graph* g, int64_t i_begin, int64_t i_end, int clean, int64_t block_rows, double* out,
+                               int mem) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  return evaluate_loo_binary_impl<double>(g, i_begin, i_end, clean, block_rows, out, mem);
 }
 
 int ss_spmat_create_csr_f32(int64_t rows, int64_t cols, const int64_t* ptr, const int32_t* idx, const float* val,

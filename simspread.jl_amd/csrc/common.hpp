@@ -58,6 +58,7 @@ struct Ctx {
   hipStream_t own_stream = nullptr;  // created by ss_init; `stream` may point at a caller's stream instead
   int num_cu = 256;
   size_t lds_per_block = 160 * 1024;
+  int binary_lds_cols = -1;          // SS_BINARY_LDS_COLS at ss_init: lowers binary_rows.hip's LDS-path row limit
   unsigned generation = 0;           // bumped by ss_shutdown: events created before belong to a dead context
 };
 Ctx& ctx();

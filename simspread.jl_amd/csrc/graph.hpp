@@ -242,6 +242,12 @@ int launch_rank_rows_validate(const PtrT* yptr, int64_t shift, const int* yidx, 
 template <class T, class PtrT>
 int launch_rank_rows(const PtrT* yptr, int64_t shift, const int* yidx, int base, const PtrT* host_ptr, const T* yhat,
                      int64_t nrows, int64_t ncols, int64_t ld, double alpha, int L, double* out);
+// binary_rows.hip: max / mean / std over every threshold of the six binary prediction metrics, per row of a row-major
+// score block against CSR positives (device inputs and out, enqueued on the stream; out[r*18 + 3*m + s]).  Labels as
+// for launch_rank_rows, checked beforehand by launch_rank_rows_validate.
+template <class T, class PtrT>
+int launch_binary_rows(const PtrT* yptr, int64_t shift, const int* yidx, int base, const T* yhat, int64_t nrows,
+                       int64_t ncols, int64_t ld, double* out);
 // ---- dense.hip (fp32 only: fp32-input MFMA)
 int launch_transfer_dense(const DenseSim<float>& d, bool loo, const float* inv_k, const float* inv_n, const int* ks,
                           int64_t row_begin, int64_t nrows, float* out, int64_t ldo, bool source_rows = false);

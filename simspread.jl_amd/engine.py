@@ -371,6 +371,19 @@ class DeviceGraph:
                     L_.SS_MEM_HOST))
         return out
 
+    def evaluate_loo_binary(self, i_begin: int = 0, i_end: Optional[int] = None, clean: bool = False,
+                            block_rows: int = 0):
+        """The leave-one-out folds [i_begin, i_end) judged by the binary prediction metrics against the graph's own
+        labels without the scores leaving the device: row i - i_begin = binary_metrics_rows(Ys[i, :], predict_loo(i)).
+        Returns (n, 18) float64 numpy, columns BINARY_ROWS_FIELDS.  block_rows: folds per device block (0: the
+        library's choice, about 1 GiB of scores)."""
+        i_end = self.ns if i_end is None else i_end
+        n = max(i_end - i_begin, 0)
+        out = np.empty((n, len(BINARY_ROWS_FIELDS)), np.float64)
+        fn = getattr(L_.lib(), f"ss_evaluate_loo_binary_{self._suf}")
+        L_.check(fn(self._h, i_begin, i_end, 1 if clean else 0, int(block_rows), out.ctypes.data, L_.SS_MEM_HOST))
+        return out
+
     def close(self):
         if self._h is not None and self._h.value:
             L.load().ss_graph_destroy(self._h)
@@ -645,6 +658,81 @@ def rank_metrics_rows(y, yhat, alpha: float = 20.0, L: int = 20):
     L_.check(fn(hp.ctypes.data, hi.ctypes.data, 0, a.ctypes.data, nrows, ncols, ncols, float(alpha), int(L),
                 out.ctypes.data, L_.SS_MEM_HOST))
     return out
+
+
+BINARY_METRICS = ("f1score", "mcc", "accuracy", "balancedaccuracy", "recall", "precision")
+BINARY_ROWS_FIELDS = tuple(f"{m}_{s}" for m in BINARY_METRICS for s in ("max", "mean", "std"))
+
+
+def binary_metrics_rows(y, yhat):
+    """Binary prediction metrics of every row of a score block over all of the row's thresholds, on the device: for
+    f1score, mcc, accuracy, balancedaccuracy, recall and precision (src/performance.jl:102-296) the max, mean and
+    corrected std over the row's distinct scores (positive when score >= threshold), as maxperformance /
+    meanperformance / meanstdperformance (src/performance.jl:420-520) give them.  Columns in BINARY_ROWS_FIELDS.
+    `y` and `yhat` take the kinds rank_metrics_rows takes; a 1-D `y` / `yhat` is one row (the reference's pooled
+    maxperformance(vec(y), vec(yhat), f1score) on a flattened block) and gives an (18,) result.  Returns
+    (nrows, 18) float64 of the same kind as `yhat`.  Bad shapes and bad label indices raise before the device is
+    touched."""
+    torch_in = type(yhat).__module__.startswith("torch")
+    if torch_in:
+        import torch
+        one = yhat.dim() == 1
+        if one:
+            yhat = yhat.reshape(1, -1)
+        if yhat.dim() != 2 or not yhat.is_contiguous() or not yhat.is_cuda:
+            raise ValueError("yhat must be a contiguous 1-D or 2-D CUDA tensor")
+        suf = {torch.float32: "f32", torch.float64: "f64"}.get(yhat.dtype)
+        if suf is None:
+            raise TypeError("yhat must be float32 or float64")
+        nrows, ncols = (int(v) for v in yhat.shape)
+    else:
+        a = np.asarray(yhat)
+        one = a.ndim == 1
+        if one:
+            a = a.reshape(1, -1)
+        if a.ndim != 2:
+            raise ValueError("yhat must be 1-D (one row) or 2-D (rows x columns)")
+        suf = _suffix(a.dtype)
+        a = np.ascontiguousarray(a)
+        nrows, ncols = a.shape
+    if not 1 <= ncols < (1 << 31):
+        raise ValueError(f"rows of {ncols} scores: the row length must lie in [1, 2^31)")
+    if one and not isinstance(y, tuple) and not hasattr(y, "tocsr"):
+        y = np.asarray(y)
+        if y.ndim != 1:
+            raise ValueError("a 1-D yhat takes 1-D labels")
+        y = y.reshape(1, -1)
+    dev_labels = isinstance(y, tuple) and type(y[0]).__module__.startswith("torch")
+    if dev_labels:
+        import torch
+        ptr_t, idx_t = y
+        if ptr_t.dtype != torch.int64 or idx_t.dtype != torch.int32 or not (ptr_t.is_cuda and idx_t.is_cuda):
+            raise TypeError("device labels are a (ptr int64, idx int32) pair of CUDA tensors")
+        if ptr_t.numel() != nrows + 1:
+            raise ValueError(f"label row pointers have {ptr_t.numel()} entries, expected {nrows + 1}")
+        # the indices stay on the device: the library checks them there before it writes anything
+    else:
+        hp, hi = _label_csr(y, nrows, ncols)
+        _check_label_order(hp, hi, ncols)
+    if dev_labels and not torch_in:
+        raise TypeError("device labels need device scores (a CUDA tensor yhat)")
+    nf = len(BINARY_ROWS_FIELDS)
+    fn = getattr(L_.lib(), f"ss_binary_metrics_rows_{suf}")
+    if torch_in:
+        _is_torch(yhat)  # order the library after the kernels that produced the scores
+        if dev_labels:
+            ptr_d, idx_d = ptr_t.contiguous(), idx_t.contiguous()
+        else:
+            ptr_d = torch.from_numpy(hp).to(yhat.device)
+            idx_d = torch.from_numpy(hi if hi.size else np.zeros(1, np.int32)).to(yhat.device)
+        out = torch.empty((nrows, nf), dtype=torch.float64, device=yhat.device)
+        L_.check(fn(ptr_d.data_ptr(), idx_d.data_ptr(), 0, yhat.data_ptr(), nrows, ncols, ncols, out.data_ptr(),
+                    L_.SS_MEM_DEVICE))
+        return out[0] if one else out
+    out = np.empty((nrows, nf), np.float64)
+    L_.check(fn(hp.ctypes.data, hi.ctypes.data, 0, a.ctypes.data, nrows, ncols, ncols, out.ctypes.data,
+                L_.SS_MEM_HOST))
+    return out[0] if one else out
 
 
 def jaccard_similarity(X, dtype=np.float64):
