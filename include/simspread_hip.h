@@ -312,6 +312,18 @@ int ss_predict_kfold_f32(ss_graph* g, const int32_t* fold_of_source, int nfolds,
                          float* out, int64_t ld, int layout, int mem);
 int ss_predict_kfold_f64(ss_graph* g, const int32_t* fold_of_source, int nfolds, int clean,
                          double* out, int64_t ld, int layout, int mem);
+/* A row range of that sweep, so that k-fold shards across ranks like leave-one-out: row i - i_begin of out is bitwise
+ * row i of ss_predict_kfold_*(g, fold_of_source, nfolds, clean), for every range and both layouts; out is
+ * (i_end - i_begin) x nt in source order whatever the fold order.  A fold's degrees depend on all of its members, so the
+ * whole fold_of_source (ns entries, in `mem` like out) is checked before anything is written: an id outside
+ * 0..nfolds-1, nfolds < 1 or a bad range gives SS_EINVAL and out is untouched.  Only the folds with members in the
+ * range are recounted and predicted; empty folds are allowed; nfolds == 1 holds every source out (all scores 0, -99
+ * when cleaned).  i_begin == i_end: no-op after the argument checks.  Same graphs and preconditions as
+ * ss_predict_kfold_* (CSR, dense-similarity, fingerprint and feature graphs). */
+int ss_predict_kfold_rows_f32(ss_graph* g, const int32_t* fold_of_source, int nfolds, int64_t i_begin, int64_t i_end,
+                              int clean, float* out, int64_t ld, int layout, int mem);
+int ss_predict_kfold_rows_f64(ss_graph* g, const int32_t* fold_of_source, int nfolds, int64_t i_begin, int64_t i_end,
+                              int clean, double* out, int64_t ld, int layout, int mem);
 
 /* Ranked evaluation without moving the scores ("next" row of the scope table: recallatL / precisionatL,
  * src/performance.jl:308-385): for every row of a row-major score block the L best columns in the order
@@ -396,6 +408,26 @@ int ss_evaluate_loo_binary_f32(ss_graph* g, int64_t i_begin, int64_t i_end, int 
                                int mem);
 int ss_evaluate_loo_binary_f64(ss_graph* g, int64_t i_begin, int64_t i_end, int clean, int64_t block_rows, double* out,
                                int mem);
+/* A k-fold sweep evaluated in place: row i - i_begin of out (6 doubles as in ss_rank_metrics_rows_*) is source i's row
+ * of ss_predict_kfold_rows_*(g, fold_of_source, nfolds, i_begin, i_end, clean) ranked against the graph's own labels
+ * Ys[i, :] -- bitwise what ss_predict_kfold_rows_* into a device buffer followed by ss_rank_metrics_rows_* gives, for
+ * every block_rows.  The library streams blocks of block_rows members (fold order; 0: its choice, about 1 GiB of
+ * scores) through a score buffer of its own, gathers the members' label rows in the same order and writes the metric
+ * rows in source order; no score leaves the device.  fold_of_source, the range and the graphs as for
+ * ss_predict_kfold_rows_* (checked whole before anything is written); alpha, L and nt as for ss_evaluate_loo_*.
+ * i_begin == i_end: no-op after the argument checks.  out (n x 6 doubles) lives in `mem` and is complete on return.
+ * ss_path_last names the metric paths used, as for ss_evaluate_loo_*. */
+int ss_evaluate_kfold_f32(ss_graph* g, const int32_t* fold_of_source, int nfolds, int64_t i_begin, int64_t i_end,
+                          int clean, double alpha, int L, int64_t block_rows, double* out, int mem);
+int ss_evaluate_kfold_f64(ss_graph* g, const int32_t* fold_of_source, int nfolds, int64_t i_begin, int64_t i_end,
+                          int clean, double alpha, int L, int64_t block_rows, double* out, int mem);
+/* The same sweep judged by the binary metrics: row i - i_begin of out (18 doubles as in ss_binary_metrics_rows_*) --
+ * bitwise ss_predict_kfold_rows_* followed by ss_binary_metrics_rows_* against Ys[i, :], for every block_rows.  Same
+ * arguments, checks and limits as ss_evaluate_kfold_* and ss_evaluate_loo_binary_*. */
+int ss_evaluate_kfold_binary_f32(ss_graph* g, const int32_t* fold_of_source, int nfolds, int64_t i_begin, int64_t i_end,
+                                 int clean, int64_t block_rows, double* out, int mem);
+int ss_evaluate_kfold_binary_f64(ss_graph* g, const int32_t* fold_of_source, int nfolds, int64_t i_begin, int64_t i_end,
+                                 int clean, int64_t block_rows, double* out, int mem);
 
 /* -------------------------------------------------------------- raw W*R SpMM --- */
 /* The resource-spreading product F = W * R on its own (kernel unit tests and the

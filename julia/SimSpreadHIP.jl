@@ -651,6 +651,85 @@ function evaluate_loo_binary(g::Graph{T}, i_begin::Integer, i_end::Integer; clea
     return Matrix{Float64}(out')
 end
 
+"""
+    predict_kfold_rows(g, fold_of_source, i_begin, i_end; clean=true) -> Matrix{Float64} (n x nt)
+
+Rows `i_begin:i_end` (1-based, inclusive) of `predict_kfold(g, fold_of_source)`, bitwise: a k-fold sweep sharded by
+source range like `predict_loo`.  The whole assignment is checked; only the folds with members in the range are
+recounted and predicted.
+"""
+function predict_kfold_rows(g::Graph{T}, fold_of_source::AbstractVector{<:Integer}, i_begin::Integer, i_end::Integer;
+                            clean::Bool=true) where {T}
+    length(fold_of_source) == g.ns || throw(AssertionError("one fold index per source is needed"))
+    folds = Vector{Int32}(fold_of_source .- 1)
+    nfolds = Int(maximum(folds)) + 1
+    lo, hi = i_begin - 1, i_end
+    out = Matrix{T}(undef, max(hi - lo, 0), g.nt)
+    rc = if T === Float32
+        ccall((:ss_predict_kfold_rows_f32, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Int32}, Cint, Int64, Int64, Cint, Ptr{Float32}, Int64, Cint, Cint),
+              g.handle, folds, nfolds, lo, hi, clean ? 1 : 0, out, max(hi - lo, 1), SS_LAYOUT_COLMAJOR, SS_MEM_HOST)
+    else
+        ccall((:ss_predict_kfold_rows_f64, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Int32}, Cint, Int64, Int64, Cint, Ptr{Float64}, Int64, Cint, Cint),
+              g.handle, folds, nfolds, lo, hi, clean ? 1 : 0, out, max(hi - lo, 1), SS_LAYOUT_COLMAJOR, SS_MEM_HOST)
+    end
+    check(rc)
+    return Matrix{Float64}(out)
+end
+
+"""
+    evaluate_kfold(g, fold_of_source, i_begin, i_end; clean=true, alpha=20.0, L=20, block_rows=0) -> Matrix{Float64} (n x 6)
+
+The k-fold rows `i_begin:i_end` (1-based, inclusive) of `predict_kfold_rows` ranked against the graph's own labels,
+without the scores leaving the device: one row of `rank_metrics_rows` per source.
+"""
+function evaluate_kfold(g::Graph{T}, fold_of_source::AbstractVector{<:Integer}, i_begin::Integer, i_end::Integer;
+                        clean::Bool=true, alpha::Float64=20.0, L::Integer=20, block_rows::Integer=0) where {T}
+    length(fold_of_source) == g.ns || throw(AssertionError("one fold index per source is needed"))
+    folds = Vector{Int32}(fold_of_source .- 1)
+    nfolds = Int(maximum(folds)) + 1
+    lo, hi = i_begin - 1, i_end
+    out = Matrix{Float64}(undef, 6, max(hi - lo, 0))
+    rc = if T === Float32
+        ccall((:ss_evaluate_kfold_f32, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Int32}, Cint, Int64, Int64, Cint, Float64, Cint, Int64, Ptr{Float64}, Cint),
+              g.handle, folds, nfolds, lo, hi, clean ? 1 : 0, alpha, L, block_rows, out, SS_MEM_HOST)
+    else
+        ccall((:ss_evaluate_kfold_f64, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Int32}, Cint, Int64, Int64, Cint, Float64, Cint, Int64, Ptr{Float64}, Cint),
+              g.handle, folds, nfolds, lo, hi, clean ? 1 : 0, alpha, L, block_rows, out, SS_MEM_HOST)
+    end
+    check(rc)
+    return Matrix{Float64}(out')
+end
+
+"""
+    evaluate_kfold_binary(g, fold_of_source, i_begin, i_end; clean=true, block_rows=0) -> Matrix{Float64} (n x 18)
+
+The k-fold rows `i_begin:i_end` (1-based, inclusive) of `predict_kfold_rows` judged by the binary prediction metrics
+against the graph's own labels, without the scores leaving the device: one row of `binary_metrics_rows` per source.
+"""
+function evaluate_kfold_binary(g::Graph{T}, fold_of_source::AbstractVector{<:Integer}, i_begin::Integer,
+                               i_end::Integer; clean::Bool=true, block_rows::Integer=0) where {T}
+    length(fold_of_source) == g.ns || throw(AssertionError("one fold index per source is needed"))
+    folds = Vector{Int32}(fold_of_source .- 1)
+    nfolds = Int(maximum(folds)) + 1
+    lo, hi = i_begin - 1, i_end
+    out = Matrix{Float64}(undef, 18, max(hi - lo, 0))
+    rc = if T === Float32
+        ccall((:ss_evaluate_kfold_binary_f32, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Int32}, Cint, Int64, Int64, Cint, Int64, Ptr{Float64}, Cint),
+              g.handle, folds, nfolds, lo, hi, clean ? 1 : 0, block_rows, out, SS_MEM_HOST)
+    else
+        ccall((:ss_evaluate_kfold_binary_f64, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Int32}, Cint, Int64, Int64, Cint, Int64, Ptr{Float64}, Cint),
+              g.handle, folds, nfolds, lo, hi, clean ? 1 : 0, block_rows, out, SS_MEM_HOST)
+    end
+    check(rc)
+    return Matrix{Float64}(out')
+end
+
 # ------------------------------------------------------------------------------------------------ raw W*R SpMM
 mutable struct SpMat{T<:Union{Float32,Float64}}
     handle::Ptr{Cvoid}

@@ -1,6 +1,7 @@
 // extern "C" surface of libsimspread_hip.so (see include/simspread_hip.h for the contract and the
 // reference methods each entry point stands behind).  Host-side orchestration only: argument
 // checks, staging of caller buffers, the stage-1 / stage-2 launch sequence, event timing.
+#include <algorithm>
 #include <cstdlib>
 #include <mutex>
 #include <new>
@@ -1222,6 +1223,340 @@ static int predict_kfold_impl(ss_graph* h, const int32_t* fold_of_source, int nf
   return SS_OK;
 }
 
+// ------------------------------------------------------------------ k-fold row blocks
+// A fold assignment checked whole (a fold's degrees depend on all of its members, wherever the asked rows lie).  The
+// folds that have members are segments of `order` (sources by fold, source order inside a fold): segment s holds fold
+// seg_fold[s], members order[seg_start[s] .. seg_start[s + 1]).  Folds without members have no segment.
+struct KfoldPlan {
+  std::vector<int32_t> fold;
+  std::vector<int> order, seg_fold, seg_start;
+};
+
+static int kfold_plan(const int32_t* fold_of_source, int nfolds, int64_t ns, int mem, KfoldPlan& p) {
+  if (nfolds < 1) return fail(SS_EINVAL, "k-fold: nfolds = %d, must be >= 1", nfolds);
+  if (!fold_of_source) return fail(SS_EINVAL, "k-fold: fold_of_source is NULL");
+  p.fold.resize((size_t)ns);
+  if (ns > 0) {
+    if (mem == SS_MEM_HOST) memcpy(p.fold.data(), fold_of_source, (size_t)ns * sizeof(int32_t));
+    else {
+      hipStream_t st = ctx().stream;
+      SS_HIP(hipMemcpyAsync(p.fold.data(), fold_of_source, (size_t)ns * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      SS_HIP(hipStreamSynchronize(st));
+    }
+  }
+  for (int64_t i = 0; i < ns; ++i)
+    if (p.fold[i] < 0 || p.fold[i] >= nfolds)
+      return fail(SS_EINVAL, "fold_of_source[%lld] = %d outside 0..%d", (long long)i, p.fold[i], nfolds - 1);
+  p.order.resize((size_t)ns);
+  for (int64_t i = 0; i < ns; ++i) p.order[i] = (int)i;
+  std::stable_sort(p.order.begin(), p.order.end(), [&](int a, int b) { return p.fold[a] < p.fold[b]; });
+  p.seg_fold.clear();
+  p.seg_start.clear();
+  for (int64_t x = 0; x < ns; ++x)
+    if (x == 0 || p.fold[p.order[x]] != p.fold[p.order[x - 1]]) {
+      p.seg_fold.push_back(p.fold[p.order[x]]);
+      p.seg_start.push_back((int)x);
+    }
+  p.seg_start.push_back((int)ns);
+  return SS_OK;
+}
+
+// The sources [i_begin, i_end) in fold order: piece k is sel[pos[k] .. pos[k + 1]), the in-range members of segment
+// seg[k] of the plan.
+struct KfoldRange {
+  std::vector<int> sel, seg;
+  std::vector<int64_t> pos;
+};
+
+static void kfold_range(const KfoldPlan& p, int64_t i_begin, int64_t i_end, KfoldRange& r) {
+  r.sel.clear();
+  r.seg.clear();
+  r.pos.assign(1, 0);
+  for (size_t s = 0; s + 1 < p.seg_start.size(); ++s) {
+    const auto b = p.order.begin() + p.seg_start[s], e = p.order.begin() + p.seg_start[s + 1];
+    const auto lo = std::lower_bound(b, e, (int)i_begin), hi = std::lower_bound(b, e, (int)i_end);
+    if (lo == hi) continue;
+    r.sel.insert(r.sel.end(), lo, hi);
+    r.seg.push_back((int)s);
+    r.pos.push_back((int64_t)r.sel.size());
+  }
+}
+
+// device side of a k-fold call: the assignment, the selected members, their output rows and one fold's degrees
+template <class T>
+struct KfoldWork {
+  DevBuf<int> d_fold, d_order, d_sel, d_map, kf, ks, kt;
+  DevBuf<T> inv_kf, inv_ks;
+  int cur_seg = -1;  // segment whose degrees kf / ks / kt / inv_* hold
+};
+
+// map[p]: output row of the p-th selected member (its source row relative to i_begin)
+template <class T>
+static int kfold_work_init(const Graph<T>& g, const KfoldPlan& p, const KfoldRange& r, const std::vector<int>& map,
+                           KfoldWork<T>& w) {
+  hipStream_t st = ctx().stream;
+  const int64_t ns = g.ns;
+  SS_TRY(w.d_fold.alloc(ns)); SS_TRY(w.d_order.alloc(ns));
+  SS_TRY(w.d_sel.alloc(r.sel.size())); SS_TRY(w.d_map.alloc(map.size()));
+  SS_TRY(w.kf.alloc(g.nf)); SS_TRY(w.ks.alloc(ns)); SS_TRY(w.kt.alloc(g.nt));
+  SS_TRY(w.inv_kf.alloc(g.nf)); SS_TRY(w.inv_ks.alloc(ns));
+  SS_HIP(hipMemcpyAsync(w.d_fold.p, p.fold.data(), ns * sizeof(int), hipMemcpyHostToDevice, st));
+  SS_HIP(hipMemcpyAsync(w.d_order.p, p.order.data(), ns * sizeof(int), hipMemcpyHostToDevice, st));
+  if (!r.sel.empty())
+    SS_HIP(hipMemcpyAsync(w.d_sel.p, r.sel.data(), r.sel.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  if (!map.empty()) SS_HIP(hipMemcpyAsync(w.d_map.p, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  w.cur_seg = -1;
+  return SS_OK;
+}
+
+// Scores of the selected members at positions [p0, p1) (fold order), the same kernels and fold set-up as
+// predict_kfold_impl: per fold the degrees are recounted once over all of its members, then its selected members go
+// through stage 1 (gathered by member id) and stage 2 in batches bounded by transfer_batch_rows.  Position p goes to
+// row row_map[p - p0] of dst, or to row p - p0 when row_map is NULL.
+template <class T>
+static int kfold_rows_device(Graph<T>& g, KfoldWork<T>& w, const KfoldPlan& plan, const KfoldRange& rg, int64_t p0,
+                             int64_t p1, int clean, T* dst, int64_t ld, const int* row_map) {
+  hipStream_t st = ctx().stream;
+  const int64_t ns = g.ns, nt = g.nt;
+  for (size_t k = 0; k < rg.seg.size(); ++k) {
+    const int64_t a = rg.pos[k] > p0 ? rg.pos[k] : p0, b = rg.pos[k + 1] < p1 ? rg.pos[k + 1] : p1;
+    if (a >= b) continue;
+    const int s = rg.seg[k];
+    if (w.cur_seg != s) {
+      const int* all = w.d_order.p + plan.seg_start[s];
+      const int64_t nall = plan.seg_start[s + 1] - plan.seg_start[s];
+      SS_HIP(hipMemcpyAsync(w.kf.p, g.kf.p, g.nf * sizeof(int), hipMemcpyDeviceToDevice, st));
+      SS_HIP(hipMemcpyAsync(w.ks.p, g.ks.p, ns * sizeof(int), hipMemcpyDeviceToDevice, st));
+      SS_HIP(hipMemcpyAsync(w.kt.p, g.kt.p, nt * sizeof(int), hipMemcpyDeviceToDevice, st));
+      if (g.dense.on) SS_TRY(dense_fold_degrees<T>(g, all, nall, w.kf.p, w.ks.p, w.kt.p));
+      else SS_TRY(launch_fold_degrees<T>(g.Xs, g.XsT, g.Ys, all, nall, w.kf.p, w.ks.p, w.kt.p));
+      SS_TRY(launch_fold_inverse<T>(w.kf.p, w.ks.p, w.d_fold.p, plan.seg_fold[s], g.nf, ns, w.inv_kf.p, w.inv_ks.p));
+      w.cur_seg = s;
+    }
+    const int* members = w.d_sel.p + a;
+    const int64_t nm = b - a;
+    const int64_t rb = transfer_batch_rows(nm, ns, sizeof(T));
+    const size_t need = (size_t)rb * (size_t)ns;
+    if (g.Tws.n < need) SS_TRY(g.Tws.alloc(need));
+    for (int64_t r0 = 0; r0 < nm; r0 += rb) {
+      const int64_t nb = (nm - r0 < rb) ? (nm - r0) : rb;
+      const int64_t o = a - p0 + r0;  // block row of the batch's first member
+      {
+        StageTimer t1(ST_TRANSFER);
+        if (g.dense.on) {
+          if constexpr (std::is_same<T, float>::value)
+            SS_TRY(launch_transfer_dense_bf16(g.dense, false, w.inv_kf.p, w.inv_ks.p, nullptr, r0, nb, g.Tws.p, ns,
+                                              false, members));
+          else
+            SS_TRY(launch_transfer_dense_f64(g.dense, false, w.inv_kf.p, w.inv_ks.p, nullptr, r0, nb, g.Tws.p, ns,
+                                             false, members));
+        } else {
+          const DevCsr<T>* L[2] = {&g.Xs, nullptr};
+          const DevChunked<T>* M[2] = {&g.XsTc, nullptr};
+          const T* inv1[2] = {w.inv_kf.p, nullptr};
+          SS_TRY(launch_transfer<T>(1, L, inv1, M, w.inv_ks.p, r0, nb, ns, g.Tws.p, ns, members));
+        }
+        timing_count(ST_NTRANSFER, 1);
+      }
+      const int* kt_clean = clean ? w.kt.p : nullptr;
+      if (!g.W.sorted) {
+        StageTimer t2(ST_SPMM);
+        if (row_map) SS_TRY(launch_spmm_sell<T>(g.W, g.Tws.p, ns, nb, dst, ld, kt_clean, row_map + o));
+        else SS_TRY(launch_spmm_sell<T>(g.W, g.Tws.p, ns, nb, dst + o * ld, ld, kt_clean));
+        timing_count(ST_NSPMM, 1);
+      } else {
+        const size_t need_s = (size_t)rb * (size_t)g.W.vrows + (row_map ? (size_t)rb * (size_t)nt : 0);
+        if (g.Sws.n < need_s) SS_TRY(g.Sws.alloc(need_s));
+        {
+          StageTimer t2(ST_SPMM);
+          SS_TRY(launch_spmm_sell<T>(g.W, g.Tws.p, ns, nb, g.Sws.p, g.W.vrows, nullptr));
+          timing_count(ST_NSPMM, 1);
+        }
+        StageTimer t3(ST_EPILOGUE);
+        if (row_map) {
+          T* packed = g.Sws.p + (size_t)rb * (size_t)g.W.vrows;  // member-ordered rows before the scatter
+          SS_TRY(launch_unpermute<T>(g.Sws.p, g.W.vrows, nb, nt, g.W.vfirst.p, g.W.inv.p, kt_clean, packed, nt));
+          SS_TRY(launch_scatter_rows<T>(packed, nt, nb, nt, row_map + o, dst, ld));
+        } else {
+          SS_TRY(launch_unpermute<T>(g.Sws.p, g.W.vrows, nb, nt, g.W.vfirst.p, g.W.inv.p, kt_clean, dst + o * ld, ld));
+        }
+      }
+    }
+  }
+  return SS_OK;
+}
+
+template <class T>
+static int kfold_graph_check(const Graph<T>& g) {
+  if (g.general || (!g.dense.on && g.nq != 0) || g.ns != g.nf)
+    return fail(SS_EINVAL, "k-fold needs a graph with nq == 0 and ns == nf (feature j named after source j)");
+  return SS_OK;
+}
+
+static int kfold_range_check(int64_t i_begin, int64_t i_end, int64_t ns) {
+  if (i_begin < 0 || i_end < i_begin || i_end > ns)
+    return fail(SS_EINVAL, "row range [%lld,%lld) outside 0..%lld", (long long)i_begin, (long long)i_end,
+                (long long)ns);
+  return SS_OK;
+}
+
+// rows [i_begin, i_end) (source order) of predict_kfold_impl
+template <class T>
+static int predict_kfold_rows_impl(ss_graph* h, const int32_t* fold_of_source, int nfolds, int64_t i_begin,
+                                   int64_t i_end, int clean, T* out, int64_t ld, int layout, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  SS_TRY(check_layout(layout));
+  Graph<T>* gp = nullptr;
+  SS_TRY(graph_check<T>(h, &gp));
+  Graph<T>& g = *gp;
+  SS_TRY(kfold_graph_check(g));
+  SS_TRY(kfold_range_check(i_begin, i_end, g.ns));
+  KfoldPlan plan;
+  SS_TRY(kfold_plan(fold_of_source, nfolds, g.ns, mem, plan));
+  const int64_t nrows = i_end - i_begin, nt = g.nt;
+  if (nrows == 0 || nt == 0) return SS_OK;
+  if (!out) return fail(SS_EINVAL, "output buffer is NULL");
+  const int64_t need_ld = (layout == SS_LAYOUT_ROWMAJOR) ? nt : nrows;
+  if (ld < need_ld) return fail(SS_EINVAL, "leading dimension %lld < %lld", (long long)ld, (long long)need_ld);
+  hipStream_t st = ctx().stream;
+  KfoldRange rg;
+  kfold_range(plan, i_begin, i_end, rg);
+  std::vector<int> map(rg.sel.size());
+  for (size_t p = 0; p < map.size(); ++p) map[p] = (int)(rg.sel[p] - i_begin);
+  KfoldWork<T> w;
+  SS_TRY(kfold_work_init<T>(g, plan, rg, map, w));
+  SS_TRY(graph_sell(g));
+  if (!g.dense.on) SS_TRY(graph_chunked(g, false));
+
+  timing_begin_call();
+  hipEvent_t e_begin, e_end;
+  SS_TRY(timing_mark(&e_begin));
+  const bool direct = (mem == SS_MEM_DEVICE && layout == SS_LAYOUT_ROWMAJOR);
+  DevBuf<T> scores;
+  T* dev_rm = out;
+  int64_t ld_rm = ld;
+  if (!direct) {
+    SS_TRY(scores.alloc((size_t)nrows * nt));
+    dev_rm = scores.p;
+    ld_rm = nt;
+  }
+  SS_TRY(kfold_rows_device<T>(g, w, plan, rg, 0, nrows, clean, dev_rm, ld_rm, w.d_map.p));
+  DevBuf<T> cm;
+  if (layout == SS_LAYOUT_COLMAJOR) {
+    StageTimer t3(ST_EPILOGUE);
+    T* dst = out;
+    int64_t dld = ld;
+    if (mem == SS_MEM_HOST) {
+      SS_TRY(cm.alloc((size_t)nrows * nt));
+      dst = cm.p;
+      dld = nrows;
+    }
+    SS_TRY(launch_transpose<T>(dev_rm, nrows, nt, ld_rm, dst, dld));
+  }
+  SS_TRY(timing_mark(&e_end));
+  timing_span(ST_TOTAL, e_begin, e_end);
+  if (mem == SS_MEM_HOST) {
+    StageTimer t5(ST_D2H);
+    if (layout == SS_LAYOUT_ROWMAJOR)
+      SS_HIP(hipMemcpy2DAsync(out, ld * sizeof(T), dev_rm, ld_rm * sizeof(T), nt * sizeof(T), nrows,
+                              hipMemcpyDeviceToHost, st));
+    else
+      SS_HIP(hipMemcpy2DAsync(out, ld * sizeof(T), cm.p, nrows * sizeof(T), nrows * sizeof(T), nt,
+                              hipMemcpyDeviceToHost, st));
+    t5.stop();
+  }
+  // the member lists and degree buffers of the call are released on return
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
+}
+
+// k-fold rows [i_begin, i_end) judged where they are produced: blocks of block_rows members in fold order through a
+// score buffer owned by the call; labels = the members' Ys rows gathered in the same order; the metric rows are then
+// scattered to source order.  binary: 18 doubles per row (launch_binary_rows), else 6 (launch_rank_rows).
+template <class T>
+static int evaluate_kfold_impl(ss_graph* h, const int32_t* fold_of_source, int nfolds, int64_t i_begin, int64_t i_end,
+                               int clean, bool binary, double alpha, int L, int64_t block_rows, double* out, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  Graph<T>* gp = nullptr;
+  SS_TRY(graph_check<T>(h, &gp));
+  Graph<T>& g = *gp;
+  SS_TRY(kfold_graph_check(g));
+  SS_TRY(kfold_range_check(i_begin, i_end, g.ns));
+  if (block_rows < 0)
+    return fail(SS_EINVAL, "%s: block_rows must be >= 0", binary ? "evaluate_kfold_binary" : "evaluate_kfold");
+  KfoldPlan plan;
+  SS_TRY(kfold_plan(fold_of_source, nfolds, g.ns, mem, plan));
+  const int64_t nrows = i_end - i_begin, nt = g.nt;
+  if (nrows == 0) return SS_OK;
+  SS_TRY(binary ? check_binary_rows_shape(nt) : check_rank_rows_shape(nt, L, alpha));
+  if (!out) return fail(SS_EINVAL, "output buffer is NULL");
+  const int nw = binary ? 18 : 6;
+  hipStream_t st = ctx().stream;
+  int64_t rb = block_rows;
+  if (rb == 0) {
+    rb = (1LL << 30) / (nt * (int64_t)sizeof(T));  // about 1 GiB of scores
+    if (rb < 1) rb = 1;
+  }
+  if (rb > nrows) rb = nrows;
+  KfoldRange rg;
+  kfold_range(plan, i_begin, i_end, rg);
+  std::vector<int> map(rg.sel.size());
+  for (size_t p = 0; p < map.size(); ++p) map[p] = (int)(rg.sel[p] - i_begin);
+  KfoldWork<T> w;
+  SS_TRY(kfold_work_init<T>(g, plan, rg, map, w));
+  // the labels are the graph's own Ys rows (checked sorted and unique when the graph was built), gathered per block in
+  // fold order: pptr = their int64 row pointers over the whole range
+  std::vector<int> hy((size_t)nrows + 1);
+  SS_HIP(hipMemcpyAsync(hy.data(), g.Ys.ptr.p + i_begin, hy.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  std::vector<int64_t> pptr((size_t)nrows + 1, 0);
+  for (int64_t p = 0; p < nrows; ++p) pptr[p + 1] = pptr[p] + (hy[map[p] + 1] - hy[map[p]]);
+  int64_t max_lab = 1;
+  for (int64_t p0 = 0; p0 < nrows; p0 += rb) {
+    const int64_t p1 = nrows - p0 < rb ? nrows : p0 + rb;
+    if (pptr[p1] - pptr[p0] > max_lab) max_lab = pptr[p1] - pptr[p0];
+  }
+  DevBuf<int64_t> d_pptr;
+  DevBuf<int> lab;
+  DevBuf<T> scores;
+  DevBuf<double> bres, bout;
+  SS_TRY(d_pptr.alloc((size_t)nrows + 1));
+  SS_TRY(lab.alloc((size_t)max_lab));
+  SS_TRY(scores.alloc((size_t)rb * nt));
+  SS_TRY(bres.alloc((size_t)rb * nw));
+  SS_HIP(hipMemcpyAsync(d_pptr.p, pptr.data(), pptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  double* dout = out;
+  if (mem == SS_MEM_HOST) {
+    SS_TRY(bout.alloc((size_t)nrows * nw));
+    dout = bout.p;
+  }
+  SS_TRY(graph_sell(g));
+  if (!g.dense.on) SS_TRY(graph_chunked(g, false));
+  timing_begin_call();
+  hipEvent_t e_begin, e_end;
+  SS_TRY(timing_mark(&e_begin));
+  for (int64_t p0 = 0; p0 < nrows; p0 += rb) {
+    const int64_t nb = nrows - p0 < rb ? nrows - p0 : rb;
+    SS_TRY(kfold_rows_device<T>(g, w, plan, rg, p0, p0 + nb, clean, scores.p, nt, nullptr));
+    StageTimer t3(ST_EPILOGUE);
+    SS_TRY(launch_gather_labels(g.Ys.ptr.p, g.Ys.idx.p, w.d_sel.p + p0, nb, d_pptr.p + p0, pptr[p0], lab.p));
+    if (binary)
+      SS_TRY((launch_binary_rows<T, int64_t>(d_pptr.p + p0, pptr[p0], lab.p, 0, scores.p, nb, nt, nt, bres.p)));
+    else
+      SS_TRY((launch_rank_rows<T, int64_t>(d_pptr.p + p0, pptr[p0], lab.p, 0, pptr.data() + p0, scores.p, nb, nt, nt,
+                                           alpha, L, bres.p)));
+    SS_TRY(launch_scatter_rows<double>(bres.p, nw, nb, nw, w.d_map.p + p0, dout, nw));
+  }
+  SS_TRY(timing_mark(&e_end));
+  timing_span(ST_TOTAL, e_begin, e_end);
+  if (mem == SS_MEM_HOST)
+    SS_HIP(hipMemcpyAsync(out, bout.p, (size_t)nrows * nw * sizeof(double), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
+}
+
 // ------------------------------------------------------------------ raw SpMM
 template <class T>
 static int spmat_check(const void* h, SpMat<T>** out) {
@@ -1909,6 +2244,49 @@ int ss_predict_kfold_f64(ss_graph* g, const int32_t* fold_of_source, int nfolds,
   if (!g) return fail(SS_EINVAL, "handle is NULL");
   SS_HANDLE_LOCK(g);
   return predict_kfold_impl<double>(g, fold_of_source, nfolds, clean, out, ld, layout, mem);
+}
+
+int ss_predict_kfold_rows_f32(ss_graph* g, const int32_t* fold_of_source, int nfolds, int64_t i_begin, int64_t i_end,
+                              int clean, float* out, int64_t ld, int layout, int mem) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  return predict_kfold_rows_impl<float>(g, fold_of_source, nfolds, i_begin, i_end, clean, out, ld, layout, mem);
+}
+int ss_predict_kfold_rows_f64(ss_graph* g, const int32_t* fold_of_source, int nfolds, int64_t i_begin, int64_t i_end,
+                              int clean, double* out, int64_t ld, int layout, int mem) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  return predict_kfold_rows_impl<double>(g, fold_of_source, nfolds, i_begin, i_end, clean, out, ld, layout, mem);
+}
+int ss_evaluate_kfold_f32(ss_graph* g, const int32_t* fold_of_source, int nfolds, int64_t i_begin, int64_t i_end,
+                          int clean, double alpha, int L, int64_t block_rows, double* out, int mem) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  return evaluate_kfold_impl<float>(g, fold_of_source, nfolds, i_begin, i_end, clean, false, alpha, L, block_rows, out, mem);
+}
+int ss_evaluate_kfold_f64(ss_graph* g, const int32_t* fold_of_source, int nfolds, int64_t i_begin, int64_t i_end,
+                          int clean, double alpha, int L, int64_t block_rows, double* out, int mem) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  return evaluate_kfold_impl<double>(g, fold_of_source, nfolds, i_begin, i_end, clean, false, alpha, L, block_rows, out, mem);
+}
+int ss_evaluate_kfold_binary_f32(ss_graph* g, const int32_t* fold_of_source, int nfolds, int64_t i_begin,
+                                 int64_t i_end, int clean, int64_t block_rows, double* out, int mem) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  return evaluate_kfold_impl<float>(g, fold_of_source, nfolds, i_begin, i_end, clean, true, 0.0, 0, block_rows, out, mem);
+}
+int ss_evaluate_kfold_binary_f64(ss_graph* g, const int32_t* fold_of_source, int nfolds, int64_t i_begin,
+                                 int64_t i_end, int clean, int64_t block_rows, double* out, int mem) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  return evaluate_kfold_impl<double>(g, fold_of_source, nfolds, i_begin, i_end, clean, true, 0.0, 0, block_rows, out, mem);
 }
 
 int ss_topl_f32(const float* scores, int64_t nrows, int64_t ncols, int64_t ld, int L, int32_t* idx, float* val,

@@ -274,6 +274,14 @@ int launch_unpermute(const T* in, int64_t ldin, int64_t nrows, int64_t nt, const
 // clean! for leave-one-out rows: target t whose only edge belongs to query i
 template <class T>
 int launch_loo_clean_fix(const DevCsr<T>& YsT, const int* kt, int64_t i_begin, int64_t nrows, T* out, int64_t ld);
+// ---- kfold_rows.hip: k-fold row blocks come out in fold order.  scatter: row q of src -> row dst_rows[q] of dst;
+// gather_labels: the Ys rows of members[0..nrows) into out, row q at out[pptr[q] - shift ..] (pptr: int64 row pointers
+// of the gathered CSR, built on the host)
+template <class T>
+int launch_scatter_rows(const T* src, int64_t lds, int64_t nrows, int64_t ncols, const int* dst_rows, T* dst,
+                        int64_t ldd);
+int launch_gather_labels(const int* ys_ptr, const int* ys_idx, const int* members, int64_t nrows, const int64_t* pptr,
+                         int64_t shift, int* out);
 
 // ---- pair_csr.hip: the host skeleton shared by the fused thresholded-similarity producers (fingerprint.hip,
 // jaccard_csr.hip).  A producer's count pass writes the kept entries of every (column tile, row) slot into counts;

@@ -384,6 +384,68 @@ class DeviceGraph:
         L_.check(fn(self._h, i_begin, i_end, 1 if clean else 0, int(block_rows), out.ctypes.data, L_.SS_MEM_HOST))
         return out
 
+    def _folds(self, fold_of_source, nfolds):
+        """(int32 numpy fold ids, nfolds) of a k-fold assignment; shape and dtype are checked here, the ids themselves by
+        the library (an id outside 0..nfolds-1 is SS_EINVAL there, before anything is written)."""
+        if type(fold_of_source).__module__.startswith("torch"):
+            fold_of_source = fold_of_source.detach().cpu().numpy()
+        a = np.asarray(fold_of_source)
+        if a.shape != (self.ns,):
+            raise ValueError(f"fold_of_source has shape {a.shape}, expected one entry per source ({self.ns},)")
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"fold_of_source must hold integer fold ids, not {a.dtype}")
+        if a.size and (int(a.min()) < -(1 << 31) or int(a.max()) >= (1 << 31)):
+            raise ValueError("fold ids must fit in int32")
+        fold = np.ascontiguousarray(a, dtype=np.int32)
+        nfolds = (int(fold.max()) + 1 if fold.size else 1) if nfolds is None else int(nfolds)
+        return fold, nfolds
+
+    def predict_kfold_rows(self, fold_of_source, nfolds: Optional[int] = None, i_begin: int = 0,
+                           i_end: Optional[int] = None, clean: bool = False, out=None, layout: str = "row"):
+        """Rows [i_begin, i_end) (source order) of predict_kfold: row i - i_begin is bitwise row i of the whole sweep,
+        so a k-fold run shards across ranks by row range like predict_loo.  `out` as for predict_loo (numpy, or a CUDA
+        tensor filled in place; layout "row" or "col")."""
+        fold, nfolds = self._folds(fold_of_source, nfolds)
+        i_end = self.ns if i_end is None else i_end
+        keep = fold
+        if _is_torch(out):
+            import torch
+            keep = torch.from_numpy(fold).to(out.device)
+        ptr = keep.data_ptr() if _is_torch(keep) else keep.ctypes.data
+        return self._run("ss_predict_kfold_rows", (ptr, nfolds, i_begin, i_end), max(i_end - i_begin, 0), clean, out,
+                         layout)
+
+    def evaluate_kfold(self, fold_of_source, nfolds: Optional[int] = None, i_begin: int = 0,
+                       i_end: Optional[int] = None, clean: bool = False, alpha: float = 20.0, L: int = 20,
+                       block_rows: int = 0):
+        """The k-fold rows [i_begin, i_end) ranked against the graph's own labels without the scores leaving the
+        device: row i - i_begin = rank_metrics_rows(Ys[i, :], predict_kfold_rows(i)).  Returns (n, 6) float64 numpy,
+        columns RANK_ROWS_FIELDS.  block_rows: members per device block (0: the library's choice, about 1 GiB of
+        scores)."""
+        fold, nfolds = self._folds(fold_of_source, nfolds)
+        i_end = self.ns if i_end is None else i_end
+        n = max(i_end - i_begin, 0)
+        _check_L(self.nt, L)
+        out = np.empty((n, len(RANK_ROWS_FIELDS)), np.float64)
+        fn = getattr(L_.lib(), f"ss_evaluate_kfold_{self._suf}")
+        L_.check(fn(self._h, fold.ctypes.data, nfolds, i_begin, i_end, 1 if clean else 0, float(alpha), int(L),
+                    int(block_rows), out.ctypes.data, L_.SS_MEM_HOST))
+        return out
+
+    def evaluate_kfold_binary(self, fold_of_source, nfolds: Optional[int] = None, i_begin: int = 0,
+                              i_end: Optional[int] = None, clean: bool = False, block_rows: int = 0):
+        """The k-fold rows [i_begin, i_end) judged by the binary prediction metrics against the graph's own labels
+        without the scores leaving the device: row i - i_begin = binary_metrics_rows(Ys[i, :], predict_kfold_rows(i)).
+        Returns (n, 18) float64 numpy, columns BINARY_ROWS_FIELDS.  block_rows as for evaluate_kfold."""
+        fold, nfolds = self._folds(fold_of_source, nfolds)
+        i_end = self.ns if i_end is None else i_end
+        n = max(i_end - i_begin, 0)
+        out = np.empty((n, len(BINARY_ROWS_FIELDS)), np.float64)
+        fn = getattr(L_.lib(), f"ss_evaluate_kfold_binary_{self._suf}")
+        L_.check(fn(self._h, fold.ctypes.data, nfolds, i_begin, i_end, 1 if clean else 0, int(block_rows),
+                    out.ctypes.data, L_.SS_MEM_HOST))
+        return out
+
     def close(self):
         if self._h is not None and self._h.value:
             L.load().ss_graph_destroy(self._h)
