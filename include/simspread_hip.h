@@ -385,9 +385,9 @@ int ss_evaluate_loo_f64(ss_graph* g, int64_t i_begin, int64_t i_end, int clean, 
  *     must not be NaN.
  *   - each metric is evaluated in double on the integer counts (tp, fp, tn, fn) exactly as the host mirror
  *     (simspread.jl_amd/metrics.py) writes it, mcc's four limit forms with eps = floatmin(Float64) included (they
- *     can reach +-Inf, as on the host).  mcc's numerator tp*tn - fp*fn is formed in int64 and converted once, its
- *     denominator as double(p_pred*n_pred) * double(p_act*n_act): bitwise the mirror's value for ncols < 1.9e8.  The
- *     mirror (Python integers) is the definition here: Julia's own Int64 products overflow above about 110k balanced
+ *     can reach +-Inf, as on the host).  mcc's numerator tp*tn - fp*fn and its denominator p_pred*n_pred*p_act*n_act
+ *     are formed exactly (128-bit products) and each rounded to double once: bitwise the mirror's value.  The mirror
+ *     (Python integers) is the definition here: Julia's own Int64 products overflow above about 110k balanced
  *     columns.
  *   - max; mean = sum / U; std = sqrt(sum((m - mean)^2) / (U - 1)) (StatsBase mean_and_std), NaN when U == 1.  A NaN
  *     at any threshold makes all three NaN (recall and balancedaccuracy when P == 0, balancedaccuracy when N == 0).
@@ -428,6 +428,78 @@ int ss_evaluate_kfold_binary_f32(ss_graph* g, const int32_t* fold_of_source, int
                                  int clean, int64_t block_rows, double* out, int mem);
 int ss_evaluate_kfold_binary_f64(ss_graph* g, const int32_t* fold_of_source, int nfolds, int64_t i_begin, int64_t i_end,
                                  int clean, int64_t block_rows, double* out, int mem);
+
+/* ------------------------------------------------------------- pooled evaluation ---- */
+/* The reference judges a model on the whole score matrix, pooled: AuROC(Bool.(vec(ytest)), vec(yhat)), AuPRC(...)
+ * (docs/src/tutorial/getting-started.jl, fishers-flowers.jl) and maxperformance(vec(y), vec(yhat), f1score) over a
+ * cross-validation written out by `save`.  Those numbers depend only on the multiset of (score, label) pairs, so a pool
+ * keeps a table of the DISTINCT scores, each with an int64 count of positives and of negatives: exact, mergeable in any
+ * order (union of the scores, counts added), and built where the scores are produced.  A pool has one precision
+ * (_f32 / _f64): scores are compared in it; -0.0 equals +0.0; clean!'s -99 is an ordinary score; NaN is refused.
+ *
+ * Out of scope: BEDROC depends on positions inside tie groups, which Julia breaks by the column-major vec order and
+ * no sharded sweep reproduces; recall@L / precision@L are per group (= per row) in the reference and are served per
+ * row by ss_rank_metrics_rows_* / ss_evaluate_*.
+ *
+ * Memory: the table holds one entry per distinct score (fp32: 4 + 16 bytes, fp64: 8 + 16).  An fp32 table is bounded
+ * (at most about 2^31 distinct non-negative scores, plus -99 and the like); an fp64 sweep can have as many distinct
+ * scores as scores.  While adds go on the table is kept as a few levels of decreasing size (an add's table absorbs the
+ * top level while that holds at most twice its entries, so an entry is merged O(log adds) times, not once per block):
+ * the entries stored can reach about twice the distinct scores until ss_pool_metrics / ss_pool_export merge them.
+ * max_entries bounds the entries stored (0 at creation: the library's choice, half the device memory free at that
+ * moment counted twice for a merge's double buffer).
+ *
+ * Every add (add_rows, add_loo, add_kfold, merge, import) is all or nothing: a NaN score, bad labels, a handle of the
+ * other precision, bad arguments (SS_EINVAL) or more than max_entries entries stored afterwards (SS_ENOMEM) leave the
+ * pool bitwise as it was.  ss_path_last names the sort ("pool_radix_u32" / "pool_radix_u64", rocPRIM radix sort of
+ * the keys); ss_timing_last reports the call in ms[0] and the pooling's share of it in ms[3] (for add_loo / add_kfold
+ * ms[1] and ms[2] are the prediction's stages). */
+typedef struct ss_pool ss_pool; /* a pooled (score, label) table, device resident */
+int ss_pool_create_f32(int64_t max_entries, ss_pool** out);
+int ss_pool_create_f64(int64_t max_entries, ss_pool** out);
+int ss_pool_destroy(ss_pool* pool);
+/* empty the pool (max_entries stays) */
+int ss_pool_reset(ss_pool* pool);
+/* info[0] = pairs pooled, [1] = positives among them, [2] = table entries stored, [3] = max_entries */
+int ss_pool_info(const ss_pool* pool, int64_t info[4]);
+/* Pool every (score, label) pair of a row-major score block: scores and CSR positives exactly as for
+ * ss_binary_metrics_rows_* (1 <= ncols < 2^31, ld >= ncols, labels sorted, unique, in range, yptr[0] may exceed
+ * index_base; all in `mem`). */
+int ss_pool_add_rows_f32(ss_pool* pool, const int64_t* yptr, const int32_t* yidx, int index_base, const float* yhat,
+                         int64_t nrows, int64_t ncols, int64_t ld, int mem);
+int ss_pool_add_rows_f64(ss_pool* pool, const int64_t* yptr, const int32_t* yidx, int index_base, const double* yhat,
+                         int64_t nrows, int64_t ncols, int64_t ld, int mem);
+/* Pool the leave-one-out folds [i_begin, i_end) against the graph's own labels Ys[i, :]: the pairs of
+ * ss_predict_loo_*(g, i_begin, i_end, clean) -- the table is bitwise that of predict_loo into a device buffer followed
+ * by ss_pool_add_rows_*, for every block_rows.  Blocks of block_rows folds stream through a score buffer of the
+ * library's (0: its choice, about 1 GiB of scores), as in ss_evaluate_loo_*; same graphs and preconditions; no score
+ * leaves the device.  The graph and the pool have the same precision. */
+int ss_pool_add_loo_f32(ss_pool* pool, ss_graph* g, int64_t i_begin, int64_t i_end, int clean, int64_t block_rows);
+int ss_pool_add_loo_f64(ss_pool* pool, ss_graph* g, int64_t i_begin, int64_t i_end, int clean, int64_t block_rows);
+/* The same for the k-fold rows [i_begin, i_end) of ss_predict_kfold_rows_*(g, fold_of_source, nfolds, ...): arguments,
+ * checks and blocks as for ss_evaluate_kfold_* (fold_of_source in `mem`). */
+int ss_pool_add_kfold_f32(ss_pool* pool, ss_graph* g, const int32_t* fold_of_source, int nfolds, int64_t i_begin,
+                          int64_t i_end, int clean, int64_t block_rows, int mem);
+int ss_pool_add_kfold_f64(ss_pool* pool, ss_graph* g, const int32_t* fold_of_source, int nfolds, int64_t i_begin,
+                          int64_t i_end, int clean, int64_t block_rows, int mem);
+/* dst gains every pair of src (same precision; src is unchanged, dst == src doubles every count) */
+int ss_pool_merge(ss_pool* dst, const ss_pool* src);
+/* The table, scores descending: *count = its entries; keys == NULL: size query (count only).  Otherwise keys[k] (the
+ * score), npos[k], nneg[k] for k < *count, all in `mem`; cap < *count: SS_EINVAL.  (Merges the levels first.) */
+int ss_pool_export_f32(ss_pool* pool, float* keys, int64_t* npos, int64_t* nneg, int64_t cap, int64_t* count, int mem);
+int ss_pool_export_f64(ss_pool* pool, double* keys, int64_t* npos, int64_t* nneg, int64_t cap, int64_t* count, int mem);
+/* Add a table such as export writes (n entries in `mem`): scores strictly descending (after -0.0 -> +0.0) and not NaN,
+ * counts >= 0, every entry with at least one pair; otherwise SS_EINVAL.  Tables of several ranks meet this way. */
+int ss_pool_import_f32(ss_pool* pool, const float* keys, const int64_t* npos, const int64_t* nneg, int64_t n, int mem);
+int ss_pool_import_f64(ss_pool* pool, const double* keys, const int64_t* npos, const int64_t* nneg, int64_t n, int mem);
+/* The pooled numbers (host out): out[0] = AuROC, out[1] = AuPRC (the conventions of ss_rank_metrics_f32: a confusion
+ * matrix at every distinct score, trapezoid without a (0,0) point, NaN when a class is missing and there are two or
+ * more distinct scores), out[2] = validity ratio (share of non-zero scores), out[3 + 3*m + s] = max / mean / std over
+ * every threshold of f1score, mcc, accuracy, balancedaccuracy, recall, precision as ss_binary_metrics_rows_* defines
+ * them for one row (counts may pass 2^31: mcc's products are the host mirror's Python integers, rounded once).
+ * Reductions run in a fixed order on the merged table: the 21 doubles are bitwise a function of the multiset of pairs,
+ * whatever the blocks, their order, the ranks or block_rows.  An empty pool: SS_EINVAL. */
+int ss_pool_metrics(ss_pool* pool, double out[21]);
 
 /* -------------------------------------------------------------- raw W*R SpMM --- */
 /* The resource-spreading product F = W * R on its own (kernel unit tests and the

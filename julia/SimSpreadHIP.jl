@@ -790,4 +790,155 @@ function spmat_cost(w::SpMat, B::Integer)
     return bytes[], flops[]
 end
 
+# ------------------------------------------------------------------------------------------------ pooled evaluation
+"""A pooled (score, label) table on the device: AuROC(vec(y), vec(ŷ)), AuPRC and maxperformance(vec(y), vec(ŷ), f)
+of a whole cross-validation, built where the scores are produced (include/simspread_hip.h, pooled evaluation)."""
+mutable struct Pool{T<:Union{Float32,Float64}}
+    handle::Ptr{Cvoid}
+    function Pool{T}(h) where {T}
+        p = new{T}(h)
+        finalizer(destroy!, p)
+        return p
+    end
+end
+
+function destroy!(p::Pool)
+    if p.handle != C_NULL
+        ccall((:ss_pool_destroy, LIB), Cint, (Ptr{Cvoid},), p.handle)
+        p.handle = C_NULL
+    end
+    return nothing
+end
+
+"An empty pool; max_entries = 0: the library's bound from the free device memory."
+function pool(T::Type=Float64; max_entries::Integer=0)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = if T === Float32
+        ccall((:ss_pool_create_f32, LIB), Cint, (Int64, Ref{Ptr{Cvoid}}), max_entries, h)
+    else
+        ccall((:ss_pool_create_f64, LIB), Cint, (Int64, Ref{Ptr{Cvoid}}), max_entries, h)
+    end
+    check(rc)
+    return Pool{T}(h[])
+end
+
+pool_reset!(p::Pool) = (check(ccall((:ss_pool_reset, LIB), Cint, (Ptr{Cvoid},), p.handle)); p)
+
+"(pairs, positives, entries stored, max_entries)"
+function pool_info(p::Pool)
+    info = zeros(Int64, 4)
+    check(ccall((:ss_pool_info, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), p.handle, info))
+    return Tuple(info)
+end
+
+"""Pool every (ŷ[i, j], y[i, j]) pair of a score matrix.  Pooling ignores order, so the column-major matrix is passed as
+the rows of its transpose, and the CSC pattern of y (same shape) is the 1-based CSR of those rows."""
+function pool_add!(p::Pool{T}, y::SparseMatrixCSC, yhat::Matrix{T}) where {T}
+    size(y) == size(yhat) || throw(DimensionMismatch("labels and scores differ in shape"))
+    yb = dropzeros(y)
+    ptr, idx = Vector{Int64}(yb.colptr), Vector{Int32}(yb.rowval)
+    nr, nc = size(yhat, 2), size(yhat, 1)
+    rc = if T === Float32
+        ccall((:ss_pool_add_rows_f32, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Cint, Ptr{Float32}, Int64, Int64, Int64, Cint),
+              p.handle, ptr, idx, 1, yhat, nr, nc, max(nc, 1), SS_MEM_HOST)
+    else
+        ccall((:ss_pool_add_rows_f64, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Cint, Ptr{Float64}, Int64, Int64, Int64, Cint),
+              p.handle, ptr, idx, 1, yhat, nr, nc, max(nc, 1), SS_MEM_HOST)
+    end
+    check(rc)
+    return p
+end
+
+"Pool the leave-one-out folds i_begin:i_end (1-based, inclusive) against the graph's own labels."
+function pool_add_loo!(p::Pool{T}, g::Graph{T}, i_begin::Integer, i_end::Integer; clean::Bool=true,
+                       block_rows::Integer=0) where {T}
+    rc = if T === Float32
+        ccall((:ss_pool_add_loo_f32, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint, Int64),
+              p.handle, g.handle, i_begin - 1, i_end, clean ? 1 : 0, block_rows)
+    else
+        ccall((:ss_pool_add_loo_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint, Int64),
+              p.handle, g.handle, i_begin - 1, i_end, clean ? 1 : 0, block_rows)
+    end
+    check(rc)
+    return p
+end
+
+"Pool the k-fold rows i_begin:i_end (1-based, inclusive; fold ids 1..k per source)."
+function pool_add_kfold!(p::Pool{T}, g::Graph{T}, fold_of_source::AbstractVector{<:Integer}, i_begin::Integer,
+                         i_end::Integer; clean::Bool=true, block_rows::Integer=0) where {T}
+    length(fold_of_source) == g.ns || throw(AssertionError("one fold index per source is needed"))
+    folds = Vector{Int32}(fold_of_source .- 1)
+    nfolds = Int(maximum(folds)) + 1
+    rc = if T === Float32
+        ccall((:ss_pool_add_kfold_f32, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Cint, Int64, Int64, Cint, Int64, Cint),
+              p.handle, g.handle, folds, nfolds, i_begin - 1, i_end, clean ? 1 : 0, block_rows, SS_MEM_HOST)
+    else
+        ccall((:ss_pool_add_kfold_f64, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Cint, Int64, Int64, Cint, Int64, Cint),
+              p.handle, g.handle, folds, nfolds, i_begin - 1, i_end, clean ? 1 : 0, block_rows, SS_MEM_HOST)
+    end
+    check(rc)
+    return p
+end
+
+"dst gains every pair of src."
+function pool_merge!(dst::Pool{T}, src::Pool{T}) where {T}
+    check(ccall((:ss_pool_merge, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), dst.handle, src.handle))
+    return dst
+end
+
+"The table: (scores descending, positives, negatives)."
+function pool_export(p::Pool{T}) where {T}
+    n = Ref{Int64}(0)
+    if T === Float32
+        check(ccall((:ss_pool_export_f32, LIB), Cint,
+                    (Ptr{Cvoid}, Ptr{Float32}, Ptr{Int64}, Ptr{Int64}, Int64, Ref{Int64}, Cint),
+                    p.handle, C_NULL, C_NULL, C_NULL, 0, n, SS_MEM_HOST))
+    else
+        check(ccall((:ss_pool_export_f64, LIB), Cint,
+                    (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Int64, Ref{Int64}, Cint),
+                    p.handle, C_NULL, C_NULL, C_NULL, 0, n, SS_MEM_HOST))
+    end
+    keys, np, nn = Vector{T}(undef, n[]), Vector{Int64}(undef, n[]), Vector{Int64}(undef, n[])
+    rc = if T === Float32
+        ccall((:ss_pool_export_f32, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Float32}, Ptr{Int64}, Ptr{Int64}, Int64, Ref{Int64}, Cint),
+              p.handle, keys, np, nn, length(keys), n, SS_MEM_HOST)
+    else
+        ccall((:ss_pool_export_f64, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Int64, Ref{Int64}, Cint),
+              p.handle, keys, np, nn, length(keys), n, SS_MEM_HOST)
+    end
+    check(rc)
+    return keys, np, nn
+end
+
+"Add a table such as pool_export returns (another rank's, for instance)."
+function pool_import!(p::Pool{T}, keys::Vector{T}, npos::Vector{Int64}, nneg::Vector{Int64}) where {T}
+    length(keys) == length(npos) == length(nneg) || throw(DimensionMismatch("table columns differ in length"))
+    rc = if T === Float32
+        ccall((:ss_pool_import_f32, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Int64}, Ptr{Int64}, Int64, Cint),
+              p.handle, keys, npos, nneg, length(keys), SS_MEM_HOST)
+    else
+        ccall((:ss_pool_import_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Int64, Cint),
+              p.handle, keys, npos, nneg, length(keys), SS_MEM_HOST)
+    end
+    check(rc)
+    return p
+end
+
+const POOL_FIELDS = (:AuROC, :AuPRC, :validity_ratio,
+                     (Symbol(m, "_", s) for m in (:f1score, :mcc, :accuracy, :balancedaccuracy, :recall, :precision)
+                      for s in (:max, :mean, :std))...)
+
+"The 21 pooled numbers as a NamedTuple (AuROC, AuPRC, validity_ratio, then max / mean / std of the six metrics)."
+function pool_metrics(p::Pool)
+    out = zeros(Float64, 21)
+    check(ccall((:ss_pool_metrics, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), p.handle, out))
+    return NamedTuple{POOL_FIELDS}(Tuple(out))
+end
+
 end # module

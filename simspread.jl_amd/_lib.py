@@ -61,6 +61,11 @@ def _sigs():
         "ss_graph_degrees": ([_vp, _vp, _vp, _vp], _int),
         "ss_spmat_destroy": ([_vp], _int),
         "ss_spmat_cost": ([_vp, _i64, _vp, _vp], _int),
+        "ss_pool_destroy": ([_vp], _int),
+        "ss_pool_reset": ([_vp], _int),
+        "ss_pool_info": ([_vp, _vp], _int),
+        "ss_pool_merge": ([_vp, _vp], _int),
+        "ss_pool_metrics": ([_vp, _vp], _int),
     }
     s["ss_topl_f32"] = ([_vp, _i64, _i64, _i64, _int, _vp, _vp, _int], _int)
     s["ss_rank_metrics_f32"] = ([_vp, _vp, _i64, f64, _vp, _int], _int)
@@ -94,6 +99,12 @@ def _sigs():
         s[f"ss_evaluate_kfold_binary_{suf}"] = ([_vp, _vp, _int, _i64, _i64, _int, _i64, _vp, _int], _int)
         s[f"ss_spmat_create_csr_{suf}"] = ([_i64, _i64, _vp, _vp, _vp, _int, _int, _vp], _int)
         s[f"ss_spmm_{suf}"] = ([_vp, _vp, _i64, _i64, _int, _vp, _i64, _int, _int], _int)
+        s[f"ss_pool_create_{suf}"] = ([_i64, _vp], _int)
+        s[f"ss_pool_add_rows_{suf}"] = ([_vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _int], _int)
+        s[f"ss_pool_add_loo_{suf}"] = ([_vp, _vp, _i64, _i64, _int, _i64], _int)
+        s[f"ss_pool_add_kfold_{suf}"] = ([_vp, _vp, _vp, _int, _i64, _i64, _int, _i64, _int], _int)
+        s[f"ss_pool_export_{suf}"] = ([_vp, _vp, _vp, _vp, _i64, _vp, _int], _int)
+        s[f"ss_pool_import_{suf}"] = ([_vp, _vp, _vp, _vp, _i64, _int], _int)
     return s
 
 

@@ -1557,6 +1557,362 @@ static int evaluate_kfold_impl(ss_graph* h, const int32_t* fold_of_source, int n
   return SS_OK;
 }
 
+// ------------------------------------------------------------------ pooled tables (pooled.hip)
+// A pool handle: the levels of its table, its pair counts and the scratch reused across adds.  An add builds its table
+// (and merges it into copies of the levels) before anything of the pool changes: on any error the pool is as it was.
+constexpr uint32_t SS_POOL_MAGIC = 0x4c4f4f50u;
+template <class T>
+struct PoolBox : HandleHead {
+  uint32_t magic = SS_POOL_MAGIC;
+  std::vector<PoolTable<pool_key_t<T>>> lv;
+  int64_t n = 0, npos = 0, max_entries = 0;
+  PoolWork<pool_key_t<T>> w;
+};
+
+static int pool_dtype(const void* h, int* dtype) {
+  if (!h) return fail(SS_EINVAL, "pool handle is NULL");
+  const PoolBox<float>* b = reinterpret_cast<const PoolBox<float>*>(h);  // the head and the tag lie alike in both
+  if (b->magic != SS_POOL_MAGIC || (b->dtype != 4 && b->dtype != 8)) return fail(SS_EINVAL, "not a pool handle");
+  *dtype = b->dtype;
+  return SS_OK;
+}
+
+template <class T>
+static int pool_check(const void* h, PoolBox<T>** out) {
+  int dt = 0;
+  SS_TRY(pool_dtype(h, &dt));
+  if (dt != (int)sizeof(T)) return fail(SS_EINVAL, "pool handle was created with the other precision");
+  *out = const_cast<PoolBox<T>*>(reinterpret_cast<const PoolBox<T>*>(h));
+  return SS_OK;
+}
+
+template <class T>
+static int pool_create_impl(int64_t max_entries, ss_pool** out) {
+  SS_TRY(require_init());
+  if (!out) return fail(SS_EINVAL, "out handle pointer is NULL");
+  *out = nullptr;
+  if (max_entries < 0) return fail(SS_EINVAL, "pool: max_entries = %lld < 0", (long long)max_entries);
+  if (max_entries == 0) {  // half the free device memory, each entry counted twice (a merge's double buffer)
+    size_t fr = 0, tot = 0;
+    SS_HIP(hipMemGetInfo(&fr, &tot));
+    max_entries = (int64_t)(fr / 2 / (2 * (sizeof(pool_key_t<T>) + 2 * sizeof(int64_t))));
+    if (max_entries < 1) max_entries = 1;
+  }
+  PoolBox<T>* box = new (std::nothrow) PoolBox<T>();
+  if (!box) return fail(SS_ENOMEM, "host allocation failed");
+  box->dtype = (int)sizeof(T);
+  box->max_entries = max_entries;
+  *out = reinterpret_cast<ss_pool*>(box);
+  return SS_OK;
+}
+
+// one finished add (its levels) into the pool, all or nothing
+template <class T>
+static int pool_commit(PoolBox<T>& p, std::vector<PoolTable<pool_key_t<T>>>& loc, int64_t n, int64_t npos) {
+  SS_TRY(pool_consolidate(loc, p.w));
+  if (!loc.empty()) SS_TRY(pool_push(p.lv, std::move(loc[0]), 0, p.max_entries, p.w));
+  p.n += n;
+  p.npos += npos;
+  return SS_OK;
+}
+
+template <class T>
+static int pool_add_rows_impl(ss_pool* h, const int64_t* yptr, const int32_t* yidx, int base, const T* yhat,
+                              int64_t nrows, int64_t ncols, int64_t ld, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  PoolBox<T>* pp = nullptr;
+  SS_TRY(pool_check<T>(h, &pp));
+  PoolBox<T>& p = *pp;
+  if (base != 0 && base != 1) return fail(SS_EINVAL, "index_base must be 0 or 1");
+  if (nrows < 0) return fail(SS_EINVAL, "pool add rows: negative row count");
+  if (nrows == 0) return SS_OK;
+  SS_TRY(check_binary_rows_shape(ncols));
+  if (nrows > ((int64_t)1 << 62) / ncols) return fail(SS_EINVAL, "pool add rows: nrows x ncols overflows");
+  if (ld < ncols)
+    return fail(SS_EINVAL, "pool add rows: leading dimension %lld < %lld", (long long)ld, (long long)ncols);
+  if (!yptr || !yhat) return fail(SS_EINVAL, "pool add rows: NULL buffer");
+  hipStream_t st = ctx().stream;
+  std::vector<int64_t> hp((size_t)nrows + 1);
+  if (mem == SS_MEM_HOST) memcpy(hp.data(), yptr, hp.size() * sizeof(int64_t));
+  else {
+    SS_HIP(hipMemcpyAsync(hp.data(), yptr, hp.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    SS_HIP(hipStreamSynchronize(st));
+  }
+  if (hp[0] < base) return fail(SS_EINVAL, "pool add rows: yptr[0] = %lld < index_base", (long long)hp[0]);
+  for (int64_t r = 0; r < nrows; ++r)
+    if (hp[r + 1] < hp[r] || hp[r + 1] - hp[r] > ncols)
+      return fail(SS_EINVAL, "pool add rows: row %lld has %lld labels (ncols %lld)", (long long)r,
+                  (long long)(hp[r + 1] - hp[r]), (long long)ncols);
+  const int64_t nnz = hp[nrows] - hp[0];
+  if (nnz > 0 && !yidx) return fail(SS_EINVAL, "pool add rows: NULL label index buffer");
+  timing_begin_call();
+  const int64_t* dptr = yptr;
+  const int* didx = yidx;
+  const T* dyhat = yhat;
+  int64_t dld = ld, shift = base;
+  DevBuf<int64_t> bptr;
+  DevBuf<int> bidx;
+  DevBuf<T> bhat;
+  if (mem == SS_MEM_HOST) {
+    SS_TRY(bptr.alloc((size_t)nrows + 1));
+    SS_TRY(bidx.alloc((size_t)nnz));
+    SS_TRY(bhat.alloc((size_t)nrows * ncols));
+    SS_TRY(upload<int64_t>(bptr.p, hp.data(), (size_t)nrows + 1, SS_MEM_HOST));
+    SS_TRY(upload<int>(bidx.p, yidx + (hp[0] - base), (size_t)nnz, SS_MEM_HOST));
+    SS_HIP(hipMemcpy2DAsync(bhat.p, ncols * sizeof(T), yhat, ld * sizeof(T), ncols * sizeof(T), nrows,
+                            hipMemcpyHostToDevice, st));
+    dptr = bptr.p;
+    didx = bidx.p;
+    dyhat = bhat.p;
+    dld = ncols;
+    shift = hp[0];
+  }
+  SS_TRY(launch_rank_rows_validate<int64_t>(dptr, shift, didx, base, nrows, ncols));
+  hipEvent_t e_begin, e_end;
+  SS_TRY(timing_mark(&e_begin));
+  PoolTable<pool_key_t<T>> t;
+  SS_TRY((pool_block_table<T, int64_t>(dptr, shift, didx, base, nnz, dyhat, nrows, ncols, dld, p.w, t)));
+  SS_TRY(pool_push(p.lv, std::move(t), 0, p.max_entries, p.w));
+  p.n += nrows * ncols;
+  p.npos += nnz;
+  SS_TRY(timing_mark(&e_end));
+  timing_span(ST_TOTAL, e_begin, e_end);
+  timing_span(ST_EPILOGUE, e_begin, e_end);
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
+}
+
+// leave-one-out folds pooled where they are produced: the blocks and checks of evaluate_loo_binary_impl
+template <class T>
+static int pool_add_loo_impl(ss_pool* ph, ss_graph* h, int64_t i_begin, int64_t i_end, int clean, int64_t block_rows) {
+  using K = pool_key_t<T>;
+  SS_TRY(require_init());
+  PoolBox<T>* pp = nullptr;
+  SS_TRY(pool_check<T>(ph, &pp));
+  PoolBox<T>& p = *pp;
+  Graph<T>* gp = nullptr;
+  SS_TRY(graph_check<T>(h, &gp));
+  Graph<T>& g = *gp;
+  if (g.general || (!g.dense.on && g.nq != 0) || g.ns != g.nf)
+    return fail(SS_EINVAL, "leave-one-out needs a graph with nq == 0 and ns == nf (feature j named after source j)");
+  if (i_begin < 0 || i_end < i_begin || i_end > g.ns)
+    return fail(SS_EINVAL, "row range [%lld,%lld) outside 0..%lld", (long long)i_begin, (long long)i_end,
+                (long long)g.ns);
+  if (block_rows < 0) return fail(SS_EINVAL, "pool add loo: block_rows must be >= 0");
+  const int64_t nrows = i_end - i_begin, nt = g.nt;
+  if (nrows == 0) return SS_OK;
+  SS_TRY(check_binary_rows_shape(nt));
+  hipStream_t st = ctx().stream;
+  int64_t rb = block_rows;
+  if (rb == 0) {
+    rb = (1LL << 30) / (nt * (int64_t)sizeof(T));  // about 1 GiB of scores
+    if (rb < 1) rb = 1;
+  }
+  if (rb > nrows) rb = nrows;
+  std::vector<int> hp((size_t)nrows + 1);
+  SS_HIP(hipMemcpyAsync(hp.data(), g.Ys.ptr.p + i_begin, hp.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  DevBuf<T> scores;
+  SS_TRY(scores.alloc((size_t)rb * nt));
+  std::vector<PoolTable<K>> loc;
+  const int64_t other = pool_stored(p.lv);
+  timing_begin_call();
+  hipEvent_t e_begin, e_end;
+  SS_TRY(timing_mark(&e_begin));
+  for (int64_t r0 = 0; r0 < nrows; r0 += rb) {
+    const int64_t nb = nrows - r0 < rb ? nrows - r0 : rb;
+    SS_TRY(predict_rows_device<T>(g, 2, i_begin + r0, i_begin + r0 + nb, clean, scores.p, nt));
+    StageTimer t3(ST_EPILOGUE);
+    PoolTable<K> t;
+    SS_TRY((pool_block_table<T, int>(g.Ys.ptr.p + i_begin + r0, 0, g.Ys.idx.p, 0, (int64_t)(hp[r0 + nb] - hp[r0]),
+                                     scores.p, nb, nt, nt, p.w, t)));
+    SS_TRY(pool_push(loc, std::move(t), other, p.max_entries, p.w));
+  }
+  {
+    StageTimer t3(ST_EPILOGUE);
+    SS_TRY(pool_commit(p, loc, nrows * nt, (int64_t)(hp[nrows] - hp[0])));
+  }
+  SS_TRY(timing_mark(&e_end));
+  timing_span(ST_TOTAL, e_begin, e_end);
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
+}
+
+// k-fold rows pooled where they are produced: the blocks, label gather and checks of evaluate_kfold_impl (the rows'
+// order does not matter to a pool, so nothing is scattered back)
+template <class T>
+static int pool_add_kfold_impl(ss_pool* ph, ss_graph* h, const int32_t* fold_of_source, int nfolds, int64_t i_begin,
+                               int64_t i_end, int clean, int64_t block_rows, int mem) {
+  using K = pool_key_t<T>;
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  PoolBox<T>* pp = nullptr;
+  SS_TRY(pool_check<T>(ph, &pp));
+  PoolBox<T>& p = *pp;
+  Graph<T>* gp = nullptr;
+  SS_TRY(graph_check<T>(h, &gp));
+  Graph<T>& g = *gp;
+  SS_TRY(kfold_graph_check(g));
+  SS_TRY(kfold_range_check(i_begin, i_end, g.ns));
+  if (block_rows < 0) return fail(SS_EINVAL, "pool add kfold: block_rows must be >= 0");
+  KfoldPlan plan;
+  SS_TRY(kfold_plan(fold_of_source, nfolds, g.ns, mem, plan));
+  const int64_t nrows = i_end - i_begin, nt = g.nt;
+  if (nrows == 0) return SS_OK;
+  SS_TRY(check_binary_rows_shape(nt));
+  hipStream_t st = ctx().stream;
+  int64_t rb = block_rows;
+  if (rb == 0) {
+    rb = (1LL << 30) / (nt * (int64_t)sizeof(T));  // about 1 GiB of scores
+    if (rb < 1) rb = 1;
+  }
+  if (rb > nrows) rb = nrows;
+  KfoldRange rg;
+  kfold_range(plan, i_begin, i_end, rg);
+  std::vector<int> map(rg.sel.size());
+  for (size_t q = 0; q < map.size(); ++q) map[q] = (int)(rg.sel[q] - i_begin);
+  KfoldWork<T> w;
+  SS_TRY(kfold_work_init<T>(g, plan, rg, map, w));
+  std::vector<int> hy((size_t)nrows + 1);
+  SS_HIP(hipMemcpyAsync(hy.data(), g.Ys.ptr.p + i_begin, hy.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  std::vector<int64_t> pptr((size_t)nrows + 1, 0);
+  for (int64_t q = 0; q < nrows; ++q) pptr[q + 1] = pptr[q] + (hy[map[q] + 1] - hy[map[q]]);
+  int64_t max_lab = 1;
+  for (int64_t p0 = 0; p0 < nrows; p0 += rb) {
+    const int64_t p1 = nrows - p0 < rb ? nrows : p0 + rb;
+    if (pptr[p1] - pptr[p0] > max_lab) max_lab = pptr[p1] - pptr[p0];
+  }
+  DevBuf<int64_t> d_pptr;
+  DevBuf<int> lab;
+  DevBuf<T> scores;
+  SS_TRY(d_pptr.alloc((size_t)nrows + 1));
+  SS_TRY(lab.alloc((size_t)max_lab));
+  SS_TRY(scores.alloc((size_t)rb * nt));
+  SS_HIP(hipMemcpyAsync(d_pptr.p, pptr.data(), pptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  SS_TRY(graph_sell(g));
+  if (!g.dense.on) SS_TRY(graph_chunked(g, false));
+  std::vector<PoolTable<K>> loc;
+  const int64_t other = pool_stored(p.lv);
+  timing_begin_call();
+  hipEvent_t e_begin, e_end;
+  SS_TRY(timing_mark(&e_begin));
+  for (int64_t p0 = 0; p0 < nrows; p0 += rb) {
+    const int64_t nb = nrows - p0 < rb ? nrows - p0 : rb;
+    SS_TRY(kfold_rows_device<T>(g, w, plan, rg, p0, p0 + nb, clean, scores.p, nt, nullptr));
+    StageTimer t3(ST_EPILOGUE);
+    SS_TRY(launch_gather_labels(g.Ys.ptr.p, g.Ys.idx.p, w.d_sel.p + p0, nb, d_pptr.p + p0, pptr[p0], lab.p));
+    PoolTable<K> t;
+    SS_TRY((pool_block_table<T, int64_t>(d_pptr.p + p0, pptr[p0], lab.p, 0, pptr[p0 + nb] - pptr[p0], scores.p, nb,
+                                         nt, nt, p.w, t)));
+    SS_TRY(pool_push(loc, std::move(t), other, p.max_entries, p.w));
+  }
+  {
+    StageTimer t3(ST_EPILOGUE);
+    SS_TRY(pool_commit(p, loc, nrows * nt, pptr[nrows]));
+  }
+  SS_TRY(timing_mark(&e_end));
+  timing_span(ST_TOTAL, e_begin, e_end);
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
+}
+
+template <class T>
+static int pool_merge_impl(ss_pool* dh, const ss_pool* sh) {
+  SS_TRY(require_init());
+  PoolBox<T>* d = nullptr;
+  PoolBox<T>* s = nullptr;
+  SS_TRY(pool_check<T>(dh, &d));
+  SS_TRY(pool_check<T>(sh, &s));
+  timing_begin_call();
+  PoolTable<pool_key_t<T>> u;
+  SS_TRY(pool_union(s->lv, d->w, u));
+  const int64_t n = s->n, npos = s->npos;  // read before d's counts change (d may be s)
+  SS_TRY(pool_push(d->lv, std::move(u), 0, d->max_entries, d->w));
+  d->n += n;
+  d->npos += npos;
+  SS_HIP(hipStreamSynchronize(ctx().stream));
+  return SS_OK;
+}
+
+template <class T>
+static int pool_export_impl(ss_pool* h, T* keys, int64_t* npos, int64_t* nneg, int64_t cap, int64_t* count, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  PoolBox<T>* pp = nullptr;
+  SS_TRY(pool_check<T>(h, &pp));
+  PoolBox<T>& p = *pp;
+  SS_TRY(pool_consolidate(p.lv, p.w));
+  const int64_t E = p.lv.empty() ? 0 : p.lv[0].n;
+  if (count) *count = E;
+  if (!keys) return SS_OK;  // size query
+  if (!npos || !nneg) return fail(SS_EINVAL, "pool export: NULL count buffer");
+  if (cap < E) return fail(SS_EINVAL, "pool export: capacity %lld < %lld entries", (long long)cap, (long long)E);
+  if (E == 0) return SS_OK;
+  hipStream_t st = ctx().stream;
+  const PoolTable<pool_key_t<T>>& t = p.lv[0];
+  if (mem == SS_MEM_DEVICE) {
+    SS_TRY(pool_export_table<T>(t, keys));
+    SS_HIP(hipMemcpyAsync(npos, t.npos.p, (size_t)E * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    SS_HIP(hipMemcpyAsync(nneg, t.nneg.p, (size_t)E * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+  } else {
+    DevBuf<T> v;
+    SS_TRY(v.alloc((size_t)E));
+    SS_TRY(pool_export_table<T>(t, v.p));
+    SS_HIP(hipMemcpyAsync(keys, v.p, (size_t)E * sizeof(T), hipMemcpyDeviceToHost, st));
+    SS_HIP(hipMemcpyAsync(npos, t.npos.p, (size_t)E * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    SS_HIP(hipMemcpyAsync(nneg, t.nneg.p, (size_t)E * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  }
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
+}
+
+template <class T>
+static int pool_import_impl(ss_pool* h, const T* keys, const int64_t* npos, const int64_t* nneg, int64_t n, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  PoolBox<T>* pp = nullptr;
+  SS_TRY(pool_check<T>(h, &pp));
+  PoolBox<T>& p = *pp;
+  if (n < 0) return fail(SS_EINVAL, "pool import: n = %lld < 0", (long long)n);
+  if (n == 0) return SS_OK;
+  if (!keys || !npos || !nneg) return fail(SS_EINVAL, "pool import: NULL buffer");
+  timing_begin_call();
+  const T* dk = keys;
+  const int64_t* dp = npos;
+  const int64_t* dn = nneg;
+  DevBuf<T> bk;
+  DevBuf<int64_t> bp, bn;
+  if (mem == SS_MEM_HOST) {
+    SS_TRY(bk.alloc((size_t)n));
+    SS_TRY(bp.alloc((size_t)n));
+    SS_TRY(bn.alloc((size_t)n));
+    SS_TRY(upload<T>(bk.p, keys, (size_t)n, SS_MEM_HOST));
+    SS_TRY(upload<int64_t>(bp.p, npos, (size_t)n, SS_MEM_HOST));
+    SS_TRY(upload<int64_t>(bn.p, nneg, (size_t)n, SS_MEM_HOST));
+    dk = bk.p;
+    dp = bp.p;
+    dn = bn.p;
+  }
+  PoolTable<pool_key_t<T>> t;
+  int64_t P = 0, N = 0;
+  SS_TRY(pool_import_table<T>(dk, dp, dn, n, p.w, t, &P, &N));
+  SS_TRY(pool_push(p.lv, std::move(t), 0, p.max_entries, p.w));
+  p.n += P + N;
+  p.npos += P;
+  SS_HIP(hipStreamSynchronize(ctx().stream));
+  return SS_OK;
+}
+
+template <class T>
+static int pool_metrics_impl(PoolBox<T>& p, double* out) {
+  if (p.n == 0) return fail(SS_EINVAL, "pool is empty");
+  timing_begin_call();
+  SS_TRY(pool_consolidate(p.lv, p.w));
+  return pool_table_metrics(p.lv[0], p.npos, p.n - p.npos, p.w, out);
+}
+
 // ------------------------------------------------------------------ raw SpMM
 template <class T>
 static int spmat_check(const void* h, SpMat<T>** out) {
@@ -2433,6 +2789,156 @@ int ss_spmat_cost(const ss_spmat* h, int64_t B, double* bytes, double* flops) {
   if (bytes) *bytes = (double)nnz * (vb + 4) + (double)(rows + 1) * 4 + (double)cols * B * vb + (double)rows * B * vb;
   if (flops) *flops = 2.0 * (double)nnz * (double)B;
   return SS_OK;
+}
+
+// ------------------------------------------------------------------ pooled tables
+int ss_pool_create_f32(int64_t max_entries, ss_pool** out) {
+  SS_API_LOCK();
+  return pool_create_impl<float>(max_entries, out);
+}
+int ss_pool_create_f64(int64_t max_entries, ss_pool** out) {
+  SS_API_LOCK();
+  return pool_create_impl<double>(max_entries, out);
+}
+int ss_pool_destroy(ss_pool* h) {
+  SS_API_LOCK();
+  if (!h) return SS_OK;
+  int dt = 0;
+  SS_TRY(pool_dtype(h, &dt));
+  {  // wait for a call that still works on the handle (the caller must not start new ones), then for the device
+    SS_HANDLE_LOCK(h);
+    if (ctx().inited) (void)hipStreamSynchronize(ctx().stream);
+  }
+  if (dt == 4) delete reinterpret_cast<PoolBox<float>*>(h);
+  else delete reinterpret_cast<PoolBox<double>*>(h);
+  return SS_OK;
+}
+int ss_pool_reset(ss_pool* h) {
+  SS_API_LOCK();
+  int dt = 0;
+  SS_TRY(pool_dtype(h, &dt));
+  SS_HANDLE_LOCK(h);
+  if (ctx().inited) (void)hipStreamSynchronize(ctx().stream);
+  auto clear = [](auto* b) {
+    b->lv.clear();
+    b->w = decltype(b->w)();
+    b->n = b->npos = 0;
+  };
+  if (dt == 4) clear(reinterpret_cast<PoolBox<float>*>(h));
+  else clear(reinterpret_cast<PoolBox<double>*>(h));
+  return SS_OK;
+}
+int ss_pool_info(const ss_pool* h, int64_t info[4]) {
+  SS_API_LOCK();
+  int dt = 0;
+  SS_TRY(pool_dtype(h, &dt));
+  if (!info) return fail(SS_EINVAL, "NULL argument");
+  SS_HANDLE_LOCK(h);
+  auto fill = [&](const auto* b) {
+    info[0] = b->n;
+    info[1] = b->npos;
+    info[2] = pool_stored(b->lv);
+    info[3] = b->max_entries;
+  };
+  if (dt == 4) fill(reinterpret_cast<const PoolBox<float>*>(h));
+  else fill(reinterpret_cast<const PoolBox<double>*>(h));
+  return SS_OK;
+}
+int ss_pool_add_rows_f32(ss_pool* pool, const int64_t* yptr, const int32_t* yidx, int index_base, const float* yhat,
+                         int64_t nrows, int64_t ncols, int64_t ld, int mem) {
+  SS_API_LOCK();
+  if (!pool) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(pool);
+  return pool_add_rows_impl<float>(pool, yptr, yidx, index_base, yhat, nrows, ncols, ld, mem);
+}
+int ss_pool_add_rows_f64(ss_pool* pool, const int64_t* yptr, const int32_t* yidx, int index_base, const double* yhat,
+                         int64_t nrows, int64_t ncols, int64_t ld, int mem) {
+  SS_API_LOCK();
+  if (!pool) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(pool);
+  return pool_add_rows_impl<double>(pool, yptr, yidx, index_base, yhat, nrows, ncols, ld, mem);
+}
+// a pool and a graph: the pool's lock first, always
+int ss_pool_add_loo_f32(ss_pool* pool, ss_graph* g, int64_t i_begin, int64_t i_end, int clean, int64_t block_rows) {
+  SS_API_LOCK();
+  if (!pool || !g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(pool);
+  std::unique_lock<std::mutex> _graph_guard(reinterpret_cast<HandleHead*>(g)->mu);
+  return pool_add_loo_impl<float>(pool, g, i_begin, i_end, clean, block_rows);
+}
+int ss_pool_add_loo_f64(ss_pool* pool, ss_graph* g, int64_t i_begin, int64_t i_end, int clean, int64_t block_rows) {
+  SS_API_LOCK();
+  if (!pool || !g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(pool);
+  std::unique_lock<std::mutex> _graph_guard(reinterpret_cast<HandleHead*>(g)->mu);
+  return pool_add_loo_impl<double>(pool, g, i_begin, i_end, clean, block_rows);
+}
+int ss_pool_add_kfold_f32(ss_pool* pool, ss_graph* g, const int32_t* fold_of_source, int nfolds, int64_t i_begin,
+                          int64_t i_end, int clean, int64_t block_rows, int mem) {
+  SS_API_LOCK();
+  if (!pool || !g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(pool);
+  std::unique_lock<std::mutex> _graph_guard(reinterpret_cast<HandleHead*>(g)->mu);
+  return pool_add_kfold_impl<float>(pool, g, fold_of_source, nfolds, i_begin, i_end, clean, block_rows, mem);
+}
+int ss_pool_add_kfold_f64(ss_pool* pool, ss_graph* g, const int32_t* fold_of_source, int nfolds, int64_t i_begin,
+                          int64_t i_end, int clean, int64_t block_rows, int mem) {
+  SS_API_LOCK();
+  if (!pool || !g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(pool);
+  std::unique_lock<std::mutex> _graph_guard(reinterpret_cast<HandleHead*>(g)->mu);
+  return pool_add_kfold_impl<double>(pool, g, fold_of_source, nfolds, i_begin, i_end, clean, block_rows, mem);
+}
+int ss_pool_merge(ss_pool* dst, const ss_pool* src) {
+  SS_API_LOCK();
+  int dd = 0, ds = 0;
+  SS_TRY(pool_dtype(dst, &dd));
+  SS_TRY(pool_dtype(src, &ds));
+  if (dd != ds) return fail(SS_EINVAL, "pool merge: the pools have different precisions");
+  // two different pools: their locks in address order, so that merge(a, b) and merge(b, a) cannot deadlock
+  HandleHead* a = reinterpret_cast<HandleHead*>(dst);
+  HandleHead* b = reinterpret_cast<HandleHead*>(const_cast<ss_pool*>(src));
+  if (b < a) std::swap(a, b);
+  std::unique_lock<std::mutex> la(a->mu);
+  std::unique_lock<std::mutex> lb;
+  if (b != a) lb = std::unique_lock<std::mutex>(b->mu);
+  return dd == 4 ? pool_merge_impl<float>(dst, src) : pool_merge_impl<double>(dst, src);
+}
+int ss_pool_export_f32(ss_pool* pool, float* keys, int64_t* npos, int64_t* nneg, int64_t cap, int64_t* count, int mem) {
+  SS_API_LOCK();
+  if (!pool) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(pool);
+  return pool_export_impl<float>(pool, keys, npos, nneg, cap, count, mem);
+}
+int ss_pool_export_f64(ss_pool* pool, double* keys, int64_t* npos, int64_t* nneg, int64_t cap, int64_t* count,
+                       int mem) {
+  SS_API_LOCK();
+  if (!pool) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(pool);
+  return pool_export_impl<double>(pool, keys, npos, nneg, cap, count, mem);
+}
+int ss_pool_import_f32(ss_pool* pool, const float* keys, const int64_t* npos, const int64_t* nneg, int64_t n, int mem) {
+  SS_API_LOCK();
+  if (!pool) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(pool);
+  return pool_import_impl<float>(pool, keys, npos, nneg, n, mem);
+}
+int ss_pool_import_f64(ss_pool* pool, const double* keys, const int64_t* npos, const int64_t* nneg, int64_t n,
+                       int mem) {
+  SS_API_LOCK();
+  if (!pool) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(pool);
+  return pool_import_impl<double>(pool, keys, npos, nneg, n, mem);
+}
+int ss_pool_metrics(ss_pool* pool, double out[21]) {
+  SS_API_LOCK();
+  SS_TRY(require_init());
+  int dt = 0;
+  SS_TRY(pool_dtype(pool, &dt));
+  if (!out) return fail(SS_EINVAL, "NULL argument");
+  SS_HANDLE_LOCK(pool);
+  return dt == 4 ? pool_metrics_impl(*reinterpret_cast<PoolBox<float>*>(pool), out)
+                 : pool_metrics_impl(*reinterpret_cast<PoolBox<double>*>(pool), out);
 }
 
 }  // extern "C"

@@ -24,6 +24,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "binary_metrics.hpp"
 #include "graph.hpp"
 
 namespace ss {
@@ -44,33 +45,6 @@ constexpr int BR_WAVES = BR_THREADS / 64;
 constexpr int BR_NM = 6;                     // metrics per row
 constexpr int BR_LDS_MAXN = 16384;           // columns per row on the LDS path: 16384 x (8 + 1) B + scratch
 constexpr int64_t BR_BATCH_ELEMS = 1 << 25;  // elements per long-path batch (bounds its scratch)
-
-__device__ inline double br_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-// mcc(a, b, eps) limit form (metrics.py): (a*e - b*e) / sqrt((a+b)*(a+e)*(b+e)*(e+e)), e = floatmin(Float64)
-__device__ inline double br_mcc_limit(long long ai, long long bi) {
-  const double a = (double)ai, b = (double)bi, e = 2.2250738585072014e-308;
-  return (a * e - b * e) / sqrt((a + b) * (a + e) * (b + e) * (e + e));
-}
-
-// the six metrics at one threshold, as metrics.py evaluates them on integer counts
-__device__ inline void br_metrics(long long tp, long long fp, long long P, long long N, double* m) {
-  const long long tn = N - fp, fn = P - tp;
-  const double d = (double)tp + 0.5 * (double)(fp + fn);
-  m[0] = d == 0.0 ? br_nan() : (double)tp / d;
-  const long long p_pred = tp + fp, n_pred = fn + tn, p_act = tp + fn, n_act = fp + tn;
-  if (p_pred == 0) m[1] = br_mcc_limit(tn, fn);
-  else if (n_pred == 0) m[1] = br_mcc_limit(tp, fp);
-  else if (p_act == 0) m[1] = br_mcc_limit(tn, fp);
-  else if (n_act == 0) m[1] = br_mcc_limit(tp, fn);
-  else m[1] = (double)(tp * tn - fp * fn) / sqrt((double)(p_pred * n_pred) * (double)(p_act * n_act));
-  m[2] = (double)(tp + tn) / (double)((tp + tn) + (fp + fn));
-  const double tpr = p_act != 0 ? (double)tp / (double)p_act : br_nan();
-  const double tnr = n_act != 0 ? (double)tn / (double)n_act : br_nan();
-  m[3] = (tpr + tnr) / 2.0;
-  m[4] = p_act == 0 ? br_nan() : (double)tp / (double)p_act;
-  m[5] = p_pred == 0 ? br_nan() : (double)tp / (double)p_pred;
-}
 
 struct BrScratch {
   double d[BR_WAVES * BR_NM];

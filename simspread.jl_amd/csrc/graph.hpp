@@ -9,6 +9,8 @@
 #pragma once
 #include "common.hpp"
 
+#include <type_traits>
+
 namespace ss {
 
 template <class T>
@@ -248,6 +250,48 @@ int launch_rank_rows(const PtrT* yptr, int64_t shift, const int* yidx, int base,
 template <class T, class PtrT>
 int launch_binary_rows(const PtrT* yptr, int64_t shift, const int* yidx, int base, const T* yhat, int64_t nrows,
                        int64_t ncols, int64_t ld, double* out);
+// ---- pooled.hip: (score, label) pairs pooled into a table of distinct scores with int64 counts of positives and
+// negatives.  Scores are order-preserving unsigned keys (u32 for fp32, u64 for fp64, -0.0 -> +0.0's key); a table's keys
+// are unique and descending.  A pool is a list of tables ("levels") whose union is its table.
+template <class T>
+using pool_key_t = typename std::conditional<sizeof(T) == 4, uint32_t, uint64_t>::type;
+template <class K>
+struct PoolTable {
+  DevBuf<K> key;
+  DevBuf<int64_t> npos, nneg;
+  int64_t n = 0;  // entries
+};
+template <class K>
+struct PoolWork {  // scratch reused across blocks
+  DevBuf<K> s, s2, q, q2, qkey;
+  DevBuf<int64_t> cnt, inc, rstart, qcnt;
+  DevBuf<unsigned char> tmp;
+  DevBuf<int> flag;
+};
+// the table of a row-major score block against CSR positives (labels as for launch_rank_rows, checked beforehand);
+// SS_EINVAL when a score is NaN.  nnz = number of label entries of the block.
+template <class T, class PtrT>
+int pool_block_table(const PtrT* yptr, int64_t shift, const int* yidx, int base, int64_t nnz, const T* yhat,
+                     int64_t nrows, int64_t ncols, int64_t ld, PoolWork<pool_key_t<T>>& w, PoolTable<pool_key_t<T>>& out);
+// push a table onto the levels (merging levels of at most twice its size); SS_ENOMEM and the levels untouched when
+// other + the entries stored afterwards exceed max_entries
+template <class K>
+int pool_push(std::vector<PoolTable<K>>& lv, PoolTable<K>&& t, int64_t other, int64_t max_entries, PoolWork<K>& w);
+template <class K>
+int pool_union(const std::vector<PoolTable<K>>& lv, PoolWork<K>& w, PoolTable<K>& out);
+template <class K>
+int pool_consolidate(std::vector<PoolTable<K>>& lv, PoolWork<K>& w);
+template <class K>
+int64_t pool_stored(const std::vector<PoolTable<K>>& lv);
+// a caller's table (device arrays: scores, npos, nneg) checked and keyed; P / N: its pair counts
+template <class T>
+int pool_import_table(const T* v, const int64_t* np, const int64_t* nn, int64_t n, PoolWork<pool_key_t<T>>& w,
+                      PoolTable<pool_key_t<T>>& out, int64_t* P, int64_t* N);
+template <class T>
+int pool_export_table(const PoolTable<pool_key_t<T>>& t, T* v);
+// the 21 pooled numbers of one table (host out)
+template <class K>
+int pool_table_metrics(const PoolTable<K>& t, int64_t P, int64_t N, PoolWork<K>& w, double* out);
 // ---- dense.hip (fp32 only: fp32-input MFMA)
 int launch_transfer_dense(const DenseSim<float>& d, bool loo, const float* inv_k, const float* inv_n, const int* ks,
                           int64_t row_begin, int64_t nrows, float* out, int64_t ldo, bool source_rows = false);

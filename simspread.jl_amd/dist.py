@@ -144,3 +144,25 @@ def lib_gather_scores(local, counts: Sequence[int], root: Optional[int] = None):
     L.check(fn(local.data_ptr(), local.shape[1], cnt, None if full is None else full.data_ptr(), -1 if root is None else int(root)))
     L.check(L.lib().ss_synchronize())
     return full
+
+
+def pooled_metrics(pool, group=None, root: int = 0):
+    """The pooled numbers of a sharded sweep: every rank has pooled its own rows (Pool.add_loo / add_kfold over its
+    shard_range, no collective on the data path); here each rank exports its finished table once, the root imports
+    all of them, in rank order, into a fresh pool and evaluates it.  Returns the metrics dict on the root, None
+    elsewhere; the caller's pool is not changed.  The tables travel through torch.distributed (gather_object)."""
+    import torch.distributed as dist
+    from .engine import Pool
+    table = pool.export()
+    rank = dist.get_rank(group)
+    tables = [None] * dist.get_world_size(group) if rank == root else None
+    dist.gather_object(table, tables, dst=_global_rank(root, group), group=group)
+    if rank != root:
+        return None
+    total = Pool(pool.dtype)
+    try:
+        for keys, npos, nneg in tables:
+            total.import_(keys, npos, nneg)
+        return total.metrics()
+    finally:
+        total.close()

@@ -446,6 +446,26 @@ class DeviceGraph:
                     out.ctypes.data, L_.SS_MEM_HOST))
         return out
 
+    def evaluate_loo_pooled(self, i_begin: int = 0, i_end: Optional[int] = None, clean: bool = False,
+                            block_rows: int = 0) -> dict:
+        """The leave-one-out folds [i_begin, i_end) judged pooled, as the reference's AuROC(vec(y), vec(yhat)) and
+        maxperformance(vec(y), vec(yhat), f) judge a whole matrix: Pool(...).add_loo(self, ...).metrics()."""
+        p = Pool(self.dtype)
+        try:
+            return p.add_loo(self, i_begin, i_end, clean=clean, block_rows=block_rows).metrics()
+        finally:
+            p.close()
+
+    def evaluate_kfold_pooled(self, fold_of_source, nfolds: Optional[int] = None, i_begin: int = 0,
+                              i_end: Optional[int] = None, clean: bool = False, block_rows: int = 0) -> dict:
+        """The k-fold rows [i_begin, i_end) judged pooled: Pool(...).add_kfold(self, ...).metrics()."""
+        p = Pool(self.dtype)
+        try:
+            return p.add_kfold(self, fold_of_source, nfolds, i_begin, i_end, clean=clean,
+                               block_rows=block_rows).metrics()
+        finally:
+            p.close()
+
     def close(self):
         if self._h is not None and self._h.value:
             L.load().ss_graph_destroy(self._h)
@@ -795,6 +815,144 @@ def binary_metrics_rows(y, yhat):
     L_.check(fn(hp.ctypes.data, hi.ctypes.data, 0, a.ctypes.data, nrows, ncols, ncols, out.ctypes.data,
                 L_.SS_MEM_HOST))
     return out[0] if one else out
+
+
+POOLED_FIELDS = ("AuROC", "AuPRC", "validity_ratio") + BINARY_ROWS_FIELDS
+
+
+class Pool:
+    """Pooled evaluation on the device: a table of the distinct scores with int64 counts of positives and negatives,
+    so that AuROC(vec(y), vec(yhat)), AuPRC and maxperformance(vec(y), vec(yhat), f) of a whole score matrix or
+    cross-validation sweep follow without the scores leaving the device (ss_pool_*).  Adds are all or nothing.
+    `metrics()` returns POOLED_FIELDS: AuROC, AuPRC, validity ratio, then max / mean / std of the six binary metrics as
+    binary_metrics_rows defines them for one row.  BEDROC and recall@L / precision@L are not pooled (see the header)."""
+
+    def __init__(self, dtype=np.float32, max_entries: int = 0):
+        self.dtype = np.dtype(dtype)
+        self._suf = _suffix(dtype)
+        h = C.c_void_p()
+        L.check(getattr(L.lib(), f"ss_pool_create_{self._suf}")(int(max_entries), C.byref(h)))
+        self._h = h
+
+    def info(self) -> dict:
+        """pairs pooled, positives among them, table entries stored, max_entries"""
+        buf = (C.c_int64 * 4)()
+        L.check(L.lib().ss_pool_info(self._h, buf))
+        return dict(n=int(buf[0]), npos=int(buf[1]), entries=int(buf[2]), max_entries=int(buf[3]))
+
+    def reset(self):
+        L.check(L.lib().ss_pool_reset(self._h))
+        return self
+
+    def add_rows(self, y, yhat):
+        """Pool every (score, label) pair of a score block: `y` and `yhat` as binary_metrics_rows takes them (numpy or
+        a contiguous CUDA tensor; labels scipy / dense 0/1 / a 0-based (ptr int64, idx int32) CSR pair)."""
+        torch_in = type(yhat).__module__.startswith("torch")
+        if torch_in:
+            import torch
+            if yhat.dim() == 1:
+                yhat = yhat.reshape(1, -1)
+            if yhat.dim() != 2 or not yhat.is_contiguous() or not yhat.is_cuda:
+                raise ValueError("yhat must be a contiguous 1-D or 2-D CUDA tensor")
+            if {torch.float32: "f32", torch.float64: "f64"}.get(yhat.dtype) != self._suf:
+                raise TypeError("yhat dtype does not match the pool precision")
+            nrows, ncols = (int(v) for v in yhat.shape)
+        else:
+            a = np.asarray(yhat)
+            if a.ndim == 1:
+                a = a.reshape(1, -1)
+            if a.ndim != 2:
+                raise ValueError("yhat must be 1-D or 2-D")
+            if a.dtype != self.dtype:
+                raise TypeError("yhat dtype does not match the pool precision")
+            a = np.ascontiguousarray(a)
+            nrows, ncols = a.shape
+        if not isinstance(y, tuple) and not hasattr(y, "tocsr"):
+            y = np.asarray(y).reshape(nrows, ncols)
+        dev_labels = isinstance(y, tuple) and type(y[0]).__module__.startswith("torch")
+        fn = getattr(L.lib(), f"ss_pool_add_rows_{self._suf}")
+        if dev_labels:
+            if not torch_in:
+                raise TypeError("device labels need device scores (a CUDA tensor yhat)")
+            ptr_d, idx_d = y[0].contiguous(), y[1].contiguous()
+        else:
+            hp, hi = _label_csr(y, nrows, ncols)
+            _check_label_order(hp, hi, ncols)
+        if torch_in:
+            import torch
+            _is_torch(yhat)
+            if not dev_labels:
+                ptr_d = torch.from_numpy(hp).to(yhat.device)
+                idx_d = torch.from_numpy(hi if hi.size else np.zeros(1, np.int32)).to(yhat.device)
+            L.check(fn(self._h, ptr_d.data_ptr(), idx_d.data_ptr(), 0, yhat.data_ptr(), nrows, ncols, ncols,
+                       L.SS_MEM_DEVICE))
+        else:
+            L.check(fn(self._h, hp.ctypes.data, hi.ctypes.data, 0, a.ctypes.data, nrows, ncols, ncols, L.SS_MEM_HOST))
+        return self
+
+    def add_loo(self, g: "DeviceGraph", i_begin: int = 0, i_end: Optional[int] = None, clean: bool = False,
+                block_rows: int = 0):
+        """Pool the leave-one-out folds [i_begin, i_end) of `g` against its own labels (ss_pool_add_loo_*)."""
+        i_end = g.ns if i_end is None else i_end
+        fn = getattr(L.lib(), f"ss_pool_add_loo_{self._suf}")
+        L.check(fn(self._h, g._h, int(i_begin), int(i_end), 1 if clean else 0, int(block_rows)))
+        return self
+
+    def add_kfold(self, g: "DeviceGraph", fold_of_source, nfolds: Optional[int] = None, i_begin: int = 0,
+                  i_end: Optional[int] = None, clean: bool = False, block_rows: int = 0):
+        """Pool the k-fold rows [i_begin, i_end) of `g` against its own labels (ss_pool_add_kfold_*)."""
+        fold, nfolds = g._folds(fold_of_source, nfolds)
+        i_end = g.ns if i_end is None else i_end
+        fn = getattr(L.lib(), f"ss_pool_add_kfold_{self._suf}")
+        L.check(fn(self._h, g._h, fold.ctypes.data, nfolds, int(i_begin), int(i_end), 1 if clean else 0,
+                   int(block_rows), L.SS_MEM_HOST))
+        return self
+
+    def merge(self, other: "Pool"):
+        """Add every pair of `other` (unchanged) to this pool."""
+        L.check(L.lib().ss_pool_merge(self._h, other._h))
+        return self
+
+    def export(self):
+        """(scores descending, npos int64, nneg int64) numpy arrays of the table."""
+        fn = getattr(L.lib(), f"ss_pool_export_{self._suf}")
+        n = C.c_int64()
+        L.check(fn(self._h, None, None, None, 0, C.byref(n), L.SS_MEM_HOST))
+        keys = np.empty(n.value, self.dtype)
+        npos, nneg = np.empty(n.value, np.int64), np.empty(n.value, np.int64)
+        L.check(fn(self._h, keys.ctypes.data, npos.ctypes.data, nneg.ctypes.data, n.value, C.byref(n), L.SS_MEM_HOST))
+        return keys, npos, nneg
+
+    def import_(self, keys, npos, nneg):
+        """Add a table such as export() returns (scores strictly descending, counts >= 0)."""
+        k = np.ascontiguousarray(keys, dtype=self.dtype)
+        p = np.ascontiguousarray(npos, dtype=np.int64)
+        q = np.ascontiguousarray(nneg, dtype=np.int64)
+        if not k.shape == p.shape == q.shape or k.ndim != 1:
+            raise ValueError("keys, npos and nneg must be 1-D arrays of one length")
+        fn = getattr(L.lib(), f"ss_pool_import_{self._suf}")
+        L.check(fn(self._h, k.ctypes.data, p.ctypes.data, q.ctypes.data, k.size, L.SS_MEM_HOST))
+        return self
+
+    def metrics_array(self) -> np.ndarray:
+        """The 21 pooled numbers, in POOLED_FIELDS order."""
+        out = np.empty(len(POOLED_FIELDS), np.float64)
+        L.check(L.lib().ss_pool_metrics(self._h, out.ctypes.data))
+        return out
+
+    def metrics(self) -> dict:
+        return dict(zip(POOLED_FIELDS, (float(v) for v in self.metrics_array())))
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            L.load().ss_pool_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def jaccard_similarity(X, dtype=np.float64):
