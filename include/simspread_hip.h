@@ -438,8 +438,8 @@ int ss_evaluate_kfold_binary_f64(ss_graph* g, const int32_t* fold_of_source, int
  * (_f32 / _f64): scores are compared in it; -0.0 equals +0.0; clean!'s -99 is an ordinary score; NaN is refused.
  *
  * Out of scope: BEDROC depends on positions inside tie groups, which Julia breaks by the column-major vec order and
- * no sharded sweep reproduces; recall@L / precision@L are per group (= per row) in the reference and are served per
- * row by ss_rank_metrics_rows_* / ss_evaluate_*.
+ * no sharded sweep reproduces; recall@L / precision@L are per group in the reference, not pooled: grouped by row they
+ * are served by ss_rank_metrics_rows_* / ss_evaluate_*, grouped by target by ss_target_topl_* (below).
  *
  * Memory: the table holds one entry per distinct score (fp32: 4 + 16 bytes, fp64: 8 + 16).  An fp32 table is bounded
  * (at most about 2^31 distinct non-negative scores, plus -99 and the like); an fp64 sweep can have as many distinct
@@ -500,6 +500,87 @@ int ss_pool_import_f64(ss_pool* pool, const double* keys, const int64_t* npos, c
  * Reductions run in a fixed order on the merged table: the 21 doubles are bitwise a function of the multiset of pairs,
  * whatever the blocks, their order, the ranks or block_rows.  An empty pool: SS_EINVAL. */
 int ss_pool_metrics(ss_pool* pool, double out[21]);
+
+/* ------------------------------------------------------------- per-target top-L ---- */
+/* recallatL(y, yhat, grouping, L) and precisionatL(y, yhat, grouping, L) (src/performance.jl:308-409) with grouping =
+ * the TARGET of every entry of vec(yhat): "for each target, are its true sources among the L highest-scored rows?"
+ * (ss_rank_metrics_rows_* / ss_evaluate_* serve the grouping by row).  Inside a target group Julia's stable
+ * sortperm(yhat_g, rev=true) orders the rows by (score descending, row ascending), vec being column-major; scores are
+ * compared as isless does: +0.0 ranks before -0.0, clean!'s -99 is an ordinary score, NaN is refused.  Under that total
+ * order the top L of a union of row blocks is the top L of the blocks' own top-L lists, so a handle keeps, per target,
+ * the L best (score, row, label) entries seen so far -- nt x L entries on the device, exact and mergeable in any order
+ * -- plus npos[t], the positives of target t over every row added.  Its rows are the virtual-screening result: per
+ * target the best L compounds of everything added.
+ *
+ * Rows are int64 ids >= 0 chosen by the caller (add_rows: row_begin + r; add_loo / add_kfold: the source index) and
+ * must be distinct across everything a handle absorbs.  A repeated id is not detected: both copies then compete as
+ * separate entries (a row can take two places), which is no longer the reference's list.  Every row adds one entry to
+ * every target, so every target holds fill = min(L, rows added) entries.
+ *
+ * Every add (add_rows, add_loo, add_kfold, merge, import) is all or nothing: a NaN score, bad labels, a handle of the
+ * other precision, ncols != nt or other bad arguments (SS_EINVAL) leave the handle bitwise as it was.  ss_path_last
+ * names the kernels: "target_topl_seed" (while a target holds fewer than L entries: its top L of them and
+ * of the block's first max(L - fill, 2L, 512) rows), "target_topl_filter" (one pass over the
+ * block keeps the scores that beat their target's L-th entry), "target_topl_merge_lds" (per target, candidates sorted
+ * and merged in LDS) and "target_topl_merge_large" (the long-list route: a target with more candidates than the LDS
+ * path holds is served by a radix select over its whole column of the block).  ss_timing_last reports the call in
+ * ms[0] and the top-L share of it in ms[3] (for add_loo / add_kfold ms[1] and ms[2] are the prediction's stages). */
+typedef struct ss_target_topl ss_target_topl; /* a per-target top-L table, device resident */
+/* nt targets (1 <= nt < 2^31), lists of L (1 <= L <= 1024) */
+int ss_target_topl_create_f32(int64_t nt, int L, ss_target_topl** out);
+int ss_target_topl_create_f64(int64_t nt, int L, ss_target_topl** out);
+int ss_target_topl_destroy(ss_target_topl* h);
+/* empty the table (nt and L stay) */
+int ss_target_topl_reset(ss_target_topl* h);
+/* info[0] = nt, [1] = L, [2] = rows added, [3] = positives among them */
+int ss_target_topl_info(const ss_target_topl* h, int64_t info[4]);
+/* Add the rows of a row-major score block (nrows x ncols, ld >= ncols, ncols == nt, 0 <= nrows < 2^31): row r is row id
+ * row_begin + r (row_begin >= 0); labels exactly as for ss_pool_add_rows_* (CSR positives sorted, unique, in range,
+ * yptr[0] may exceed index_base); all in `mem`. */
+int ss_target_topl_add_rows_f32(ss_target_topl* h, const int64_t* yptr, const int32_t* yidx, int index_base,
+                                const float* yhat, int64_t nrows, int64_t ncols, int64_t ld, int64_t row_begin,
+                                int mem);
+int ss_target_topl_add_rows_f64(ss_target_topl* h, const int64_t* yptr, const int32_t* yidx, int index_base,
+                                const double* yhat, int64_t nrows, int64_t ncols, int64_t ld, int64_t row_begin,
+                                int mem);
+/* Add the leave-one-out folds [i_begin, i_end) against the graph's own labels Ys[i, :], fold i as row id i: bitwise
+ * ss_predict_loo_* into a device buffer followed by ss_target_topl_add_rows_*(..., row_begin = i_begin), for every
+ * block_rows.  Blocks stream as in ss_pool_add_loo_* (0: about 1 GiB of scores); same graphs and preconditions; the
+ * graph has the handle's nt and precision; no score leaves the device. */
+int ss_target_topl_add_loo_f32(ss_target_topl* h, ss_graph* g, int64_t i_begin, int64_t i_end, int clean,
+                               int64_t block_rows);
+int ss_target_topl_add_loo_f64(ss_target_topl* h, ss_graph* g, int64_t i_begin, int64_t i_end, int clean,
+                               int64_t block_rows);
+/* The same for the k-fold rows [i_begin, i_end) of ss_predict_kfold_rows_*, source i as row id i (bitwise
+ * predict_kfold_rows followed by add_rows with row_begin = i_begin); arguments, checks and blocks as for
+ * ss_pool_add_kfold_* (fold_of_source in `mem`). */
+int ss_target_topl_add_kfold_f32(ss_target_topl* h, ss_graph* g, const int32_t* fold_of_source, int nfolds,
+                                 int64_t i_begin, int64_t i_end, int clean, int64_t block_rows, int mem);
+int ss_target_topl_add_kfold_f64(ss_target_topl* h, ss_graph* g, const int32_t* fold_of_source, int nfolds,
+                                 int64_t i_begin, int64_t i_end, int clean, int64_t block_rows, int mem);
+/* dst gains every row of src (same precision, nt and L; src is unchanged; dst == src adds every row a second time) */
+int ss_target_topl_merge(ss_target_topl* dst, const ss_target_topl* src);
+/* The table: target t's fill entries in order at [t*fill, (t+1)*fill) of vals (the scores), rows (row ids) and labels
+ * (0 / 1), npos[t] for every target (nt); all in `mem`, any of them may be NULL.  *rows_added (host, may be NULL) gives
+ * fill = min(L, rows added). */
+int ss_target_topl_export_f32(ss_target_topl* h, float* vals, int64_t* rows, uint8_t* labels, int64_t* npos,
+                              int64_t* rows_added, int mem);
+int ss_target_topl_export_f64(ss_target_topl* h, double* vals, int64_t* rows, uint8_t* labels, int64_t* npos,
+                              int64_t* rows_added, int mem);
+/* Add a table such as export writes (nt x min(L, rows_added) entries and nt npos, in `mem`), validated whole first:
+ * scores not NaN, rows >= 0, labels 0 / 1, every target's entries strictly in (score desc, row asc) order, npos >= the
+ * target's labelled entries; otherwise SS_EINVAL.  rows_added == 0: no-op.  Tables of several ranks meet this way. */
+int ss_target_topl_import_f32(ss_target_topl* h, const float* vals, const int64_t* rows, const uint8_t* labels,
+                              const int64_t* npos, int64_t rows_added, int mem);
+int ss_target_topl_import_f64(ss_target_topl* h, const double* vals, const int64_t* rows, const uint8_t* labels,
+                              const int64_t* npos, int64_t rows_added, int mem);
+/* hits[t] = positives among target t's L entries and npos[t] (nt each, in `mem`, either may be NULL); out (host):
+ * out[0] = mean recall@L over the targets in target order, exactly the reference's: a target without positives gives
+ * NaN and skipmissing does not skip NaN, so the mean is NaN then; out[1] = mean precision@L (hits / L).  Beyond the
+ * reference: out[2] = mean recall@L over the targets that have positives (NaN if none), out[3] = how many do.  The
+ * means are sums in target order divided by the count (Julia's mean over an iterator).  Rows added <= L: SS_EINVAL
+ * (the reference's `length(y) > L` assertion). */
+int ss_target_topl_metrics(ss_target_topl* h, int64_t* hits, int64_t* npos, double out[4], int mem);
 
 /* -------------------------------------------------------------- raw W*R SpMM --- */
 /* The resource-spreading product F = W * R on its own (kernel unit tests and the

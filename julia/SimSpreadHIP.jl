@@ -941,4 +941,152 @@ function pool_metrics(p::Pool)
     return NamedTuple{POOL_FIELDS}(Tuple(out))
 end
 
+# ------------------------------------------------------------------------------------------------ per-target top-L
+"""Per target the L best rows seen so far on the device: recallatL / precisionatL(y, ŷ, grouping, L) with grouping =
+the target of every entry of vec(ŷ), and the virtual-screening list of every target (include/simspread_hip.h,
+per-target top-L)."""
+mutable struct TargetTopL{T<:Union{Float32,Float64}}
+    handle::Ptr{Cvoid}
+    function TargetTopL{T}(h) where {T}
+        p = new{T}(h)
+        finalizer(destroy!, p)
+        return p
+    end
+end
+
+function destroy!(p::TargetTopL)
+    if p.handle != C_NULL
+        ccall((:ss_target_topl_destroy, LIB), Cint, (Ptr{Cvoid},), p.handle)
+        p.handle = C_NULL
+    end
+    return nothing
+end
+
+"An empty table for nt targets, lists of L (1 <= L <= 1024)."
+function target_topl(T::Type, nt::Integer, L::Integer=20)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = if T === Float32
+        ccall((:ss_target_topl_create_f32, LIB), Cint, (Int64, Cint, Ref{Ptr{Cvoid}}), nt, L, h)
+    else
+        ccall((:ss_target_topl_create_f64, LIB), Cint, (Int64, Cint, Ref{Ptr{Cvoid}}), nt, L, h)
+    end
+    check(rc)
+    return TargetTopL{T}(h[])
+end
+
+target_topl_reset!(p::TargetTopL) = (check(ccall((:ss_target_topl_reset, LIB), Cint, (Ptr{Cvoid},), p.handle)); p)
+
+"(nt, L, rows added, positives)"
+function target_topl_info(p::TargetTopL)
+    info = zeros(Int64, 4)
+    check(ccall((:ss_target_topl_info, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), p.handle, info))
+    return Tuple(info)
+end
+
+"""Add the rows of a score matrix ŷ (rows x targets) with labels y (same shape); row i gets the id
+row_begin + i - 1 (0-based ids, distinct across adds)."""
+function target_topl_add!(p::TargetTopL{T}, y::SparseMatrixCSC, yhat::Matrix{T}; row_begin::Integer=0) where {T}
+    size(y) == size(yhat) || throw(DimensionMismatch("labels and scores differ in shape"))
+    yr = permutedims(yhat)                       # column-major nt x n = the rows of ŷ, row-major
+    yt = dropzeros(copy(transpose(y)))           # its CSC = the 1-based CSR of y's rows
+    ptr, idx = Vector{Int64}(yt.colptr), Vector{Int32}(yt.rowval)
+    nr, nc = size(yhat, 1), size(yhat, 2)
+    rc = if T === Float32
+        ccall((:ss_target_topl_add_rows_f32, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Cint, Ptr{Float32}, Int64, Int64, Int64, Int64, Cint),
+              p.handle, ptr, idx, 1, yr, nr, nc, max(nc, 1), row_begin, SS_MEM_HOST)
+    else
+        ccall((:ss_target_topl_add_rows_f64, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Cint, Ptr{Float64}, Int64, Int64, Int64, Int64, Cint),
+              p.handle, ptr, idx, 1, yr, nr, nc, max(nc, 1), row_begin, SS_MEM_HOST)
+    end
+    check(rc)
+    return p
+end
+
+"Add the leave-one-out folds i_begin:i_end (1-based, inclusive) against the graph's own labels."
+function target_topl_add_loo!(p::TargetTopL{T}, g::Graph{T}, i_begin::Integer, i_end::Integer; clean::Bool=true,
+                              block_rows::Integer=0) where {T}
+    rc = if T === Float32
+        ccall((:ss_target_topl_add_loo_f32, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint, Int64),
+              p.handle, g.handle, i_begin - 1, i_end, clean ? 1 : 0, block_rows)
+    else
+        ccall((:ss_target_topl_add_loo_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint, Int64),
+              p.handle, g.handle, i_begin - 1, i_end, clean ? 1 : 0, block_rows)
+    end
+    check(rc)
+    return p
+end
+
+"Add the k-fold rows i_begin:i_end (1-based, inclusive; fold ids 1..k per source)."
+function target_topl_add_kfold!(p::TargetTopL{T}, g::Graph{T}, fold_of_source::AbstractVector{<:Integer},
+                                i_begin::Integer, i_end::Integer; clean::Bool=true, block_rows::Integer=0) where {T}
+    length(fold_of_source) == g.ns || throw(AssertionError("one fold index per source is needed"))
+    folds = Vector{Int32}(fold_of_source .- 1)
+    nfolds = Int(maximum(folds)) + 1
+    rc = if T === Float32
+        ccall((:ss_target_topl_add_kfold_f32, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Cint, Int64, Int64, Cint, Int64, Cint),
+              p.handle, g.handle, folds, nfolds, i_begin - 1, i_end, clean ? 1 : 0, block_rows, SS_MEM_HOST)
+    else
+        ccall((:ss_target_topl_add_kfold_f64, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Cint, Int64, Int64, Cint, Int64, Cint),
+              p.handle, g.handle, folds, nfolds, i_begin - 1, i_end, clean ? 1 : 0, block_rows, SS_MEM_HOST)
+    end
+    check(rc)
+    return p
+end
+
+"dst gains every row of src."
+function target_topl_merge!(dst::TargetTopL{T}, src::TargetTopL{T}) where {T}
+    check(ccall((:ss_target_topl_merge, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), dst.handle, src.handle))
+    return dst
+end
+
+"The table: (scores, row ids, labels) as fill x nt matrices (column t = target t's list), npos, rows added."
+function target_topl_export(p::TargetTopL{T}) where {T}
+    nt, L, rows, _ = target_topl_info(p)
+    fill = min(L, rows)
+    vals, rid, lab = Matrix{T}(undef, fill, nt), Matrix{Int64}(undef, fill, nt), Matrix{UInt8}(undef, fill, nt)
+    np, n = Vector{Int64}(undef, nt), Ref{Int64}(0)
+    rc = if T === Float32
+        ccall((:ss_target_topl_export_f32, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Float32}, Ptr{Int64}, Ptr{UInt8}, Ptr{Int64}, Ref{Int64}, Cint),
+              p.handle, vals, rid, lab, np, n, SS_MEM_HOST)
+    else
+        ccall((:ss_target_topl_export_f64, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}, Ptr{UInt8}, Ptr{Int64}, Ref{Int64}, Cint),
+              p.handle, vals, rid, lab, np, n, SS_MEM_HOST)
+    end
+    check(rc)
+    return vals, rid, lab, np, n[]
+end
+
+"Add a table such as target_topl_export returns (another rank's, for instance)."
+function target_topl_import!(p::TargetTopL{T}, vals::Matrix{T}, rid::Matrix{Int64}, lab::Matrix{UInt8},
+                             npos::Vector{Int64}, rows_added::Integer) where {T}
+    rc = if T === Float32
+        ccall((:ss_target_topl_import_f32, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Float32}, Ptr{Int64}, Ptr{UInt8}, Ptr{Int64}, Int64, Cint),
+              p.handle, vals, rid, lab, npos, rows_added, SS_MEM_HOST)
+    else
+        ccall((:ss_target_topl_import_f64, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}, Ptr{UInt8}, Ptr{Int64}, Int64, Cint),
+              p.handle, vals, rid, lab, npos, rows_added, SS_MEM_HOST)
+    end
+    check(rc)
+    return p
+end
+
+"""(recallatL, precisionatL, recall over the targets with positives, targets with positives, hits, npos): the first
+two are the reference's grouped numbers with grouping = target."""
+function target_topl_metrics(p::TargetTopL)
+    nt = target_topl_info(p)[1]
+    hits, np, out = Vector{Int64}(undef, nt), Vector{Int64}(undef, nt), zeros(Float64, 4)
+    check(ccall((:ss_target_topl_metrics, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Cint),
+                p.handle, hits, np, out, SS_MEM_HOST))
+    return (recallatL=out[1], precisionatL=out[2], recall_with_positives=out[3], targets_with_positives=Int(out[4]),
+            hits=hits, npos=np)
+end
+
 end # module

@@ -66,6 +66,11 @@ def _sigs():
         "ss_pool_info": ([_vp, _vp], _int),
         "ss_pool_merge": ([_vp, _vp], _int),
         "ss_pool_metrics": ([_vp, _vp], _int),
+        "ss_target_topl_destroy": ([_vp], _int),
+        "ss_target_topl_reset": ([_vp], _int),
+        "ss_target_topl_info": ([_vp, _vp], _int),
+        "ss_target_topl_merge": ([_vp, _vp], _int),
+        "ss_target_topl_metrics": ([_vp, _vp, _vp, _vp, _int], _int),
     }
     s["ss_topl_f32"] = ([_vp, _i64, _i64, _i64, _int, _vp, _vp, _int], _int)
     s["ss_rank_metrics_f32"] = ([_vp, _vp, _i64, f64, _vp, _int], _int)
@@ -105,6 +110,12 @@ def _sigs():
         s[f"ss_pool_add_kfold_{suf}"] = ([_vp, _vp, _vp, _int, _i64, _i64, _int, _i64, _int], _int)
         s[f"ss_pool_export_{suf}"] = ([_vp, _vp, _vp, _vp, _i64, _vp, _int], _int)
         s[f"ss_pool_import_{suf}"] = ([_vp, _vp, _vp, _vp, _i64, _int], _int)
+        s[f"ss_target_topl_create_{suf}"] = ([_i64, _int, _vp], _int)
+        s[f"ss_target_topl_add_rows_{suf}"] = ([_vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _i64, _int], _int)
+        s[f"ss_target_topl_add_loo_{suf}"] = ([_vp, _vp, _i64, _i64, _int, _i64], _int)
+        s[f"ss_target_topl_add_kfold_{suf}"] = ([_vp, _vp, _vp, _int, _i64, _i64, _int, _i64, _int], _int)
+        s[f"ss_target_topl_export_{suf}"] = ([_vp, _vp, _vp, _vp, _vp, _vp, _int], _int)
+        s[f"ss_target_topl_import_{suf}"] = ([_vp, _vp, _vp, _vp, _vp, _i64, _int], _int)
     return s
 
 

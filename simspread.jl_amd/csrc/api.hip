@@ -2,6 +2,7 @@
 // reference methods each entry point stands behind).  Host-side orchestration only: argument
 // checks, staging of caller buffers, the stage-1 / stage-2 launch sequence, event timing.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <mutex>
 #include <new>
@@ -1913,6 +1914,418 @@ static int pool_metrics_impl(PoolBox<T>& p, double* out) {
   return pool_table_metrics(p.lv[0], p.npos, p.n - p.npos, p.w, out);
 }
 
+// ------------------------------------------------------------------ per-target top-L tables (target_topl.hip)
+// A handle: the committed table, a second one every add builds in, the counts and the scratch reused across adds.  An
+// add copies the table into the second buffer, streams its blocks into that copy and swaps the two only when every
+// block has gone in and no score was NaN: on any error the handle is as it was.
+constexpr uint32_t SS_TOPL_MAGIC = 0x4c504f54u;
+template <class T>
+struct TlBox : HandleHead {
+  uint32_t magic = SS_TOPL_MAGIC;
+  int64_t nt = 0, rows = 0, npos = 0;
+  int L = 0;
+  TlTable<pool_key_t<T>> t, nx;
+  TlWork<pool_key_t<T>> w;
+  int64_t fill() const { return rows < L ? rows : L; }
+};
+
+static int tl_dtype(const void* h, int* dtype) {
+  if (!h) return fail(SS_EINVAL, "target top-L handle is NULL");
+  const TlBox<float>* b = reinterpret_cast<const TlBox<float>*>(h);  // the head and the tag lie alike in both
+  if (b->magic != SS_TOPL_MAGIC || (b->dtype != 4 && b->dtype != 8)) return fail(SS_EINVAL, "not a target top-L handle");
+  *dtype = b->dtype;
+  return SS_OK;
+}
+
+template <class T>
+static int tl_check(const void* h, TlBox<T>** out) {
+  int dt = 0;
+  SS_TRY(tl_dtype(h, &dt));
+  if (dt != (int)sizeof(T)) return fail(SS_EINVAL, "target top-L handle was created with the other precision");
+  *out = const_cast<TlBox<T>*>(reinterpret_cast<const TlBox<T>*>(h));
+  return SS_OK;
+}
+
+template <class T>
+static int tl_create_impl(int64_t nt, int L, ss_target_topl** out) {
+  SS_TRY(require_init());
+  if (!out) return fail(SS_EINVAL, "out handle pointer is NULL");
+  *out = nullptr;
+  if (nt < 1 || nt >= (1LL << 31)) return fail(SS_EINVAL, "target top-L: nt = %lld outside [1, 2^31)", (long long)nt);
+  if (L < 1 || L > 1024) return fail(SS_EINVAL, "target top-L: L = %d outside [1, 1024]", L);
+  TlBox<T>* box = new (std::nothrow) TlBox<T>();
+  if (!box) return fail(SS_ENOMEM, "host allocation failed");
+  box->dtype = (int)sizeof(T);
+  box->nt = nt;
+  box->L = L;
+  int rc = tl_alloc(box->t, nt, L);
+  if (rc == SS_OK) rc = hipStreamSynchronize(ctx().stream) == hipSuccess ? SS_OK : fail(SS_EHIP, "stream sync failed");
+  if (rc != SS_OK) {
+    delete box;
+    return rc;
+  }
+  *out = reinterpret_cast<ss_target_topl*>(box);
+  return SS_OK;
+}
+
+// an add starts on a copy of the table ...
+template <class T>
+static int tl_start(TlBox<T>& b) {
+  SS_TRY(tl_copy(b.t, b.nx, b.nt, b.L, b.fill()));
+  return tl_begin(b.w, b.nt, b.L);
+}
+
+// ... which replaces the table once every block has gone in
+template <class T>
+static int tl_commit(TlBox<T>& b, int64_t nrows, int64_t npos) {
+  SS_TRY(tl_finish(b.w));
+  std::swap(b.t, b.nx);
+  b.rows += nrows;
+  b.npos += npos;
+  return SS_OK;
+}
+
+template <class T>
+static int tl_add_rows_impl(ss_target_topl* h, const int64_t* yptr, const int32_t* yidx, int base, const T* yhat,
+                            int64_t nrows, int64_t ncols, int64_t ld, int64_t row_begin, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  TlBox<T>* bp = nullptr;
+  SS_TRY(tl_check<T>(h, &bp));
+  TlBox<T>& b = *bp;
+  if (base != 0 && base != 1) return fail(SS_EINVAL, "index_base must be 0 or 1");
+  if (nrows < 0 || nrows >= (1LL << 31))
+    return fail(SS_EINVAL, "target top-L add rows: nrows = %lld outside [0, 2^31)", (long long)nrows);
+  if (ncols != b.nt)
+    return fail(SS_EINVAL, "target top-L add rows: ncols = %lld, the handle has nt = %lld", (long long)ncols,
+                (long long)b.nt);
+  if (ld < ncols)
+    return fail(SS_EINVAL, "target top-L add rows: leading dimension %lld < %lld", (long long)ld, (long long)ncols);
+  if (row_begin < 0 || row_begin > INT64_MAX - nrows)
+    return fail(SS_EINVAL, "target top-L add rows: row_begin = %lld out of range", (long long)row_begin);
+  if (nrows == 0) return SS_OK;
+  if (!yptr || !yhat) return fail(SS_EINVAL, "target top-L add rows: NULL buffer");
+  hipStream_t st = ctx().stream;
+  std::vector<int64_t> hp((size_t)nrows + 1);
+  if (mem == SS_MEM_HOST) memcpy(hp.data(), yptr, hp.size() * sizeof(int64_t));
+  else {
+    SS_HIP(hipMemcpyAsync(hp.data(), yptr, hp.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    SS_HIP(hipStreamSynchronize(st));
+  }
+  if (hp[0] < base) return fail(SS_EINVAL, "target top-L add rows: yptr[0] = %lld < index_base", (long long)hp[0]);
+  for (int64_t r = 0; r < nrows; ++r)
+    if (hp[r + 1] < hp[r] || hp[r + 1] - hp[r] > ncols)
+      return fail(SS_EINVAL, "target top-L add rows: row %lld has %lld labels (ncols %lld)", (long long)r,
+                  (long long)(hp[r + 1] - hp[r]), (long long)ncols);
+  const int64_t nnz = hp[nrows] - hp[0];
+  if (nnz > 0 && !yidx) return fail(SS_EINVAL, "target top-L add rows: NULL label index buffer");
+  timing_begin_call();
+  const int64_t* dptr = yptr;
+  const int* didx = yidx;
+  const T* dyhat = yhat;
+  int64_t dld = ld, shift = base;
+  DevBuf<int64_t> bptr;
+  DevBuf<int> bidx;
+  DevBuf<T> bhat;
+  if (mem == SS_MEM_HOST) {
+    SS_TRY(bptr.alloc((size_t)nrows + 1));
+    SS_TRY(bidx.alloc((size_t)nnz));
+    SS_TRY(bhat.alloc((size_t)nrows * ncols));
+    SS_TRY(upload<int64_t>(bptr.p, hp.data(), (size_t)nrows + 1, SS_MEM_HOST));
+    SS_TRY(upload<int>(bidx.p, yidx + (hp[0] - base), (size_t)nnz, SS_MEM_HOST));
+    SS_HIP(hipMemcpy2DAsync(bhat.p, ncols * sizeof(T), yhat, ld * sizeof(T), ncols * sizeof(T), nrows,
+                            hipMemcpyHostToDevice, st));
+    dptr = bptr.p;
+    didx = bidx.p;
+    dyhat = bhat.p;
+    dld = ncols;
+    shift = hp[0];
+  }
+  SS_TRY(launch_rank_rows_validate<int64_t>(dptr, shift, didx, base, nrows, ncols));
+  hipEvent_t e_begin, e_end;
+  SS_TRY(timing_mark(&e_begin));
+  SS_TRY(tl_start(b));
+  SS_TRY((tl_add_block<T, int64_t>(b.nx, b.nt, b.L, b.fill(), dptr, shift, didx, base, nnz, dyhat, nrows, dld,
+                                   row_begin, nullptr, b.w)));
+  SS_TRY(timing_mark(&e_end));
+  timing_span(ST_TOTAL, e_begin, e_end);
+  timing_span(ST_EPILOGUE, e_begin, e_end);
+  return tl_commit(b, nrows, nnz);
+}
+
+// leave-one-out folds into the table where they are produced: the blocks and checks of pool_add_loo_impl; row id =
+// source index
+template <class T>
+static int tl_add_loo_impl(ss_target_topl* th, ss_graph* h, int64_t i_begin, int64_t i_end, int clean,
+                           int64_t block_rows) {
+  SS_TRY(require_init());
+  TlBox<T>* bp = nullptr;
+  SS_TRY(tl_check<T>(th, &bp));
+  TlBox<T>& b = *bp;
+  Graph<T>* gp = nullptr;
+  SS_TRY(graph_check<T>(h, &gp));
+  Graph<T>& g = *gp;
+  if (g.general || (!g.dense.on && g.nq != 0) || g.ns != g.nf)
+    return fail(SS_EINVAL, "leave-one-out needs a graph with nq == 0 and ns == nf (feature j named after source j)");
+  if (i_begin < 0 || i_end < i_begin || i_end > g.ns)
+    return fail(SS_EINVAL, "row range [%lld,%lld) outside 0..%lld", (long long)i_begin, (long long)i_end,
+                (long long)g.ns);
+  if (block_rows < 0) return fail(SS_EINVAL, "target top-L add loo: block_rows must be >= 0");
+  if (g.nt != b.nt)
+    return fail(SS_EINVAL, "target top-L add loo: the graph has %lld targets, the handle %lld", (long long)g.nt,
+                (long long)b.nt);
+  const int64_t nrows = i_end - i_begin, nt = g.nt;
+  if (nrows == 0) return SS_OK;
+  hipStream_t st = ctx().stream;
+  int64_t rb = block_rows;
+  if (rb == 0) {
+    rb = (1LL << 30) / (nt * (int64_t)sizeof(T));  // about 1 GiB of scores
+    if (rb < 1) rb = 1;
+  }
+  if (rb > nrows) rb = nrows;
+  std::vector<int> hp((size_t)nrows + 1);
+  SS_HIP(hipMemcpyAsync(hp.data(), g.Ys.ptr.p + i_begin, hp.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  DevBuf<T> scores;
+  SS_TRY(scores.alloc((size_t)rb * nt));
+  timing_begin_call();
+  hipEvent_t e_begin, e_end;
+  SS_TRY(timing_mark(&e_begin));
+  {
+    StageTimer t3(ST_EPILOGUE);
+    SS_TRY(tl_start(b));
+  }
+  int64_t fill = b.fill();
+  for (int64_t r0 = 0; r0 < nrows; r0 += rb) {
+    const int64_t nb = nrows - r0 < rb ? nrows - r0 : rb;
+    SS_TRY(predict_rows_device<T>(g, 2, i_begin + r0, i_begin + r0 + nb, clean, scores.p, nt));
+    StageTimer t3(ST_EPILOGUE);
+    SS_TRY((tl_add_block<T, int>(b.nx, nt, b.L, fill, g.Ys.ptr.p + i_begin + r0, 0, g.Ys.idx.p, 0,
+                                 (int64_t)(hp[r0 + nb] - hp[r0]), scores.p, nb, nt, i_begin + r0, nullptr, b.w)));
+    fill = fill + nb < b.L ? fill + nb : b.L;
+  }
+  SS_TRY(timing_mark(&e_end));
+  timing_span(ST_TOTAL, e_begin, e_end);
+  return tl_commit(b, nrows, (int64_t)(hp[nrows] - hp[0]));
+}
+
+// k-fold rows into the table where they are produced: the blocks, label gather and checks of pool_add_kfold_impl; a
+// block's rows are its members (fold order), each under its source index
+template <class T>
+static int tl_add_kfold_impl(ss_target_topl* th, ss_graph* h, const int32_t* fold_of_source, int nfolds, int64_t i_begin,
+                             int64_t i_end, int clean, int64_t block_rows, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  TlBox<T>* bp = nullptr;
+  SS_TRY(tl_check<T>(th, &bp));
+  TlBox<T>& b = *bp;
+  Graph<T>* gp = nullptr;
+  SS_TRY(graph_check<T>(h, &gp));
+  Graph<T>& g = *gp;
+  SS_TRY(kfold_graph_check(g));
+  SS_TRY(kfold_range_check(i_begin, i_end, g.ns));
+  if (block_rows < 0) return fail(SS_EINVAL, "target top-L add kfold: block_rows must be >= 0");
+  if (g.nt != b.nt)
+    return fail(SS_EINVAL, "target top-L add kfold: the graph has %lld targets, the handle %lld", (long long)g.nt,
+                (long long)b.nt);
+  KfoldPlan plan;
+  SS_TRY(kfold_plan(fold_of_source, nfolds, g.ns, mem, plan));
+  const int64_t nrows = i_end - i_begin, nt = g.nt;
+  if (nrows == 0) return SS_OK;
+  hipStream_t st = ctx().stream;
+  int64_t rb = block_rows;
+  if (rb == 0) {
+    rb = (1LL << 30) / (nt * (int64_t)sizeof(T));  // about 1 GiB of scores
+    if (rb < 1) rb = 1;
+  }
+  if (rb > nrows) rb = nrows;
+  KfoldRange rg;
+  kfold_range(plan, i_begin, i_end, rg);
+  std::vector<int> map(rg.sel.size());
+  for (size_t q = 0; q < map.size(); ++q) map[q] = (int)(rg.sel[q] - i_begin);
+  KfoldWork<T> w;
+  SS_TRY(kfold_work_init<T>(g, plan, rg, map, w));
+  std::vector<int> hy((size_t)nrows + 1);
+  SS_HIP(hipMemcpyAsync(hy.data(), g.Ys.ptr.p + i_begin, hy.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  std::vector<int64_t> pptr((size_t)nrows + 1, 0);
+  for (int64_t q = 0; q < nrows; ++q) pptr[q + 1] = pptr[q] + (hy[map[q] + 1] - hy[map[q]]);
+  int64_t max_lab = 1;
+  for (int64_t p0 = 0; p0 < nrows; p0 += rb) {
+    const int64_t p1 = nrows - p0 < rb ? nrows : p0 + rb;
+    if (pptr[p1] - pptr[p0] > max_lab) max_lab = pptr[p1] - pptr[p0];
+  }
+  DevBuf<int64_t> d_pptr;
+  DevBuf<int> lab;
+  DevBuf<T> scores;
+  SS_TRY(d_pptr.alloc((size_t)nrows + 1));
+  SS_TRY(lab.alloc((size_t)max_lab));
+  SS_TRY(scores.alloc((size_t)rb * nt));
+  SS_HIP(hipMemcpyAsync(d_pptr.p, pptr.data(), pptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  SS_TRY(graph_sell(g));
+  if (!g.dense.on) SS_TRY(graph_chunked(g, false));
+  timing_begin_call();
+  hipEvent_t e_begin, e_end;
+  SS_TRY(timing_mark(&e_begin));
+  {
+    StageTimer t3(ST_EPILOGUE);
+    SS_TRY(tl_start(b));
+  }
+  int64_t fill = b.fill();
+  for (int64_t p0 = 0; p0 < nrows; p0 += rb) {
+    const int64_t nb = nrows - p0 < rb ? nrows - p0 : rb;
+    SS_TRY(kfold_rows_device<T>(g, w, plan, rg, p0, p0 + nb, clean, scores.p, nt, nullptr));
+    StageTimer t3(ST_EPILOGUE);
+    SS_TRY(launch_gather_labels(g.Ys.ptr.p, g.Ys.idx.p, w.d_sel.p + p0, nb, d_pptr.p + p0, pptr[p0], lab.p));
+    SS_TRY((tl_add_block<T, int64_t>(b.nx, nt, b.L, fill, d_pptr.p + p0, pptr[p0], lab.p, 0, pptr[p0 + nb] - pptr[p0],
+                                     scores.p, nb, nt, 0, w.d_sel.p + p0, b.w)));
+    fill = fill + nb < b.L ? fill + nb : b.L;
+  }
+  SS_TRY(timing_mark(&e_end));
+  timing_span(ST_TOTAL, e_begin, e_end);
+  return tl_commit(b, nrows, pptr[nrows]);
+}
+
+template <class T>
+static int tl_merge_impl(ss_target_topl* dh, const ss_target_topl* sh) {
+  SS_TRY(require_init());
+  TlBox<T>* d = nullptr;
+  TlBox<T>* s = nullptr;
+  SS_TRY(tl_check<T>(dh, &d));
+  SS_TRY(tl_check<T>(sh, &s));
+  if (d->nt != s->nt || d->L != s->L)
+    return fail(SS_EINVAL, "target top-L merge: nt / L differ (%lld, %d) vs (%lld, %d)", (long long)d->nt, d->L,
+                (long long)s->nt, s->L);
+  timing_begin_call();
+  const int64_t rows = s->rows, npos = s->npos;  // read before d's counts change (d may be s)
+  SS_TRY(tl_merge_tables(d->t, d->fill(), s->t, s->fill(), d->nt, d->L, d->nx));
+  SS_HIP(hipStreamSynchronize(ctx().stream));
+  std::swap(d->t, d->nx);
+  d->rows += rows;
+  d->npos += npos;
+  return SS_OK;
+}
+
+template <class T>
+static int tl_export_impl(ss_target_topl* h, T* vals, int64_t* rows, uint8_t* labels, int64_t* npos,
+                          int64_t* rows_added, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  TlBox<T>* bp = nullptr;
+  SS_TRY(tl_check<T>(h, &bp));
+  TlBox<T>& b = *bp;
+  if (rows_added) *rows_added = b.rows;
+  const int64_t fill = b.fill(), n = b.nt * fill;
+  hipStream_t st = ctx().stream;
+  if (mem == SS_MEM_DEVICE) {
+    SS_TRY(tl_export_table<T>(b.t, b.nt, b.L, fill, vals, rows, labels));
+    if (npos) SS_HIP(hipMemcpyAsync(npos, b.t.npos.p, (size_t)b.nt * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+  } else {
+    DevBuf<T> v;
+    DevBuf<int64_t> r;
+    DevBuf<uint8_t> l;
+    if (vals) SS_TRY(v.alloc((size_t)n));
+    if (rows) SS_TRY(r.alloc((size_t)n));
+    if (labels) SS_TRY(l.alloc((size_t)n));
+    SS_TRY(tl_export_table<T>(b.t, b.nt, b.L, fill, vals ? v.p : nullptr, rows ? r.p : nullptr, labels ? l.p : nullptr));
+    if (vals && n) SS_HIP(hipMemcpyAsync(vals, v.p, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, st));
+    if (rows && n) SS_HIP(hipMemcpyAsync(rows, r.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (labels && n) SS_HIP(hipMemcpyAsync(labels, l.p, (size_t)n, hipMemcpyDeviceToHost, st));
+    if (npos) SS_HIP(hipMemcpyAsync(npos, b.t.npos.p, (size_t)b.nt * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    SS_HIP(hipStreamSynchronize(st));
+  }
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
+}
+
+template <class T>
+static int tl_import_impl(ss_target_topl* h, const T* vals, const int64_t* rows, const uint8_t* labels,
+                          const int64_t* npos, int64_t rows_added, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  TlBox<T>* bp = nullptr;
+  SS_TRY(tl_check<T>(h, &bp));
+  TlBox<T>& b = *bp;
+  if (rows_added < 0) return fail(SS_EINVAL, "target top-L import: rows_added = %lld < 0", (long long)rows_added);
+  if (rows_added > INT64_MAX - b.rows) return fail(SS_EINVAL, "target top-L import: rows_added overflows");
+  if (rows_added == 0) return SS_OK;
+  const int64_t fill = rows_added < b.L ? rows_added : b.L, n = b.nt * fill;
+  if (!vals || !rows || !labels || !npos) return fail(SS_EINVAL, "target top-L import: NULL buffer");
+  timing_begin_call();
+  const T* dv = vals;
+  const int64_t* dr = rows;
+  const uint8_t* dl = labels;
+  const int64_t* dn = npos;
+  DevBuf<T> bv;
+  DevBuf<int64_t> br, bn;
+  DevBuf<uint8_t> bl;
+  if (mem == SS_MEM_HOST) {
+    SS_TRY(bv.alloc((size_t)n));
+    SS_TRY(br.alloc((size_t)n));
+    SS_TRY(bl.alloc((size_t)n));
+    SS_TRY(bn.alloc((size_t)b.nt));
+    SS_TRY(upload<T>(bv.p, vals, (size_t)n, SS_MEM_HOST));
+    SS_TRY(upload<int64_t>(br.p, rows, (size_t)n, SS_MEM_HOST));
+    SS_TRY(upload<uint8_t>(bl.p, labels, (size_t)n, SS_MEM_HOST));
+    SS_TRY(upload<int64_t>(bn.p, npos, (size_t)b.nt, SS_MEM_HOST));
+    dv = bv.p;
+    dr = br.p;
+    dl = bl.p;
+    dn = bn.p;
+  }
+  TlTable<pool_key_t<T>> src;
+  int64_t P = 0;
+  SS_TRY(tl_import_table<T>(dv, dr, dl, dn, b.nt, b.L, fill, src, &P));
+  SS_TRY(tl_merge_tables(b.t, b.fill(), src, fill, b.nt, b.L, b.nx));
+  SS_HIP(hipStreamSynchronize(ctx().stream));
+  std::swap(b.t, b.nx);
+  b.rows += rows_added;
+  b.npos += P;
+  return SS_OK;
+}
+
+template <class T>
+static int tl_metrics_impl(TlBox<T>& b, int64_t* hits, int64_t* npos, double* out, int mem) {
+  SS_TRY(check_mem(mem));
+  if (b.rows <= b.L)
+    return fail(SS_EINVAL, "target top-L metrics: %lld rows added, recall@L needs more than L = %d", (long long)b.rows,
+                b.L);
+  timing_begin_call();
+  hipStream_t st = ctx().stream;
+  const int64_t nt = b.nt;
+  DevBuf<int64_t> dh;
+  SS_TRY(dh.alloc((size_t)nt));
+  SS_TRY(tl_hits(b.t, nt, b.L, b.fill(), dh.p));
+  std::vector<int64_t> hh((size_t)nt), hn((size_t)nt);
+  SS_HIP(hipMemcpyAsync(hh.data(), dh.p, (size_t)nt * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipMemcpyAsync(hn.data(), b.t.npos.p, (size_t)nt * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  if (hits) SS_HIP(hipMemcpyAsync(hits, dh.p, (size_t)nt * sizeof(int64_t),
+                                  mem == SS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+  if (npos) SS_HIP(hipMemcpyAsync(npos, b.t.npos.p, (size_t)nt * sizeof(int64_t),
+                                  mem == SS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+  SS_HIP(hipStreamSynchronize(st));
+  // sums in target order, as Julia's mean over the groups in first-seen order
+  double rec = 0.0, prec = 0.0, rec_pos = 0.0;
+  int64_t with_pos = 0;
+  const double Ld = (double)b.L;
+  for (int64_t t = 0; t < nt; ++t) {
+    const double h = (double)hh[(size_t)t];
+    const int64_t p = hn[(size_t)t];
+    const double r = p > 0 ? h / (double)p : std::nan("");
+    rec += r;
+    prec += h / Ld;
+    if (p > 0) {
+      rec_pos += r;
+      ++with_pos;
+    }
+  }
+  out[0] = rec / (double)nt;
+  out[1] = prec / (double)nt;
+  out[2] = with_pos > 0 ? rec_pos / (double)with_pos : std::nan("");
+  out[3] = (double)with_pos;
+  return SS_OK;
+}
+
 // ------------------------------------------------------------------ raw SpMM
 template <class T>
 static int spmat_check(const void* h, SpMat<T>** out) {
@@ -2939,6 +3352,162 @@ int ss_pool_metrics(ss_pool* pool, double out[21]) {
   SS_HANDLE_LOCK(pool);
   return dt == 4 ? pool_metrics_impl(*reinterpret_cast<PoolBox<float>*>(pool), out)
                  : pool_metrics_impl(*reinterpret_cast<PoolBox<double>*>(pool), out);
+}
+
+// ------------------------------------------------------------------ per-target top-L tables
+int ss_target_topl_create_f32(int64_t nt, int L, ss_target_topl** out) {
+  SS_API_LOCK();
+  return tl_create_impl<float>(nt, L, out);
+}
+int ss_target_topl_create_f64(int64_t nt, int L, ss_target_topl** out) {
+  SS_API_LOCK();
+  return tl_create_impl<double>(nt, L, out);
+}
+int ss_target_topl_destroy(ss_target_topl* h) {
+  SS_API_LOCK();
+  if (!h) return SS_OK;
+  int dt = 0;
+  SS_TRY(tl_dtype(h, &dt));
+  {  // wait for a call that still works on the handle (the caller must not start new ones), then for the device
+    SS_HANDLE_LOCK(h);
+    if (ctx().inited) (void)hipStreamSynchronize(ctx().stream);
+  }
+  if (dt == 4) delete reinterpret_cast<TlBox<float>*>(h);
+  else delete reinterpret_cast<TlBox<double>*>(h);
+  return SS_OK;
+}
+int ss_target_topl_reset(ss_target_topl* h) {
+  SS_API_LOCK();
+  int dt = 0;
+  SS_TRY(tl_dtype(h, &dt));
+  SS_HANDLE_LOCK(h);
+  SS_TRY(require_init());
+  auto clear = [](auto* b) -> int {
+    SS_HIP(hipStreamSynchronize(ctx().stream));
+    SS_HIP(hipMemsetAsync(b->t.npos.p, 0, (size_t)b->nt * sizeof(int64_t), ctx().stream));
+    SS_HIP(hipStreamSynchronize(ctx().stream));
+    b->rows = b->npos = 0;
+    return SS_OK;
+  };
+  return dt == 4 ? clear(reinterpret_cast<TlBox<float>*>(h)) : clear(reinterpret_cast<TlBox<double>*>(h));
+}
+int ss_target_topl_info(const ss_target_topl* h, int64_t info[4]) {
+  SS_API_LOCK();
+  int dt = 0;
+  SS_TRY(tl_dtype(h, &dt));
+  if (!info) return fail(SS_EINVAL, "NULL argument");
+  SS_HANDLE_LOCK(h);
+  auto fill = [&](const auto* b) {
+    info[0] = b->nt;
+    info[1] = b->L;
+    info[2] = b->rows;
+    info[3] = b->npos;
+  };
+  if (dt == 4) fill(reinterpret_cast<const TlBox<float>*>(h));
+  else fill(reinterpret_cast<const TlBox<double>*>(h));
+  return SS_OK;
+}
+int ss_target_topl_add_rows_f32(ss_target_topl* h, const int64_t* yptr, const int32_t* yidx, int index_base,
+                                const float* yhat, int64_t nrows, int64_t ncols, int64_t ld, int64_t row_begin,
+                                int mem) {
+  SS_API_LOCK();
+  if (!h) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  return tl_add_rows_impl<float>(h, yptr, yidx, index_base, yhat, nrows, ncols, ld, row_begin, mem);
+}
+int ss_target_topl_add_rows_f64(ss_target_topl* h, const int64_t* yptr, const int32_t* yidx, int index_base,
+                                const double* yhat, int64_t nrows, int64_t ncols, int64_t ld, int64_t row_begin,
+                                int mem) {
+  SS_API_LOCK();
+  if (!h) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  return tl_add_rows_impl<double>(h, yptr, yidx, index_base, yhat, nrows, ncols, ld, row_begin, mem);
+}
+// a table and a graph: the table's lock first, always
+int ss_target_topl_add_loo_f32(ss_target_topl* h, ss_graph* g, int64_t i_begin, int64_t i_end, int clean,
+                               int64_t block_rows) {
+  SS_API_LOCK();
+  if (!h || !g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  std::unique_lock<std::mutex> _graph_guard(reinterpret_cast<HandleHead*>(g)->mu);
+  return tl_add_loo_impl<float>(h, g, i_begin, i_end, clean, block_rows);
+}
+int ss_target_topl_add_loo_f64(ss_target_topl* h, ss_graph* g, int64_t i_begin, int64_t i_end, int clean,
+                               int64_t block_rows) {
+  SS_API_LOCK();
+  if (!h || !g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  std::unique_lock<std::mutex> _graph_guard(reinterpret_cast<HandleHead*>(g)->mu);
+  return tl_add_loo_impl<double>(h, g, i_begin, i_end, clean, block_rows);
+}
+int ss_target_topl_add_kfold_f32(ss_target_topl* h, ss_graph* g, const int32_t* fold_of_source, int nfolds,
+                                 int64_t i_begin, int64_t i_end, int clean, int64_t block_rows, int mem) {
+  SS_API_LOCK();
+  if (!h || !g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  std::unique_lock<std::mutex> _graph_guard(reinterpret_cast<HandleHead*>(g)->mu);
+  return tl_add_kfold_impl<float>(h, g, fold_of_source, nfolds, i_begin, i_end, clean, block_rows, mem);
+}
+int ss_target_topl_add_kfold_f64(ss_target_topl* h, ss_graph* g, const int32_t* fold_of_source, int nfolds,
+                                 int64_t i_begin, int64_t i_end, int clean, int64_t block_rows, int mem) {
+  SS_API_LOCK();
+  if (!h || !g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  std::unique_lock<std::mutex> _graph_guard(reinterpret_cast<HandleHead*>(g)->mu);
+  return tl_add_kfold_impl<double>(h, g, fold_of_source, nfolds, i_begin, i_end, clean, block_rows, mem);
+}
+int ss_target_topl_merge(ss_target_topl* dst, const ss_target_topl* src) {
+  SS_API_LOCK();
+  int dd = 0, ds = 0;
+  SS_TRY(tl_dtype(dst, &dd));
+  SS_TRY(tl_dtype(src, &ds));
+  if (dd != ds) return fail(SS_EINVAL, "target top-L merge: the handles have different precisions");
+  // two different handles: their locks in address order, so that merge(a, b) and merge(b, a) cannot deadlock
+  HandleHead* a = reinterpret_cast<HandleHead*>(dst);
+  HandleHead* b = reinterpret_cast<HandleHead*>(const_cast<ss_target_topl*>(src));
+  if (b < a) std::swap(a, b);
+  std::unique_lock<std::mutex> la(a->mu);
+  std::unique_lock<std::mutex> lb;
+  if (b != a) lb = std::unique_lock<std::mutex>(b->mu);
+  return dd == 4 ? tl_merge_impl<float>(dst, src) : tl_merge_impl<double>(dst, src);
+}
+int ss_target_topl_export_f32(ss_target_topl* h, float* vals, int64_t* rows, uint8_t* labels, int64_t* npos,
+                              int64_t* rows_added, int mem) {
+  SS_API_LOCK();
+  if (!h) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  return tl_export_impl<float>(h, vals, rows, labels, npos, rows_added, mem);
+}
+int ss_target_topl_export_f64(ss_target_topl* h, double* vals, int64_t* rows, uint8_t* labels, int64_t* npos,
+                              int64_t* rows_added, int mem) {
+  SS_API_LOCK();
+  if (!h) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  return tl_export_impl<double>(h, vals, rows, labels, npos, rows_added, mem);
+}
+int ss_target_topl_import_f32(ss_target_topl* h, const float* vals, const int64_t* rows, const uint8_t* labels,
+                              const int64_t* npos, int64_t rows_added, int mem) {
+  SS_API_LOCK();
+  if (!h) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  return tl_import_impl<float>(h, vals, rows, labels, npos, rows_added, mem);
+}
+int ss_target_topl_import_f64(ss_target_topl* h, const double* vals, const int64_t* rows, const uint8_t* labels,
+                              const int64_t* npos, int64_t rows_added, int mem) {
+  SS_API_LOCK();
+  if (!h) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  return tl_import_impl<double>(h, vals, rows, labels, npos, rows_added, mem);
+}
+int ss_target_topl_metrics(ss_target_topl* h, int64_t* hits, int64_t* npos, double out[4], int mem) {
+  SS_API_LOCK();
+  SS_TRY(require_init());
+  int dt = 0;
+  SS_TRY(tl_dtype(h, &dt));
+  if (!out) return fail(SS_EINVAL, "NULL argument");
+  SS_HANDLE_LOCK(h);
+  return dt == 4 ? tl_metrics_impl(*reinterpret_cast<TlBox<float>*>(h), hits, npos, out, mem)
+                 : tl_metrics_impl(*reinterpret_cast<TlBox<double>*>(h), hits, npos, out, mem);
 }
 
 }  // extern "C"

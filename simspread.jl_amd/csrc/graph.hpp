@@ -292,6 +292,56 @@ int pool_export_table(const PoolTable<pool_key_t<T>>& t, T* v);
 // the 21 pooled numbers of one table (host out)
 template <class K>
 int pool_table_metrics(const PoolTable<K>& t, int64_t P, int64_t N, PoolWork<K>& w, double* out);
+// ---- target_topl.hip: per target the L best rows under (score desc by isless, row asc).  Entry j of target t lies at
+// t*L + j of key / row / lab; the first `fill` entries of every target are valid and sorted.  Keys are order-preserving
+// unsigned images of the scores WITHOUT -0.0 -> +0.0 (isless ranks +0.0 before -0.0).
+template <class K>
+struct TlTable {
+  DevBuf<K> key;
+  DevBuf<int64_t> row;
+  DevBuf<uint8_t> lab;
+  DevBuf<int64_t> npos;  // nt positives seen per target
+};
+template <class K>
+struct TlWork {  // scratch reused across blocks
+  int64_t cap = 0;  // candidates kept per target per block (more: the long-list route)
+  DevBuf<K> ck, thk;
+  DevBuf<int64_t> cr, thr;
+  DevBuf<uint8_t> cl;
+  DevBuf<int> cnt, act, ovf, ctr, flag;
+};
+template <class K>
+int tl_alloc(TlTable<K>& t, int64_t nt, int L);
+// b = a (the first `fill` entries of every target and npos)
+template <class K>
+int tl_copy(const TlTable<K>& a, TlTable<K>& b, int64_t nt, int L, int64_t fill);
+// scratch for one add; clears the add's flags
+template <class K>
+int tl_begin(TlWork<K>& w, int64_t nt, int L);
+// One row-major score block (nb x nt, ld) into t, enqueued only: its rows are row_begin + r (rowmap == NULL) or
+// rowmap[r]; labels as for launch_rank_rows (checked beforehand).  fill: entries per target before the block.
+template <class T, class PtrT>
+int tl_add_block(TlTable<pool_key_t<T>>& t, int64_t nt, int L, int64_t fill, const PtrT* yptr, int64_t shift,
+                 const int* yidx, int base, int64_t nnz, const T* yhat, int64_t nb, int64_t ld, int64_t row_begin,
+                 const int* rowmap, TlWork<pool_key_t<T>>& w);
+// the add's verdict (syncs): SS_EINVAL when a score was NaN; names the long-list route when it ran
+template <class K>
+int tl_finish(TlWork<K>& w);
+// out = top L of a (fa entries per target) and b (fb), npos added
+template <class K>
+int tl_merge_tables(const TlTable<K>& a, int64_t fa, const TlTable<K>& b, int64_t fb, int64_t nt, int L,
+                    TlTable<K>& out);
+// a caller's table (device arrays, nt x fill row-major) checked and keyed into out (fill <= L)
+template <class T>
+int tl_import_table(const T* vals, const int64_t* rows, const uint8_t* labels, const int64_t* npos, int64_t nt, int L,
+                    int64_t fill, TlTable<pool_key_t<T>>& out, int64_t* P);
+// the table as nt x fill row-major device arrays (any of them may be NULL)
+template <class T>
+int tl_export_table(const TlTable<pool_key_t<T>>& t, int64_t nt, int L, int64_t fill, T* vals, int64_t* rows,
+                    uint8_t* labels);
+// hits[t] = positives among target t's entries (device)
+template <class K>
+int tl_hits(const TlTable<K>& t, int64_t nt, int L, int64_t fill, int64_t* hits);
 // ---- dense.hip (fp32 only: fp32-input MFMA)
 int launch_transfer_dense(const DenseSim<float>& d, bool loo, const float* inv_k, const float* inv_n, const int* ks,
                           int64_t row_begin, int64_t nrows, float* out, int64_t ldo, bool source_rows = false);

@@ -166,3 +166,24 @@ def pooled_metrics(pool, group=None, root: int = 0):
         return total.metrics()
     finally:
         total.close()
+
+
+def target_topl(handle, group=None, root: int = 0):
+    """The per-target top-L table of a sharded sweep: every rank has added its own rows (TargetTopL.add_loo / add_kfold
+    over its shard_range, no collective on the data path); here each rank exports its table once and the root imports
+    all of them, in rank order, into a fresh handle.  Returns that TargetTopL on the root (its metrics() / table() are
+    the sweep's), None elsewhere; the caller's handle is not changed.  The tables travel through torch.distributed
+    (gather_object)."""
+    import torch.distributed as dist
+    from .engine import TargetTopL
+    table = handle.export()
+    info = handle.info()
+    rank = dist.get_rank(group)
+    tables = [None] * dist.get_world_size(group) if rank == root else None
+    dist.gather_object(table, tables, dst=_global_rank(root, group), group=group)
+    if rank != root:
+        return None
+    total = TargetTopL(info["nt"], info["L"], handle.dtype)
+    for vals, rows, labels, npos, rows_added in tables:
+        total.import_(vals, rows, labels, npos, rows_added)
+    return total

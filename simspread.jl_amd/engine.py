@@ -955,6 +955,196 @@ class Pool:
             pass
 
 
+TARGET_TOPL_FIELDS = ("recallatL", "precisionatL", "recall_with_positives", "targets_with_positives")
+
+
+class TargetTopL:
+    """Per target the L best rows seen so far, on the device (ss_target_topl_*): recallatL(y, yhat, grouping, L) and
+    precisionatL with grouping = the target of every entry of vec(yhat) (src/performance.jl:308-409), and each target's
+    screening list -- its L best rows under (score descending, row ascending), the order Julia's stable sortperm gives
+    inside a target group.  Row ids are int64 >= 0 and must be distinct across adds; adds are all or nothing, and the
+    table is one and the same whatever the blocks, their order, merges or export -> import."""
+
+    def __init__(self, nt: int, L: int = 20, dtype=np.float32):
+        self.dtype = np.dtype(dtype)
+        self._suf = _suffix(dtype)
+        h = C.c_void_p()
+        L_.check(getattr(L_.lib(), f"ss_target_topl_create_{self._suf}")(int(nt), int(L), C.byref(h)))
+        self._h = h
+
+    def info(self) -> dict:
+        """nt, L, rows added, positives among them"""
+        buf = (C.c_int64 * 4)()
+        L_.check(L_.lib().ss_target_topl_info(self._h, buf))
+        return dict(nt=int(buf[0]), L=int(buf[1]), rows=int(buf[2]), npos=int(buf[3]))
+
+    def reset(self):
+        L_.check(L_.lib().ss_target_topl_reset(self._h))
+        return self
+
+    def add_rows(self, y, yhat, row_begin: int = 0):
+        """Add the rows of a score block (nrows, nt): row r gets the id row_begin + r.  `y` and `yhat` as Pool.add_rows
+        takes them (numpy or a contiguous CUDA tensor; labels scipy / dense 0/1 / a 0-based (ptr int64, idx int32) CSR
+        pair, on the host or, with device scores, on the device)."""
+        torch_in = _is_torch(yhat)
+        if torch_in:
+            import torch
+            if yhat.dim() == 1:
+                yhat = yhat.reshape(1, -1)
+            if yhat.dim() != 2 or not yhat.is_contiguous() or not yhat.is_cuda:
+                raise ValueError("yhat must be a contiguous 1-D or 2-D CUDA tensor")
+            if {torch.float32: "f32", torch.float64: "f64"}.get(yhat.dtype) != self._suf:
+                raise TypeError("yhat dtype does not match the table precision")
+            nrows, ncols = (int(v) for v in yhat.shape)
+        else:
+            a = np.asarray(yhat)
+            if a.ndim == 1:
+                a = a.reshape(1, -1)
+            if a.ndim != 2:
+                raise ValueError("yhat must be 1-D or 2-D")
+            if a.dtype != self.dtype:
+                raise TypeError("yhat dtype does not match the table precision")
+            a = np.ascontiguousarray(a)
+            nrows, ncols = a.shape
+        if not isinstance(y, tuple) and not hasattr(y, "tocsr"):
+            y = np.asarray(y).reshape(nrows, ncols)
+        dev_labels = isinstance(y, tuple) and _is_torch(y[0])
+        fn = getattr(L_.lib(), f"ss_target_topl_add_rows_{self._suf}")
+        if dev_labels:
+            if not torch_in:
+                raise TypeError("device labels need device scores (a CUDA tensor yhat)")
+            ptr_d, idx_d = y[0].contiguous(), y[1].contiguous()
+        else:
+            hp, hi = _label_csr(y, nrows, ncols)
+            _check_label_order(hp, hi, ncols)
+        if torch_in:
+            import torch
+            if not dev_labels:
+                ptr_d = torch.from_numpy(hp).to(yhat.device)
+                idx_d = torch.from_numpy(hi if hi.size else np.zeros(1, np.int32)).to(yhat.device)
+            L_.check(fn(self._h, ptr_d.data_ptr(), idx_d.data_ptr(), 0, yhat.data_ptr(), nrows, ncols, ncols,
+                        int(row_begin), L_.SS_MEM_DEVICE))
+        else:
+            L_.check(fn(self._h, hp.ctypes.data, hi.ctypes.data, 0, a.ctypes.data, nrows, ncols, ncols, int(row_begin),
+                        L_.SS_MEM_HOST))
+        return self
+
+    def add_loo(self, g: "DeviceGraph", i_begin: int = 0, i_end: Optional[int] = None, clean: bool = False,
+                block_rows: int = 0):
+        """Add the leave-one-out folds [i_begin, i_end) of `g` against its own labels, fold i as row i
+        (ss_target_topl_add_loo_*)."""
+        i_end = g.ns if i_end is None else i_end
+        fn = getattr(L_.lib(), f"ss_target_topl_add_loo_{self._suf}")
+        L_.check(fn(self._h, g._h, int(i_begin), int(i_end), 1 if clean else 0, int(block_rows)))
+        return self
+
+    def add_kfold(self, g: "DeviceGraph", fold_of_source, nfolds: Optional[int] = None, i_begin: int = 0,
+                  i_end: Optional[int] = None, clean: bool = False, block_rows: int = 0):
+        """Add the k-fold rows [i_begin, i_end) of `g` against its own labels, source i as row i
+        (ss_target_topl_add_kfold_*)."""
+        fold, nfolds = g._folds(fold_of_source, nfolds)
+        i_end = g.ns if i_end is None else i_end
+        fn = getattr(L_.lib(), f"ss_target_topl_add_kfold_{self._suf}")
+        L_.check(fn(self._h, g._h, fold.ctypes.data, nfolds, int(i_begin), int(i_end), 1 if clean else 0,
+                    int(block_rows), L_.SS_MEM_HOST))
+        return self
+
+    def add_predict(self, g: "DeviceGraph", rows: str = "query", begin: int = 0, end: Optional[int] = None,
+                    clean: bool = False, y=None, block_rows: int = 0):
+        """Virtual screening: the scores of rows [begin, end) of the query (or source) nodes, predicted block by block
+        into a device buffer (DeviceGraph.predict(..., out=tensor)) and added with row ids begin..end-1.  `y`: labels
+        of those rows (scipy / dense 0/1, shape (end - begin, nt)) or None -- unlabelled rows count as negatives.
+        block_rows: rows per block (0: about 1 GiB of scores)."""
+        import scipy.sparse as sp
+        import torch
+        limit = g.nq if rows == "query" else g.ns
+        end = limit if end is None else end
+        n = end - begin
+        if n <= 0:
+            return self
+        nt = g.nt
+        if y is None:
+            Y = sp.csr_matrix((n, nt), dtype=np.float64)
+        else:
+            Y = sp.csr_matrix(y)
+            if Y.shape != (n, nt):
+                raise ValueError(f"labels have shape {Y.shape}, expected {(n, nt)}")
+        rb = int(block_rows) if block_rows > 0 else max(1, (1 << 30) // (nt * self.dtype.itemsize))
+        rb = min(rb, n)
+        buf = torch.empty((rb, nt), dtype=torch.float32 if self._suf == "f32" else torch.float64, device="cuda")
+        for r0 in range(0, n, rb):
+            nb = min(rb, n - r0)
+            out = buf[:nb]
+            g.predict(rows, begin + r0, begin + r0 + nb, clean=clean, out=out)
+            self.add_rows(Y[r0:r0 + nb], out, row_begin=begin + r0)
+        return self
+
+    def merge(self, other: "TargetTopL"):
+        """Add every row of `other` (unchanged) to this table."""
+        L_.check(L_.lib().ss_target_topl_merge(self._h, other._h))
+        return self
+
+    def export(self):
+        """(scores, rows int64, labels uint8) as (nt, fill) numpy arrays, npos (nt,) int64 and the rows added."""
+        i = self.info()
+        fill = min(i["L"], i["rows"])
+        vals = np.empty((i["nt"], fill), self.dtype)
+        rows = np.empty((i["nt"], fill), np.int64)
+        labels = np.empty((i["nt"], fill), np.uint8)
+        npos = np.empty(i["nt"], np.int64)
+        n = C.c_int64()
+        fn = getattr(L_.lib(), f"ss_target_topl_export_{self._suf}")
+        L_.check(fn(self._h, vals.ctypes.data, rows.ctypes.data, labels.ctypes.data, npos.ctypes.data, C.byref(n),
+                    L_.SS_MEM_HOST))
+        return vals, rows, labels, npos, int(n.value)
+
+    def import_(self, vals, rows, labels, npos, rows_added: int):
+        """Add a table such as export() returns (another rank's, for instance)."""
+        i = self.info()
+        fill = min(i["L"], int(rows_added))
+        v = np.ascontiguousarray(vals, dtype=self.dtype)
+        r = np.ascontiguousarray(rows, dtype=np.int64)
+        lab = np.ascontiguousarray(labels, dtype=np.uint8)
+        p = np.ascontiguousarray(npos, dtype=np.int64)
+        if rows_added > 0 and not (v.shape == r.shape == lab.shape == (i["nt"], fill) and p.shape == (i["nt"],)):
+            raise ValueError(f"the table must be (nt, fill) = {(i['nt'], fill)} arrays and npos (nt,)")
+        fn = getattr(L_.lib(), f"ss_target_topl_import_{self._suf}")
+        L_.check(fn(self._h, v.ctypes.data, r.ctypes.data, lab.ctypes.data, p.ctypes.data, int(rows_added),
+                    L_.SS_MEM_HOST))
+        return self
+
+    def table(self):
+        """(rows, scores, labels) of every target's list as (nt, fill) numpy arrays: row [t] is target t's screening
+        result, best first."""
+        vals, rows, labels, _, _ = self.export()
+        return rows, vals, labels
+
+    def metrics(self) -> dict:
+        """TARGET_TOPL_FIELDS (recallatL and precisionatL exactly as the reference's grouped means with grouping =
+        target; then, beyond the reference, mean recall over the targets that have positives and their number) plus
+        the per-target arrays `hits` and `npos`."""
+        nt = self.info()["nt"]
+        hits, npos = np.empty(nt, np.int64), np.empty(nt, np.int64)
+        out = np.empty(4, np.float64)
+        L_.check(L_.lib().ss_target_topl_metrics(self._h, hits.ctypes.data, npos.ctypes.data, out.ctypes.data,
+                                                 L_.SS_MEM_HOST))
+        d = dict(zip(TARGET_TOPL_FIELDS, (float(v) for v in out)))
+        d["targets_with_positives"] = int(out[3])
+        d["hits"], d["npos"] = hits, npos
+        return d
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            L_.load().ss_target_topl_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def jaccard_similarity(X, dtype=np.float64):
     """Weighted Jaccard (Ruzicka) similarity between the rows of a feature matrix, on the device: the similarity
     producer of the reference's tutorial (`1 .- pairwise(Jaccard(), X, dims=1)`, docs/src/tutorial/fishers-flowers.jl:66).
