@@ -750,6 +750,13 @@ static int predict_rows_device(Graph<T>& g, int kind, int64_t row_begin, int64_t
   return SS_OK;
 }
 
+template <class T>
+static int loo_graph_check(const Graph<T>& g) {
+  if (g.general || (!g.dense.on && g.nq != 0) || g.ns != g.nf)
+    return fail(SS_EINVAL, "leave-one-out needs a graph with nq == 0 and ns == nf (feature j named after source j)");
+  return SS_OK;
+}
+
 // kind: SS_ROWS_QUERY, SS_ROWS_SOURCE, or 2 = leave-one-out
 template <class T>
 static int predict_impl(ss_graph* h, int kind, int64_t row_begin, int64_t row_end, int clean, T* out, int64_t ld,
@@ -764,8 +771,7 @@ static int predict_impl(ss_graph* h, int kind, int64_t row_begin, int64_t row_en
   if (g.general && kind != SS_ROWS_QUERY)
     return fail(SS_EINVAL, "a general graph serves SS_ROWS_QUERY only");
   if (kind == 2) {
-    if ((!g.dense.on && g.nq != 0) || g.ns != g.nf)
-      return fail(SS_EINVAL, "leave-one-out needs a graph with nq == 0 and ns == nf (feature j named after source j)");
+    SS_TRY(loo_graph_check(g));  // a general graph was refused above
   } else if (kind != SS_ROWS_QUERY && kind != SS_ROWS_SOURCE) {
     return fail(SS_EINVAL, "rows_kind must be SS_ROWS_QUERY or SS_ROWS_SOURCE");
   }
@@ -837,6 +843,138 @@ static int check_rank_rows_shape(int64_t ncols, int L, double alpha) {
   return SS_OK;
 }
 
+// ------------------------------------------------------------------ what the consumers of score rows share
+// Caller-supplied score rows and their labels (CSR, index_base 0 or 1) as the row kernels take them: on the device,
+// the row pointers on the host as well.  Host inputs are copied into buffers this owns, the label slice rebased to its
+// first entry (row r's labels are didx[dptr[r] - shift .. dptr[r + 1] - shift), still carrying index_base).
+template <class T>
+struct StagedRows {
+  std::vector<int64_t> hp;  // yptr[0 .. nrows]
+  const int64_t* dptr = nullptr;
+  const int* didx = nullptr;
+  const T* dyhat = nullptr;
+  int64_t shift = 0, dld = 0, nnz = 0;
+  DevBuf<int64_t> bptr;
+  DevBuf<int> bidx;
+  DevBuf<T> bhat;
+};
+
+// Checks yptr on the host, begins the call's timing, stages host inputs and checks the labels on the device (sorted,
+// unique, in range; syncs): a consumer writes nothing before this has passed.  what: the call's name in messages.
+template <class T>
+static int stage_label_rows(const char* what, const int64_t* yptr, const int32_t* yidx, int base, const T* yhat,
+                            int64_t nrows, int64_t ncols, int64_t ld, int mem, StagedRows<T>& s) {
+  hipStream_t st = ctx().stream;
+  std::vector<int64_t>& hp = s.hp;
+  hp.resize((size_t)nrows + 1);
+  if (mem == SS_MEM_HOST) memcpy(hp.data(), yptr, hp.size() * sizeof(int64_t));
+  else {
+    SS_HIP(hipMemcpyAsync(hp.data(), yptr, hp.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    SS_HIP(hipStreamSynchronize(st));
+  }
+  if (hp[0] < base) return fail(SS_EINVAL, "%s: yptr[0] = %lld < index_base", what, (long long)hp[0]);
+  for (int64_t r = 0; r < nrows; ++r)
+    if (hp[r + 1] < hp[r] || hp[r + 1] - hp[r] > ncols)
+      return fail(SS_EINVAL, "%s: row %lld has %lld labels (ncols %lld)", what, (long long)r,
+                  (long long)(hp[r + 1] - hp[r]), (long long)ncols);
+  s.nnz = hp[nrows] - hp[0];
+  if (s.nnz > 0 && !yidx) return fail(SS_EINVAL, "%s: NULL label index buffer", what);
+  timing_begin_call();
+  s.dptr = yptr;
+  s.didx = yidx;
+  s.dyhat = yhat;
+  s.dld = ld;
+  s.shift = base;
+  if (mem == SS_MEM_HOST) {
+    SS_TRY(s.bptr.alloc((size_t)nrows + 1));
+    SS_TRY(s.bidx.alloc((size_t)s.nnz));
+    SS_TRY(s.bhat.alloc((size_t)nrows * ncols));
+    SS_TRY(upload<int64_t>(s.bptr.p, hp.data(), (size_t)nrows + 1, SS_MEM_HOST));
+    SS_TRY(upload<int>(s.bidx.p, yidx + (hp[0] - base), (size_t)s.nnz, SS_MEM_HOST));
+    SS_HIP(hipMemcpy2DAsync(s.bhat.p, ncols * sizeof(T), yhat, ld * sizeof(T), ncols * sizeof(T), nrows,
+                            hipMemcpyHostToDevice, st));
+    s.dptr = s.bptr.p;
+    s.didx = s.bidx.p;
+    s.dyhat = s.bhat.p;
+    s.dld = ncols;
+    s.shift = hp[0];
+  }
+  return launch_rank_rows_validate<int64_t>(s.dptr, s.shift, s.didx, base, nrows, ncols);
+}
+
+static int range_check(int64_t i_begin, int64_t i_end, int64_t ns) {
+  if (i_begin < 0 || i_end < i_begin || i_end > ns)
+    return fail(SS_EINVAL, "row range [%lld,%lld) outside 0..%lld", (long long)i_begin, (long long)i_end,
+                (long long)ns);
+  return SS_OK;
+}
+
+static int check_block_rows(const char* what, int64_t block_rows) {
+  if (block_rows < 0) return fail(SS_EINVAL, "%s: block_rows must be >= 0", what);
+  return SS_OK;
+}
+
+// rows of scores a sweep holds at once: block_rows, or about 1 GiB of scores when that is 0
+template <class T>
+static int64_t sweep_block_rows(int64_t block_rows, int64_t nrows, int64_t nt) {
+  int64_t rb = block_rows;
+  if (rb == 0) {
+    rb = (1LL << 30) / (nt * (int64_t)sizeof(T));
+    if (rb < 1) rb = 1;
+  }
+  return rb > nrows ? nrows : rb;
+}
+
+// What a sweep (loo_blocks, kfold_blocks) hands its consumer per block: nb rows of scores and their labels, the rows of
+// the graph's own Ys (checked sorted and unique when the graph was built), as CSR with index base 0: row r's labels are
+// idx[ptr[r] - shift .. ptr[r + 1] - shift).
+template <class T, class P>
+struct SweepBlock {
+  const P* ptr;         // device row pointers of the block, nb + 1 of them
+  int64_t shift;
+  const int* idx;
+  int64_t nlab;         // labels in the block
+  const P* hptr;        // ptr on the host
+  const T* scores;      // row-major nb x nt, leading dimension nt
+  int64_t nb, nt;
+  int64_t r0;           // position of the block's first row in the sweep
+  int64_t row0;         // without ids: row r is source row0 + r
+  const int* ids;       // device; row r is source ids[r] (k-fold: the members in fold order)
+  const int* out_rows;  // device; ids[r] - i_begin, the row of source order a result of row r belongs in (k-fold)
+};
+
+static int no_step() { return SS_OK; }
+
+// The leave-one-out folds [i_begin, i_end) in blocks of rb through a score buffer owned by the call.  begin() runs once
+// inside the call's ST_TOTAL span before the first block, each(block) after every block's scores under ST_EPILOGUE,
+// finish() after the last block before the span closes; begin and finish time themselves.
+template <class T, class Begin, class Each, class Finish>
+static int loo_blocks(Graph<T>& g, int64_t i_begin, int64_t i_end, int clean, int64_t rb, Begin begin, Each each,
+                      Finish finish) {
+  hipStream_t st = ctx().stream;
+  const int64_t nrows = i_end - i_begin, nt = g.nt;
+  std::vector<int> hp((size_t)nrows + 1);
+  SS_HIP(hipMemcpyAsync(hp.data(), g.Ys.ptr.p + i_begin, hp.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  DevBuf<T> scores;
+  SS_TRY(scores.alloc((size_t)rb * nt));
+  timing_begin_call();
+  hipEvent_t e_begin, e_end;
+  SS_TRY(timing_mark(&e_begin));
+  SS_TRY(begin());
+  for (int64_t r0 = 0; r0 < nrows; r0 += rb) {
+    const int64_t nb = nrows - r0 < rb ? nrows - r0 : rb;
+    SS_TRY(predict_rows_device<T>(g, 2, i_begin + r0, i_begin + r0 + nb, clean, scores.p, nt));
+    StageTimer t3(ST_EPILOGUE);
+    SS_TRY(each(SweepBlock<T, int>{g.Ys.ptr.p + i_begin + r0, 0, g.Ys.idx.p, (int64_t)(hp[r0 + nb] - hp[r0]),
+                                   hp.data() + r0, scores.p, nb, nt, r0, i_begin + r0, nullptr, nullptr}));
+  }
+  SS_TRY(finish());
+  SS_TRY(timing_mark(&e_end));
+  timing_span(ST_TOTAL, e_begin, e_end);
+  return SS_OK;
+}
+
 template <class T>
 static int rank_rows_impl(const int64_t* yptr, const int32_t* yidx, int base, const T* yhat, int64_t nrows,
                           int64_t ncols, int64_t ld, double alpha, int L, double* out, int mem) {
@@ -849,51 +987,18 @@ static int rank_rows_impl(const int64_t* yptr, const int32_t* yidx, int base, co
   if (ld < ncols) return fail(SS_EINVAL, "rank metrics rows: leading dimension %lld < %lld", (long long)ld, (long long)ncols);
   if (!yptr || !yhat || !out) return fail(SS_EINVAL, "rank metrics rows: NULL buffer");
   hipStream_t st = ctx().stream;
-  std::vector<int64_t> hp((size_t)nrows + 1);
-  if (mem == SS_MEM_HOST) memcpy(hp.data(), yptr, hp.size() * sizeof(int64_t));
-  else {
-    SS_HIP(hipMemcpyAsync(hp.data(), yptr, hp.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    SS_HIP(hipStreamSynchronize(st));
-  }
-  if (hp[0] < base) return fail(SS_EINVAL, "rank metrics rows: yptr[0] = %lld < index_base", (long long)hp[0]);
-  for (int64_t r = 0; r < nrows; ++r)
-    if (hp[r + 1] < hp[r] || hp[r + 1] - hp[r] > ncols)
-      return fail(SS_EINVAL, "rank metrics rows: row %lld has %lld labels (ncols %lld)", (long long)r,
-                  (long long)(hp[r + 1] - hp[r]), (long long)ncols);
-  const int64_t nnz = hp[nrows] - hp[0];
-  if (nnz > 0 && !yidx) return fail(SS_EINVAL, "rank metrics rows: NULL label index buffer");
-  timing_begin_call();
-  const int64_t* dptr = yptr;
-  const int* didx = yidx;
-  const T* dyhat = yhat;
-  int64_t dld = ld, shift = base;
+  StagedRows<T> s;
+  SS_TRY(stage_label_rows("rank metrics rows", yptr, yidx, base, yhat, nrows, ncols, ld, mem, s));
   double* dout = out;
-  DevBuf<int64_t> bptr;
-  DevBuf<int> bidx;
-  DevBuf<T> bhat;
   DevBuf<double> bout;
   if (mem == SS_MEM_HOST) {
-    // the label slice this call reads, rebased to its first entry
-    SS_TRY(bptr.alloc((size_t)nrows + 1));
-    SS_TRY(bidx.alloc((size_t)nnz));
-    SS_TRY(bhat.alloc((size_t)nrows * ncols));
     SS_TRY(bout.alloc((size_t)nrows * 6));
-    SS_TRY(upload<int64_t>(bptr.p, hp.data(), (size_t)nrows + 1, SS_MEM_HOST));
-    SS_TRY(upload<int>(bidx.p, yidx + (hp[0] - base), (size_t)nnz, SS_MEM_HOST));
-    SS_HIP(hipMemcpy2DAsync(bhat.p, ncols * sizeof(T), yhat, ld * sizeof(T), ncols * sizeof(T), nrows,
-                            hipMemcpyHostToDevice, st));
-    dptr = bptr.p;
-    didx = bidx.p;
-    dyhat = bhat.p;
-    dld = ncols;
-    shift = hp[0];
     dout = bout.p;
   }
-  // nothing is written before the labels have passed the check
-  SS_TRY(launch_rank_rows_validate<int64_t>(dptr, shift, didx, base, nrows, ncols));
   hipEvent_t e_begin, e_end;
   SS_TRY(timing_mark(&e_begin));
-  SS_TRY((launch_rank_rows<T, int64_t>(dptr, shift, didx, base, hp.data(), dyhat, nrows, ncols, dld, alpha, L, dout)));
+  SS_TRY((launch_rank_rows<T, int64_t>(s.dptr, s.shift, s.didx, base, s.hp.data(), s.dyhat, nrows, ncols, s.dld, alpha,
+                                       L, dout)));
   SS_TRY(timing_mark(&e_end));
   timing_span(ST_TOTAL, e_begin, e_end);
   if (mem == SS_MEM_HOST)
@@ -902,7 +1007,7 @@ static int rank_rows_impl(const int64_t* yptr, const int32_t* yidx, int base, co
   return SS_OK;
 }
 
-// leave-one-out folds evaluated where they are produced: blocks of folds through a score buffer owned by the call
+// leave-one-out folds evaluated where they are produced
 template <class T>
 static int evaluate_loo_impl(ss_graph* h, int64_t i_begin, int64_t i_end, int clean, double alpha, int L,
                              int64_t block_rows, double* out, int mem) {
@@ -911,47 +1016,26 @@ static int evaluate_loo_impl(ss_graph* h, int64_t i_begin, int64_t i_end, int cl
   Graph<T>* gp = nullptr;
   SS_TRY(graph_check<T>(h, &gp));
   Graph<T>& g = *gp;
-  if (g.general || (!g.dense.on && g.nq != 0) || g.ns != g.nf)
-    return fail(SS_EINVAL, "leave-one-out needs a graph with nq == 0 and ns == nf (feature j named after source j)");
-  if (i_begin < 0 || i_end < i_begin || i_end > g.ns)
-    return fail(SS_EINVAL, "row range [%lld,%lld) outside 0..%lld", (long long)i_begin, (long long)i_end,
-                (long long)g.ns);
-  if (block_rows < 0) return fail(SS_EINVAL, "evaluate_loo: block_rows must be >= 0");
+  SS_TRY(loo_graph_check(g));
+  SS_TRY(range_check(i_begin, i_end, g.ns));
+  SS_TRY(check_block_rows("evaluate_loo", block_rows));
   const int64_t nrows = i_end - i_begin, nt = g.nt;
   if (nrows == 0) return SS_OK;
   SS_TRY(check_rank_rows_shape(nt, L, alpha));
   if (!out) return fail(SS_EINVAL, "output buffer is NULL");
   hipStream_t st = ctx().stream;
-  int64_t rb = block_rows;
-  if (rb == 0) {
-    rb = (1LL << 30) / (nt * (int64_t)sizeof(T));  // about 1 GiB of scores
-    if (rb < 1) rb = 1;
-  }
-  if (rb > nrows) rb = nrows;
-  // the labels are the graph's own Ys rows (checked sorted and unique when the graph was built)
-  std::vector<int> hp((size_t)nrows + 1);
-  SS_HIP(hipMemcpyAsync(hp.data(), g.Ys.ptr.p + i_begin, hp.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-  SS_HIP(hipStreamSynchronize(st));
-  DevBuf<T> scores;
-  DevBuf<double> bout;
-  SS_TRY(scores.alloc((size_t)rb * nt));
   double* dout = out;
+  DevBuf<double> bout;
   if (mem == SS_MEM_HOST) {
     SS_TRY(bout.alloc((size_t)nrows * 6));
     dout = bout.p;
   }
-  timing_begin_call();
-  hipEvent_t e_begin, e_end;
-  SS_TRY(timing_mark(&e_begin));
-  for (int64_t r0 = 0; r0 < nrows; r0 += rb) {
-    const int64_t nb = nrows - r0 < rb ? nrows - r0 : rb;
-    SS_TRY(predict_rows_device<T>(g, 2, i_begin + r0, i_begin + r0 + nb, clean, scores.p, nt));
-    StageTimer t3(ST_EPILOGUE);
-    SS_TRY((launch_rank_rows<T, int>(g.Ys.ptr.p + i_begin + r0, 0, g.Ys.idx.p, 0, hp.data() + r0, scores.p, nb, nt, nt,
-                                     alpha, L, dout + r0 * 6)));
-  }
-  SS_TRY(timing_mark(&e_end));
-  timing_span(ST_TOTAL, e_begin, e_end);
+  SS_TRY(loo_blocks<T>(g, i_begin, i_end, clean, sweep_block_rows<T>(block_rows, nrows, nt), no_step,
+                       [&](const SweepBlock<T, int>& k) {
+                         return launch_rank_rows<T, int>(k.ptr, k.shift, k.idx, 0, k.hptr, k.scores, k.nb, nt, nt, alpha,
+                                                         L, dout + k.r0 * 6);
+                       },
+                       no_step));
   if (mem == SS_MEM_HOST)
     SS_HIP(hipMemcpyAsync(out, bout.p, (size_t)nrows * 6 * sizeof(double), hipMemcpyDeviceToHost, st));
   SS_HIP(hipStreamSynchronize(st));
@@ -978,51 +1062,17 @@ static int binary_rows_impl(const int64_t* yptr, const int32_t* yidx, int base, 
     return fail(SS_EINVAL, "binary metrics rows: leading dimension %lld < %lld", (long long)ld, (long long)ncols);
   if (!yptr || !yhat || !out) return fail(SS_EINVAL, "binary metrics rows: NULL buffer");
   hipStream_t st = ctx().stream;
-  std::vector<int64_t> hp((size_t)nrows + 1);
-  if (mem == SS_MEM_HOST) memcpy(hp.data(), yptr, hp.size() * sizeof(int64_t));
-  else {
-    SS_HIP(hipMemcpyAsync(hp.data(), yptr, hp.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    SS_HIP(hipStreamSynchronize(st));
-  }
-  if (hp[0] < base) return fail(SS_EINVAL, "binary metrics rows: yptr[0] = %lld < index_base", (long long)hp[0]);
-  for (int64_t r = 0; r < nrows; ++r)
-    if (hp[r + 1] < hp[r] || hp[r + 1] - hp[r] > ncols)
-      return fail(SS_EINVAL, "binary metrics rows: row %lld has %lld labels (ncols %lld)", (long long)r,
-                  (long long)(hp[r + 1] - hp[r]), (long long)ncols);
-  const int64_t nnz = hp[nrows] - hp[0];
-  if (nnz > 0 && !yidx) return fail(SS_EINVAL, "binary metrics rows: NULL label index buffer");
-  timing_begin_call();
-  const int64_t* dptr = yptr;
-  const int* didx = yidx;
-  const T* dyhat = yhat;
-  int64_t dld = ld, shift = base;
+  StagedRows<T> s;
+  SS_TRY(stage_label_rows("binary metrics rows", yptr, yidx, base, yhat, nrows, ncols, ld, mem, s));
   double* dout = out;
-  DevBuf<int64_t> bptr;
-  DevBuf<int> bidx;
-  DevBuf<T> bhat;
   DevBuf<double> bout;
   if (mem == SS_MEM_HOST) {
-    // the label slice this call reads, rebased to its first entry
-    SS_TRY(bptr.alloc((size_t)nrows + 1));
-    SS_TRY(bidx.alloc((size_t)nnz));
-    SS_TRY(bhat.alloc((size_t)nrows * ncols));
     SS_TRY(bout.alloc((size_t)nrows * 18));
-    SS_TRY(upload<int64_t>(bptr.p, hp.data(), (size_t)nrows + 1, SS_MEM_HOST));
-    SS_TRY(upload<int>(bidx.p, yidx + (hp[0] - base), (size_t)nnz, SS_MEM_HOST));
-    SS_HIP(hipMemcpy2DAsync(bhat.p, ncols * sizeof(T), yhat, ld * sizeof(T), ncols * sizeof(T), nrows,
-                            hipMemcpyHostToDevice, st));
-    dptr = bptr.p;
-    didx = bidx.p;
-    dyhat = bhat.p;
-    dld = ncols;
-    shift = hp[0];
     dout = bout.p;
   }
-  // nothing is written before the labels have passed the check
-  SS_TRY(launch_rank_rows_validate<int64_t>(dptr, shift, didx, base, nrows, ncols));
   hipEvent_t e_begin, e_end;
   SS_TRY(timing_mark(&e_begin));
-  SS_TRY((launch_binary_rows<T, int64_t>(dptr, shift, didx, base, dyhat, nrows, ncols, dld, dout)));
+  SS_TRY((launch_binary_rows<T, int64_t>(s.dptr, s.shift, s.didx, base, s.dyhat, nrows, ncols, s.dld, dout)));
   SS_TRY(timing_mark(&e_end));
   timing_span(ST_TOTAL, e_begin, e_end);
   if (mem == SS_MEM_HOST)
@@ -1031,7 +1081,7 @@ static int binary_rows_impl(const int64_t* yptr, const int32_t* yidx, int base, 
   return SS_OK;
 }
 
-// leave-one-out folds judged by the binary metrics where they are produced (as evaluate_loo_impl)
+// leave-one-out folds judged by the binary metrics where they are produced
 template <class T>
 static int evaluate_loo_binary_impl(ss_graph* h, int64_t i_begin, int64_t i_end, int clean, int64_t block_rows,
                                     double* out, int mem) {
@@ -1040,44 +1090,26 @@ static int evaluate_loo_binary_impl(ss_graph* h, int64_t i_begin, int64_t i_end,
   Graph<T>* gp = nullptr;
   SS_TRY(graph_check<T>(h, &gp));
   Graph<T>& g = *gp;
-  if (g.general || (!g.dense.on && g.nq != 0) || g.ns != g.nf)
-    return fail(SS_EINVAL, "leave-one-out needs a graph with nq == 0 and ns == nf (feature j named after source j)");
-  if (i_begin < 0 || i_end < i_begin || i_end > g.ns)
-    return fail(SS_EINVAL, "row range [%lld,%lld) outside 0..%lld", (long long)i_begin, (long long)i_end,
-                (long long)g.ns);
-  if (block_rows < 0) return fail(SS_EINVAL, "evaluate_loo_binary: block_rows must be >= 0");
+  SS_TRY(loo_graph_check(g));
+  SS_TRY(range_check(i_begin, i_end, g.ns));
+  SS_TRY(check_block_rows("evaluate_loo_binary", block_rows));
   const int64_t nrows = i_end - i_begin, nt = g.nt;
   if (nrows == 0) return SS_OK;
   SS_TRY(check_binary_rows_shape(nt));
   if (!out) return fail(SS_EINVAL, "output buffer is NULL");
   hipStream_t st = ctx().stream;
-  int64_t rb = block_rows;
-  if (rb == 0) {
-    rb = (1LL << 30) / (nt * (int64_t)sizeof(T));  // about 1 GiB of scores
-    if (rb < 1) rb = 1;
-  }
-  if (rb > nrows) rb = nrows;
-  // the labels are the graph's own Ys rows (checked sorted and unique when the graph was built)
-  DevBuf<T> scores;
-  DevBuf<double> bout;
-  SS_TRY(scores.alloc((size_t)rb * nt));
   double* dout = out;
+  DevBuf<double> bout;
   if (mem == SS_MEM_HOST) {
     SS_TRY(bout.alloc((size_t)nrows * 18));
     dout = bout.p;
   }
-  timing_begin_call();
-  hipEvent_t e_begin, e_end;
-  SS_TRY(timing_mark(&e_begin));
-  for (int64_t r0 = 0; r0 < nrows; r0 += rb) {
-    const int64_t nb = nrows - r0 < rb ? nrows - r0 : rb;
-    SS_TRY(predict_rows_device<T>(g, 2, i_begin + r0, i_begin + r0 + nb, clean, scores.p, nt));
-    StageTimer t3(ST_EPILOGUE);
-    SS_TRY((launch_binary_rows<T, int>(g.Ys.ptr.p + i_begin + r0, 0, g.Ys.idx.p, 0, scores.p, nb, nt, nt,
-                                       dout + r0 * 18)));
-  }
-  SS_TRY(timing_mark(&e_end));
-  timing_span(ST_TOTAL, e_begin, e_end);
+  SS_TRY(loo_blocks<T>(g, i_begin, i_end, clean, sweep_block_rows<T>(block_rows, nrows, nt), no_step,
+                       [&](const SweepBlock<T, int>& k) {
+                         return launch_binary_rows<T, int>(k.ptr, k.shift, k.idx, 0, k.scores, k.nb, nt, nt,
+                                                           dout + k.r0 * 18);
+                       },
+                       no_step));
   if (mem == SS_MEM_HOST)
     SS_HIP(hipMemcpyAsync(out, bout.p, (size_t)nrows * 18 * sizeof(double), hipMemcpyDeviceToHost, st));
   SS_HIP(hipStreamSynchronize(st));
@@ -1394,10 +1426,55 @@ static int kfold_graph_check(const Graph<T>& g) {
   return SS_OK;
 }
 
-static int kfold_range_check(int64_t i_begin, int64_t i_end, int64_t ns) {
-  if (i_begin < 0 || i_end < i_begin || i_end > ns)
-    return fail(SS_EINVAL, "row range [%lld,%lld) outside 0..%lld", (long long)i_begin, (long long)i_end,
-                (long long)ns);
+// The k-fold rows [i_begin, i_end) in blocks of rb positions in fold order, with no row map (each block is contiguous),
+// through a score buffer owned by the call; a block's labels are its members' Ys rows gathered in the same order.
+// begin / each / finish as for loo_blocks.
+template <class T, class Begin, class Each, class Finish>
+static int kfold_blocks(Graph<T>& g, const KfoldPlan& plan, int64_t i_begin, int64_t i_end, int clean, int64_t rb,
+                        Begin begin, Each each, Finish finish) {
+  hipStream_t st = ctx().stream;
+  const int64_t nrows = i_end - i_begin, nt = g.nt;
+  KfoldRange rg;
+  kfold_range(plan, i_begin, i_end, rg);
+  std::vector<int> map(rg.sel.size());
+  for (size_t p = 0; p < map.size(); ++p) map[p] = (int)(rg.sel[p] - i_begin);
+  KfoldWork<T> w;
+  SS_TRY(kfold_work_init<T>(g, plan, rg, map, w));
+  // pptr = the int64 row pointers of the members' Ys rows over the whole range
+  std::vector<int> hy((size_t)nrows + 1);
+  SS_HIP(hipMemcpyAsync(hy.data(), g.Ys.ptr.p + i_begin, hy.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  std::vector<int64_t> pptr((size_t)nrows + 1, 0);
+  for (int64_t p = 0; p < nrows; ++p) pptr[p + 1] = pptr[p] + (hy[map[p] + 1] - hy[map[p]]);
+  int64_t max_lab = 1;
+  for (int64_t p0 = 0; p0 < nrows; p0 += rb) {
+    const int64_t p1 = nrows - p0 < rb ? nrows : p0 + rb;
+    if (pptr[p1] - pptr[p0] > max_lab) max_lab = pptr[p1] - pptr[p0];
+  }
+  DevBuf<int64_t> d_pptr;
+  DevBuf<int> lab;
+  DevBuf<T> scores;
+  SS_TRY(d_pptr.alloc((size_t)nrows + 1));
+  SS_TRY(lab.alloc((size_t)max_lab));
+  SS_TRY(scores.alloc((size_t)rb * nt));
+  SS_HIP(hipMemcpyAsync(d_pptr.p, pptr.data(), pptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  SS_TRY(graph_sell(g));
+  if (!g.dense.on) SS_TRY(graph_chunked(g, false));
+  timing_begin_call();
+  hipEvent_t e_begin, e_end;
+  SS_TRY(timing_mark(&e_begin));
+  SS_TRY(begin());
+  for (int64_t p0 = 0; p0 < nrows; p0 += rb) {
+    const int64_t nb = nrows - p0 < rb ? nrows - p0 : rb;
+    SS_TRY(kfold_rows_device<T>(g, w, plan, rg, p0, p0 + nb, clean, scores.p, nt, nullptr));
+    StageTimer t3(ST_EPILOGUE);
+    SS_TRY(launch_gather_labels(g.Ys.ptr.p, g.Ys.idx.p, w.d_sel.p + p0, nb, d_pptr.p + p0, pptr[p0], lab.p));
+    SS_TRY(each(SweepBlock<T, int64_t>{d_pptr.p + p0, pptr[p0], lab.p, pptr[p0 + nb] - pptr[p0], pptr.data() + p0,
+                                       scores.p, nb, nt, p0, 0, w.d_sel.p + p0, w.d_map.p + p0}));
+  }
+  SS_TRY(finish());
+  SS_TRY(timing_mark(&e_end));
+  timing_span(ST_TOTAL, e_begin, e_end);
   return SS_OK;
 }
 
@@ -1412,7 +1489,7 @@ static int predict_kfold_rows_impl(ss_graph* h, const int32_t* fold_of_source, i
   SS_TRY(graph_check<T>(h, &gp));
   Graph<T>& g = *gp;
   SS_TRY(kfold_graph_check(g));
-  SS_TRY(kfold_range_check(i_begin, i_end, g.ns));
+  SS_TRY(range_check(i_begin, i_end, g.ns));
   KfoldPlan plan;
   SS_TRY(kfold_plan(fold_of_source, nfolds, g.ns, mem, plan));
   const int64_t nrows = i_end - i_begin, nt = g.nt;
@@ -1472,9 +1549,8 @@ static int predict_kfold_rows_impl(ss_graph* h, const int32_t* fold_of_source, i
   return SS_OK;
 }
 
-// k-fold rows [i_begin, i_end) judged where they are produced: blocks of block_rows members in fold order through a
-// score buffer owned by the call; labels = the members' Ys rows gathered in the same order; the metric rows are then
-// scattered to source order.  binary: 18 doubles per row (launch_binary_rows), else 6 (launch_rank_rows).
+// k-fold rows [i_begin, i_end) judged where they are produced; a block's metric rows are scattered to source order.
+// binary: 18 doubles per row (launch_binary_rows), else 6 (launch_rank_rows).
 template <class T>
 static int evaluate_kfold_impl(ss_graph* h, const int32_t* fold_of_source, int nfolds, int64_t i_begin, int64_t i_end,
                                int clean, bool binary, double alpha, int L, int64_t block_rows, double* out, int mem) {
@@ -1484,9 +1560,8 @@ static int evaluate_kfold_impl(ss_graph* h, const int32_t* fold_of_source, int n
   SS_TRY(graph_check<T>(h, &gp));
   Graph<T>& g = *gp;
   SS_TRY(kfold_graph_check(g));
-  SS_TRY(kfold_range_check(i_begin, i_end, g.ns));
-  if (block_rows < 0)
-    return fail(SS_EINVAL, "%s: block_rows must be >= 0", binary ? "evaluate_kfold_binary" : "evaluate_kfold");
+  SS_TRY(range_check(i_begin, i_end, g.ns));
+  SS_TRY(check_block_rows(binary ? "evaluate_kfold_binary" : "evaluate_kfold", block_rows));
   KfoldPlan plan;
   SS_TRY(kfold_plan(fold_of_source, nfolds, g.ns, mem, plan));
   const int64_t nrows = i_end - i_begin, nt = g.nt;
@@ -1495,63 +1570,25 @@ static int evaluate_kfold_impl(ss_graph* h, const int32_t* fold_of_source, int n
   if (!out) return fail(SS_EINVAL, "output buffer is NULL");
   const int nw = binary ? 18 : 6;
   hipStream_t st = ctx().stream;
-  int64_t rb = block_rows;
-  if (rb == 0) {
-    rb = (1LL << 30) / (nt * (int64_t)sizeof(T));  // about 1 GiB of scores
-    if (rb < 1) rb = 1;
-  }
-  if (rb > nrows) rb = nrows;
-  KfoldRange rg;
-  kfold_range(plan, i_begin, i_end, rg);
-  std::vector<int> map(rg.sel.size());
-  for (size_t p = 0; p < map.size(); ++p) map[p] = (int)(rg.sel[p] - i_begin);
-  KfoldWork<T> w;
-  SS_TRY(kfold_work_init<T>(g, plan, rg, map, w));
-  // the labels are the graph's own Ys rows (checked sorted and unique when the graph was built), gathered per block in
-  // fold order: pptr = their int64 row pointers over the whole range
-  std::vector<int> hy((size_t)nrows + 1);
-  SS_HIP(hipMemcpyAsync(hy.data(), g.Ys.ptr.p + i_begin, hy.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-  SS_HIP(hipStreamSynchronize(st));
-  std::vector<int64_t> pptr((size_t)nrows + 1, 0);
-  for (int64_t p = 0; p < nrows; ++p) pptr[p + 1] = pptr[p] + (hy[map[p] + 1] - hy[map[p]]);
-  int64_t max_lab = 1;
-  for (int64_t p0 = 0; p0 < nrows; p0 += rb) {
-    const int64_t p1 = nrows - p0 < rb ? nrows : p0 + rb;
-    if (pptr[p1] - pptr[p0] > max_lab) max_lab = pptr[p1] - pptr[p0];
-  }
-  DevBuf<int64_t> d_pptr;
-  DevBuf<int> lab;
-  DevBuf<T> scores;
+  const int64_t rb = sweep_block_rows<T>(block_rows, nrows, nt);
   DevBuf<double> bres, bout;
-  SS_TRY(d_pptr.alloc((size_t)nrows + 1));
-  SS_TRY(lab.alloc((size_t)max_lab));
-  SS_TRY(scores.alloc((size_t)rb * nt));
   SS_TRY(bres.alloc((size_t)rb * nw));
-  SS_HIP(hipMemcpyAsync(d_pptr.p, pptr.data(), pptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
   double* dout = out;
   if (mem == SS_MEM_HOST) {
     SS_TRY(bout.alloc((size_t)nrows * nw));
     dout = bout.p;
   }
-  SS_TRY(graph_sell(g));
-  if (!g.dense.on) SS_TRY(graph_chunked(g, false));
-  timing_begin_call();
-  hipEvent_t e_begin, e_end;
-  SS_TRY(timing_mark(&e_begin));
-  for (int64_t p0 = 0; p0 < nrows; p0 += rb) {
-    const int64_t nb = nrows - p0 < rb ? nrows - p0 : rb;
-    SS_TRY(kfold_rows_device<T>(g, w, plan, rg, p0, p0 + nb, clean, scores.p, nt, nullptr));
-    StageTimer t3(ST_EPILOGUE);
-    SS_TRY(launch_gather_labels(g.Ys.ptr.p, g.Ys.idx.p, w.d_sel.p + p0, nb, d_pptr.p + p0, pptr[p0], lab.p));
-    if (binary)
-      SS_TRY((launch_binary_rows<T, int64_t>(d_pptr.p + p0, pptr[p0], lab.p, 0, scores.p, nb, nt, nt, bres.p)));
-    else
-      SS_TRY((launch_rank_rows<T, int64_t>(d_pptr.p + p0, pptr[p0], lab.p, 0, pptr.data() + p0, scores.p, nb, nt, nt,
-                                           alpha, L, bres.p)));
-    SS_TRY(launch_scatter_rows<double>(bres.p, nw, nb, nw, w.d_map.p + p0, dout, nw));
-  }
-  SS_TRY(timing_mark(&e_end));
-  timing_span(ST_TOTAL, e_begin, e_end);
+  SS_TRY(kfold_blocks<T>(g, plan, i_begin, i_end, clean, rb, no_step,
+                         [&](const SweepBlock<T, int64_t>& k) {
+                           if (binary)
+                             SS_TRY((launch_binary_rows<T, int64_t>(k.ptr, k.shift, k.idx, 0, k.scores, k.nb, nt, nt,
+                                                                    bres.p)));
+                           else
+                             SS_TRY((launch_rank_rows<T, int64_t>(k.ptr, k.shift, k.idx, 0, k.hptr, k.scores, k.nb, nt,
+                                                                  nt, alpha, L, bres.p)));
+                           return launch_scatter_rows<double>(bres.p, nw, k.nb, nw, k.out_rows, dout, nw);
+                         },
+                         no_step));
   if (mem == SS_MEM_HOST)
     SS_HIP(hipMemcpyAsync(out, bout.p, (size_t)nrows * nw * sizeof(double), hipMemcpyDeviceToHost, st));
   SS_HIP(hipStreamSynchronize(st));
@@ -1633,189 +1670,90 @@ static int pool_add_rows_impl(ss_pool* h, const int64_t* yptr, const int32_t* yi
   if (ld < ncols)
     return fail(SS_EINVAL, "pool add rows: leading dimension %lld < %lld", (long long)ld, (long long)ncols);
   if (!yptr || !yhat) return fail(SS_EINVAL, "pool add rows: NULL buffer");
-  hipStream_t st = ctx().stream;
-  std::vector<int64_t> hp((size_t)nrows + 1);
-  if (mem == SS_MEM_HOST) memcpy(hp.data(), yptr, hp.size() * sizeof(int64_t));
-  else {
-    SS_HIP(hipMemcpyAsync(hp.data(), yptr, hp.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    SS_HIP(hipStreamSynchronize(st));
-  }
-  if (hp[0] < base) return fail(SS_EINVAL, "pool add rows: yptr[0] = %lld < index_base", (long long)hp[0]);
-  for (int64_t r = 0; r < nrows; ++r)
-    if (hp[r + 1] < hp[r] || hp[r + 1] - hp[r] > ncols)
-      return fail(SS_EINVAL, "pool add rows: row %lld has %lld labels (ncols %lld)", (long long)r,
-                  (long long)(hp[r + 1] - hp[r]), (long long)ncols);
-  const int64_t nnz = hp[nrows] - hp[0];
-  if (nnz > 0 && !yidx) return fail(SS_EINVAL, "pool add rows: NULL label index buffer");
-  timing_begin_call();
-  const int64_t* dptr = yptr;
-  const int* didx = yidx;
-  const T* dyhat = yhat;
-  int64_t dld = ld, shift = base;
-  DevBuf<int64_t> bptr;
-  DevBuf<int> bidx;
-  DevBuf<T> bhat;
-  if (mem == SS_MEM_HOST) {
-    SS_TRY(bptr.alloc((size_t)nrows + 1));
-    SS_TRY(bidx.alloc((size_t)nnz));
-    SS_TRY(bhat.alloc((size_t)nrows * ncols));
-    SS_TRY(upload<int64_t>(bptr.p, hp.data(), (size_t)nrows + 1, SS_MEM_HOST));
-    SS_TRY(upload<int>(bidx.p, yidx + (hp[0] - base), (size_t)nnz, SS_MEM_HOST));
-    SS_HIP(hipMemcpy2DAsync(bhat.p, ncols * sizeof(T), yhat, ld * sizeof(T), ncols * sizeof(T), nrows,
-                            hipMemcpyHostToDevice, st));
-    dptr = bptr.p;
-    didx = bidx.p;
-    dyhat = bhat.p;
-    dld = ncols;
-    shift = hp[0];
-  }
-  SS_TRY(launch_rank_rows_validate<int64_t>(dptr, shift, didx, base, nrows, ncols));
+  StagedRows<T> s;
+  SS_TRY(stage_label_rows("pool add rows", yptr, yidx, base, yhat, nrows, ncols, ld, mem, s));
   hipEvent_t e_begin, e_end;
   SS_TRY(timing_mark(&e_begin));
   PoolTable<pool_key_t<T>> t;
-  SS_TRY((pool_block_table<T, int64_t>(dptr, shift, didx, base, nnz, dyhat, nrows, ncols, dld, p.w, t)));
+  SS_TRY((pool_block_table<T, int64_t>(s.dptr, s.shift, s.didx, base, s.nnz, s.dyhat, nrows, ncols, s.dld, p.w, t)));
   SS_TRY(pool_push(p.lv, std::move(t), 0, p.max_entries, p.w));
   p.n += nrows * ncols;
-  p.npos += nnz;
+  p.npos += s.nnz;
   SS_TRY(timing_mark(&e_end));
   timing_span(ST_TOTAL, e_begin, e_end);
   timing_span(ST_EPILOGUE, e_begin, e_end);
-  SS_HIP(hipStreamSynchronize(st));
+  SS_HIP(hipStreamSynchronize(ctx().stream));
   return SS_OK;
 }
 
-// leave-one-out folds pooled where they are produced: the blocks and checks of evaluate_loo_binary_impl
+// A sweep into a pool: every block's table goes onto the add's own levels (the rows' order does not matter to a pool),
+// which pool_commit puts into the pool after the last block.
+template <class T>
+struct PoolAdd {
+  PoolBox<T>& p;
+  std::vector<PoolTable<pool_key_t<T>>> loc;
+  int64_t other, n = 0, npos = 0;
+  explicit PoolAdd(PoolBox<T>& pool) : p(pool), other(pool_stored(pool.lv)) {}
+  template <class P>
+  int block(const SweepBlock<T, P>& k) {
+    PoolTable<pool_key_t<T>> t;
+    SS_TRY((pool_block_table<T, P>(k.ptr, k.shift, k.idx, 0, k.nlab, k.scores, k.nb, k.nt, k.nt, p.w, t)));
+    SS_TRY(pool_push(loc, std::move(t), other, p.max_entries, p.w));
+    n += k.nb * k.nt;
+    npos += k.nlab;
+    return SS_OK;
+  }
+  int commit() {
+    StageTimer t3(ST_EPILOGUE);
+    return pool_commit(p, loc, n, npos);
+  }
+};
+
+// leave-one-out folds pooled where they are produced
 template <class T>
 static int pool_add_loo_impl(ss_pool* ph, ss_graph* h, int64_t i_begin, int64_t i_end, int clean, int64_t block_rows) {
-  using K = pool_key_t<T>;
   SS_TRY(require_init());
   PoolBox<T>* pp = nullptr;
   SS_TRY(pool_check<T>(ph, &pp));
-  PoolBox<T>& p = *pp;
   Graph<T>* gp = nullptr;
   SS_TRY(graph_check<T>(h, &gp));
   Graph<T>& g = *gp;
-  if (g.general || (!g.dense.on && g.nq != 0) || g.ns != g.nf)
-    return fail(SS_EINVAL, "leave-one-out needs a graph with nq == 0 and ns == nf (feature j named after source j)");
-  if (i_begin < 0 || i_end < i_begin || i_end > g.ns)
-    return fail(SS_EINVAL, "row range [%lld,%lld) outside 0..%lld", (long long)i_begin, (long long)i_end,
-                (long long)g.ns);
-  if (block_rows < 0) return fail(SS_EINVAL, "pool add loo: block_rows must be >= 0");
+  SS_TRY(loo_graph_check(g));
+  SS_TRY(range_check(i_begin, i_end, g.ns));
+  SS_TRY(check_block_rows("pool add loo", block_rows));
   const int64_t nrows = i_end - i_begin, nt = g.nt;
   if (nrows == 0) return SS_OK;
   SS_TRY(check_binary_rows_shape(nt));
-  hipStream_t st = ctx().stream;
-  int64_t rb = block_rows;
-  if (rb == 0) {
-    rb = (1LL << 30) / (nt * (int64_t)sizeof(T));  // about 1 GiB of scores
-    if (rb < 1) rb = 1;
-  }
-  if (rb > nrows) rb = nrows;
-  std::vector<int> hp((size_t)nrows + 1);
-  SS_HIP(hipMemcpyAsync(hp.data(), g.Ys.ptr.p + i_begin, hp.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-  SS_HIP(hipStreamSynchronize(st));
-  DevBuf<T> scores;
-  SS_TRY(scores.alloc((size_t)rb * nt));
-  std::vector<PoolTable<K>> loc;
-  const int64_t other = pool_stored(p.lv);
-  timing_begin_call();
-  hipEvent_t e_begin, e_end;
-  SS_TRY(timing_mark(&e_begin));
-  for (int64_t r0 = 0; r0 < nrows; r0 += rb) {
-    const int64_t nb = nrows - r0 < rb ? nrows - r0 : rb;
-    SS_TRY(predict_rows_device<T>(g, 2, i_begin + r0, i_begin + r0 + nb, clean, scores.p, nt));
-    StageTimer t3(ST_EPILOGUE);
-    PoolTable<K> t;
-    SS_TRY((pool_block_table<T, int>(g.Ys.ptr.p + i_begin + r0, 0, g.Ys.idx.p, 0, (int64_t)(hp[r0 + nb] - hp[r0]),
-                                     scores.p, nb, nt, nt, p.w, t)));
-    SS_TRY(pool_push(loc, std::move(t), other, p.max_entries, p.w));
-  }
-  {
-    StageTimer t3(ST_EPILOGUE);
-    SS_TRY(pool_commit(p, loc, nrows * nt, (int64_t)(hp[nrows] - hp[0])));
-  }
-  SS_TRY(timing_mark(&e_end));
-  timing_span(ST_TOTAL, e_begin, e_end);
-  SS_HIP(hipStreamSynchronize(st));
+  PoolAdd<T> add(*pp);
+  SS_TRY(loo_blocks<T>(g, i_begin, i_end, clean, sweep_block_rows<T>(block_rows, nrows, nt), no_step,
+                       [&](const SweepBlock<T, int>& k) { return add.block(k); }, [&] { return add.commit(); }));
+  SS_HIP(hipStreamSynchronize(ctx().stream));
   return SS_OK;
 }
 
-// k-fold rows pooled where they are produced: the blocks, label gather and checks of evaluate_kfold_impl (the rows'
-// order does not matter to a pool, so nothing is scattered back)
+// k-fold rows pooled where they are produced
 template <class T>
 static int pool_add_kfold_impl(ss_pool* ph, ss_graph* h, const int32_t* fold_of_source, int nfolds, int64_t i_begin,
                                int64_t i_end, int clean, int64_t block_rows, int mem) {
-  using K = pool_key_t<T>;
   SS_TRY(require_init());
   SS_TRY(check_mem(mem));
   PoolBox<T>* pp = nullptr;
   SS_TRY(pool_check<T>(ph, &pp));
-  PoolBox<T>& p = *pp;
   Graph<T>* gp = nullptr;
   SS_TRY(graph_check<T>(h, &gp));
   Graph<T>& g = *gp;
   SS_TRY(kfold_graph_check(g));
-  SS_TRY(kfold_range_check(i_begin, i_end, g.ns));
-  if (block_rows < 0) return fail(SS_EINVAL, "pool add kfold: block_rows must be >= 0");
+  SS_TRY(range_check(i_begin, i_end, g.ns));
+  SS_TRY(check_block_rows("pool add kfold", block_rows));
   KfoldPlan plan;
   SS_TRY(kfold_plan(fold_of_source, nfolds, g.ns, mem, plan));
   const int64_t nrows = i_end - i_begin, nt = g.nt;
   if (nrows == 0) return SS_OK;
   SS_TRY(check_binary_rows_shape(nt));
-  hipStream_t st = ctx().stream;
-  int64_t rb = block_rows;
-  if (rb == 0) {
-    rb = (1LL << 30) / (nt * (int64_t)sizeof(T));  // about 1 GiB of scores
-    if (rb < 1) rb = 1;
-  }
-  if (rb > nrows) rb = nrows;
-  KfoldRange rg;
-  kfold_range(plan, i_begin, i_end, rg);
-  std::vector<int> map(rg.sel.size());
-  for (size_t q = 0; q < map.size(); ++q) map[q] = (int)(rg.sel[q] - i_begin);
-  KfoldWork<T> w;
-  SS_TRY(kfold_work_init<T>(g, plan, rg, map, w));
-  std::vector<int> hy((size_t)nrows + 1);
-  SS_HIP(hipMemcpyAsync(hy.data(), g.Ys.ptr.p + i_begin, hy.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-  SS_HIP(hipStreamSynchronize(st));
-  std::vector<int64_t> pptr((size_t)nrows + 1, 0);
-  for (int64_t q = 0; q < nrows; ++q) pptr[q + 1] = pptr[q] + (hy[map[q] + 1] - hy[map[q]]);
-  int64_t max_lab = 1;
-  for (int64_t p0 = 0; p0 < nrows; p0 += rb) {
-    const int64_t p1 = nrows - p0 < rb ? nrows : p0 + rb;
-    if (pptr[p1] - pptr[p0] > max_lab) max_lab = pptr[p1] - pptr[p0];
-  }
-  DevBuf<int64_t> d_pptr;
-  DevBuf<int> lab;
-  DevBuf<T> scores;
-  SS_TRY(d_pptr.alloc((size_t)nrows + 1));
-  SS_TRY(lab.alloc((size_t)max_lab));
-  SS_TRY(scores.alloc((size_t)rb * nt));
-  SS_HIP(hipMemcpyAsync(d_pptr.p, pptr.data(), pptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-  SS_TRY(graph_sell(g));
-  if (!g.dense.on) SS_TRY(graph_chunked(g, false));
-  std::vector<PoolTable<K>> loc;
-  const int64_t other = pool_stored(p.lv);
-  timing_begin_call();
-  hipEvent_t e_begin, e_end;
-  SS_TRY(timing_mark(&e_begin));
-  for (int64_t p0 = 0; p0 < nrows; p0 += rb) {
-    const int64_t nb = nrows - p0 < rb ? nrows - p0 : rb;
-    SS_TRY(kfold_rows_device<T>(g, w, plan, rg, p0, p0 + nb, clean, scores.p, nt, nullptr));
-    StageTimer t3(ST_EPILOGUE);
-    SS_TRY(launch_gather_labels(g.Ys.ptr.p, g.Ys.idx.p, w.d_sel.p + p0, nb, d_pptr.p + p0, pptr[p0], lab.p));
-    PoolTable<K> t;
-    SS_TRY((pool_block_table<T, int64_t>(d_pptr.p + p0, pptr[p0], lab.p, 0, pptr[p0 + nb] - pptr[p0], scores.p, nb,
-                                         nt, nt, p.w, t)));
-    SS_TRY(pool_push(loc, std::move(t), other, p.max_entries, p.w));
-  }
-  {
-    StageTimer t3(ST_EPILOGUE);
-    SS_TRY(pool_commit(p, loc, nrows * nt, pptr[nrows]));
-  }
-  SS_TRY(timing_mark(&e_end));
-  timing_span(ST_TOTAL, e_begin, e_end);
-  SS_HIP(hipStreamSynchronize(st));
+  PoolAdd<T> add(*pp);
+  SS_TRY(kfold_blocks<T>(g, plan, i_begin, i_end, clean, sweep_block_rows<T>(block_rows, nrows, nt), no_step,
+                         [&](const SweepBlock<T, int64_t>& k) { return add.block(k); }, [&] { return add.commit(); }));
+  SS_HIP(hipStreamSynchronize(ctx().stream));
   return SS_OK;
 }
 
@@ -2005,112 +1943,67 @@ static int tl_add_rows_impl(ss_target_topl* h, const int64_t* yptr, const int32_
     return fail(SS_EINVAL, "target top-L add rows: row_begin = %lld out of range", (long long)row_begin);
   if (nrows == 0) return SS_OK;
   if (!yptr || !yhat) return fail(SS_EINVAL, "target top-L add rows: NULL buffer");
-  hipStream_t st = ctx().stream;
-  std::vector<int64_t> hp((size_t)nrows + 1);
-  if (mem == SS_MEM_HOST) memcpy(hp.data(), yptr, hp.size() * sizeof(int64_t));
-  else {
-    SS_HIP(hipMemcpyAsync(hp.data(), yptr, hp.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    SS_HIP(hipStreamSynchronize(st));
-  }
-  if (hp[0] < base) return fail(SS_EINVAL, "target top-L add rows: yptr[0] = %lld < index_base", (long long)hp[0]);
-  for (int64_t r = 0; r < nrows; ++r)
-    if (hp[r + 1] < hp[r] || hp[r + 1] - hp[r] > ncols)
-      return fail(SS_EINVAL, "target top-L add rows: row %lld has %lld labels (ncols %lld)", (long long)r,
-                  (long long)(hp[r + 1] - hp[r]), (long long)ncols);
-  const int64_t nnz = hp[nrows] - hp[0];
-  if (nnz > 0 && !yidx) return fail(SS_EINVAL, "target top-L add rows: NULL label index buffer");
-  timing_begin_call();
-  const int64_t* dptr = yptr;
-  const int* didx = yidx;
-  const T* dyhat = yhat;
-  int64_t dld = ld, shift = base;
-  DevBuf<int64_t> bptr;
-  DevBuf<int> bidx;
-  DevBuf<T> bhat;
-  if (mem == SS_MEM_HOST) {
-    SS_TRY(bptr.alloc((size_t)nrows + 1));
-    SS_TRY(bidx.alloc((size_t)nnz));
-    SS_TRY(bhat.alloc((size_t)nrows * ncols));
-    SS_TRY(upload<int64_t>(bptr.p, hp.data(), (size_t)nrows + 1, SS_MEM_HOST));
-    SS_TRY(upload<int>(bidx.p, yidx + (hp[0] - base), (size_t)nnz, SS_MEM_HOST));
-    SS_HIP(hipMemcpy2DAsync(bhat.p, ncols * sizeof(T), yhat, ld * sizeof(T), ncols * sizeof(T), nrows,
-                            hipMemcpyHostToDevice, st));
-    dptr = bptr.p;
-    didx = bidx.p;
-    dyhat = bhat.p;
-    dld = ncols;
-    shift = hp[0];
-  }
-  SS_TRY(launch_rank_rows_validate<int64_t>(dptr, shift, didx, base, nrows, ncols));
+  StagedRows<T> s;
+  SS_TRY(stage_label_rows("target top-L add rows", yptr, yidx, base, yhat, nrows, ncols, ld, mem, s));
   hipEvent_t e_begin, e_end;
   SS_TRY(timing_mark(&e_begin));
   SS_TRY(tl_start(b));
-  SS_TRY((tl_add_block<T, int64_t>(b.nx, b.nt, b.L, b.fill(), dptr, shift, didx, base, nnz, dyhat, nrows, dld,
-                                   row_begin, nullptr, b.w)));
+  SS_TRY((tl_add_block<T, int64_t>(b.nx, b.nt, b.L, b.fill(), s.dptr, s.shift, s.didx, base, s.nnz, s.dyhat, nrows,
+                                   s.dld, row_begin, nullptr, b.w)));
   SS_TRY(timing_mark(&e_end));
   timing_span(ST_TOTAL, e_begin, e_end);
   timing_span(ST_EPILOGUE, e_begin, e_end);
-  return tl_commit(b, nrows, nnz);
+  return tl_commit(b, nrows, s.nnz);
 }
 
-// leave-one-out folds into the table where they are produced: the blocks and checks of pool_add_loo_impl; row id =
-// source index
+// A sweep into a top-L handle: tl_start before the first block, every block into the copy under its rows' source
+// indices (fill follows the rows taken so far), tl_commit once the call's ST_TOTAL span is closed.
+template <class T>
+struct TlAdd {
+  TlBox<T>& b;
+  int64_t fill, nrows = 0, npos = 0;
+  explicit TlAdd(TlBox<T>& box) : b(box), fill(box.fill()) {}
+  int start() {
+    StageTimer t3(ST_EPILOGUE);
+    return tl_start(b);
+  }
+  template <class P>
+  int block(const SweepBlock<T, P>& k) {
+    SS_TRY((tl_add_block<T, P>(b.nx, b.nt, b.L, fill, k.ptr, k.shift, k.idx, 0, k.nlab, k.scores, k.nb, k.nt, k.row0,
+                               k.ids, b.w)));
+    fill = fill + k.nb < b.L ? fill + k.nb : b.L;
+    nrows += k.nb;
+    npos += k.nlab;
+    return SS_OK;
+  }
+  int commit() { return tl_commit(b, nrows, npos); }
+};
+
+// leave-one-out folds into the table where they are produced
 template <class T>
 static int tl_add_loo_impl(ss_target_topl* th, ss_graph* h, int64_t i_begin, int64_t i_end, int clean,
                            int64_t block_rows) {
   SS_TRY(require_init());
   TlBox<T>* bp = nullptr;
   SS_TRY(tl_check<T>(th, &bp));
-  TlBox<T>& b = *bp;
   Graph<T>* gp = nullptr;
   SS_TRY(graph_check<T>(h, &gp));
   Graph<T>& g = *gp;
-  if (g.general || (!g.dense.on && g.nq != 0) || g.ns != g.nf)
-    return fail(SS_EINVAL, "leave-one-out needs a graph with nq == 0 and ns == nf (feature j named after source j)");
-  if (i_begin < 0 || i_end < i_begin || i_end > g.ns)
-    return fail(SS_EINVAL, "row range [%lld,%lld) outside 0..%lld", (long long)i_begin, (long long)i_end,
-                (long long)g.ns);
-  if (block_rows < 0) return fail(SS_EINVAL, "target top-L add loo: block_rows must be >= 0");
-  if (g.nt != b.nt)
+  SS_TRY(loo_graph_check(g));
+  SS_TRY(range_check(i_begin, i_end, g.ns));
+  SS_TRY(check_block_rows("target top-L add loo", block_rows));
+  if (g.nt != bp->nt)
     return fail(SS_EINVAL, "target top-L add loo: the graph has %lld targets, the handle %lld", (long long)g.nt,
-                (long long)b.nt);
+                (long long)bp->nt);
   const int64_t nrows = i_end - i_begin, nt = g.nt;
   if (nrows == 0) return SS_OK;
-  hipStream_t st = ctx().stream;
-  int64_t rb = block_rows;
-  if (rb == 0) {
-    rb = (1LL << 30) / (nt * (int64_t)sizeof(T));  // about 1 GiB of scores
-    if (rb < 1) rb = 1;
-  }
-  if (rb > nrows) rb = nrows;
-  std::vector<int> hp((size_t)nrows + 1);
-  SS_HIP(hipMemcpyAsync(hp.data(), g.Ys.ptr.p + i_begin, hp.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-  SS_HIP(hipStreamSynchronize(st));
-  DevBuf<T> scores;
-  SS_TRY(scores.alloc((size_t)rb * nt));
-  timing_begin_call();
-  hipEvent_t e_begin, e_end;
-  SS_TRY(timing_mark(&e_begin));
-  {
-    StageTimer t3(ST_EPILOGUE);
-    SS_TRY(tl_start(b));
-  }
-  int64_t fill = b.fill();
-  for (int64_t r0 = 0; r0 < nrows; r0 += rb) {
-    const int64_t nb = nrows - r0 < rb ? nrows - r0 : rb;
-    SS_TRY(predict_rows_device<T>(g, 2, i_begin + r0, i_begin + r0 + nb, clean, scores.p, nt));
-    StageTimer t3(ST_EPILOGUE);
-    SS_TRY((tl_add_block<T, int>(b.nx, nt, b.L, fill, g.Ys.ptr.p + i_begin + r0, 0, g.Ys.idx.p, 0,
-                                 (int64_t)(hp[r0 + nb] - hp[r0]), scores.p, nb, nt, i_begin + r0, nullptr, b.w)));
-    fill = fill + nb < b.L ? fill + nb : b.L;
-  }
-  SS_TRY(timing_mark(&e_end));
-  timing_span(ST_TOTAL, e_begin, e_end);
-  return tl_commit(b, nrows, (int64_t)(hp[nrows] - hp[0]));
+  TlAdd<T> add(*bp);
+  SS_TRY(loo_blocks<T>(g, i_begin, i_end, clean, sweep_block_rows<T>(block_rows, nrows, nt),
+                       [&] { return add.start(); }, [&](const SweepBlock<T, int>& k) { return add.block(k); }, no_step));
+  return add.commit();
 }
 
-// k-fold rows into the table where they are produced: the blocks, label gather and checks of pool_add_kfold_impl; a
-// block's rows are its members (fold order), each under its source index
+// k-fold rows into the table where they are produced
 template <class T>
 static int tl_add_kfold_impl(ss_target_topl* th, ss_graph* h, const int32_t* fold_of_source, int nfolds, int64_t i_begin,
                              int64_t i_end, int clean, int64_t block_rows, int mem) {
@@ -2118,72 +2011,24 @@ static int tl_add_kfold_impl(ss_target_topl* th, ss_graph* h, const int32_t* fol
   SS_TRY(check_mem(mem));
   TlBox<T>* bp = nullptr;
   SS_TRY(tl_check<T>(th, &bp));
-  TlBox<T>& b = *bp;
   Graph<T>* gp = nullptr;
   SS_TRY(graph_check<T>(h, &gp));
   Graph<T>& g = *gp;
   SS_TRY(kfold_graph_check(g));
-  SS_TRY(kfold_range_check(i_begin, i_end, g.ns));
-  if (block_rows < 0) return fail(SS_EINVAL, "target top-L add kfold: block_rows must be >= 0");
-  if (g.nt != b.nt)
+  SS_TRY(range_check(i_begin, i_end, g.ns));
+  SS_TRY(check_block_rows("target top-L add kfold", block_rows));
+  if (g.nt != bp->nt)
     return fail(SS_EINVAL, "target top-L add kfold: the graph has %lld targets, the handle %lld", (long long)g.nt,
-                (long long)b.nt);
+                (long long)bp->nt);
   KfoldPlan plan;
   SS_TRY(kfold_plan(fold_of_source, nfolds, g.ns, mem, plan));
   const int64_t nrows = i_end - i_begin, nt = g.nt;
   if (nrows == 0) return SS_OK;
-  hipStream_t st = ctx().stream;
-  int64_t rb = block_rows;
-  if (rb == 0) {
-    rb = (1LL << 30) / (nt * (int64_t)sizeof(T));  // about 1 GiB of scores
-    if (rb < 1) rb = 1;
-  }
-  if (rb > nrows) rb = nrows;
-  KfoldRange rg;
-  kfold_range(plan, i_begin, i_end, rg);
-  std::vector<int> map(rg.sel.size());
-  for (size_t q = 0; q < map.size(); ++q) map[q] = (int)(rg.sel[q] - i_begin);
-  KfoldWork<T> w;
-  SS_TRY(kfold_work_init<T>(g, plan, rg, map, w));
-  std::vector<int> hy((size_t)nrows + 1);
-  SS_HIP(hipMemcpyAsync(hy.data(), g.Ys.ptr.p + i_begin, hy.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-  SS_HIP(hipStreamSynchronize(st));
-  std::vector<int64_t> pptr((size_t)nrows + 1, 0);
-  for (int64_t q = 0; q < nrows; ++q) pptr[q + 1] = pptr[q] + (hy[map[q] + 1] - hy[map[q]]);
-  int64_t max_lab = 1;
-  for (int64_t p0 = 0; p0 < nrows; p0 += rb) {
-    const int64_t p1 = nrows - p0 < rb ? nrows : p0 + rb;
-    if (pptr[p1] - pptr[p0] > max_lab) max_lab = pptr[p1] - pptr[p0];
-  }
-  DevBuf<int64_t> d_pptr;
-  DevBuf<int> lab;
-  DevBuf<T> scores;
-  SS_TRY(d_pptr.alloc((size_t)nrows + 1));
-  SS_TRY(lab.alloc((size_t)max_lab));
-  SS_TRY(scores.alloc((size_t)rb * nt));
-  SS_HIP(hipMemcpyAsync(d_pptr.p, pptr.data(), pptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-  SS_TRY(graph_sell(g));
-  if (!g.dense.on) SS_TRY(graph_chunked(g, false));
-  timing_begin_call();
-  hipEvent_t e_begin, e_end;
-  SS_TRY(timing_mark(&e_begin));
-  {
-    StageTimer t3(ST_EPILOGUE);
-    SS_TRY(tl_start(b));
-  }
-  int64_t fill = b.fill();
-  for (int64_t p0 = 0; p0 < nrows; p0 += rb) {
-    const int64_t nb = nrows - p0 < rb ? nrows - p0 : rb;
-    SS_TRY(kfold_rows_device<T>(g, w, plan, rg, p0, p0 + nb, clean, scores.p, nt, nullptr));
-    StageTimer t3(ST_EPILOGUE);
-    SS_TRY(launch_gather_labels(g.Ys.ptr.p, g.Ys.idx.p, w.d_sel.p + p0, nb, d_pptr.p + p0, pptr[p0], lab.p));
-    SS_TRY((tl_add_block<T, int64_t>(b.nx, nt, b.L, fill, d_pptr.p + p0, pptr[p0], lab.p, 0, pptr[p0 + nb] - pptr[p0],
-                                     scores.p, nb, nt, 0, w.d_sel.p + p0, b.w)));
-    fill = fill + nb < b.L ? fill + nb : b.L;
-  }
-  SS_TRY(timing_mark(&e_end));
-  timing_span(ST_TOTAL, e_begin, e_end);
-  return tl_commit(b, nrows, pptr[nrows]);
+  TlAdd<T> add(*bp);
+  SS_TRY(kfold_blocks<T>(g, plan, i_begin, i_end, clean, sweep_block_rows<T>(block_rows, nrows, nt),
+                         [&] { return add.start(); }, [&](const SweepBlock<T, int64_t>& k) { return add.block(k); },
+                         no_step));
+  return add.commit();
 }
 
 template <class T>
