@@ -85,7 +85,7 @@ int ss_synchronize(void);
  * [6] number of SpMM launches, [7] number of stage-1 launches.  Writes min(n,8) values. */
 int ss_timing_last(double* ms, int n);
 /* Which kernels the last predict / spmm / fingerprint call of this host thread went through: a comma-separated list of tags
- * ("tanimoto_csr_sym", "tanimoto_csr_cross", "jaccard_csr_sym", "jaccard_csr_cross", "transfer", "transfer_loo", "transfer_dense_bf16_ring", "transfer_dense_bf16_128", "transfer_dense_f32_mfma",
+ * ("tanimoto_csr_sym", "tanimoto_csr_cross", "jaccard_csr_sym", "jaccard_csr_cross", "cutoff_csr", "recut", "transfer", "transfer_loo", "transfer_dense_bf16_ring", "transfer_dense_bf16_128", "transfer_dense_f32_mfma",
  * "spmm_sell", "spmm_sell_sorted", "spmm_csell", "spmm_colgroup", "spmm_chunked_narrow", ...), NUL-terminated, truncated
  * to n - 1 characters.  Lets a caller (and the parity tests) assert that a size-dependent routing decision was the one
  * expected.  Has no counterpart in the reference (its only switch is GPU::Bool, src/core.jl:402,404). */
@@ -172,6 +172,25 @@ int ss_cutoff_f32(const float* X, int64_t rows, int64_t cols, int64_t ld, float 
                   int weighted, float* out, int64_t ldo, int mem);
 int ss_cutoff_f64(const double* X, int64_t rows, int64_t cols, int64_t ld, double alpha,
                   int weighted, double* out, int64_t ldo, int mem);
+/* featurize(X, alpha, weighted) (src/core.jl:106-112) on a matrix that is already CSR: the reference's featurize takes
+ * any X, so it also cuts an already-featurized one.  Output entry (i, j) exists iff the input stores v at (i, j),
+ * v >= alpha (inclusive) and w = weighted ? v : 1 is non-zero; for alpha > 0 these are exactly the non-zeros of
+ * ss_cutoff_* on the densified matrix.  alpha <= 0 or NaN: SS_EINVAL (an unstored zero would pass an unweighted cutoff
+ * at alpha <= 0, which CSR cannot represent).  Input: rows x cols CSR as for ss_graph_create_csr_* (ptr[rows + 1] int64,
+ * idx int32 strictly ascending within a row, index_base 0 or 1, val == NULL: every stored value is 1), checked the same
+ * way.  Output and size protocol as ss_similarity_tanimoto_csr_*: optr[rows + 1] (int64), oidx[nnz] (int32, 0-BASED
+ * whatever index_base is, ascending within each row), oval[nnz] (oval == NULL: not written), all in `mem`; deterministic
+ * run to run.  oidx == NULL: size query -- writes optr and *nnz only.  capacity < nnz: SS_EINVAL with *nnz set.
+ * Cost: the caller's CSR is first staged and checked like a graph block (ss_graph_create_csr_*: upload when `mem` is
+ * host, one validating pass, one compaction into a device copy of idx and val -- also when `mem` is device), then cut
+ * by two streaming passes over that copy (ss_path_last: "cutoff_csr"); about twice the traffic of the cut alone and a
+ * temporary of the input's size.  ss_graph_recut_* cuts resident blocks directly and pays the two passes only. */
+int ss_cutoff_csr_f32(int64_t rows, int64_t cols, const int64_t* ptr, const int32_t* idx, const float* val,
+                      int index_base, float alpha, int weighted, int64_t* optr, int32_t* oidx, float* oval,
+                      int64_t capacity, int64_t* nnz, int mem);
+int ss_cutoff_csr_f64(int64_t rows, int64_t cols, const int64_t* ptr, const int32_t* idx, const double* val,
+                      int index_base, double alpha, int weighted, int64_t* optr, int32_t* oidx, double* oval,
+                      int64_t capacity, int64_t* nnz, int mem);
 /* k(G): number of non-zeros in every row (src/graphs.jl:9-11). */
 int ss_row_degree_f32(const float* G, int64_t rows, int64_t cols, int64_t ld, int64_t* deg, int mem);
 int ss_row_degree_f64(const double* G, int64_t rows, int64_t cols, int64_t ld, int64_t* deg, int mem);
@@ -270,6 +289,31 @@ int ss_graph_create_general_f64(int64_t n, int64_t nr, int64_t nc,
                                 const int64_t* b_ptr, const int32_t* b_idx, const double* b_val,
                                 const int64_t* w_ptr, const int32_t* w_idx, const double* w_val,
                                 int index_base, int mem, ss_graph** out);
+/* Cutoff sweeps.  ss_graph_recut_*: a new, independent handle equal to `parent` with Xq and Xs (and the transpose of Xs)
+ * replaced by their cutoff under the rule of ss_cutoff_csr_*; the labels are copied on the device, the degrees are
+ * recounted, lazily built operands start empty.  The parent is untouched, stays usable and may be destroyed before the
+ * child.  Nothing is re-read from the caller and no all-pairs producer or sort runs: the cost is two streaming passes
+ * over the parent's three similarity blocks (ss_path_last: "recut").
+ * Contract: for a parent built WEIGHTED at a cutoff a0 > 0 by ss_graph_create_fingerprint_*, _features_*, _dense_* (with
+ * apply_cutoff) and a child at alpha >= a0, the child is the graph the parent's own constructor builds at (alpha,
+ * weighted): ss_graph_info, ss_graph_degrees and every score of ss_predict_*, ss_predict_loo_* and
+ * ss_predict_kfold_rows_* match bit for bit, hence every evaluator too (the edges with s >= alpha are a subset of those
+ * with s >= a0, and a weighted graph stores s itself).  For any other parent (ss_graph_create_csr_*, an unweighted
+ * parent, alpha < a0) it is featurize applied to the stored X.  A child can be cut again.
+ * alpha <= 0 or NaN: SS_EINVAL.  A general graph: SS_EUNSUPPORTED.  A dense-similarity graph: SS_EUNSUPPORTED (use
+ * ss_graph_set_cutoff_*).  A handle of the other precision: SS_EINVAL.  On any error *out is NULL. */
+int ss_graph_recut_f32(const ss_graph* parent, float alpha, int weighted, ss_graph** out);
+int ss_graph_recut_f64(const ss_graph* parent, double alpha, int weighted, ss_graph** out);
+/* The same for a dense-similarity graph (ss_graph_create_similarity_*), IN PLACE: the raw similarities are resident and
+ * the cutoff is applied inside the stage-1 product, so a new cutoff only replaces (alpha, weighted) in the handle,
+ * recounts the degrees and drops the cached bf16 planes of the thresholded source side; nothing is copied or re-staged,
+ * and alpha may go down as well as up.  Afterwards every serving call gives, bit for bit, what a fresh
+ * ss_graph_create_similarity_* at (alpha, weighted) gives.  Any alpha the constructor accepts is accepted.  A graph of
+ * another kind: SS_EUNSUPPORTED (use ss_graph_recut_*), handle untouched.  SS_ENOMEM / SS_EHIP from the degree recount
+ * (it re-allocates the degree buffers) leave the handle with the new cutoff and without valid degrees: call
+ * ss_graph_set_cutoff_* again until it succeeds, or destroy the handle, before any serving call. */
+int ss_graph_set_cutoff_f32(ss_graph* g, float alpha, int weighted);
+int ss_graph_set_cutoff_f64(ss_graph* g, double alpha, int weighted);
 int ss_graph_destroy(ss_graph* g);
 /* sizes[0..6] = nq, ns, nf, nt, nnz(Xq), nnz(Xs), nnz(Ys) after dropping stored zeros. */
 int ss_graph_info(const ss_graph* g, int64_t sizes[7]);

@@ -28,7 +28,7 @@ using SparseArrays
 include("SimSpreadHIP.jl")
 using .SimSpreadHIP
 
-export k, cutoff, cutoff!, featurize, featurize!, construct, spread, predict, clean!, Network, predict_loo, predict_kfold
+export k, cutoff, cutoff!, featurize, featurize!, construct, spread, predict, clean!, Network, predict_loo, predict_kfold, recut
 
 const NamedMatrix = NamedArrays.NamedMatrix
 
@@ -125,6 +125,26 @@ function device(N::Network, ::Type{T}) where {T<:Union{Float32,Float64}}
     get!(N.dev, T) do
         SimSpreadHIP.graph(isempty(N.queries) ? nothing : N.Xq, N.Xs, N.Ys; T=T)
     end
+end
+
+"""
+    recut(N::Network, alpha, weighted=true)
+
+Cutoff sweeps: the network `construct` would return for `featurize(X, alpha, weighted)` of the similarities `N` was built
+from, when `N` itself was built from weighted features at a cutoff `<= alpha` (`alpha > 0`).  The host blocks go through
+`cutoff` in Float64; a Float64 handle `N` already holds on the device is cut there (`SimSpreadHIP.recut`: two streaming
+passes, nothing re-uploaded) with the same Float64 comparison, so it holds exactly the host blocks.  A Float32 handle is
+not carried over: rounding a similarity and the cutoff to Float32 can move an edge that sits on the threshold, so
+`device(N, Float32)` builds it from the cut host blocks at first use, as for any other network.  `N` is left as it is.
+"""
+function recut(N::Network, alpha::AbstractFloat, weighted::Bool=true)
+    alpha > 0 || throw(ArgumentError("recut needs alpha > 0"))
+    a = Float64(alpha)
+    Xq = isempty(N.Xq) ? copy(N.Xq) : cutoff(N.Xq, a, weighted)
+    Xs = cutoff(N.Xs, a, weighted)
+    dev = Dict{DataType,SimSpreadHIP.Graph}()
+    haskey(N.dev, Float64) && (dev[Float64] = SimSpreadHIP.recut(N.dev[Float64], a; weighted=weighted))
+    return Network(N.kind, N.queries, N.sources, N.features, N.targets, Xq, Xs, N.Ys, dev)
 end
 
 # The reference compares the two sorted name vectors element-wise (src/core.jl:156,231,314): unequal lengths throw a

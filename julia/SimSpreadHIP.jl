@@ -232,6 +232,36 @@ function jaccard_csr(Fa::Matrix{T}, Fb::Union{Nothing,Matrix{T}}=nothing; alpha:
     return permutedims(SparseMatrixCSC(nb, na, ptr .+ 1, Vector{Int}(idx) .+ 1, val))
 end
 
+"""
+    cutoff_csr(X::SparseMatrixCSC{T}, alpha; weighted=false) where T<:Union{Float32,Float64}
+
+`featurize(X, alpha, weighted)` (src/core.jl:106-112) on a sparse matrix, on the device: a stored `v` stays iff
+`v >= alpha`, as `v` when `weighted` and `1` otherwise.  `alpha` must be positive (an unstored zero would pass an
+unweighted cutoff at `alpha <= 0`).  Returns a `SparseMatrixCSC` of the same size.
+"""
+function cutoff_csr(X::SparseMatrixCSC{T}, alpha::Real; weighted::Bool=false) where {T<:Union{Float32,Float64}}
+    rows, cols = size(X)
+    ip, ii, iv = _csr(X, T)
+    ptr = Vector{Int64}(undef, rows + 1)
+    nnz = Ref{Int64}(0)
+    call(idx, val, cap) = if T === Float32
+        ccall((:ss_cutoff_csr_f32, LIB), Cint,
+              (Int64, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Float32}, Cint, Float32, Cint, Ptr{Int64}, Ptr{Int32},
+               Ptr{Float32}, Int64, Ptr{Int64}, Cint),
+              rows, cols, ip, ii, iv, 1, Float32(alpha), weighted ? 1 : 0, ptr, idx, val, cap, nnz, SS_MEM_HOST)
+    else
+        ccall((:ss_cutoff_csr_f64, LIB), Cint,
+              (Int64, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Cint, Float64, Cint, Ptr{Int64}, Ptr{Int32},
+               Ptr{Float64}, Int64, Ptr{Int64}, Cint),
+              rows, cols, ip, ii, iv, 1, Float64(alpha), weighted ? 1 : 0, ptr, idx, val, cap, nnz, SS_MEM_HOST)
+    end
+    check(call(Ptr{Int32}(C_NULL), Ptr{T}(C_NULL), 0))             # size query
+    idx, val = Vector{Int32}(undef, nnz[]), Vector{T}(undef, nnz[])
+    check(call(idx, val, nnz[]))
+    # the result is 0-based row-major CSR of (rows x cols) == CSC of its transpose
+    return permutedims(SparseMatrixCSC(cols, rows, ptr .+ 1, Vector{Int}(idx) .+ 1, val))
+end
+
 # ------------------------------------------------------------------------------------------------ graph handles
 mutable struct Graph{T<:Union{Float32,Float64}}
     handle::Ptr{Cvoid}
@@ -431,6 +461,43 @@ function graph_general(L::SparseMatrixCSC, B::SparseMatrixCSC, Wt::SparseMatrixC
     end
     check(rc)
     return Graph{T}(h[], nr, n, n, nc)
+end
+
+"""
+    recut(g::Graph, alpha; weighted=true)
+
+Cutoff sweeps: a new, independent graph equal to `g` with `Xq`, `Xs` replaced by `featurize(X, alpha, weighted)` of the
+blocks resident on the device (two streaming passes; no all-pairs producer, no sort).  For a parent built weighted at a
+cutoff `a0 > 0` and `alpha >= a0` the child is bitwise the graph the parent's constructor builds at `(alpha, weighted)`.
+`g` stays usable and may be destroyed first.  Dense-similarity graphs use `set_cutoff!`.
+"""
+function recut(g::Graph{T}, alpha::Real; weighted::Bool=true) where {T}
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = if T === Float32
+        ccall((:ss_graph_recut_f32, LIB), Cint, (Ptr{Cvoid}, Float32, Cint, Ref{Ptr{Cvoid}}),
+              g.handle, Float32(alpha), weighted ? 1 : 0, h)
+    else
+        ccall((:ss_graph_recut_f64, LIB), Cint, (Ptr{Cvoid}, Float64, Cint, Ref{Ptr{Cvoid}}),
+              g.handle, Float64(alpha), weighted ? 1 : 0, h)
+    end
+    check(rc)
+    return Graph{T}(h[], g.nq, g.ns, g.nf, g.nt)
+end
+
+"""
+    set_cutoff!(g::Graph, alpha; weighted=true)
+
+Dense-similarity graphs (`graph_similarity`): move the cutoff in place.  The raw similarities stay resident; afterwards
+`g` behaves bitwise like a fresh `graph_similarity` at `(alpha, weighted)`.  `alpha` may go down as well as up.
+"""
+function set_cutoff!(g::Graph{T}, alpha::Real; weighted::Bool=true) where {T}
+    rc = if T === Float32
+        ccall((:ss_graph_set_cutoff_f32, LIB), Cint, (Ptr{Cvoid}, Float32, Cint), g.handle, Float32(alpha), weighted ? 1 : 0)
+    else
+        ccall((:ss_graph_set_cutoff_f64, LIB), Cint, (Ptr{Cvoid}, Float64, Cint), g.handle, Float64(alpha), weighted ? 1 : 0)
+    end
+    check(rc)
+    return g
 end
 
 "sizes after dropping stored zeros: (nq, ns, nf, nt, nnz(Xq), nnz(Xs), nnz(Ys))."

@@ -89,6 +89,9 @@ def _sigs():
         s[f"ss_graph_create_features_{suf}"] = ([_i64] * 4 + [_vp, _i64, _vp, _i64] + [_vp] * 3 + [_int, ft, _int, _int, _vp],
                                                 _int)
 
+        s[f"ss_cutoff_csr_{suf}"] = ([_i64, _i64, _vp, _vp, _vp, _int, ft, _int, _vp, _vp, _vp, _i64, _vp, _int], _int)
+        s[f"ss_graph_recut_{suf}"] = ([_vp, ft, _int, _vp], _int)
+        s[f"ss_graph_set_cutoff_{suf}"] = ([_vp, ft, _int], _int)
         s[f"ss_cutoff_{suf}"] = ([_vp, _i64, _i64, _i64, ft, _int, _vp, _i64, _int], _int)
         s[f"ss_similarity_jaccard_{suf}"] = ([_vp, _i64, _i64, _i64, _vp, _i64, _int], _int)
         s[f"ss_row_degree_{suf}"] = ([_vp, _i64, _i64, _i64, _vp, _int], _int)

@@ -581,6 +581,66 @@ static int graph_create_features_impl(int64_t nq, int64_t ns, int64_t nt, int64_
       "jaccard_csr_cross", y_ptr, y_idx, y_val, index_base, mem, out);
 }
 
+// ------------------------------------------------------------------ cutoff sweeps: featurize on resident CSR
+// an unstored zero passes an unweighted cutoff at alpha <= 0, which CSR cannot hold
+template <class T>
+static int check_cut_alpha(const char* what, T alpha) {
+  if (!(alpha > T(0))) return fail(SS_EINVAL, "%s: alpha must be > 0 and not NaN (alpha <= 0 keeps unstored zeros)", what);
+  return SS_OK;
+}
+
+template <class T>
+static int cutoff_csr_impl(int64_t rows, int64_t cols, const int64_t* ptr, const int32_t* idx, const T* val,
+                           int index_base, T alpha, int weighted, int64_t* optr, int32_t* oidx, T* oval,
+                           int64_t capacity, int64_t* nnz, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  path_note().clear();
+  SS_TRY(check_cut_alpha("cutoff_csr", alpha));
+  if (!optr || !nnz) return fail(SS_EINVAL, "cutoff_csr: optr and nnz must not be NULL");
+  DevCsr<T> in;  // checked, 0-based, stored zeros dropped (they fail v >= alpha > 0 anyway)
+  SS_TRY(csr_from_user<T>(rows, cols, ptr, idx, val, index_base, mem, in));
+  CutCsr<T> cc;
+  SS_TRY(cc.count(in, alpha, weighted != 0));
+  path_add("cutoff_csr");
+  return emit_pair_csr<T>(cc, rows, optr, oidx, oval, capacity, nnz, mem);
+}
+
+template <class T>
+static int graph_recut_impl(const ss_graph* h, T alpha, int weighted, ss_graph** out) {
+  if (!out) return fail(SS_EINVAL, "out handle pointer is NULL");
+  *out = nullptr;
+  Graph<T>* p = nullptr;
+  SS_TRY(graph_check<T>(h, &p));
+  path_note().clear();
+  if (p->general) return fail(SS_EUNSUPPORTED, "recut: a general graph carries no featurize cutoff");
+  if (p->dense.on)
+    return fail(SS_EUNSUPPORTED, "recut: a dense-similarity graph re-thresholds in place, use ss_graph_set_cutoff_*");
+  SS_TRY(check_cut_alpha("recut", alpha));
+  GraphBox<T>* box = new (std::nothrow) GraphBox<T>();
+  if (!box) return fail(SS_ENOMEM, "host allocation failed");
+  box->dtype = (int)sizeof(T);
+  const int rc = graph_recut<T>(*p, alpha, weighted != 0, box->g);
+  if (rc != SS_OK) { delete box; return rc; }
+  path_add("recut");
+  *out = reinterpret_cast<ss_graph*>(box);
+  return SS_OK;
+}
+
+// dense-similarity graph: the cutoff lives in the handle, the raw similarities stay where they are
+template <class T>
+static int graph_set_cutoff_impl(ss_graph* h, T alpha, int weighted) {
+  Graph<T>* g = nullptr;
+  SS_TRY(graph_check<T>(h, &g));
+  if (!g->dense.on)
+    return fail(SS_EUNSUPPORTED, "set_cutoff: only a dense-similarity graph holds raw similarities, use ss_graph_recut_*");
+  DenseSim<T>& d = g->dense;
+  d.alpha = alpha;
+  d.weighted = weighted != 0;
+  d.Bpl_np = 0;  // the bf16 planes of the thresholded source side are rebuilt by the next prediction
+  return dense_degrees(*g);  // kf, ks, their reciprocals and 1/(kf-1); synchronises
+}
+
 // stage-2 operand of a graph: W = Ys' cut for the tile width of this precision
 template <class T>
 static int graph_sell(Graph<T>& g) {
@@ -2755,6 +2815,49 @@ int ss_graph_create_features_f64(int64_t nq, int64_t ns, int64_t nt, int64_t d, 
   SS_API_LOCK();
   return graph_create_features_impl<double>(nq, ns, nt, d, Fq, ldq, Fs, lds, y_ptr, y_idx, y_val, index_base, alpha,
                                             weighted, mem, out);
+}
+
+int ss_cutoff_csr_f32(int64_t rows, int64_t cols, const int64_t* ptr, const int32_t* idx, const float* val,
+                      int index_base, float alpha, int weighted, int64_t* optr, int32_t* oidx, float* oval,
+                      int64_t capacity, int64_t* nnz, int mem) {
+  SS_API_LOCK();
+  return cutoff_csr_impl<float>(rows, cols, ptr, idx, val, index_base, alpha, weighted, optr, oidx, oval, capacity, nnz,
+                                mem);
+}
+int ss_cutoff_csr_f64(int64_t rows, int64_t cols, const int64_t* ptr, const int32_t* idx, const double* val,
+                      int index_base, double alpha, int weighted, int64_t* optr, int32_t* oidx, double* oval,
+                      int64_t capacity, int64_t* nnz, int mem) {
+  SS_API_LOCK();
+  return cutoff_csr_impl<double>(rows, cols, ptr, idx, val, index_base, alpha, weighted, optr, oidx, oval, capacity, nnz,
+                                 mem);
+}
+int ss_graph_recut_f32(const ss_graph* parent, float alpha, int weighted, ss_graph** out) {
+  SS_API_LOCK();
+  SS_TRY(require_init());
+  if (!parent) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(parent);
+  return graph_recut_impl<float>(parent, alpha, weighted, out);
+}
+int ss_graph_recut_f64(const ss_graph* parent, double alpha, int weighted, ss_graph** out) {
+  SS_API_LOCK();
+  SS_TRY(require_init());
+  if (!parent) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(parent);
+  return graph_recut_impl<double>(parent, alpha, weighted, out);
+}
+int ss_graph_set_cutoff_f32(ss_graph* g, float alpha, int weighted) {
+  SS_API_LOCK();
+  SS_TRY(require_init());
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  return graph_set_cutoff_impl<float>(g, alpha, weighted);
+}
+int ss_graph_set_cutoff_f64(ss_graph* g, double alpha, int weighted) {
+  SS_API_LOCK();
+  SS_TRY(require_init());
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  return graph_set_cutoff_impl<double>(g, alpha, weighted);
 }
 
 int ss_graph_destroy(ss_graph* h) {

@@ -1179,9 +1179,14 @@ __global__ void degree_kernel(const int* __restrict__ pa, const int* __restrict_
 
 template <class T>
 int graph_finalize(Graph<T>& g) {
-  hipStream_t st = ctx().stream;
   SS_TRY(csr_transpose(g.Xs, g.XsT));
   SS_TRY(csr_transpose(g.Ys, g.YsT));
+  return graph_degrees(g);
+}
+
+template <class T>
+int graph_degrees(Graph<T>& g) {
+  hipStream_t st = ctx().stream;
   SS_TRY(g.kf.alloc(g.nf));
   SS_TRY(g.ks.alloc(g.ns));
   SS_TRY(g.kt.alloc(g.nt));
@@ -1257,6 +1262,7 @@ int graph_finalize_general_targets(Graph<T>& g) {
   template int chunked_build<T>(const DevCsr<T>&, int, int, DevChunked<T>&);                                     \
   template int sell_build<T>(const DevCsr<T>&, int, DevSell<T>&, int);                                            \
   template int graph_finalize<T>(Graph<T>&);                                                                   \
+  template int graph_degrees<T>(Graph<T>&);                                                                    \
   template int graph_finalize_general<T>(Graph<T>&);
 SS_INSTANTIATE(float)
 SS_INSTANTIATE(double)

@@ -155,6 +155,8 @@ int csell_build(const DevCsr<T>& in, int KC, int QT, DevCsell<T>& out);   // out
 template <class T>
 int graph_finalize(Graph<T>& g);  // transposes + degrees
 template <class T>
+int graph_degrees(Graph<T>& g);   // kf, ks, kt and their reciprocals from the row pointers of XsT, Xs + Ys, YsT (synchronises)
+template <class T>
 int graph_finalize_general(Graph<T>& g);  // degrees = row counts of B (held in XsT)
 template <class T>
 int graph_finalize_general_targets(Graph<T>& g);  // kt / inv_kt from YsT only
@@ -429,6 +431,21 @@ struct JaccardCsr : PairCsr<T> {
             bool weighted);
   int fill(int* idx, T* val, bool* binary) override;
 };
+
+// ---- recut.hip: featurize on a device CSR matrix (entry kept iff v >= alpha, alpha > 0; as v when weighted, else 1),
+// two streaming passes over `in`, which must outlive the producer.  graph_recut: g = p with Xq, Xs, XsT cut, the labels
+// copied and the degrees recounted; lazily built operands of g stay empty.
+template <class T>
+struct CutCsr : PairCsr<T> {
+  using PairCsr<T>::what, PairCsr<T>::na, PairCsr<T>::nb, PairCsr<T>::ntj, PairCsr<T>::nnz, PairCsr<T>::alpha,
+      PairCsr<T>::weighted, PairCsr<T>::sym, PairCsr<T>::counts, PairCsr<T>::ptr;
+  const DevCsr<T>* in = nullptr;
+  int gshift = 6;  // log2 of the lanes that share a row
+  int count(const DevCsr<T>& in, T alpha, bool weighted);
+  int fill(int* idx, T* val, bool* binary) override;
+};
+template <class T>
+int graph_recut(const Graph<T>& p, T alpha, bool weighted, Graph<T>& g);
 
 // ---- comm.hip: in-library score gather over RCCL (dlopen'ed), one process per GPU
 int comm_unique_id(char* id128);

@@ -466,6 +466,29 @@ class DeviceGraph:
         finally:
             p.close()
 
+    # ---------------------------------------------------------------- cutoff sweeps
+    def _ctype(self):
+        return C.c_float if self.dtype == np.float32 else C.c_double
+
+    def recut(self, alpha: float, weighted: bool = True) -> "DeviceGraph":
+        """A new, independent graph equal to this one with Xq, Xs replaced by ``featurize(X, alpha, weighted)`` of the
+        blocks resident on the device (two streaming passes; no producer, no sort, nothing re-read from the caller).
+        For a parent built weighted at a cutoff a0 > 0 and alpha >= a0 the child is bitwise the graph the parent's own
+        constructor builds at (alpha, weighted): build one parent at the lowest cutoff of a sweep and cut the rest from
+        it.  The parent stays usable and may be closed first.  Dense-similarity graphs use ``set_cutoff``."""
+        h = C.c_void_p()
+        fn = getattr(L.lib(), f"ss_graph_recut_{self._suf}")
+        L.check(fn(self._h, self._ctype()(alpha), 1 if weighted else 0, C.byref(h)))
+        return DeviceGraph(h, self.dtype)
+
+    def set_cutoff(self, alpha: float, weighted: bool = True) -> "DeviceGraph":
+        """Dense-similarity graphs (``from_similarity``): move the cutoff in place.  The raw similarities stay resident,
+        only (alpha, weighted), the degrees and the cached operand planes change; afterwards the graph behaves bitwise
+        like a fresh ``from_similarity`` at (alpha, weighted).  alpha may go down as well as up.  Returns self."""
+        fn = getattr(L.lib(), f"ss_graph_set_cutoff_{self._suf}")
+        L.check(fn(self._h, self._ctype()(alpha), 1 if weighted else 0))
+        return self
+
     def close(self):
         if self._h is not None and self._h.value:
             L.load().ss_graph_destroy(self._h)
@@ -1322,3 +1345,46 @@ def jaccard_csr(Fa, Fb=None, alpha=None, weighted: bool = True, dtype=np.float32
                 nnz.value, C.byref(nnz), L_.SS_MEM_HOST))
     del keep
     return sp.csr_matrix((val[:nnz.value], idx[:nnz.value], ptr), shape=(na, nb))
+
+
+def cutoff_csr(X, alpha: float, weighted: bool = False, dtype=np.float32, shape=None):
+    """``featurize(X, alpha, weighted)`` on a sparse matrix, on the device: entry (i, j) with stored value v stays iff
+    v >= alpha, as v when weighted and 1 otherwise (alpha > 0: the non-zeros of ``cutoff`` on the densified matrix).
+    X: a scipy.sparse matrix (returns a scipy.sparse.csr_matrix), or device CSR parts (ptr int64, idx int32, val or
+    None) of torch CUDA tensors with ``shape=(rows, cols)`` (returns (ptr, idx, val) tensors, 0-based)."""
+    dt = _feature_dtype(dtype)
+    fn = getattr(L_.lib(), f"ss_cutoff_csr_{_suffix(dt)}")
+    ctype = C.c_float if dt == np.float32 else C.c_double
+    nnz = C.c_int64(0)
+    w = 1 if weighted else 0
+    if isinstance(X, (tuple, list)) and _is_torch(X[0]):
+        import torch
+        if shape is None:
+            raise TypeError("device CSR parts need shape=(rows, cols)")
+        rows, cols = int(shape[0]), int(shape[1])
+        want = torch.float32 if dt == np.float32 else torch.float64
+        ip, ii, iv = X[0].to(torch.int64).contiguous(), X[1].to(torch.int32).contiguous(), X[2]
+        iv = None if iv is None else iv.to(want).contiguous()
+        if ip.numel() != rows + 1:
+            raise ValueError("ptr must have rows + 1 entries")
+        pv = None if iv is None else iv.data_ptr()
+        ptr = torch.empty(rows + 1, dtype=torch.int64, device=ip.device)
+        L_.check(fn(rows, cols, ip.data_ptr(), ii.data_ptr(), pv, 0, ctype(alpha), w, ptr.data_ptr(), None, None, 0,
+                    C.byref(nnz), L_.SS_MEM_DEVICE))
+        idx = torch.empty(max(nnz.value, 1), dtype=torch.int32, device=ip.device)
+        val = torch.empty(max(nnz.value, 1), dtype=want, device=ip.device)
+        L_.check(fn(rows, cols, ip.data_ptr(), ii.data_ptr(), pv, 0, ctype(alpha), w, ptr.data_ptr(), idx.data_ptr(),
+                    val.data_ptr(), nnz.value, C.byref(nnz), L_.SS_MEM_DEVICE))
+        return ptr, idx[:nnz.value], val[:nnz.value]
+    import scipy.sparse as sp
+    X = sp.csr_matrix(X)
+    rows, cols = X.shape
+    ip, ii, iv = _csr_parts(X, dt)
+    ptr = np.zeros(rows + 1, np.int64)
+    L_.check(fn(rows, cols, _ptr(ip), _ptr(ii), _ptr(iv), 0, ctype(alpha), w, ptr.ctypes.data, None, None, 0,
+                C.byref(nnz), L_.SS_MEM_HOST))
+    idx = np.empty(max(nnz.value, 1), np.int32)
+    val = np.empty(max(nnz.value, 1), dt)
+    L_.check(fn(rows, cols, _ptr(ip), _ptr(ii), _ptr(iv), 0, ctype(alpha), w, ptr.ctypes.data, idx.ctypes.data,
+                val.ctypes.data, nnz.value, C.byref(nnz), L_.SS_MEM_HOST))
+    return sp.csr_matrix((val[:nnz.value], idx[:nnz.value], ptr), shape=(rows, cols))
