@@ -57,6 +57,7 @@ enum {
 enum { SS_MEM_HOST = 0, SS_MEM_DEVICE = 1 };
 enum { SS_ROWS_QUERY = 0, SS_ROWS_SOURCE = 1 };
 enum { SS_LAYOUT_ROWMAJOR = 0, SS_LAYOUT_COLMAJOR = 1 };
+enum { SS_SIM_COSINE = 0, SS_SIM_TANIMOTO = 1, SS_SIM_DICE = 2 }; /* `metric` of ss_similarity_dot_csr_* */
 
 typedef struct ss_graph ss_graph; /* tri-partite query/source/feature/target graph, device resident */
 typedef struct ss_spmat ss_spmat; /* one sparse operand W of F = W*R, device resident            */
@@ -85,7 +86,7 @@ int ss_synchronize(void);
  * [6] number of SpMM launches, [7] number of stage-1 launches.  Writes min(n,8) values. */
 int ss_timing_last(double* ms, int n);
 /* Which kernels the last predict / spmm / fingerprint call of this host thread went through: a comma-separated list of tags
- * ("tanimoto_csr_sym", "tanimoto_csr_cross", "jaccard_csr_sym", "jaccard_csr_cross", "cutoff_csr", "recut", "transfer", "transfer_loo", "transfer_dense_bf16_ring", "transfer_dense_bf16_128", "transfer_dense_f32_mfma",
+ * ("tanimoto_csr_sym", "tanimoto_csr_cross", "jaccard_csr_sym", "jaccard_csr_cross", "dot_csr_sym", "dot_csr_cross", "cutoff_csr", "recut", "transfer", "transfer_loo", "transfer_dense_bf16_ring", "transfer_dense_bf16_128", "transfer_dense_f32_mfma",
  * "spmm_sell", "spmm_sell_sorted", "spmm_csell", "spmm_colgroup", "spmm_chunked_narrow", ...), NUL-terminated, truncated
  * to n - 1 characters.  Lets a caller (and the parity tests) assert that a size-dependent routing decision was the one
  * expected.  Has no counterpart in the reference (its only switch is GPU::Bool, src/core.jl:402,404). */
@@ -163,6 +164,29 @@ int ss_similarity_jaccard_csr_f32(const float* Fa, int64_t na, int64_t lda, cons
 int ss_similarity_jaccard_csr_f64(const double* Fa, int64_t na, int64_t lda, const double* Fb, int64_t nb, int64_t ldb,
                                   int64_t d, double alpha, int weighted, int64_t* ptr, int32_t* idx, double* val,
                                   int64_t capacity, int64_t* nnz, int mem);
+
+/* featurize(S, alpha, weighted) with S an inner-product similarity of real-valued rows (learned embeddings, continuous
+ * descriptors), as CSR; the dense n x n similarity never exists and the Gram blocks run on the matrix cores in full
+ * T = float / double precision.  For row i of Fa and row j of Fb:
+ *     g = sum_k a_k b_k, A = sum_k a_k^2, B = sum_k b_k^2, accumulated in T in an order the implementation chooses;
+ *     everything after the three sums is fixed, in T, with correctly rounded sqrt, *, /:
+ *       metric SS_SIM_COSINE    den = sqrt(A) * sqrt(B)   s = clamp(g / den, -1, 1)
+ *       metric SS_SIM_TANIMOTO  den = (A + B) - g         s = g / den
+ *       metric SS_SIM_DICE      den = A + B               s = (g + g) / den
+ *       den == 0:               s = (A == 0 && B == 0) ? 1 : 0    (two all-zero rows are identical; d = 0: s = 1)
+ *     Fb == NULL (symmetric): entry (i, i) has s = 1 exactly and entry (j, i) carries the bits of (i, j);
+ *     entry (i, j) is kept iff s >= alpha and v != 0, v = weighted ? s : 1  (a NaN s, from infinite features, is dropped).
+ * s of a pair does not depend on alpha, weighted or the run.  When every product and partial sum is exactly
+ * representable in T (small-integer features), g, A and B are exact in any order and the CSR is bitwise defined by the
+ * rule; otherwise g differs from the exact sum by at most the usual bound of a d-term sum in T.
+ * A NaN feature or a NaN alpha is SS_EINVAL, checked before anything is written; so is a metric outside 0..2.  Any
+ * other alpha is accepted.  Layout, output and size protocol exactly as ss_similarity_jaccard_csr_*. */
+int ss_similarity_dot_csr_f32(const float* Fa, int64_t na, int64_t lda, const float* Fb, int64_t nb, int64_t ldb,
+                              int64_t d, int metric, float alpha, int weighted, int64_t* ptr, int32_t* idx,
+                              float* val, int64_t capacity, int64_t* nnz, int mem);
+int ss_similarity_dot_csr_f64(const double* Fa, int64_t na, int64_t lda, const double* Fb, int64_t nb, int64_t ldb,
+                              int64_t d, int metric, double alpha, int weighted, int64_t* ptr, int32_t* idx,
+                              double* val, int64_t capacity, int64_t* nnz, int mem);
 
 /* ------------------------------------------------------- cutoff / k / spread -- */
 /* cutoff(X, alpha, weighted): out = x >= alpha ? (weighted ? x : 1) : 0, element-wise
@@ -271,6 +295,19 @@ int ss_graph_create_features_f64(int64_t nq, int64_t ns, int64_t nt, int64_t d,
                                  const double* Fq, int64_t ldq, const double* Fs, int64_t lds,
                                  const int64_t* y_ptr, const int32_t* y_idx, const double* y_val,
                                  int index_base, double alpha, int weighted, int mem, ss_graph** out);
+/* construct(y, X, ...) with X = featurize(S(F), alpha, weighted), S the inner-product similarity `metric` of real-valued
+ * rows (layout and rule as in ss_similarity_dot_csr_*): Xq = cut(S(Fq, Fs)) (nq x ns), Xs = cut(S(Fs, Fs)) (ns x ns), the
+ * features named after the sources (nf = ns); Y (ns x nt CSR) as in ss_graph_create_similarity_*.  The CSR blocks are
+ * produced on the device (ss_path_last: "dot_csr_sym", "dot_csr_cross").  nq may be 0 (Fq may then be NULL).
+ * Serves ss_predict_* (query and source rows), ss_predict_loo_*, ss_predict_kfold_* and ss_evaluate_loo_*. */
+int ss_graph_create_vectors_f32(int64_t nq, int64_t ns, int64_t nt, int64_t d, int metric,
+                                const float* Fq, int64_t ldq, const float* Fs, int64_t lds,
+                                const int64_t* y_ptr, const int32_t* y_idx, const float* y_val,
+                                int index_base, float alpha, int weighted, int mem, ss_graph** out);
+int ss_graph_create_vectors_f64(int64_t nq, int64_t ns, int64_t nt, int64_t d, int metric,
+                                const double* Fq, int64_t ldq, const double* Fs, int64_t lds,
+                                const int64_t* y_ptr, const int32_t* y_idx, const double* y_val,
+                                int index_base, double alpha, int weighted, int mem, ss_graph** out);
 /* General form for caller-built adjacency matrices: predict accepts ANY named A, B
  * (src/core.jl:402-425; the reference's own test passes hand-written 9 x 9 matrices,
  * test/runtests.jl:120-158).  With n nodes, the caller passes
@@ -294,7 +331,7 @@ int ss_graph_create_general_f64(int64_t n, int64_t nr, int64_t nc,
  * recounted, lazily built operands start empty.  The parent is untouched, stays usable and may be destroyed before the
  * child.  Nothing is re-read from the caller and no all-pairs producer or sort runs: the cost is two streaming passes
  * over the parent's three similarity blocks (ss_path_last: "recut").
- * Contract: for a parent built WEIGHTED at a cutoff a0 > 0 by ss_graph_create_fingerprint_*, _features_*, _dense_* (with
+ * Contract: for a parent built WEIGHTED at a cutoff a0 > 0 by ss_graph_create_fingerprint_*, _features_*, _vectors_*, _dense_* (with
  * apply_cutoff) and a child at alpha >= a0, the child is the graph the parent's own constructor builds at (alpha,
  * weighted): ss_graph_info, ss_graph_degrees and every score of ss_predict_*, ss_predict_loo_* and
  * ss_predict_kfold_rows_* match bit for bit, hence every evaluator too (the edges with s >= alpha are a subset of those

@@ -28,7 +28,7 @@ using SparseArrays
 include("SimSpreadHIP.jl")
 using .SimSpreadHIP
 
-export k, cutoff, cutoff!, featurize, featurize!, construct, spread, predict, clean!, Network, predict_loo, predict_kfold, recut
+export k, cutoff, cutoff!, featurize, featurize!, featurize_vectors, construct, spread, predict, clean!, Network, predict_loo, predict_kfold, recut
 
 const NamedMatrix = NamedArrays.NamedMatrix
 
@@ -66,6 +66,18 @@ function featurize!(X::NamedArray, alpha::AbstractFloat, weighted::Bool=true)   
     X.array = cutoff(Matrix{Float64}(X.array), Float64(alpha), weighted)
     setnames!(X, ["f$f" for f in names(X, 2)], 2)
     return X
+end
+
+"""
+    featurize_vectors(F::NamedArray, alpha, weighted=true; metric=:cosine)
+
+`featurize(S, alpha, weighted)` with `S` the inner-product similarity `metric` (`:cosine`, `:tanimoto`, `:dice`) between
+the rows of `F` (samples x descriptors), produced thresholded on the device (`SimSpreadHIP.dot_csr`): the dense `S` is
+never built.  Rows keep the sample names, columns are the features `"f" * name`, as `featurize` names them.
+"""
+function featurize_vectors(F::NamedArray, alpha::AbstractFloat, weighted::Bool=true; metric::Symbol=:cosine)
+    X = SimSpreadHIP.dot_csr(Matrix{Float64}(F.array); metric=metric, alpha=Float64(alpha), weighted=weighted)
+    return NamedArray(Matrix(X), (names(F, 1), ["f$f" for f in names(F, 1)]))
 end
 
 "spread(G): `W = G ./ k(G)` with zero-degree rows giving 0 (src/core.jl:365-371,373,375-380)."

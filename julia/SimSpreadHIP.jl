@@ -232,6 +232,49 @@ function jaccard_csr(Fa::Matrix{T}, Fb::Union{Nothing,Matrix{T}}=nothing; alpha:
     return permutedims(SparseMatrixCSC(nb, na, ptr .+ 1, Vector{Int}(idx) .+ 1, val))
 end
 
+const SIM_METRICS = Dict(:cosine => 0, :tanimoto => 1, :dice => 2)   # SS_SIM_* of include/simspread_hip.h
+_sim_metric(m::Symbol) = haskey(SIM_METRICS, m) ? Cint(SIM_METRICS[m]) :
+    throw(ArgumentError("metric must be :cosine, :tanimoto or :dice, got $(repr(m))"))
+
+"""
+    dot_csr(Fa::Matrix{T}, Fb=nothing; metric=:cosine, alpha, weighted=true) where T<:Union{Float32,Float64}
+
+`featurize(S, alpha, weighted)` with `S` an inner-product similarity of real-valued rows (embeddings, continuous
+descriptors), produced as CSR on the device without the dense similarity, the Gram blocks on the matrix cores in full `T`
+precision.  With `g = a⋅b`: `:cosine` `g / (|a| |b|)`, `:tanimoto` `g / (|a|² + |b|² - g)`, `:dice` `2g / (|a|² + |b|²)`;
+two all-zero rows have `s = 1`.  `Fa` is `na x d` with one sample per row; `Fb === nothing`: the symmetric block of `Fa`
+against itself (diagonal exactly 1).  Returns the `na x nb` matrix as a `SparseMatrixCSC`.
+"""
+function dot_csr(Fa::Matrix{T}, Fb::Union{Nothing,Matrix{T}}=nothing; metric::Symbol=:cosine, alpha::Real,
+                 weighted::Bool=true) where {T<:Union{Float32,Float64}}
+    na, d = size(Fa)
+    nb = Fb === nothing ? na : size(Fb, 1)
+    Fb === nothing || size(Fb, 2) == d || throw(ArgumentError("Fa and Fb have different numbers of features"))
+    pb = Fb === nothing ? Ptr{T}(C_NULL) : pointer(Fb)
+    m = _sim_metric(metric)
+    ptr = Vector{Int64}(undef, na + 1)
+    nnz = Ref{Int64}(0)
+    call(idx, val, cap) = if T === Float32
+        ccall((:ss_similarity_dot_csr_f32, LIB), Cint,
+              (Ptr{Float32}, Int64, Int64, Ptr{Float32}, Int64, Int64, Int64, Cint, Float32, Cint, Ptr{Int64}, Ptr{Int32},
+               Ptr{Float32}, Int64, Ptr{Int64}, Cint),
+              Fa, na, max(na, 1), pb, nb, max(nb, 1), d, m, Float32(alpha), weighted ? 1 : 0, ptr, idx, val, cap, nnz,
+              SS_MEM_HOST)
+    else
+        ccall((:ss_similarity_dot_csr_f64, LIB), Cint,
+              (Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Int64, Cint, Float64, Cint, Ptr{Int64}, Ptr{Int32},
+               Ptr{Float64}, Int64, Ptr{Int64}, Cint),
+              Fa, na, max(na, 1), pb, nb, max(nb, 1), d, m, Float64(alpha), weighted ? 1 : 0, ptr, idx, val, cap, nnz,
+              SS_MEM_HOST)
+    end
+    GC.@preserve Fa Fb begin
+        check(call(Ptr{Int32}(C_NULL), Ptr{T}(C_NULL), 0))             # size query
+        idx, val = Vector{Int32}(undef, nnz[]), Vector{T}(undef, nnz[])
+        check(call(idx, val, nnz[]))
+    end
+    return permutedims(SparseMatrixCSC(nb, na, ptr .+ 1, Vector{Int}(idx) .+ 1, val))
+end
+
 """
     cutoff_csr(X::SparseMatrixCSC{T}, alpha; weighted=false) where T<:Union{Float32,Float64}
 
@@ -431,6 +474,41 @@ function graph_features(Fq::Union{Nothing,Matrix{T}}, Fs::Matrix{T}, Y::SparseMa
               (Int64, Int64, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int32},
                Ptr{Float64}, Cint, Float64, Cint, Cint, Ref{Ptr{Cvoid}}),
               nq, ns, nt, d, pq, max(nq, 1), Fs, max(ns, 1), yp, yi, yv, 1, Float64(alpha), weighted ? 1 : 0,
+              SS_MEM_HOST, h)
+    end
+    check(rc)
+    return Graph{T}(h[], nq, ns, ns, nt)
+end
+
+"""
+    graph_vectors(Fq, Fs::Matrix{T}, Y::SparseMatrixCSC; metric=:cosine, alpha, weighted=true)
+
+`construct(y, X)` with `X = featurize(S(F), alpha, weighted)`, `S` the inner-product similarity `metric` of `dot_csr`
+between real-valued rows (`n x d` matrices, one sample per row): the thresholded blocks are produced as CSR on the
+device.  `Fq === nothing`: the 3-layer graph of `construct(y, X)` (leave-one-out / k-fold).
+"""
+function graph_vectors(Fq::Union{Nothing,Matrix{T}}, Fs::Matrix{T}, Y::SparseMatrixCSC; metric::Symbol=:cosine,
+                       alpha::Real, weighted::Bool=true) where {T<:Union{Float32,Float64}}
+    ns, d = size(Fs)
+    nq = Fq === nothing ? 0 : size(Fq, 1)
+    Fq === nothing || size(Fq, 2) == d || throw(ArgumentError("Fq and Fs have different numbers of features"))
+    size(Y, 1) == ns || throw(AssertionError("Labels and features have different number of source nodes"))
+    pq = Fq === nothing ? Ptr{T}(C_NULL) : pointer(Fq)
+    m = _sim_metric(metric)
+    yp, yi, yv = _csr(Y, T)
+    nt = size(Y, 2)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = GC.@preserve Fq if T === Float32
+        ccall((:ss_graph_create_vectors_f32, LIB), Cint,
+              (Int64, Int64, Int64, Int64, Cint, Ptr{Float32}, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Ptr{Int32},
+               Ptr{Float32}, Cint, Float32, Cint, Cint, Ref{Ptr{Cvoid}}),
+              nq, ns, nt, d, m, pq, max(nq, 1), Fs, max(ns, 1), yp, yi, yv, 1, Float32(alpha), weighted ? 1 : 0,
+              SS_MEM_HOST, h)
+    else
+        ccall((:ss_graph_create_vectors_f64, LIB), Cint,
+              (Int64, Int64, Int64, Int64, Cint, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int32},
+               Ptr{Float64}, Cint, Float64, Cint, Cint, Ref{Ptr{Cvoid}}),
+              nq, ns, nt, d, m, pq, max(nq, 1), Fs, max(ns, 1), yp, yi, yv, 1, Float64(alpha), weighted ? 1 : 0,
               SS_MEM_HOST, h)
     end
     check(rc)

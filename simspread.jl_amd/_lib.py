@@ -88,6 +88,10 @@ def _sigs():
                                                    _int], _int)
         s[f"ss_graph_create_features_{suf}"] = ([_i64] * 4 + [_vp, _i64, _vp, _i64] + [_vp] * 3 + [_int, ft, _int, _int, _vp],
                                                 _int)
+        s[f"ss_similarity_dot_csr_{suf}"] = ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, ft, _int, _vp, _vp, _vp, _i64, _vp,
+                                               _int], _int)
+        s[f"ss_graph_create_vectors_{suf}"] = ([_i64] * 4 + [_int, _vp, _i64, _vp, _i64] + [_vp] * 3
+                                               + [_int, ft, _int, _int, _vp], _int)
 
         s[f"ss_cutoff_csr_{suf}"] = ([_i64, _i64, _vp, _vp, _vp, _int, ft, _int, _vp, _vp, _vp, _i64, _vp, _int], _int)
         s[f"ss_graph_recut_{suf}"] = ([_vp, ft, _int, _vp], _int)

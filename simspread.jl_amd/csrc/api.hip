@@ -581,6 +581,72 @@ static int graph_create_features_impl(int64_t nq, int64_t ns, int64_t nt, int64_
       "jaccard_csr_cross", y_ptr, y_idx, y_val, index_base, mem, out);
 }
 
+// --------------------------------------------- real-valued rows -> thresholded cosine / Tanimoto / Dice CSR (MFMA)
+static int check_sim_metric(int metric) {
+  if (metric != SS_SIM_COSINE && metric != SS_SIM_TANIMOTO && metric != SS_SIM_DICE)
+    return fail(SS_EINVAL, "dot_csr: metric %d is not SS_SIM_COSINE, SS_SIM_TANIMOTO or SS_SIM_DICE", metric);
+  return SS_OK;
+}
+
+template <class T>
+static int dot_csr_impl(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d,
+                        int metric, T alpha, int weighted, int64_t* ptr, int32_t* idx, T* val, int64_t capacity,
+                        int64_t* nnz, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  path_note().clear();
+  const bool sym = (Fb == nullptr);
+  if (sym) {
+    nb = na;
+    ldb = lda;
+  }
+  SS_TRY(check_sim_metric(metric));
+  if (d < 0) return fail(SS_EINVAL, "dot_csr: negative feature count");
+  if (alpha != alpha) return fail(SS_EINVAL, "dot_csr: alpha is NaN");
+  SS_TRY(check_features("Fa", Fa, na, lda, d));
+  if (!sym) SS_TRY(check_features("Fb", Fb, nb, ldb, d));
+  if (!ptr || !nnz) return fail(SS_EINVAL, "dot_csr: ptr and nnz must not be NULL");
+  DevBuf<T> ba, bb;
+  const T *da = nullptr, *db = nullptr;
+  int64_t la = 0, lb = 0;
+  SS_TRY(stage_features(Fa, na, lda, d, mem, ba, &da, &la));
+  if (!sym) SS_TRY(stage_features(Fb, nb, ldb, d, mem, bb, &db, &lb));
+  DotCsr<T> dc;
+  SS_TRY(dc.count(da, na, la, sym ? nullptr : db, nb, lb, d, metric, alpha, weighted != 0));
+  path_add(sym ? "dot_csr_sym" : "dot_csr_cross");
+  return emit_pair_csr<T>(dc, na, ptr, idx, val, capacity, nnz, mem);
+}
+
+// construct(y, X, ...) with X = featurize(S(F), alpha, weighted), S the inner-product similarity `metric` of the rows:
+// Xs = cut(S(Fs, Fs)), Xq = cut(S(Fq, Fs)), features named after the sources
+template <class T>
+static int graph_create_vectors_impl(int64_t nq, int64_t ns, int64_t nt, int64_t d, int metric, const T* Fq,
+                                     int64_t ldq, const T* Fs, int64_t lds_, const int64_t* y_ptr, const int32_t* y_idx,
+                                     const T* y_val, int index_base, T alpha, int weighted, int mem, ss_graph** out) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  if (!out) return fail(SS_EINVAL, "out handle pointer is NULL");
+  *out = nullptr;
+  path_note().clear();
+  if (nt < 0) return fail(SS_EINVAL, "negative node count");
+  if (nt >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "dimension >= 2^31");
+  SS_TRY(check_sim_metric(metric));
+  if (d < 0) return fail(SS_EINVAL, "dot_csr: negative feature count");
+  if (alpha != alpha) return fail(SS_EINVAL, "dot_csr: alpha is NaN");
+  SS_TRY(check_features("Fq", Fq, nq, ldq, d));
+  SS_TRY(check_features("Fs", Fs, ns, lds_, d));
+  DevBuf<T> bq, bs;
+  const T *dq = nullptr, *ds = nullptr;
+  int64_t lq = 0, ls = 0;
+  SS_TRY(stage_features(Fs, ns, lds_, d, mem, bs, &ds, &ls));
+  SS_TRY(stage_features(Fq, nq, ldq, d, mem, bq, &dq, &lq));
+  const bool wgt = weighted != 0;
+  return graph_from_producers<T, DotCsr<T>>(
+      nq, ns, nt, [&](DotCsr<T>& p) { return p.count(ds, ns, ls, nullptr, ns, ls, d, metric, alpha, wgt); },
+      [&](DotCsr<T>& p) { return p.count(dq, nq, lq, ds, ns, ls, d, metric, alpha, wgt); }, "dot_csr_sym",
+      "dot_csr_cross", y_ptr, y_idx, y_val, index_base, mem, out);
+}
+
 // ------------------------------------------------------------------ cutoff sweeps: featurize on resident CSR
 // an unstored zero passes an unweighted cutoff at alpha <= 0, which CSR cannot hold
 template <class T>
@@ -2815,6 +2881,34 @@ int ss_graph_create_features_f64(int64_t nq, int64_t ns, int64_t nt, int64_t d, 
   SS_API_LOCK();
   return graph_create_features_impl<double>(nq, ns, nt, d, Fq, ldq, Fs, lds, y_ptr, y_idx, y_val, index_base, alpha,
                                             weighted, mem, out);
+}
+
+int ss_similarity_dot_csr_f32(const float* Fa, int64_t na, int64_t lda, const float* Fb, int64_t nb, int64_t ldb,
+                              int64_t d, int metric, float alpha, int weighted, int64_t* ptr, int32_t* idx, float* val,
+                              int64_t capacity, int64_t* nnz, int mem) {
+  SS_API_LOCK();
+  return dot_csr_impl<float>(Fa, na, lda, Fb, nb, ldb, d, metric, alpha, weighted, ptr, idx, val, capacity, nnz, mem);
+}
+int ss_similarity_dot_csr_f64(const double* Fa, int64_t na, int64_t lda, const double* Fb, int64_t nb, int64_t ldb,
+                              int64_t d, int metric, double alpha, int weighted, int64_t* ptr, int32_t* idx,
+                              double* val, int64_t capacity, int64_t* nnz, int mem) {
+  SS_API_LOCK();
+  return dot_csr_impl<double>(Fa, na, lda, Fb, nb, ldb, d, metric, alpha, weighted, ptr, idx, val, capacity, nnz, mem);
+}
+int ss_graph_create_vectors_f32(int64_t nq, int64_t ns, int64_t nt, int64_t d, int metric, const float* Fq, int64_t ldq,
+                                const float* Fs, int64_t lds, const int64_t* y_ptr, const int32_t* y_idx,
+                                const float* y_val, int index_base, float alpha, int weighted, int mem, ss_graph** out) {
+  SS_API_LOCK();
+  return graph_create_vectors_impl<float>(nq, ns, nt, d, metric, Fq, ldq, Fs, lds, y_ptr, y_idx, y_val, index_base,
+                                          alpha, weighted, mem, out);
+}
+int ss_graph_create_vectors_f64(int64_t nq, int64_t ns, int64_t nt, int64_t d, int metric, const double* Fq,
+                                int64_t ldq, const double* Fs, int64_t lds, const int64_t* y_ptr, const int32_t* y_idx,
+                                const double* y_val, int index_base, double alpha, int weighted, int mem,
+                                ss_graph** out) {
+  SS_API_LOCK();
+  return graph_create_vectors_impl<double>(nq, ns, nt, d, metric, Fq, ldq, Fs, lds, y_ptr, y_idx, y_val, index_base,
+                                           alpha, weighted, mem, out);
 }
 
 int ss_cutoff_csr_f32(int64_t rows, int64_t cols, const int64_t* ptr, const int32_t* idx, const float* val,

@@ -380,7 +380,7 @@ int launch_gather_labels(const int* ys_ptr, const int* ys_idx, const int* member
                          int64_t shift, int* out);
 
 // ---- pair_csr.hip: the host skeleton shared by the fused thresholded-similarity producers (fingerprint.hip,
-// jaccard_csr.hip).  A producer's count pass writes the kept entries of every (column tile, row) slot into counts;
+// jaccard_csr.hip, dot_csr.hip).  A producer's count pass writes the kept entries of every (column tile, row) slot into counts;
 // scan() turns them into in-row offsets and a 64-bit scan of the row totals into ptr and nnz; the producer's fill pass
 // writes every slot at ptr[i] + its offset in column order.
 template <class T>
@@ -428,6 +428,28 @@ struct JaccardCsr : PairCsr<T> {
   int64_t lda = 0, ldb = 0, d = 0;
   DevBuf<int> tile_nz;  // per launched tile: 1 when the count pass kept a pair in it (the fill pass skips the others)
   int count(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d, T alpha,
+            bool weighted);
+  int fill(int* idx, T* val, bool* binary) override;
+};
+
+// flag[0] = 1 when F (n x d, column-major, ld >= n; padding rows are not read) holds a NaN; enqueued only
+template <class T>
+int launch_feature_nan_scan(const T* F, int64_t n, int64_t ld, int64_t d, int* flag);
+
+// ---- dot_csr.hip: thresholded inner-product similarity (metric: SS_SIM_COSINE, SS_SIM_TANIMOTO, SS_SIM_DICE) of
+// real-valued rows as CSR; the Gram block of every 128 x 128 tile runs on the matrix cores in T (fp32 / fp64 MFMA).
+// Layout, symmetric mode and the NaN refusal as for JaccardCsr; the rule is the header comment of dot_csr.hip.
+template <class T>
+struct DotCsr : PairCsr<T> {
+  using PairCsr<T>::what, PairCsr<T>::na, PairCsr<T>::nb, PairCsr<T>::ntj, PairCsr<T>::nnz, PairCsr<T>::alpha,
+      PairCsr<T>::weighted, PairCsr<T>::sym, PairCsr<T>::counts, PairCsr<T>::ptr;
+  const T* Fa = nullptr;
+  const T* Fb = nullptr;
+  int64_t lda = 0, ldb = 0, d = 0;
+  int metric = 0;
+  DevBuf<T> norm_a, norm_b;  // squared row norms of each side (norm_b unused in symmetric mode)
+  DevBuf<int> tile_nz;       // per launched tile: 1 when the count pass kept a pair in it (the fill pass skips the others)
+  int count(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d, int metric, T alpha,
             bool weighted);
   int fill(int* idx, T* val, bool* binary) override;
 };

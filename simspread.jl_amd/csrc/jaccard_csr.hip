@@ -259,16 +259,18 @@ constexpr int threads() {
   return NTX * (TILE / Block<T>::RA);
 }
 
+}  // namespace
+
 template <class T>
-int has_nan(const T* F, int64_t n, int64_t ld, int64_t d, int* flag) {
+int launch_feature_nan_scan(const T* F, int64_t n, int64_t ld, int64_t d, int* flag) {
   if (n == 0 || d == 0) return SS_OK;
   const int64_t blocks = std::min<int64_t>(ceil_div(n * d, 256), 4096);
   hipLaunchKernelGGL(nan_scan_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, ctx().stream, F, n, ld, d, flag);
   SS_LAUNCH_CHECK();
   return SS_OK;
 }
-
-}  // namespace
+template int launch_feature_nan_scan<float>(const float*, int64_t, int64_t, int64_t, int*);
+template int launch_feature_nan_scan<double>(const double*, int64_t, int64_t, int64_t, int*);
 
 template <class T>
 int JaccardCsr<T>::count(const T* Fa_, int64_t na_, int64_t lda_, const T* Fb_, int64_t nb_, int64_t ldb_, int64_t d_,
@@ -289,8 +291,8 @@ int JaccardCsr<T>::count(const T* Fa_, int64_t na_, int64_t lda_, const T* Fb_, 
     DevBuf<int> flag;
     SS_TRY(flag.alloc(1));
     SS_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-    SS_TRY(has_nan<T>(Fa, na_, lda, d, flag.p));
-    if (!sym) SS_TRY(has_nan<T>(Fb, nb_, ldb, d, flag.p));
+    SS_TRY(launch_feature_nan_scan<T>(Fa, na_, lda, d, flag.p));
+    if (!sym) SS_TRY(launch_feature_nan_scan<T>(Fb, nb_, ldb, d, flag.p));
     int bad = 0;
     SS_HIP(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
     SS_HIP(hipStreamSynchronize(st));

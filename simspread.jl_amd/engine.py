@@ -284,6 +284,33 @@ class DeviceGraph:
         return cls(h, dt)
 
     @classmethod
+    def from_vectors(cls, Fq, Fs, Y, alpha: float, metric="cosine", weighted: bool = True, dtype=np.float32):
+        """``construct(y, X)`` with ``X = featurize(S(F), alpha, weighted)``, S the inner-product similarity ``metric``
+        ("cosine", "tanimoto", "dice") of ``dot_csr`` between real-valued rows (embeddings, continuous descriptors): Xq =
+        cut(S(Fq, Fs)), Xs = cut(S(Fs, Fs)), features named after the sources, produced as CSR on the device (the dense
+        similarity never exists).  Fq may be None (3-layer graph: predict_loo / predict_kfold / evaluate_loo).  Inputs
+        as ``from_features``."""
+        dt = _feature_dtype(dtype)
+        m = _sim_metric(metric)
+        dev = _is_torch(Fs)
+        keep = []
+        fq, nq, dq, ldq = _features(Fq, dt, dev, keep)
+        fs, ns, d, lds = _features(Fs, dt, dev, keep)
+        if Fq is not None and dq != d:
+            raise ValueError("Fq and Fs have different numbers of features")
+        yptr, yidx, yval, nt, mem = _source_labels(Y, ns, dt, dev, keep)
+        lib = L.lib()
+        h = C.c_void_p()
+        ctype = C.c_float if dt == np.float32 else C.c_double
+        fn = getattr(lib, f"ss_graph_create_vectors_{_suffix(dt)}")
+        L.check(fn(nq, ns, nt, d, m, fq, ldq, fs, lds, yptr, yidx, yval, 0, ctype(alpha), 1 if weighted else 0, mem,
+                   C.byref(h)))
+        if dev:
+            L.check(lib.ss_synchronize())
+        del keep
+        return cls(h, dt)
+
+    @classmethod
     def general(cls, A_rows, B, B_cols_T, dtype=np.float64):
         """predict for caller-built A, B (src/core.jl:402-425): A_rows = A[rows, :], B, B_cols_T = B[:, cols]'."""
         import scipy.sparse as sp
@@ -1303,14 +1330,18 @@ def _features(F, dt, dev, keep):
     return a.ctypes.data, a.shape[0], a.shape[1], max(a.shape[0], 1)
 
 
-def jaccard_csr(Fa, Fb=None, alpha=None, weighted: bool = True, dtype=np.float32):
-    """``featurize(1 .- pairwise(Jaccard(), X, dims=1), alpha, weighted)`` for real-valued feature rows, produced as CSR
-    on the device without the dense similarity: entry (i, j) = J(Fa[i], Fb[j]) = sum(min) / sum(max) (1 when both rows
-    are all zero) when it is >= alpha (1 when not weighted), bitwise what ``jaccard_similarity`` followed by the cutoff
-    gives.  Fb None: Fb = Fa.  Host input ((n, d) numpy) returns a scipy.sparse.csr_matrix; device input ((n, d) CUDA
-    tensors of dtype) returns (ptr int64, idx int32, val) tensors.  A NaN feature or alpha raises SimSpreadError."""
-    if alpha is None:
-        raise TypeError("jaccard_csr needs alpha")
+SIM_METRICS = {"cosine": 0, "tanimoto": 1, "dice": 2}       # SS_SIM_* of include/simspread_hip.h
+
+
+def _sim_metric(metric):
+    if metric not in SIM_METRICS:
+        raise ValueError(f"metric must be one of {sorted(SIM_METRICS)}, got {metric!r}")
+    return SIM_METRICS[metric]
+
+
+def _feature_pair_csr(name, Fa, Fb, mid, alpha, weighted, dtype):
+    """The size protocol shared by the feature-row producers ss_similarity_<name>_csr_*: `mid` are the arguments between
+    d and alpha."""
     dt = _feature_dtype(dtype)
     dev = _is_torch(Fa)
     keep = []
@@ -1320,31 +1351,50 @@ def jaccard_csr(Fa, Fb=None, alpha=None, weighted: bool = True, dtype=np.float32
         nb, db, ldb = na, d, lda
     if db != d:
         raise ValueError("Fa and Fb have different numbers of features")
-    fn = getattr(L_.lib(), f"ss_similarity_jaccard_csr_{_suffix(dt)}")
+    fn = getattr(L_.lib(), f"ss_similarity_{name}_csr_{_suffix(dt)}")
     ctype = C.c_float if dt == np.float32 else C.c_double
     nnz = C.c_int64(0)
-    w = 1 if weighted else 0
+    head = (pa, na, lda, pb, nb, ldb, d) + tuple(mid) + (ctype(alpha), 1 if weighted else 0)
     if dev:
         import torch
         ptr = torch.empty(na + 1, dtype=torch.int64, device=Fa.device)
-        L_.check(fn(pa, na, lda, pb, nb, ldb, d, ctype(alpha), w, ptr.data_ptr(), None, None, 0, C.byref(nnz),
-                    L_.SS_MEM_DEVICE))
+        L_.check(fn(*head, ptr.data_ptr(), None, None, 0, C.byref(nnz), L_.SS_MEM_DEVICE))
         idx = torch.empty(max(nnz.value, 1), dtype=torch.int32, device=Fa.device)
         val = torch.empty(max(nnz.value, 1), dtype=torch.float32 if dt == np.float32 else torch.float64, device=Fa.device)
-        L_.check(fn(pa, na, lda, pb, nb, ldb, d, ctype(alpha), w, ptr.data_ptr(), idx.data_ptr(), val.data_ptr(),
-                    nnz.value, C.byref(nnz), L_.SS_MEM_DEVICE))
+        L_.check(fn(*head, ptr.data_ptr(), idx.data_ptr(), val.data_ptr(), nnz.value, C.byref(nnz), L_.SS_MEM_DEVICE))
         del keep
         return ptr, idx[:nnz.value], val[:nnz.value]
     import scipy.sparse as sp
     ptr = np.zeros(na + 1, np.int64)
-    L_.check(fn(pa, na, lda, pb, nb, ldb, d, ctype(alpha), w, ptr.ctypes.data, None, None, 0, C.byref(nnz),
-                L_.SS_MEM_HOST))
+    L_.check(fn(*head, ptr.ctypes.data, None, None, 0, C.byref(nnz), L_.SS_MEM_HOST))
     idx = np.empty(max(nnz.value, 1), np.int32)
     val = np.empty(max(nnz.value, 1), dt)
-    L_.check(fn(pa, na, lda, pb, nb, ldb, d, ctype(alpha), w, ptr.ctypes.data, idx.ctypes.data, val.ctypes.data,
-                nnz.value, C.byref(nnz), L_.SS_MEM_HOST))
+    L_.check(fn(*head, ptr.ctypes.data, idx.ctypes.data, val.ctypes.data, nnz.value, C.byref(nnz), L_.SS_MEM_HOST))
     del keep
     return sp.csr_matrix((val[:nnz.value], idx[:nnz.value], ptr), shape=(na, nb))
+
+
+def jaccard_csr(Fa, Fb=None, alpha=None, weighted: bool = True, dtype=np.float32):
+    """``featurize(1 .- pairwise(Jaccard(), X, dims=1), alpha, weighted)`` for real-valued feature rows, produced as CSR
+    on the device without the dense similarity: entry (i, j) = J(Fa[i], Fb[j]) = sum(min) / sum(max) (1 when both rows
+    are all zero) when it is >= alpha (1 when not weighted), bitwise what ``jaccard_similarity`` followed by the cutoff
+    gives.  Fb None: Fb = Fa.  Host input ((n, d) numpy) returns a scipy.sparse.csr_matrix; device input ((n, d) CUDA
+    tensors of dtype) returns (ptr int64, idx int32, val) tensors.  A NaN feature or alpha raises SimSpreadError."""
+    if alpha is None:
+        raise TypeError("jaccard_csr needs alpha")
+    return _feature_pair_csr("jaccard", Fa, Fb, (), alpha, weighted, dtype)
+
+
+def dot_csr(Fa, Fb=None, metric="cosine", alpha=None, weighted: bool = True, dtype=np.float32):
+    """``featurize(S, alpha, weighted)`` with S an inner-product similarity of real-valued rows (embeddings, continuous
+    descriptors), produced as CSR on the device without the dense similarity; the Gram blocks run on the matrix cores in
+    full ``dtype`` precision.  metric: "cosine" g / (|a| |b|), "tanimoto" g / (|a|^2 + |b|^2 - g), "dice" 2g / (|a|^2 +
+    |b|^2), g = a.b; two all-zero rows have s = 1, a zero row against a non-zero one s = 0.  Entry (i, j) = s when it
+    is >= alpha (1 when not weighted).  Fb None: Fb = Fa (the diagonal is exactly 1 and the matrix bitwise symmetric).
+    Inputs and outputs as ``jaccard_csr``.  A NaN feature or alpha raises SimSpreadError."""
+    if alpha is None:
+        raise TypeError("dot_csr needs alpha")
+    return _feature_pair_csr("dot", Fa, Fb, (_sim_metric(metric),), alpha, weighted, dtype)
 
 
 def cutoff_csr(X, alpha: float, weighted: bool = False, dtype=np.float32, shape=None):
