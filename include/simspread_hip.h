@@ -86,7 +86,7 @@ int ss_synchronize(void);
  * [6] number of SpMM launches, [7] number of stage-1 launches.  Writes min(n,8) values. */
 int ss_timing_last(double* ms, int n);
 /* Which kernels the last predict / spmm / fingerprint call of this host thread went through: a comma-separated list of tags
- * ("tanimoto_csr_sym", "tanimoto_csr_cross", "jaccard_csr_sym", "jaccard_csr_cross", "dot_csr_sym", "dot_csr_cross", "cutoff_csr", "recut", "transfer", "transfer_loo", "transfer_dense_bf16_ring", "transfer_dense_bf16_128", "transfer_dense_f32_mfma",
+ * ("tanimoto_csr_sym", "tanimoto_csr_cross", "jaccard_csr_sym", "jaccard_csr_cross", "dot_csr_sym", "dot_csr_cross", "cutoff_csr", "recut", "transfer", "transfer_loo", "transfer_dense_bf16_ring", "transfer_dense_bf16_128", "transfer_dense_f32_mfma", "transfer_dense_f32_mfma_256",
  * "spmm_sell", "spmm_sell_sorted", "spmm_csell", "spmm_colgroup", "spmm_chunked_narrow", ...), NUL-terminated, truncated
  * to n - 1 characters.  Lets a caller (and the parity tests) assert that a size-dependent routing decision was the one
  * expected.  Has no counterpart in the reference (its only switch is GPU::Bool, src/core.jl:402,404). */
@@ -259,7 +259,13 @@ int ss_graph_create_dense_f64(int64_t nq, int64_t ns, int64_t nf, int64_t nt,
  * after the sources; nq may be 0.  Serves ss_predict_f32 (query and source rows), ss_predict_loo_f32 and
  * ss_predict_kfold_f32.
  * _f32: bf16 matrix cores on exact bf16 planes (the reference's GPU=true precision, src/core.jl:404); _f64: the fp64
- * matrix instruction (the reference's default precision, src/core.jl:402 GPU=false). */
+ * matrix instruction (the reference's default precision, src/core.jl:402 GPU=false).
+ * Input domain, the same in every engine and in ss_graph_set_cutoff_*: the rule is featurize's
+ * x >= alpha ? (weighted ? x : 1) : 0, and an edge is a non-zero result.  Any finite alpha is accepted, zero and negative
+ * included: unweighted, alpha <= 0 makes every finite entry an edge (zeros and negatives too); weighted, a zero of either
+ * sign is no edge and a negative weight is kept with its sign.  A NaN similarity is no edge anywhere.  Not supported:
+ * +-Inf and, in _f32, magnitudes from 2^127 * (2 - 2^-8) up (they overflow the bf16 split of the operands); results
+ * are then undefined, nothing is checked. */
 int ss_graph_create_similarity_f32(int64_t nq, int64_t ns, int64_t nt,
                                    const float* Sq, int64_t ldq, const float* Ss, int64_t lds,
                                    const int64_t* y_ptr, const int32_t* y_idx, const float* y_val,

@@ -244,7 +244,6 @@ __global__ void __launch_bounds__(256) transfer_dense_kernel(DenseArgs a) {
 int launch_transfer_dense(const DenseSim<float>& d, bool loo, const float* inv_k, const float* inv_n, const int* ks,
                           int64_t row_begin, int64_t nrows, float* out, int64_t ldo, bool source_rows) {
   if (nrows <= 0 || d.ns <= 0) return SS_OK;
-  path_add("transfer_dense_f32_mfma");
   DenseArgs a{};
   if (loo || source_rows) { a.A = d.Ss.p + row_begin; a.lda = d.ns; }  // rows of the source similarity itself
   else { a.A = d.Sq.p + row_begin; a.lda = d.nq; }
@@ -265,6 +264,7 @@ int launch_transfer_dense(const DenseSim<float>& d, bool loo, const float* inv_k
   // but 128 accumulator + 200 other registers leave one wave per SIMD -- measured 87 vs 99 TFLOP/s at 50k
   int tm = 128;
   if (const char* e = getenv("SS_DENSE_TILE")) tm = atoi(e) == 256 ? 256 : 128;
+  path_add(tm == 256 ? "transfer_dense_f32_mfma_256" : "transfer_dense_f32_mfma");
   a.gx = (int)ceil_div(d.ns, 128);
   a.gy = (int)ceil_div(nrows, tm);
   dim3 grid((unsigned)(a.gx * a.gy));

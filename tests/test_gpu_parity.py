@@ -807,6 +807,8 @@ def test_dense_similarity_path_query_and_loo(shape, weighted, engine, monkeypatc
         monkeypatch.setenv("SS_DENSE_BF16", "0")
     if engine == "bf16-planes-ring":     # the 256 x 256 ring kernel that large shapes pick by themselves
         monkeypatch.setenv("SS_DENSE_RING", "1")
+    tag = {"bf16-planes": "transfer_dense_bf16_128", "bf16-planes-ring": "transfer_dense_bf16_ring",
+           "fp32-mfma": "transfer_dense_f32_mfma"}[engine]
     nq, ns, nt = shape
     rng = np.random.default_rng(ns)
     Ss = rng.random((ns, ns)).astype(np.float32); Ss = ((Ss + Ss.T) / 2).astype(np.float32); np.fill_diagonal(Ss, 1.0)
@@ -822,16 +824,21 @@ def test_dense_similarity_path_query_and_loo(shape, weighted, engine, monkeypatc
     okf, oks, okt = O.degrees(Xs, Y64)
     np.testing.assert_array_equal(kf, okf); np.testing.assert_array_equal(ks, oks); np.testing.assert_array_equal(kt, okt)
     assert_close(g.predict("query"), O.predict_factored(Xq, Xs, Y64), np.float32)
+    assert tag in ss.path_last(), ss.path_last()      # the switch was honoured: three engines, not one three times
     want = O.predict_loo_factored(Xs, Y64, clean_flag=True)
     assert_close(g.predict_loo(clean=True), want, np.float32)
+    assert tag in ss.path_last(), ss.path_last()
     lo, hi = ns // 3, ns - 1
     assert_close(g.predict_loo(lo, hi, clean=True, layout="col"), want[lo:hi], np.float32)
+    assert tag in ss.path_last(), ss.path_last()
     # source rows (= predict(A, ytrain), src/core.jl:446-466): feature path on the matrix cores + sparse target path,
     # against the CPU oracle's source-row form (not against another device path)
     want_src = O.predict_factored(None, Xs, Y64, rows="source")
     assert_close(g.predict("source"), want_src, np.float32)
+    assert tag in ss.path_last(), ss.path_last()
     want_clean = want_src.copy(); want_clean[:, okt == 0] = -99.0        # clean!: targets without any edge in A (src/core.jl:479)
     assert_close(g.predict("source", lo, hi, clean=True), want_clean[lo:hi], np.float32)
+    assert tag in ss.path_last(), ss.path_last()
 
 
 @pytest.mark.parametrize("weighted", [False, True])
