@@ -358,7 +358,8 @@ int ss_graph_recut_f64(const ss_graph* parent, double alpha, int weighted, ss_gr
 int ss_graph_set_cutoff_f32(ss_graph* g, float alpha, int weighted);
 int ss_graph_set_cutoff_f64(ss_graph* g, double alpha, int weighted);
 int ss_graph_destroy(ss_graph* g);
-/* sizes[0..6] = nq, ns, nf, nt, nnz(Xq), nnz(Xs), nnz(Ys) after dropping stored zeros. */
+/* sizes[0..6] = nq, ns, nf, nt, nnz(Xq), nnz(Xs), nnz(Ys) after dropping stored zeros.  A general graph reports
+ * nr, n, n, nc, nnz(L), nnz(Bm), nnz(Wt). */
 int ss_graph_info(const ss_graph* g, int64_t sizes[7]);
 /* Count degrees of the query-free graph B: kf[nf], ks[ns], kt[nt] (host buffers; any may be NULL). */
 int ss_graph_degrees(const ss_graph* g, int64_t* kf, int64_t* ks, int64_t* kt);

@@ -2977,7 +2977,10 @@ int ss_graph_info(const ss_graph* h, int64_t sizes[7]) {
   const int dtype = *reinterpret_cast<const int*>(h);
   auto fill = [&](auto* b) {
     sizes[0] = b->g.nq; sizes[1] = b->g.ns; sizes[2] = b->g.nf; sizes[3] = b->g.nt;
-    sizes[4] = b->g.Xq.nnz; sizes[5] = b->g.Xs.nnz; sizes[6] = b->g.Ys.nnz;
+    // a general graph holds B and the asked-for columns only as the transposed operands XsT and YsT
+    sizes[4] = b->g.Xq.nnz;
+    sizes[5] = b->g.general ? b->g.XsT.nnz : b->g.Xs.nnz;
+    sizes[6] = b->g.general ? b->g.YsT.nnz : b->g.Ys.nnz;
   };
   if (dtype == 4) fill(reinterpret_cast<const GraphBox<float>*>(h));
   else if (dtype == 8) fill(reinterpret_cast<const GraphBox<double>*>(h));

@@ -117,11 +117,13 @@ class DeviceGraph:
         return cls(h, dtype)
 
     @classmethod
-    def from_dense(cls, Sq, Ss, Y, alpha: Optional[float] = None, weighted: bool = True, dtype=np.float32):
+    def from_dense(cls, Sq, Ss, Y, alpha: Optional[float] = None, weighted: bool = True, dtype=np.float32,
+                   ld_pad: int = 0):
         """Dense blocks; with ``alpha`` the featurize cutoff (src/core.jl:106-112) is applied on the
         device while the CSR operands are assembled.  Arrays may be numpy (any order) or torch CUDA
         tensors; they are read as column-major (a C-order array is passed as its transpose... no copy
-        is made for Fortran-order inputs)."""
+        is made for Fortran-order inputs).  ld_pad > 0: every block is handed over with a leading dimension of
+        rows + ld_pad, the padding rows filled with NaN (a view into a larger column-major array)."""
         lib = L.lib()
         dt = np.dtype(dtype)
 
@@ -134,12 +136,14 @@ class DeviceGraph:
                 want = torch.float32 if dt == np.float32 else torch.float64
                 t = a.to(want)
                 # column-major rows x cols == row-major cols x rows: need t.T contiguous
-                tt = t.t().contiguous()
-                return tt.data_ptr(), t.shape[0], t.shape[0], t.shape[1], L.SS_MEM_DEVICE, tt
-            arr = np.asfortranarray(np.asarray(a, dtype=dt))
+                tt = _padded_colmajor(t, ld_pad)
+                return tt.data_ptr(), max(t.shape[0] + ld_pad, 1), t.shape[0], t.shape[1], L.SS_MEM_DEVICE, tt
+            arr = np.asarray(a, dtype=dt)
             if arr.ndim != 2:
                 raise ValueError("dense blocks must be matrices")
-            return arr.ctypes.data, max(arr.shape[0], 1), arr.shape[0], arr.shape[1], L.SS_MEM_HOST, arr
+            rows, cols = arr.shape
+            arr = _padded_colmajor(arr, ld_pad)
+            return arr.ctypes.data, max(rows + ld_pad, 1), rows, cols, L.SS_MEM_HOST, arr
 
         pq, ldq, nq, nfq, memq, kq = prep(Sq)
         ps, lds, ns, nf, mems, ks_ = prep(Ss)
@@ -161,13 +165,15 @@ class DeviceGraph:
         return cls(h, dtype)
 
     @classmethod
-    def from_similarity(cls, Sq, Ss, Y, alpha: float, weighted: bool = True, dtype=np.float32):
+    def from_similarity(cls, Sq, Ss, Y, alpha: float, weighted: bool = True, dtype=np.float32, index_base: int = 0,
+                        ld_pad: int = 0):
         """Dense-similarity regime: raw similarities Sq (nq x ns, may be None) and Ss (ns x ns) stay dense on the
         device, the cutoff is applied inside the MFMA stage-1 product; Y (ns x nt) is sparse.  dtype float32: bf16
         matrix cores on exact bf16 planes (the reference's GPU=true precision); float64: the fp64 matrix instruction
         (the reference's default precision).  Inputs: numpy arrays / scipy matrix on the host, or torch CUDA tensors
-        for Sq, Ss with Y = (ptr, idx, val) device CSR.  Serves predict (query / source rows), predict_loo and
-        predict_kfold."""
+        for Sq, Ss with Y = (ptr, idx, val, nt) device CSR.  Serves predict (query / source rows), predict_loo and
+        predict_kfold.  index_base and a host (ptr, idx, val, nt) tuple as for ``from_fingerprints``; ld_pad as for
+        ``from_dense``."""
         import scipy.sparse as sp
         lib = L.lib()
         dev = _is_torch(Ss)
@@ -181,12 +187,14 @@ class DeviceGraph:
                 return None, 1, 0
             if dev:
                 import torch
-                t = a.to(torch.float32 if dt == np.float32 else torch.float64).t().contiguous()   # row-major transpose == column-major original
+                # row-major transpose == column-major original
+                t = _padded_colmajor(a.to(torch.float32 if dt == np.float32 else torch.float64), ld_pad)
                 keep.append(t)
-                return t.data_ptr(), a.shape[0], a.shape[0]
-            arr = np.asfortranarray(np.asarray(a, dtype=dt))
+                return t.data_ptr(), max(a.shape[0] + ld_pad, 1), a.shape[0]
+            rows = np.shape(a)[0]
+            arr = _padded_colmajor(np.asarray(a, dtype=dt), ld_pad)
             keep.append(arr)
-            return arr.ctypes.data, max(arr.shape[0], 1), arr.shape[0]
+            return arr.ctypes.data, max(rows + ld_pad, 1), rows
 
         pq, ldq, nq = dense_cm(Sq)
         ps, lds, ns = dense_cm(Ss)
@@ -208,20 +216,13 @@ class DeviceGraph:
             yptr, yidx, yval = yp.data_ptr(), yi.data_ptr(), (None if yv is None else yv.data_ptr())
             mem = L.SS_MEM_DEVICE
         else:
-            Y = sp.csr_matrix(Y)
-            if Y.shape[0] != ns:
-                raise AssertionError("Labels and features have different number of source nodes")
-            nt = Y.shape[1]
-            parts = _csr_parts(Y, dt)
-            keep.append(parts)
-            yptr, yidx, yval = _ptr(parts[0]), _ptr(parts[1]), _ptr(parts[2])
-            mem = L.SS_MEM_HOST
+            yptr, yidx, yval, nt, mem = _source_labels(Y, ns, dt, False, keep, index_base)
         h = C.c_void_p()
         if dt == np.float32:
-            L.check(lib.ss_graph_create_similarity_f32(nq, ns, nt, pq, ldq, ps, lds, yptr, yidx, yval, 0,
+            L.check(lib.ss_graph_create_similarity_f32(nq, ns, nt, pq, ldq, ps, lds, yptr, yidx, yval, index_base,
                                                        C.c_float(alpha), 1 if weighted else 0, mem, C.byref(h)))
         else:
-            L.check(lib.ss_graph_create_similarity_f64(nq, ns, nt, pq, ldq, ps, lds, yptr, yidx, yval, 0,
+            L.check(lib.ss_graph_create_similarity_f64(nq, ns, nt, pq, ldq, ps, lds, yptr, yidx, yval, index_base,
                                                        C.c_double(alpha), 1 if weighted else 0, mem, C.byref(h)))
         if dev:
             L.check(lib.ss_synchronize())
@@ -229,12 +230,14 @@ class DeviceGraph:
         return cls(h, dt)
 
     @classmethod
-    def from_fingerprints(cls, Fq, Fs, Y, alpha: float, weighted: bool = True, dtype=np.float32):
+    def from_fingerprints(cls, Fq, Fs, Y, alpha: float, weighted: bool = True, dtype=np.float32, index_base: int = 0):
         """``construct(y, X)`` with ``X = featurize(Tanimoto(F), alpha, weighted)`` for packed binary fingerprints (see
         ``pack_fingerprints``): Xq = cut(T(Fq, Fs)), Xs = cut(T(Fs, Fs)), features named after the sources, produced as
         CSR on the device (the dense similarity never exists).  Fq may be None (3-layer graph: predict_loo /
         predict_kfold).  Fq, Fs: uint64 numpy arrays (n, nwords) with Y a scipy matrix (ns x nt), or int64 torch CUDA
-        tensors with Y = (ptr, idx, val, nt) device CSR."""
+        tensors with Y = (ptr, idx, val, nt) device CSR.  index_base (0 or 1) is the base of the label CSR handed to the
+        library: a scipy matrix is converted, a (ptr, idx, val, nt) tuple (numpy arrays on the host) is taken as it
+        is."""
         lib = L.lib()
         dt = np.dtype(dtype).type
         if dt not in (np.float32, np.float64):
@@ -245,11 +248,11 @@ class DeviceGraph:
         fs, ns, nwords = _fingerprints(Fs, dev, keep)
         if Fq is not None and nwq != nwords:
             raise ValueError("Fq and Fs have different fingerprint widths")
-        yptr, yidx, yval, nt, mem = _source_labels(Y, ns, dt, dev, keep)
+        yptr, yidx, yval, nt, mem = _source_labels(Y, ns, dt, dev, keep, index_base)
         h = C.c_void_p()
         ctype = C.c_float if dt == np.float32 else C.c_double
         fn = getattr(lib, f"ss_graph_create_fingerprint_{_suffix(dt)}")
-        L.check(fn(nq, ns, nt, nwords, fq, fs, yptr, yidx, yval, 0, ctype(alpha), 1 if weighted else 0, mem,
+        L.check(fn(nq, ns, nt, nwords, fq, fs, yptr, yidx, yval, index_base, ctype(alpha), 1 if weighted else 0, mem,
                    C.byref(h)))
         if dev:
             L.check(lib.ss_synchronize())
@@ -257,13 +260,14 @@ class DeviceGraph:
         return cls(h, dt)
 
     @classmethod
-    def from_features(cls, Fq, Fs, Y, alpha: float, weighted: bool = True, dtype=np.float32):
+    def from_features(cls, Fq, Fs, Y, alpha: float, weighted: bool = True, dtype=np.float32, index_base: int = 0):
         """``construct(y, X)`` with ``X = featurize(1 .- pairwise(Jaccard(), F, dims=1), alpha, weighted)`` for
         real-valued feature rows (the reference's tutorial, docs/src/tutorial/fishers-flowers.jl:66,95-96): Xq =
         cut(J(Fq, Fs)), Xs = cut(J(Fs, Fs)) with J the weighted Jaccard similarity of ``jaccard_csr``, features named
         after the sources, produced as CSR on the device (the dense similarity never exists).  Fq may be None (3-layer
         graph: predict_loo / predict_kfold / evaluate_loo).  Fq, Fs: (n, d) numpy arrays with Y a scipy matrix (ns x
-        nt), or float CUDA tensors of the graph's dtype with Y = (ptr, idx, val, nt) device CSR."""
+        nt), or float CUDA tensors of the graph's dtype with Y = (ptr, idx, val, nt) device CSR.  index_base as for
+        ``from_fingerprints``."""
         dt = _feature_dtype(dtype)
         dev = _is_torch(Fs)
         keep = []
@@ -271,12 +275,12 @@ class DeviceGraph:
         fs, ns, d, lds = _features(Fs, dt, dev, keep)
         if Fq is not None and dq != d:
             raise ValueError("Fq and Fs have different numbers of features")
-        yptr, yidx, yval, nt, mem = _source_labels(Y, ns, dt, dev, keep)
+        yptr, yidx, yval, nt, mem = _source_labels(Y, ns, dt, dev, keep, index_base)
         lib = L.lib()
         h = C.c_void_p()
         ctype = C.c_float if dt == np.float32 else C.c_double
         fn = getattr(lib, f"ss_graph_create_features_{_suffix(dt)}")
-        L.check(fn(nq, ns, nt, d, fq, ldq, fs, lds, yptr, yidx, yval, 0, ctype(alpha), 1 if weighted else 0, mem,
+        L.check(fn(nq, ns, nt, d, fq, ldq, fs, lds, yptr, yidx, yval, index_base, ctype(alpha), 1 if weighted else 0, mem,
                    C.byref(h)))
         if dev:
             L.check(lib.ss_synchronize())
@@ -284,7 +288,8 @@ class DeviceGraph:
         return cls(h, dt)
 
     @classmethod
-    def from_vectors(cls, Fq, Fs, Y, alpha: float, metric="cosine", weighted: bool = True, dtype=np.float32):
+    def from_vectors(cls, Fq, Fs, Y, alpha: float, metric="cosine", weighted: bool = True, dtype=np.float32,
+                     index_base: int = 0):
         """``construct(y, X)`` with ``X = featurize(S(F), alpha, weighted)``, S the inner-product similarity ``metric``
         ("cosine", "tanimoto", "dice") of ``dot_csr`` between real-valued rows (embeddings, continuous descriptors): Xq =
         cut(S(Fq, Fs)), Xs = cut(S(Fs, Fs)), features named after the sources, produced as CSR on the device (the dense
@@ -298,12 +303,13 @@ class DeviceGraph:
         fs, ns, d, lds = _features(Fs, dt, dev, keep)
         if Fq is not None and dq != d:
             raise ValueError("Fq and Fs have different numbers of features")
-        yptr, yidx, yval, nt, mem = _source_labels(Y, ns, dt, dev, keep)
+        yptr, yidx, yval, nt, mem = _source_labels(Y, ns, dt, dev, keep, index_base)
         lib = L.lib()
         h = C.c_void_p()
         ctype = C.c_float if dt == np.float32 else C.c_double
         fn = getattr(lib, f"ss_graph_create_vectors_{_suffix(dt)}")
-        L.check(fn(nq, ns, nt, d, m, fq, ldq, fs, lds, yptr, yidx, yval, 0, ctype(alpha), 1 if weighted else 0, mem,
+        L.check(fn(nq, ns, nt, d, m, fq, ldq, fs, lds, yptr, yidx, yval, index_base, ctype(alpha), 1 if weighted else 0,
+                   mem,
                    C.byref(h)))
         if dev:
             L.check(lib.ss_synchronize())
@@ -528,9 +534,28 @@ class DeviceGraph:
             pass
 
 
-def _source_labels(Y, ns, dt, dev, keep):
+def _padded_colmajor(a, ld_pad):
+    """The column-major copy of a matrix (numpy array or CUDA tensor) the dense entry points read, with ld_pad rows of
+    NaN under the last row: a Fortran-order numpy array, or the row-major transpose as a tensor."""
+    if type(a).__module__.startswith("torch"):
+        import torch
+        if ld_pad <= 0:
+            return a.t().contiguous()
+        t = torch.full((a.shape[1], a.shape[0] + ld_pad), float("nan"), dtype=a.dtype, device=a.device)
+        t[:, :a.shape[0]] = a.t()
+        return t
+    if ld_pad <= 0:
+        return np.asfortranarray(a)
+    buf = np.full((a.shape[0] + ld_pad, a.shape[1]), np.nan, dtype=a.dtype, order="F")
+    buf[:a.shape[0]] = a
+    return buf
+
+
+def _source_labels(Y, ns, dt, dev, keep, index_base=0):
     """(ptr, idx, val, nt, mem) of the source labels of a graph built from raw data: a scipy matrix (ns x nt) on the
-    host, or (ptr, idx, val, nt) device CSR tensors (converted to the ABI's types and kept alive in ``keep``)."""
+    host, or (ptr, idx, val, nt) device CSR tensors (converted to the ABI's types and kept alive in ``keep``).  A CSR
+    tuple (device tensors, or numpy arrays on the host) is taken as it is and must already have the base index_base; a
+    scipy matrix is shifted to it."""
     if dev:
         import torch
         want = torch.float32 if dt == np.float32 else torch.float64
@@ -540,11 +565,20 @@ def _source_labels(Y, ns, dt, dev, keep):
             raise AssertionError("Labels and features have different number of source nodes")
         keep.extend([yp, yi, yv])
         return yp.data_ptr(), yi.data_ptr(), (None if yv is None else yv.data_ptr()), nt, L.SS_MEM_DEVICE
+    if isinstance(Y, tuple):
+        parts = (np.ascontiguousarray(Y[0], dtype=np.int64), np.ascontiguousarray(Y[1], dtype=np.int32),
+                 None if Y[2] is None else np.ascontiguousarray(Y[2], dtype=dt))
+        if parts[0].shape != (ns + 1,):
+            raise AssertionError("Labels and features have different number of source nodes")
+        keep.append(parts)
+        return _ptr(parts[0]), _ptr(parts[1]), _ptr(parts[2]), int(Y[3]), L.SS_MEM_HOST
     import scipy.sparse as sp
     Y = sp.csr_matrix(Y)
     if Y.shape[0] != ns:
         raise AssertionError("Labels and features have different number of source nodes")
     parts = _csr_parts(Y, dt)
+    if index_base:
+        parts = (parts[0] + index_base, parts[1] + np.int32(index_base), parts[2])
     keep.append(parts)
     return _ptr(parts[0]), _ptr(parts[1]), _ptr(parts[2]), Y.shape[1], L.SS_MEM_HOST
 
