@@ -417,6 +417,19 @@ static int emit_pair_csr(PairCsr<T>& pc, int64_t na, int64_t* ptr, int32_t* idx,
   return SS_OK;
 }
 
+// the common head of the graph constructors below: the library and `mem` are usable, *out is cleared, the path note is
+// emptied and nt is in range
+static int graph_create_begin(int mem, int64_t nt, ss_graph** out) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  if (!out) return fail(SS_EINVAL, "out handle pointer is NULL");
+  *out = nullptr;
+  path_note().clear();
+  if (nt < 0) return fail(SS_EINVAL, "negative node count");
+  if (nt >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "dimension >= 2^31");
+  return SS_OK;
+}
+
 // construct(y, X, ...) from two fused producers: Xs = count_s() (ns x ns, tag_s), Xq = count_q() (nq x ns, tag_q, noted
 // when nq > 0), features named after the sources; Y and the finalisation as for the other graphs
 template <class T, class Prod, class CountS, class CountQ>
@@ -478,13 +491,7 @@ static int graph_create_fingerprint_impl(int64_t nq, int64_t ns, int64_t nt, int
                                          const uint64_t* Fs, const int64_t* y_ptr, const int32_t* y_idx,
                                          const T* y_val, int index_base, T alpha, int weighted, int mem,
                                          ss_graph** out) {
-  SS_TRY(require_init());
-  SS_TRY(check_mem(mem));
-  if (!out) return fail(SS_EINVAL, "out handle pointer is NULL");
-  *out = nullptr;
-  path_note().clear();
-  if (nt < 0) return fail(SS_EINVAL, "negative node count");
-  if (nt >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "dimension >= 2^31");
+  SS_TRY(graph_create_begin(mem, nt, out));
   SS_TRY(check_nwords(nwords));
   SS_TRY(check_fingerprints("Fq", Fq, nq, nwords));
   SS_TRY(check_fingerprints("Fs", Fs, ns, nwords));
@@ -499,7 +506,7 @@ static int graph_create_fingerprint_impl(int64_t nq, int64_t ns, int64_t nt, int
       "tanimoto_csr_cross", y_ptr, y_idx, y_val, index_base, mem, out);
 }
 
-// ------------------------------------------------------- real-valued features -> thresholded weighted Jaccard CSR
+// ------------------- real-valued rows -> thresholded weighted Jaccard CSR, or cosine / Tanimoto / Dice CSR (MFMA)
 static int check_features(const char* what, const void* F, int64_t n, int64_t ld, int64_t d) {
   if (n < 0) return fail(SS_EINVAL, "%s: negative row count", what);
   if (n >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "%s: %lld rows (>= 2^31)", what, (long long)n);
@@ -524,74 +531,46 @@ static int stage_features(const T* F, int64_t n, int64_t ld, int64_t d, int mem,
   return SS_OK;
 }
 
-template <class T>
-static int jaccard_csr_impl(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d,
-                            T alpha, int weighted, int64_t* ptr, int32_t* idx, T* val, int64_t capacity, int64_t* nnz,
-                            int mem) {
-  SS_TRY(require_init());
-  SS_TRY(check_mem(mem));
-  path_note().clear();
-  const bool sym = (Fb == nullptr);
-  if (sym) {
-    nb = na;
-    ldb = lda;
-  }
-  if (d < 0) return fail(SS_EINVAL, "jaccard: negative feature count");
-  if (alpha != alpha) return fail(SS_EINVAL, "jaccard: alpha is NaN");
-  SS_TRY(check_features("Fa", Fa, na, lda, d));
-  if (!sym) SS_TRY(check_features("Fb", Fb, nb, ldb, d));
-  if (!ptr || !nnz) return fail(SS_EINVAL, "jaccard: ptr and nnz must not be NULL");
-  DevBuf<T> ba, bb;
-  const T *da = nullptr, *db = nullptr;
-  int64_t la = 0, lb = 0;
-  SS_TRY(stage_features(Fa, na, lda, d, mem, ba, &da, &la));
-  if (!sym) SS_TRY(stage_features(Fb, nb, ldb, d, mem, bb, &db, &lb));
-  JaccardCsr<T> jc;
-  SS_TRY(jc.count(da, na, la, sym ? nullptr : db, nb, lb, d, alpha, weighted != 0));
-  path_add(sym ? "jaccard_csr_sym" : "jaccard_csr_cross");
-  return emit_pair_csr<T>(jc, na, ptr, idx, val, capacity, nnz, mem);
-}
+// What tells the fused producers of column-major feature rows apart on this level: how their messages start, their path
+// tags, check(), the check of the producer's own arguments, and count(p, Fa, na, lda, Fb, nb, ldb), the count pass of
+// producer p on device rows (Fb == NULL: symmetric).
+struct FeatureNames {
+  const char *msg, *tag_sym, *tag_cross;
+};
+static const FeatureNames jaccard_names = {"jaccard", "jaccard_csr_sym", "jaccard_csr_cross"};
+static const FeatureNames dot_names = {"dot_csr", "dot_csr_sym", "dot_csr_cross"};
 
-// construct(y, X, ...) with X = featurize(J(F), alpha, weighted), J the weighted Jaccard similarity of the feature
-// rows: Xs = cut(J(Fs, Fs)), Xq = cut(J(Fq, Fs)), features named after the sources
-template <class T>
-static int graph_create_features_impl(int64_t nq, int64_t ns, int64_t nt, int64_t d, const T* Fq, int64_t ldq,
-                                      const T* Fs, int64_t lds_, const int64_t* y_ptr, const int32_t* y_idx,
-                                      const T* y_val, int index_base, T alpha, int weighted, int mem, ss_graph** out) {
-  SS_TRY(require_init());
-  SS_TRY(check_mem(mem));
-  if (!out) return fail(SS_EINVAL, "out handle pointer is NULL");
-  *out = nullptr;
-  path_note().clear();
-  if (nt < 0) return fail(SS_EINVAL, "negative node count");
-  if (nt >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "dimension >= 2^31");
-  if (d < 0) return fail(SS_EINVAL, "jaccard: negative feature count");
-  if (alpha != alpha) return fail(SS_EINVAL, "jaccard: alpha is NaN");
-  SS_TRY(check_features("Fq", Fq, nq, ldq, d));
-  SS_TRY(check_features("Fs", Fs, ns, lds_, d));
-  DevBuf<T> bq, bs;
-  const T *dq = nullptr, *ds = nullptr;
-  int64_t lq = 0, ls = 0;
-  SS_TRY(stage_features(Fs, ns, lds_, d, mem, bs, &ds, &ls));
-  SS_TRY(stage_features(Fq, nq, ldq, d, mem, bq, &dq, &lq));
-  const bool wgt = weighted != 0;
-  return graph_from_producers<T, JaccardCsr<T>>(
-      nq, ns, nt, [&](JaccardCsr<T>& p) { return p.count(ds, ns, ls, nullptr, ns, ls, d, alpha, wgt); },
-      [&](JaccardCsr<T>& p) { return p.count(dq, nq, lq, ds, ns, ls, d, alpha, wgt); }, "jaccard_csr_sym",
-      "jaccard_csr_cross", y_ptr, y_idx, y_val, index_base, mem, out);
-}
-
-// --------------------------------------------- real-valued rows -> thresholded cosine / Tanimoto / Dice CSR (MFMA)
 static int check_sim_metric(int metric) {
   if (metric != SS_SIM_COSINE && metric != SS_SIM_TANIMOTO && metric != SS_SIM_DICE)
     return fail(SS_EINVAL, "dot_csr: metric %d is not SS_SIM_COSINE, SS_SIM_TANIMOTO or SS_SIM_DICE", metric);
   return SS_OK;
 }
-
 template <class T>
-static int dot_csr_impl(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d,
-                        int metric, T alpha, int weighted, int64_t* ptr, int32_t* idx, T* val, int64_t capacity,
-                        int64_t* nnz, int mem) {
+static auto jaccard_count(int64_t d, T alpha, int weighted) {
+  return [=](JaccardCsr<T>& p, const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb) {
+    return p.count(Fa, na, lda, Fb, nb, ldb, d, alpha, weighted != 0);
+  };
+}
+template <class T>
+static auto dot_count(int64_t d, int metric, T alpha, int weighted) {
+  return [=](DotCsr<T>& p, const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb) {
+    return p.count(Fa, na, lda, Fb, nb, ldb, d, metric, alpha, weighted != 0);
+  };
+}
+
+template <class T, class Check>
+static int check_feature_args(const FeatureNames& nm, Check check, int64_t d, T alpha) {
+  SS_TRY(check());
+  if (d < 0) return fail(SS_EINVAL, "%s: negative feature count", nm.msg);
+  if (alpha != alpha) return fail(SS_EINVAL, "%s: alpha is NaN", nm.msg);
+  return SS_OK;
+}
+
+// Fa (na x d) against Fb (nb x d; NULL: Fa against itself) as CSR, under the size protocol of emit_pair_csr
+template <class T, class Prod, class Check, class Count>
+static int features_csr_impl(const FeatureNames& nm, Check check, Count count, const T* Fa, int64_t na, int64_t lda,
+                             const T* Fb, int64_t nb, int64_t ldb, int64_t d, T alpha, int64_t* ptr, int32_t* idx,
+                             T* val, int64_t capacity, int64_t* nnz, int mem) {
   SS_TRY(require_init());
   SS_TRY(check_mem(mem));
   path_note().clear();
@@ -600,39 +579,29 @@ static int dot_csr_impl(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64
     nb = na;
     ldb = lda;
   }
-  SS_TRY(check_sim_metric(metric));
-  if (d < 0) return fail(SS_EINVAL, "dot_csr: negative feature count");
-  if (alpha != alpha) return fail(SS_EINVAL, "dot_csr: alpha is NaN");
+  SS_TRY(check_feature_args(nm, check, d, alpha));
   SS_TRY(check_features("Fa", Fa, na, lda, d));
   if (!sym) SS_TRY(check_features("Fb", Fb, nb, ldb, d));
-  if (!ptr || !nnz) return fail(SS_EINVAL, "dot_csr: ptr and nnz must not be NULL");
+  if (!ptr || !nnz) return fail(SS_EINVAL, "%s: ptr and nnz must not be NULL", nm.msg);
   DevBuf<T> ba, bb;
   const T *da = nullptr, *db = nullptr;
   int64_t la = 0, lb = 0;
   SS_TRY(stage_features(Fa, na, lda, d, mem, ba, &da, &la));
   if (!sym) SS_TRY(stage_features(Fb, nb, ldb, d, mem, bb, &db, &lb));
-  DotCsr<T> dc;
-  SS_TRY(dc.count(da, na, la, sym ? nullptr : db, nb, lb, d, metric, alpha, weighted != 0));
-  path_add(sym ? "dot_csr_sym" : "dot_csr_cross");
-  return emit_pair_csr<T>(dc, na, ptr, idx, val, capacity, nnz, mem);
+  Prod p;
+  SS_TRY(count(p, da, na, la, sym ? nullptr : db, nb, lb));
+  path_add(sym ? nm.tag_sym : nm.tag_cross);
+  return emit_pair_csr<T>(p, na, ptr, idx, val, capacity, nnz, mem);
 }
 
-// construct(y, X, ...) with X = featurize(S(F), alpha, weighted), S the inner-product similarity `metric` of the rows:
+// construct(y, X, ...) with X = featurize(S(F), alpha, weighted), S the producer's similarity of the feature rows:
 // Xs = cut(S(Fs, Fs)), Xq = cut(S(Fq, Fs)), features named after the sources
-template <class T>
-static int graph_create_vectors_impl(int64_t nq, int64_t ns, int64_t nt, int64_t d, int metric, const T* Fq,
-                                     int64_t ldq, const T* Fs, int64_t lds_, const int64_t* y_ptr, const int32_t* y_idx,
-                                     const T* y_val, int index_base, T alpha, int weighted, int mem, ss_graph** out) {
-  SS_TRY(require_init());
-  SS_TRY(check_mem(mem));
-  if (!out) return fail(SS_EINVAL, "out handle pointer is NULL");
-  *out = nullptr;
-  path_note().clear();
-  if (nt < 0) return fail(SS_EINVAL, "negative node count");
-  if (nt >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "dimension >= 2^31");
-  SS_TRY(check_sim_metric(metric));
-  if (d < 0) return fail(SS_EINVAL, "dot_csr: negative feature count");
-  if (alpha != alpha) return fail(SS_EINVAL, "dot_csr: alpha is NaN");
+template <class T, class Prod, class Check, class Count>
+static int features_graph_impl(const FeatureNames& nm, Check check, Count count, int64_t nq, int64_t ns, int64_t nt,
+                               int64_t d, const T* Fq, int64_t ldq, const T* Fs, int64_t lds_, const int64_t* y_ptr,
+                               const int32_t* y_idx, const T* y_val, int index_base, T alpha, int mem, ss_graph** out) {
+  SS_TRY(graph_create_begin(mem, nt, out));
+  SS_TRY(check_feature_args(nm, check, d, alpha));
   SS_TRY(check_features("Fq", Fq, nq, ldq, d));
   SS_TRY(check_features("Fs", Fs, ns, lds_, d));
   DevBuf<T> bq, bs;
@@ -640,11 +609,43 @@ static int graph_create_vectors_impl(int64_t nq, int64_t ns, int64_t nt, int64_t
   int64_t lq = 0, ls = 0;
   SS_TRY(stage_features(Fs, ns, lds_, d, mem, bs, &ds, &ls));
   SS_TRY(stage_features(Fq, nq, ldq, d, mem, bq, &dq, &lq));
-  const bool wgt = weighted != 0;
-  return graph_from_producers<T, DotCsr<T>>(
-      nq, ns, nt, [&](DotCsr<T>& p) { return p.count(ds, ns, ls, nullptr, ns, ls, d, metric, alpha, wgt); },
-      [&](DotCsr<T>& p) { return p.count(dq, nq, lq, ds, ns, ls, d, metric, alpha, wgt); }, "dot_csr_sym",
-      "dot_csr_cross", y_ptr, y_idx, y_val, index_base, mem, out);
+  return graph_from_producers<T, Prod>(
+      nq, ns, nt, [&](Prod& p) { return count(p, ds, ns, ls, nullptr, ns, ls); },
+      [&](Prod& p) { return count(p, dq, nq, lq, ds, ns, ls); }, nm.tag_sym, nm.tag_cross, y_ptr, y_idx, y_val,
+      index_base, mem, out);
+}
+
+static int no_check() { return SS_OK; }
+
+template <class T>
+static int jaccard_csr_impl(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d,
+                            T alpha, int weighted, int64_t* ptr, int32_t* idx, T* val, int64_t capacity, int64_t* nnz,
+                            int mem) {
+  return features_csr_impl<T, JaccardCsr<T>>(jaccard_names, no_check, jaccard_count<T>(d, alpha, weighted), Fa, na, lda,
+                                             Fb, nb, ldb, d, alpha, ptr, idx, val, capacity, nnz, mem);
+}
+template <class T>
+static int graph_create_features_impl(int64_t nq, int64_t ns, int64_t nt, int64_t d, const T* Fq, int64_t ldq,
+                                      const T* Fs, int64_t lds_, const int64_t* y_ptr, const int32_t* y_idx,
+                                      const T* y_val, int index_base, T alpha, int weighted, int mem, ss_graph** out) {
+  return features_graph_impl<T, JaccardCsr<T>>(jaccard_names, no_check, jaccard_count<T>(d, alpha, weighted), nq, ns, nt,
+                                               d, Fq, ldq, Fs, lds_, y_ptr, y_idx, y_val, index_base, alpha, mem, out);
+}
+template <class T>
+static int dot_csr_impl(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d,
+                        int metric, T alpha, int weighted, int64_t* ptr, int32_t* idx, T* val, int64_t capacity,
+                        int64_t* nnz, int mem) {
+  return features_csr_impl<T, DotCsr<T>>(
+      dot_names, [=] { return check_sim_metric(metric); }, dot_count<T>(d, metric, alpha, weighted), Fa, na, lda, Fb, nb,
+      ldb, d, alpha, ptr, idx, val, capacity, nnz, mem);
+}
+template <class T>
+static int graph_create_vectors_impl(int64_t nq, int64_t ns, int64_t nt, int64_t d, int metric, const T* Fq,
+                                     int64_t ldq, const T* Fs, int64_t lds_, const int64_t* y_ptr, const int32_t* y_idx,
+                                     const T* y_val, int index_base, T alpha, int weighted, int mem, ss_graph** out) {
+  return features_graph_impl<T, DotCsr<T>>(
+      dot_names, [=] { return check_sim_metric(metric); }, dot_count<T>(d, metric, alpha, weighted), nq, ns, nt, d, Fq,
+      ldq, Fs, lds_, y_ptr, y_idx, y_val, index_base, alpha, mem, out);
 }
 
 // ------------------------------------------------------------------ cutoff sweeps: featurize on resident CSR

@@ -14,13 +14,6 @@
 
 namespace ss {
 
-#define SS_LAUNCH_CHECK()                                                             \
-  do {                                                                                \
-    hipError_t _e = hipGetLastError();                                                \
-    if (_e != hipSuccess)                                                             \
-      return fail(SS_EHIP, "%s:%d kernel launch: %s", __FILE__, __LINE__, hipGetErrorString(_e)); \
-  } while (0)
-
 static inline int grid_for(int64_t work, int block, int cap = 256 * 16) {
   int64_t g = ceil_div(work, block);
   if (g < 1) g = 1;

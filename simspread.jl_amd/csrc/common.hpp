@@ -29,6 +29,15 @@ int fail(int code, const char* fmt, ...);
     }                                                                                 \
   } while (0)
 
+// after a kernel launch: the launch error, if any, with the place of the launch
+#define SS_LAUNCH_CHECK()                                                             \
+  do {                                                                                \
+    hipError_t _e = hipGetLastError();                                                \
+    if (_e != hipSuccess)                                                             \
+      return ss::fail(SS_EHIP, "%s:%d kernel launch: %s", __FILE__, __LINE__,         \
+                      hipGetErrorString(_e));                                         \
+  } while (0)
+
 #define SS_TRY(expr)                \
   do {                              \
     int _rc = (expr);               \

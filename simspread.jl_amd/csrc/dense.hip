@@ -10,13 +10,6 @@
 
 namespace ss {
 
-#define SS_LAUNCH_CHECK()                                                             \
-  do {                                                                                \
-    hipError_t _e = hipGetLastError();                                                \
-    if (_e != hipSuccess)                                                             \
-      return fail(SS_EHIP, "%s:%d kernel launch: %s", __FILE__, __LINE__, hipGetErrorString(_e)); \
-  } while (0)
-
 template <class T>
 __device__ __forceinline__ T cut_val(T x, T alpha, int weighted) {
   // cutoff(x, alpha, weighted); a kept weight of 0 is no edge

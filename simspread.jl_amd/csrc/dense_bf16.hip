@@ -26,13 +26,6 @@
 
 namespace ss {
 
-#define SS_LAUNCH_CHECK()                                                             \
-  do {                                                                                \
-    hipError_t _e = hipGetLastError();                                                \
-    if (_e != hipSuccess)                                                             \
-      return fail(SS_EHIP, "%s:%d kernel launch: %s", __FILE__, __LINE__, hipGetErrorString(_e)); \
-  } while (0)
-
 __device__ __forceinline__ unsigned short bf16_rne(float x) {
   unsigned u = __float_as_uint(x);
   u += 0x7FFFu + ((u >> 16) & 1u);  // round to nearest even (inputs are finite)

@@ -13,13 +13,6 @@
 
 namespace ss {
 
-#define SS_LAUNCH_CHECK()                                                             \
-  do {                                                                                \
-    hipError_t _e = hipGetLastError();                                                \
-    if (_e != hipSuccess)                                                             \
-      return fail(SS_EHIP, "%s:%d kernel launch: %s", __FILE__, __LINE__, hipGetErrorString(_e)); \
-  } while (0)
-
 __device__ __forceinline__ double cut64(double x, double alpha, int weighted) {
   return (x >= alpha) ? (weighted ? x : 1.0) : 0.0;
 }

@@ -19,7 +19,8 @@
 // exact whatever the order, and the CSR is then bitwise defined by the rule above.  NaN features are refused before
 // anything is written.
 //
-// Two passes over 128 x 128 tiles of (row, column) pairs, the skeleton of jaccard_csr.hip (pair_csr.hip):
+// Two passes over 128 x 128 tiles of (row, column) pairs; which tile a block owns and the symmetric mode are
+// pair_tile.hpp, the host side PairCsr (pair_csr.hip):
 //   count  per (column tile, row): the number of kept entries -> counts[jt * rows + i]; per tile: any kept -> tile_nz
 //   fill   the tiles that kept something, again, each slot written at ptr[i] + its offset in column order.
 // A tile's Gram block runs on the matrix cores in full T precision: v_mfma_f32_32x32x2_f32 (a wave owns 2 x 2 MFMA tiles
@@ -32,15 +33,9 @@
 #include <hip/hip_runtime.h>
 
 #include "graph.hpp"
+#include "pair_tile.hpp"
 
 namespace ss {
-
-#define SS_LAUNCH_CHECK()                                                                              \
-  do {                                                                                                 \
-    hipError_t _e = hipGetLastError();                                                                 \
-    if (_e != hipSuccess)                                                                              \
-      return fail(SS_EHIP, "%s:%d kernel launch: %s", __FILE__, __LINE__, hipGetErrorString(_e));      \
-  } while (0)
 
 namespace {
 
@@ -97,18 +92,6 @@ __device__ __forceinline__ T dot_sim(T g, T ra, T rb, int metric) {
   return s;
 }
 
-// tile (it, jt) of the upper triangle (it <= jt) from its linear index t (the enumeration of fingerprint.hip)
-__device__ __forceinline__ void triangle_tile(int64_t t, int64_t nt, int64_t& it, int64_t& jt) {
-  const double b = 2.0 * (double)nt + 1.0;
-  int64_t r = (int64_t)((b - sqrt(b * b - 8.0 * (double)t)) * 0.5);
-  if (r < 0) r = 0;
-  if (r > nt - 1) r = nt - 1;
-  while (r > 0 && r * nt - r * (r - 1) / 2 > t) --r;
-  while (r + 1 < nt && (r + 1) * nt - (r + 1) * r / 2 <= t) ++r;
-  it = r;
-  jt = r + (t - (r * nt - r * (r - 1) / 2));
-}
-
 // N[i] = sum_k F[i, k]^2 in T, one thread per row (consecutive threads read consecutive rows of a column)
 template <class T>
 __global__ void row_norm_kernel(const T* __restrict__ F, int64_t n, int64_t ld, int64_t d, T* __restrict__ N) {
@@ -140,7 +123,7 @@ __device__ __forceinline__ int bits_before(const uint32_t (*m)[4], int r, int c)
 template <class T, bool SYM, bool FILL>
 __global__ void __launch_bounds__(NT) dot_tile_kernel(
     const T* __restrict__ Fa, int64_t na, int64_t lda, const T* __restrict__ Fb, int64_t nb, int64_t ldb, int64_t d,
-    const T* __restrict__ norm_a, const T* __restrict__ norm_b, int metric, T alpha, int weighted, int64_t ntiles,
+    const T* __restrict__ norm_a, const T* __restrict__ norm_b, int metric, T alpha, int weighted, int64_t nti,
     int* __restrict__ counts, int* __restrict__ tile_nz, const int64_t* __restrict__ ptr, int* __restrict__ oidx,
     T* __restrict__ oval, int* __restrict__ not_binary) {
   using M = Mma<T>;
@@ -154,19 +137,12 @@ __global__ void __launch_bounds__(NT) dot_tile_kernel(
   __shared__ uint32_t rowbits[TILE][4];  // [row]: bit c = pair (row, c) is kept
   __shared__ uint32_t colbits[TILE][4];  // [column]: bit r = pair (r, column) is kept (SYM, off-diagonal tiles)
 
-  const int64_t tlin = SYM ? (int64_t)blockIdx.x : (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-  if (FILL && tile_nz[tlin] == 0) return;  // uniform over the block
-  int64_t it, jt;
-  if (SYM) {
-    triangle_tile(blockIdx.x, ntiles, it, jt);
-  } else {
-    it = blockIdx.y;
-    jt = blockIdx.x;
-  }
-  const int64_t i0 = it * TILE, j0 = jt * TILE;
+  if (FILL && tile_nz[pair_tile_index<SYM>()] == 0) return;  // uniform over the block
+  const PairTile t = pair_tile<SYM, TILE>(nti);
+  const int64_t tlin = t.tlin, it = t.it, jt = t.jt, i0 = t.i0, j0 = t.j0;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  const bool mirror = SYM && it != jt;
+  const bool mirror = t.mirror;
 
   typename M::acc_t acc[NM][NM];
 #pragma unroll
@@ -320,25 +296,9 @@ int DotCsr<T>::count(const T* Fa_, int64_t na_, int64_t lda_, const T* Fb_, int6
   if (metric != SS_SIM_COSINE && metric != SS_SIM_TANIMOTO && metric != SS_SIM_DICE)
     return fail(SS_EINVAL, "dot_csr: unknown metric %d", metric);
   if (alpha != alpha) return fail(SS_EINVAL, "dot_csr: alpha is NaN");
-  // NaN features: refused before anything (the row pointers included) is written
-  {
-    DevBuf<int> flag;
-    SS_TRY(flag.alloc(1));
-    SS_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-    SS_TRY(launch_feature_nan_scan<T>(Fa, na_, lda, d, flag.p));
-    if (!sym) SS_TRY(launch_feature_nan_scan<T>(Fb, nb_, ldb, d, flag.p));
-    int bad = 0;
-    SS_HIP(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    SS_HIP(hipStreamSynchronize(st));
-    if (bad) return fail(SS_EINVAL, "dot_csr: the features hold a NaN");
-  }
-  SS_TRY(this->begin(na_, sym ? na_ : nb_, TILE));
+  SS_TRY(this->refuse_nan_features(Fa, na_, lda, Fb, nb_, ldb, d));
+  SS_TRY(this->begin_tiles(na_, sym ? na_ : nb_, TILE, true));
   if (na == 0 || nb == 0) return SS_OK;
-  const int64_t nti = ceil_div(na, TILE);
-  const int64_t nblocks = sym ? nti * (nti + 1) / 2 : nti * ntj;
-  if (sym ? nblocks >= (1LL << 31) : (ntj >= (1LL << 31) || nti > 65535))
-    return fail(SS_EUNSUPPORTED, "dot_csr: %lld x %lld pairs need more tiles than one launch holds", (long long)na,
-                (long long)nb);
   SS_TRY(norm_a.alloc((size_t)na));
   hipLaunchKernelGGL(row_norm_kernel<T>, dim3((unsigned)ceil_div(na, 256)), dim3(256), 0, st, Fa, na, lda, d, norm_a.p);
   SS_LAUNCH_CHECK();
@@ -348,46 +308,17 @@ int DotCsr<T>::count(const T* Fa_, int64_t na_, int64_t lda_, const T* Fb_, int6
                        norm_b.p);
     SS_LAUNCH_CHECK();
   }
-  SS_TRY(counts.alloc((size_t)ntj * (size_t)na));
-  SS_TRY(tile_nz.alloc((size_t)nblocks));
-  const T* nbp = sym ? norm_a.p : norm_b.p;
-  if (sym) {
-    hipLaunchKernelGGL((dot_tile_kernel<T, true, false>), dim3((unsigned)nblocks), dim3(NT), 0, st, Fa, na, lda, Fb, nb,
-                       ldb, d, norm_a.p, nbp, metric, alpha, weighted ? 1 : 0, nti, counts.p, tile_nz.p,
-                       (const int64_t*)nullptr, (int*)nullptr, (T*)nullptr, (int*)nullptr);
-  } else {
-    hipLaunchKernelGGL((dot_tile_kernel<T, false, false>), dim3((unsigned)ntj, (unsigned)nti), dim3(NT), 0, st, Fa, na,
-                       lda, Fb, nb, ldb, d, norm_a.p, nbp, metric, alpha, weighted ? 1 : 0, ntj, counts.p, tile_nz.p,
-                       (const int64_t*)nullptr, (int*)nullptr, (T*)nullptr, (int*)nullptr);
-  }
-  SS_LAUNCH_CHECK();
-  return this->scan();
+  return this->count_pass();
 }
 
 template <class T>
-int DotCsr<T>::fill(int* idx, T* val, bool* binary) {
-  hipStream_t st = ctx().stream;
-  if (binary) *binary = true;
-  if (nnz == 0) return SS_OK;
-  DevBuf<int> flag;
-  SS_TRY(flag.alloc(1));
-  SS_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-  const int64_t nti = ceil_div(na, TILE);
-  const T* nbp = sym ? norm_a.p : norm_b.p;
-  if (sym) {
-    hipLaunchKernelGGL((dot_tile_kernel<T, true, true>), dim3((unsigned)(nti * (nti + 1) / 2)), dim3(NT), 0, st, Fa, na,
-                       lda, Fb, nb, ldb, d, norm_a.p, nbp, metric, alpha, weighted ? 1 : 0, nti, counts.p, tile_nz.p,
-                       ptr.p, idx, val, flag.p);
-  } else {
-    hipLaunchKernelGGL((dot_tile_kernel<T, false, true>), dim3((unsigned)ntj, (unsigned)nti), dim3(NT), 0, st, Fa, na,
-                       lda, Fb, nb, ldb, d, norm_a.p, nbp, metric, alpha, weighted ? 1 : 0, ntj, counts.p, tile_nz.p,
-                       ptr.p, idx, val, flag.p);
-  }
+int DotCsr<T>::launch(bool fill, int* idx, T* val, int* flag) {
+  auto* kernel = sym ? (fill ? dot_tile_kernel<T, true, true> : dot_tile_kernel<T, true, false>)
+                     : (fill ? dot_tile_kernel<T, false, true> : dot_tile_kernel<T, false, false>);
+  hipLaunchKernelGGL(kernel, this->tile_grid(), dim3(NT), 0, ctx().stream, Fa, na, lda, Fb, nb, ldb, d, norm_a.p,
+                     sym ? norm_a.p : norm_b.p, metric, alpha, weighted ? 1 : 0, nti, counts.p, tile_nz.p, ptr.p, idx,
+                     val, flag);
   SS_LAUNCH_CHECK();
-  int notbin = 0;
-  SS_HIP(hipMemcpyAsync(&notbin, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-  SS_HIP(hipStreamSynchronize(st));
-  if (binary) *binary = (notbin == 0);
   return SS_OK;
 }
 

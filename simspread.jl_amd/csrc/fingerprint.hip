@@ -8,29 +8,23 @@
 // The counts are exact integers and the quotient is one correctly rounded division, the same one jaccard_kernel
 // (kernels.hip) performs on the float sums of min / max, so the CSR is bitwise equal to the dense route.
 //
-// Two passes over 128 x 128 tiles of (row, column) pairs, 256 threads, an 8 x 8 block of pairs per thread:
+// Two passes over 128 x 128 tiles of (row, column) pairs, 256 threads, an 8 x 8 block of pairs per thread; the tiles,
+// the symmetric mode and the emit epilogue are pair_tile.hpp, the host side PairCsr (pair_csr.hip):
 //   count  per (column tile, row): the number of kept entries          -> counts[jt * rows + i]
 //   (per row: in-row exclusive offsets of the slots and the row total; a 64-bit scan of the totals gives ptr, and the
 //    nnz >= 2^31 refusal happens there, before any output exists)
-//   fill   the same tiles again, each slot written at ptr[i] + its offset in column order.
-// In symmetric mode (Fb = Fa) only the tiles on and above the diagonal run (1-D grid over the triangle); an
-// off-diagonal tile emits its pairs for its rows and, mirrored, for its columns.  No atomics decide any position,
-// so the output is bitwise repeatable.
+//   fill   the same tiles again (every one: this producer keeps no per-tile flag), each slot written at ptr[i] + its
+//          offset in column order.
+// This file holds what is the producer's own: the row popcounts, the staging, the AND-popcount sums and the keep rule.
 #include <cstdlib>
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
 #include "graph.hpp"
+#include "pair_tile.hpp"
 
 namespace ss {
-
-#define SS_LAUNCH_CHECK()                                                                              \
-  do {                                                                                                 \
-    hipError_t _e = hipGetLastError();                                                                 \
-    if (_e != hipSuccess)                                                                              \
-      return fail(SS_EHIP, "%s:%d kernel launch: %s", __FILE__, __LINE__, hipGetErrorString(_e));      \
-  } while (0)
 
 namespace {
 
@@ -55,41 +49,19 @@ __device__ __forceinline__ bool tanimoto_keep(int c, int pa, int pb, T alpha, bo
   return s >= alpha && v != T(0);
 }
 
-// tile (it, jt) of the upper triangle (it <= jt) from its linear index t: rows of the triangle hold nt, nt-1, ... tiles
-__device__ __forceinline__ void triangle_tile(int64_t t, int64_t nt, int64_t& it, int64_t& jt) {
-  // first tile of row r: r * nt - r * (r - 1) / 2
-  const double b = 2.0 * (double)nt + 1.0;
-  int64_t r = (int64_t)((b - sqrt(b * b - 8.0 * (double)t)) * 0.5);
-  if (r < 0) r = 0;
-  if (r > nt - 1) r = nt - 1;
-  while (r > 0 && r * nt - r * (r - 1) / 2 > t) --r;
-  while (r + 1 < nt && (r + 1) * nt - (r + 1) * r / 2 <= t) ++r;
-  it = r;
-  jt = r + (t - (r * nt - r * (r - 1) / 2));
-}
-
 // FILL == false: write the per-(tile, row) counts.  FILL == true: write the entries (counts then hold in-row offsets).
 template <class T, bool SYM, bool FILL>
 __global__ void __launch_bounds__(256) tanimoto_tile_kernel(
     const uint64_t* __restrict__ Fa, int64_t na, const uint64_t* __restrict__ Fb, int64_t nb, int64_t nwords,
-    const int* __restrict__ pop_a, const int* __restrict__ pop_b, T alpha, int weighted, int64_t ntiles,
+    const int* __restrict__ pop_a, const int* __restrict__ pop_b, T alpha, int weighted, int64_t nti,
     int* __restrict__ counts, const int64_t* __restrict__ ptr, int* __restrict__ oidx, T* __restrict__ oval,
     int* __restrict__ not_binary) {
   __shared__ __attribute__((aligned(16))) uint32_t As[BK][TILE];
   __shared__ __attribute__((aligned(16))) uint32_t Bs[BK][TILE];
-  __shared__ int rc[TILE][17];  // [row][tx]: kept entries of the row in the columns of thread column tx -> offsets
-  __shared__ int cc[TILE][17];  // [column][ty]: the same for the mirror (SYM, off-diagonal tiles)
 
-  int64_t it, jt;
-  if (SYM) {
-    triangle_tile(blockIdx.x, ntiles, it, jt);
-  } else {
-    it = blockIdx.y;
-    jt = blockIdx.x;
-  }
-  const int64_t i0 = it * TILE, j0 = jt * TILE;
+  const PairTile t = pair_tile<SYM, TILE>(nti);
+  const int64_t i0 = t.i0, j0 = t.j0;
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-  const bool mirror = SYM && it != jt;
 
   uint32_t acc[RB][RB];
 #pragma unroll
@@ -128,100 +100,22 @@ __global__ void __launch_bounds__(256) tanimoto_tile_kernel(
     __syncthreads();
   }
 
-  // which of the 64 pairs are kept: bit b of rmask[a] = bit a of cmask[b] = pair (row RB*ty + a, column RB*tx + b)
+  // popcounts of the thread's rows and columns; those past the last row / column are never used
   int pa[RB], pb[RB];
 #pragma unroll
   for (int a = 0; a < RB; ++a) {
     const int64_t i = i0 + RB * ty + a;
-    pa[a] = i < na ? pop_a[i] : -1;
+    pa[a] = i < na ? pop_a[i] : 0;
   }
 #pragma unroll
   for (int b = 0; b < RB; ++b) {
     const int64_t j = j0 + RB * tx + b;
-    pb[b] = j < nb ? pop_b[j] : -1;
+    pb[b] = j < nb ? pop_b[j] : 0;
   }
-  uint32_t rmask[RB], cmask[RB];
-#pragma unroll
-  for (int b = 0; b < RB; ++b) cmask[b] = 0;
   const bool wgt = weighted != 0;
-#pragma unroll
-  for (int a = 0; a < RB; ++a) {
-    rmask[a] = 0;
-#pragma unroll
-    for (int b = 0; b < RB; ++b) {
-      T v;
-      const bool k = pa[a] >= 0 && pb[b] >= 0 && tanimoto_keep<T>((int)acc[a][b], pa[a], pb[b], alpha, wgt, v);
-      rmask[a] |= (k ? 1u : 0u) << b;
-      cmask[b] |= (k ? 1u : 0u) << a;
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < RB; ++a) rc[RB * ty + a][tx] = __popc(rmask[a]);
-  if (mirror) {
-#pragma unroll
-    for (int b = 0; b < RB; ++b) cc[RB * tx + b][ty] = __popc(cmask[b]);
-  }
-  __syncthreads();
-  // exclusive scans: threads 0..127 over the 16 thread columns of row tid, threads 128..255 over the 16 thread rows
-  // of column tid - 128
-  {
-    int(*tab)[17] = tid < TILE ? rc : cc;
-    const int r = tid & (TILE - 1);
-    if (tid < TILE || mirror) {
-      int run = 0;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int c = tab[r][q];
-        tab[r][q] = run;
-        run += c;
-      }
-      if (!FILL) {
-        if (tid < TILE) {
-          if (i0 + r < na) counts[jt * na + i0 + r] = run;
-        } else if (j0 + r < nb) {
-          counts[it * na + j0 + r] = run;  // SYM: na == nb
-        }
-      }
-    }
-  }
-  if (!FILL) return;
-  __syncthreads();
-
-  bool nb_flag = false;
-#pragma unroll
-  for (int a = 0; a < RB; ++a) {
-    if (!rmask[a]) continue;
-    const int64_t i = i0 + RB * ty + a;
-    int64_t o = ptr[i] + counts[jt * na + i] + rc[RB * ty + a][tx];
-#pragma unroll
-    for (int b = 0; b < RB; ++b) {
-      if (!((rmask[a] >> b) & 1u)) continue;
-      T v;
-      (void)tanimoto_keep<T>((int)acc[a][b], pa[a], pb[b], alpha, wgt, v);
-      oidx[o] = (int)(j0 + RB * tx + b);
-      if (oval) oval[o] = v;
-      nb_flag |= (v != T(1));
-      ++o;
-    }
-  }
-  if (mirror) {
-#pragma unroll
-    for (int b = 0; b < RB; ++b) {
-      if (!cmask[b]) continue;
-      const int64_t j = j0 + RB * tx + b;
-      int64_t o = ptr[j] + counts[it * na + j] + cc[RB * tx + b][ty];
-#pragma unroll
-      for (int a = 0; a < RB; ++a) {
-        if (!((cmask[b] >> a) & 1u)) continue;
-        T v;
-        (void)tanimoto_keep<T>((int)acc[a][b], pa[a], pb[b], alpha, wgt, v);
-        oidx[o] = (int)(i0 + RB * ty + a);
-        if (oval) oval[o] = v;
-        ++o;
-      }
-    }
-  }
-  if (nb_flag) *not_binary = 1;
+  pair_tile_emit<T, TILE, RB, RB, SYM, FILL, false>(
+      t, na, nb, [&](int a, int b, T& v) { return tanimoto_keep<T>((int)acc[a][b], pa[a], pb[b], alpha, wgt, v); },
+      counts, nullptr, ptr, oidx, oval, not_binary);
 }
 
 }  // namespace
@@ -237,13 +131,8 @@ int TanimotoCsr<T>::count(const uint64_t* Fa_, int64_t na_, const uint64_t* Fb_,
   nwords = nwords_;
   alpha = alpha_;
   weighted = weighted_;
-  SS_TRY(this->begin(na_, sym ? na_ : nb_, TILE));
+  SS_TRY(this->begin_tiles(na_, sym ? na_ : nb_, TILE, false));
   if (na == 0 || nb == 0) return SS_OK;
-  const int64_t nti = ceil_div(na, TILE);
-  const int64_t nblocks = sym ? nti * (nti + 1) / 2 : nti * ntj;
-  if (sym ? nblocks >= (1LL << 31) : (ntj >= (1LL << 31) || nti > 65535))
-    return fail(SS_EUNSUPPORTED, "tanimoto: %lld x %lld pairs need more tiles than one launch holds", (long long)na,
-                (long long)nb);
   SS_TRY(pop_a.alloc(na));
   hipLaunchKernelGGL(popcount_rows_kernel, dim3((unsigned)ceil_div(na, 256)), dim3(256), 0, st, Fa, na, nwords, pop_a.p);
   SS_LAUNCH_CHECK();
@@ -253,43 +142,16 @@ int TanimotoCsr<T>::count(const uint64_t* Fa_, int64_t na_, const uint64_t* Fb_,
                        pop_b.p);
     SS_LAUNCH_CHECK();
   }
-  SS_TRY(counts.alloc((size_t)ntj * (size_t)na));
-  if (sym) {
-    hipLaunchKernelGGL((tanimoto_tile_kernel<T, true, false>), dim3((unsigned)nblocks), dim3(256), 0, st, Fa, na, Fb, nb,
-                       nwords, pop_a.p, pop_a.p, alpha, weighted ? 1 : 0, nti, counts.p, (const int64_t*)nullptr,
-                       (int*)nullptr, (T*)nullptr, (int*)nullptr);
-  } else {
-    hipLaunchKernelGGL((tanimoto_tile_kernel<T, false, false>), dim3((unsigned)ntj, (unsigned)nti), dim3(256), 0, st, Fa,
-                       na, Fb, nb, nwords, pop_a.p, pop_b.p, alpha, weighted ? 1 : 0, ntj, counts.p,
-                       (const int64_t*)nullptr, (int*)nullptr, (T*)nullptr, (int*)nullptr);
-  }
-  SS_LAUNCH_CHECK();
-  return this->scan();
+  return this->count_pass();
 }
 
 template <class T>
-int TanimotoCsr<T>::fill(int* idx, T* val, bool* binary) {
-  hipStream_t st = ctx().stream;
-  if (binary) *binary = true;
-  if (nnz == 0) return SS_OK;
-  DevBuf<int> flag;
-  SS_TRY(flag.alloc(1));
-  SS_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-  const int64_t nti = ceil_div(na, TILE);
-  if (sym) {
-    hipLaunchKernelGGL((tanimoto_tile_kernel<T, true, true>), dim3((unsigned)(nti * (nti + 1) / 2)), dim3(256), 0, st, Fa,
-                       na, Fb, nb, nwords, pop_a.p, pop_a.p, alpha, weighted ? 1 : 0, nti, counts.p, ptr.p, idx, val,
-                       flag.p);
-  } else {
-    hipLaunchKernelGGL((tanimoto_tile_kernel<T, false, true>), dim3((unsigned)ntj, (unsigned)nti), dim3(256), 0, st, Fa,
-                       na, Fb, nb, nwords, pop_a.p, pop_b.p, alpha, weighted ? 1 : 0, ntj, counts.p, ptr.p, idx, val,
-                       flag.p);
-  }
+int TanimotoCsr<T>::launch(bool fill, int* idx, T* val, int* flag) {
+  auto* kernel = sym ? (fill ? tanimoto_tile_kernel<T, true, true> : tanimoto_tile_kernel<T, true, false>)
+                     : (fill ? tanimoto_tile_kernel<T, false, true> : tanimoto_tile_kernel<T, false, false>);
+  hipLaunchKernelGGL(kernel, this->tile_grid(), dim3(256), 0, ctx().stream, Fa, na, Fb, nb, nwords, pop_a.p,
+                     sym ? pop_a.p : pop_b.p, alpha, weighted ? 1 : 0, nti, counts.p, ptr.p, idx, val, flag);
   SS_LAUNCH_CHECK();
-  int notbin = 0;
-  SS_HIP(hipMemcpyAsync(&notbin, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-  SS_HIP(hipStreamSynchronize(st));
-  if (binary) *binary = (notbin == 0);
   return SS_OK;
 }
 

@@ -380,39 +380,61 @@ int launch_gather_labels(const int* ys_ptr, const int* ys_idx, const int* member
                          int64_t shift, int* out);
 
 // ---- pair_csr.hip: the host skeleton shared by the fused thresholded-similarity producers (fingerprint.hip,
-// jaccard_csr.hip, dot_csr.hip).  A producer's count pass writes the kept entries of every (column tile, row) slot into counts;
-// scan() turns them into in-row offsets and a 64-bit scan of the row totals into ptr and nnz; the producer's fill pass
-// writes every slot at ptr[i] + its offset in column order.
+// jaccard_csr.hip, dot_csr.hip; their device skeleton is pair_tile.hpp) and by the streaming cutoff (recut.hip).  A
+// producer's count pass writes the kept entries of every (column tile, row) slot into counts; scan() turns them into
+// in-row offsets and a 64-bit scan of the row totals into ptr and nnz; the producer's fill pass writes every slot at
+// ptr[i] + its offset in column order.  A producer's count() sets the members its kernel reads, sizes the output with
+// begin() or begin_tiles() and ends in count_pass(); launch() is its one hook.
 template <class T>
 struct PairCsr {
   const char* what = "";  // producer name for messages
   int64_t na = 0, nb = 0;
-  int64_t ntj = 0;      // column tiles
+  int64_t nti = 0, ntj = 0;  // row tiles (tiled producers), column tiles
   int64_t nnz = 0;      // set by count(), summed in 64 bits (may be >= 2^31: the caller refuses it)
   T alpha = T(0);
   bool weighted = true, sym = false;
   DevBuf<int> counts;   // [ntj][na] in-row offset of every (column tile, row) slot
+  DevBuf<int> tile_nz;  // per launched tile, producers that ask for it: 1 when the count pass kept a pair in it (their
+                        // fill pass skips the others)
   DevBuf<int64_t> ptr;  // [na + 1] row pointers
   virtual ~PairCsr() = default;
-  int begin(int64_t na, int64_t nb, int64_t tile);     // sizes, ptr (zeroed and synchronised when na or nb is 0)
-  int scan();                                          // counts -> offsets, row totals -> ptr, nnz (synchronises)
-  virtual int fill(int* idx, T* val, bool* binary) = 0;  // device idx[nnz], val[nnz] (val may be null);
-                                                         // binary: every value == 1
-  int to_dev_csr(DevCsr<T>& out);                      // fill a DevCsr (SS_EUNSUPPORTED when nnz >= 2^31)
+  int fill(int* idx, T* val, bool* binary);  // device idx[nnz], val[nnz] (val may be null); binary: every value == 1
+  int to_dev_csr(DevCsr<T>& out);            // fill a DevCsr (SS_EUNSUPPORTED when nnz >= 2^31)
+
+ protected:
+  int begin(int64_t na, int64_t nb, int64_t tile);  // sizes, ptr (zeroed and synchronised when na or nb is 0)
+  // begin() for tile x tile blocks of pairs, then (unless na or nb is 0) counts and, with_tile_nz, tile_nz; refuses
+  // more tiles than one launch holds
+  int begin_tiles(int64_t na, int64_t nb, int64_t tile, bool with_tile_nz);
+  dim3 tile_grid() const;  // sym: the upper triangle of nti x nti tiles as a 1-D grid; else (ntj, nti)
+  // SS_EINVAL when Fa (na x d, column-major, lda >= na; padding rows are not read) or, unless sym, Fb holds a NaN
+  // (synchronises); called before begin(), so that nothing, the row pointers included, is written
+  int refuse_nan_features(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d);
+  int count_pass() { SS_TRY(launch(false, nullptr, nullptr, nullptr)); return scan(); }
+  int scan();  // counts -> offsets, row totals -> ptr, nnz (synchronises)
+  // enqueue the producer's kernel: the count pass (fill == false: counts, tile_nz) or the fill pass (idx, val, which
+  // may be null, and *flag = 1 when a value is not 1), over tile_grid() when it is tiled
+  virtual int launch(bool fill, int* idx, T* val, int* flag) = 0;
 };
+// the members a producer names unqualified
+#define SS_PAIR_CSR_MEMBERS(T)                                                                                       \
+  using PairCsr<T>::what, PairCsr<T>::na, PairCsr<T>::nb, PairCsr<T>::nti, PairCsr<T>::ntj, PairCsr<T>::nnz,          \
+      PairCsr<T>::alpha, PairCsr<T>::weighted, PairCsr<T>::sym, PairCsr<T>::counts, PairCsr<T>::tile_nz,              \
+      PairCsr<T>::ptr
 
 // ---- fingerprint.hip: thresholded Tanimoto similarity of packed binary fingerprints as CSR (two passes: count, fill).
 // Fa (na x nwords) against Fb (nb x nwords), both device-resident uint64 rows; Fb == nullptr: Fb = Fa (symmetric).
 template <class T>
 struct TanimotoCsr : PairCsr<T> {
-  using PairCsr<T>::what, PairCsr<T>::na, PairCsr<T>::nb, PairCsr<T>::ntj, PairCsr<T>::nnz, PairCsr<T>::alpha,
-      PairCsr<T>::weighted, PairCsr<T>::sym, PairCsr<T>::counts, PairCsr<T>::ptr;
+  SS_PAIR_CSR_MEMBERS(T);
   const uint64_t* Fa = nullptr;
   const uint64_t* Fb = nullptr;
   int64_t nwords = 0;
-  DevBuf<int> pop_a, pop_b;  // popcount of every row
+  DevBuf<int> pop_a, pop_b;  // popcount of every row (pop_b unused in symmetric mode)
   int count(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords, T alpha, bool weighted);
-  int fill(int* idx, T* val, bool* binary) override;
+
+ protected:
+  int launch(bool fill, int* idx, T* val, int* flag) override;
 };
 
 // ---- jaccard_csr.hip: thresholded weighted Jaccard (Ruzicka) similarity of real-valued feature rows as CSR, bitwise
@@ -421,37 +443,33 @@ struct TanimotoCsr : PairCsr<T> {
 // SS_EINVAL before anything is written.
 template <class T>
 struct JaccardCsr : PairCsr<T> {
-  using PairCsr<T>::what, PairCsr<T>::na, PairCsr<T>::nb, PairCsr<T>::ntj, PairCsr<T>::nnz, PairCsr<T>::alpha,
-      PairCsr<T>::weighted, PairCsr<T>::sym, PairCsr<T>::counts, PairCsr<T>::ptr;
+  SS_PAIR_CSR_MEMBERS(T);
   const T* Fa = nullptr;
   const T* Fb = nullptr;
   int64_t lda = 0, ldb = 0, d = 0;
-  DevBuf<int> tile_nz;  // per launched tile: 1 when the count pass kept a pair in it (the fill pass skips the others)
   int count(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d, T alpha,
             bool weighted);
-  int fill(int* idx, T* val, bool* binary) override;
-};
 
-// flag[0] = 1 when F (n x d, column-major, ld >= n; padding rows are not read) holds a NaN; enqueued only
-template <class T>
-int launch_feature_nan_scan(const T* F, int64_t n, int64_t ld, int64_t d, int* flag);
+ protected:
+  int launch(bool fill, int* idx, T* val, int* flag) override;
+};
 
 // ---- dot_csr.hip: thresholded inner-product similarity (metric: SS_SIM_COSINE, SS_SIM_TANIMOTO, SS_SIM_DICE) of
 // real-valued rows as CSR; the Gram block of every 128 x 128 tile runs on the matrix cores in T (fp32 / fp64 MFMA).
 // Layout, symmetric mode and the NaN refusal as for JaccardCsr; the rule is the header comment of dot_csr.hip.
 template <class T>
 struct DotCsr : PairCsr<T> {
-  using PairCsr<T>::what, PairCsr<T>::na, PairCsr<T>::nb, PairCsr<T>::ntj, PairCsr<T>::nnz, PairCsr<T>::alpha,
-      PairCsr<T>::weighted, PairCsr<T>::sym, PairCsr<T>::counts, PairCsr<T>::ptr;
+  SS_PAIR_CSR_MEMBERS(T);
   const T* Fa = nullptr;
   const T* Fb = nullptr;
   int64_t lda = 0, ldb = 0, d = 0;
   int metric = 0;
   DevBuf<T> norm_a, norm_b;  // squared row norms of each side (norm_b unused in symmetric mode)
-  DevBuf<int> tile_nz;       // per launched tile: 1 when the count pass kept a pair in it (the fill pass skips the others)
   int count(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d, int metric, T alpha,
             bool weighted);
-  int fill(int* idx, T* val, bool* binary) override;
+
+ protected:
+  int launch(bool fill, int* idx, T* val, int* flag) override;
 };
 
 // ---- recut.hip: featurize on a device CSR matrix (entry kept iff v >= alpha, alpha > 0; as v when weighted, else 1),
@@ -459,12 +477,13 @@ struct DotCsr : PairCsr<T> {
 // copied and the degrees recounted; lazily built operands of g stay empty.
 template <class T>
 struct CutCsr : PairCsr<T> {
-  using PairCsr<T>::what, PairCsr<T>::na, PairCsr<T>::nb, PairCsr<T>::ntj, PairCsr<T>::nnz, PairCsr<T>::alpha,
-      PairCsr<T>::weighted, PairCsr<T>::sym, PairCsr<T>::counts, PairCsr<T>::ptr;
+  SS_PAIR_CSR_MEMBERS(T);
   const DevCsr<T>* in = nullptr;
   int gshift = 6;  // log2 of the lanes that share a row
   int count(const DevCsr<T>& in, T alpha, bool weighted);
-  int fill(int* idx, T* val, bool* binary) override;
+
+ protected:
+  int launch(bool fill, int* idx, T* val, int* flag) override;
 };
 template <class T>
 int graph_recut(const Graph<T>& p, T alpha, bool weighted, Graph<T>& g);

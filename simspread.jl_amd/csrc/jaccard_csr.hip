@@ -12,25 +12,18 @@
 // dense kernel: for non-NaN inputs they differ only in the sign of a zero, and adding -0 instead of +0 to a sum that
 // started at +0 changes nothing.  NaN features are refused before anything is written.
 //
-// Two passes over 128 x 128 tiles of (row, column) pairs, the skeleton of fingerprint.hip (pair_csr.hip):
+// Two passes over 128 x 128 tiles of (row, column) pairs; the tiles, the symmetric mode and the emit epilogue are
+// pair_tile.hpp, the host side PairCsr (pair_csr.hip):
 //   count  per (column tile, row): the number of kept entries -> counts[jt * rows + i]; per tile: any kept -> tile_nz
 //   fill   the tiles that kept something, again, each slot written at ptr[i] + its offset in column order.
 // Register blocks: fp32 8 x 8 pairs per thread (256 threads, 128 accumulator VGPRs), fp64 4 x 8 (512 threads, the
-// same 128 VGPRs).  In symmetric mode (Fb = Fa) only the tiles on and above the diagonal run; an off-diagonal tile
-// emits its pairs for its rows and, mirrored, for its columns.  No atomics decide any position.
-#include <algorithm>
+// same 128 VGPRs).  This file holds what is the producer's own: the staging, the two sums and the keep rule.
 #include <hip/hip_runtime.h>
 
 #include "graph.hpp"
+#include "pair_tile.hpp"
 
 namespace ss {
-
-#define SS_LAUNCH_CHECK()                                                                              \
-  do {                                                                                                 \
-    hipError_t _e = hipGetLastError();                                                                 \
-    if (_e != hipSuccess)                                                                              \
-      return fail(SS_EHIP, "%s:%d kernel launch: %s", __FILE__, __LINE__, hipGetErrorString(_e));      \
-  } while (0)
 
 namespace {
 
@@ -62,57 +55,23 @@ __device__ __forceinline__ bool jaccard_keep(T smin, T smax, T alpha, bool weigh
   return s >= alpha && v != T(0);
 }
 
-// tile (it, jt) of the upper triangle (it <= jt) from its linear index t (the enumeration of fingerprint.hip)
-__device__ __forceinline__ void triangle_tile(int64_t t, int64_t nt, int64_t& it, int64_t& jt) {
-  const double b = 2.0 * (double)nt + 1.0;
-  int64_t r = (int64_t)((b - sqrt(b * b - 8.0 * (double)t)) * 0.5);
-  if (r < 0) r = 0;
-  if (r > nt - 1) r = nt - 1;
-  while (r > 0 && r * nt - r * (r - 1) / 2 > t) --r;
-  while (r + 1 < nt && (r + 1) * nt - (r + 1) * r / 2 <= t) ++r;
-  it = r;
-  jt = r + (t - (r * nt - r * (r - 1) / 2));
-}
-
-template <class T>
-__global__ void nan_scan_kernel(const T* __restrict__ F, int64_t n, int64_t ld, int64_t d, int* __restrict__ flag) {
-  const int64_t total = n * d;
-  bool bad = false;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t k = e / n, i = e - k * n;
-    const T x = F[i + k * ld];
-    bad |= (x != x);
-  }
-  if (bad) *flag = 1;
-}
-
 // FILL == false: write the per-(tile, row) counts and the tile flag.  FILL == true: write the entries of the tiles that
 // kept something (counts then hold in-row offsets).
 template <class T, bool SYM, bool FILL>
 __global__ void __launch_bounds__(NTX * (TILE / Block<T>::RA)) jaccard_tile_kernel(
     const T* __restrict__ Fa, int64_t na, int64_t lda, const T* __restrict__ Fb, int64_t nb, int64_t ldb, int64_t d,
-    T alpha, int weighted, int64_t ntiles, int* __restrict__ counts, int* __restrict__ tile_nz,
+    T alpha, int weighted, int64_t nti, int* __restrict__ counts, int* __restrict__ tile_nz,
     const int64_t* __restrict__ ptr, int* __restrict__ oidx, T* __restrict__ oval, int* __restrict__ not_binary) {
   constexpr int RA = Block<T>::RA;
   constexpr int NTY = TILE / RA;       // thread rows
   constexpr int NT = NTX * NTY;        // threads
   __shared__ __attribute__((aligned(16))) T As[BK][TILE];
   __shared__ __attribute__((aligned(16))) T Bs[BK][TILE];
-  __shared__ int rc[TILE][NTX + 1];  // [row][tx]: kept entries of the row in the columns of thread column tx -> offsets
-  __shared__ int cc[TILE][NTY + 1];  // [column][ty]: the same for the mirror (SYM, off-diagonal tiles)
 
-  const int64_t tlin = SYM ? (int64_t)blockIdx.x : (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-  if (FILL && tile_nz[tlin] == 0) return;  // uniform over the block
-  int64_t it, jt;
-  if (SYM) {
-    triangle_tile(blockIdx.x, ntiles, it, jt);
-  } else {
-    it = blockIdx.y;
-    jt = blockIdx.x;
-  }
-  const int64_t i0 = it * TILE, j0 = jt * TILE;
+  if (FILL && tile_nz[pair_tile_index<SYM>()] == 0) return;  // uniform over the block
+  const PairTile t = pair_tile<SYM, TILE>(nti);
+  const int64_t i0 = t.i0, j0 = t.j0;
   const int tid = threadIdx.x, tx = tid % NTX, ty = tid / NTX;
-  const bool mirror = SYM && it != jt;
 
   // acc[a][b] = (smin, smax) of one pair: the two sums sit in adjacent registers, so that fp32 adds them with one
   // v_pk_add_f32 (lane-wise, each lane one correctly rounded add -- the same two adds)
@@ -163,95 +122,10 @@ __global__ void __launch_bounds__(NTX * (TILE / Block<T>::RA)) jaccard_tile_kern
     __syncthreads();
   }
 
-  // which pairs are kept: bit b of rmask[a] = bit a of cmask[b] = pair (row RA*ty + a, column RC*tx + b)
-  uint32_t rmask[RA], cmask[RC];
-#pragma unroll
-  for (int b = 0; b < RC; ++b) cmask[b] = 0;
   const bool wgt = weighted != 0;
-#pragma unroll
-  for (int a = 0; a < RA; ++a) {
-    rmask[a] = 0;
-    const bool va = i0 + RA * ty + a < na;
-#pragma unroll
-    for (int b = 0; b < RC; ++b) {
-      T v;
-      const bool k = va && j0 + RC * tx + b < nb && jaccard_keep<T>(acc[a][b].x, acc[a][b].y, alpha, wgt, v);
-      rmask[a] |= (k ? 1u : 0u) << b;
-      cmask[b] |= (k ? 1u : 0u) << a;
-    }
-  }
-  bool any = false;
-#pragma unroll
-  for (int a = 0; a < RA; ++a) {
-    rc[RA * ty + a][tx] = __popc(rmask[a]);
-    any |= rmask[a] != 0;
-  }
-  if (mirror) {
-#pragma unroll
-    for (int b = 0; b < RC; ++b) cc[RC * tx + b][ty] = __popc(cmask[b]);
-  }
-  any = __syncthreads_or(any);
-  if (!FILL && tid == 0) tile_nz[tlin] = any ? 1 : 0;
-  // exclusive scans: threads 0..127 over the NTX thread columns of row tid, threads 128..255 over the NTY thread rows
-  // of column tid - 128
-  if (tid < TILE) {
-    int run = 0;
-#pragma unroll
-    for (int q = 0; q < NTX; ++q) {
-      const int c = rc[tid][q];
-      rc[tid][q] = run;
-      run += c;
-    }
-    if (!FILL && i0 + tid < na) counts[jt * na + i0 + tid] = run;
-  } else if (tid < 2 * TILE && mirror) {
-    const int r = tid - TILE;
-    int run = 0;
-#pragma unroll
-    for (int q = 0; q < NTY; ++q) {
-      const int c = cc[r][q];
-      cc[r][q] = run;
-      run += c;
-    }
-    if (!FILL && j0 + r < nb) counts[it * na + j0 + r] = run;  // SYM: na == nb
-  }
-  if (!FILL) return;
-  __syncthreads();
-
-  bool nb_flag = false;
-#pragma unroll
-  for (int a = 0; a < RA; ++a) {
-    if (!rmask[a]) continue;
-    const int64_t i = i0 + RA * ty + a;
-    int64_t o = ptr[i] + counts[jt * na + i] + rc[RA * ty + a][tx];
-#pragma unroll
-    for (int b = 0; b < RC; ++b) {
-      if (!((rmask[a] >> b) & 1u)) continue;
-      T v;
-      (void)jaccard_keep<T>(acc[a][b].x, acc[a][b].y, alpha, wgt, v);
-      oidx[o] = (int)(j0 + RC * tx + b);
-      if (oval) oval[o] = v;
-      nb_flag |= (v != T(1));
-      ++o;
-    }
-  }
-  if (mirror) {
-#pragma unroll
-    for (int b = 0; b < RC; ++b) {
-      if (!cmask[b]) continue;
-      const int64_t j = j0 + RC * tx + b;
-      int64_t o = ptr[j] + counts[it * na + j] + cc[RC * tx + b][ty];
-#pragma unroll
-      for (int a = 0; a < RA; ++a) {
-        if (!((cmask[b] >> a) & 1u)) continue;
-        T v;
-        (void)jaccard_keep<T>(acc[a][b].x, acc[a][b].y, alpha, wgt, v);
-        oidx[o] = (int)(i0 + RA * ty + a);
-        if (oval) oval[o] = v;
-        ++o;
-      }
-    }
-  }
-  if (nb_flag) *not_binary = 1;
+  pair_tile_emit<T, TILE, RA, RC, SYM, FILL, true>(
+      t, na, nb, [&](int a, int b, T& v) { return jaccard_keep<T>(acc[a][b].x, acc[a][b].y, alpha, wgt, v); }, counts,
+      tile_nz, ptr, oidx, oval, not_binary);
 }
 
 template <class T>
@@ -262,20 +136,8 @@ constexpr int threads() {
 }  // namespace
 
 template <class T>
-int launch_feature_nan_scan(const T* F, int64_t n, int64_t ld, int64_t d, int* flag) {
-  if (n == 0 || d == 0) return SS_OK;
-  const int64_t blocks = std::min<int64_t>(ceil_div(n * d, 256), 4096);
-  hipLaunchKernelGGL(nan_scan_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, ctx().stream, F, n, ld, d, flag);
-  SS_LAUNCH_CHECK();
-  return SS_OK;
-}
-template int launch_feature_nan_scan<float>(const float*, int64_t, int64_t, int64_t, int*);
-template int launch_feature_nan_scan<double>(const double*, int64_t, int64_t, int64_t, int*);
-
-template <class T>
 int JaccardCsr<T>::count(const T* Fa_, int64_t na_, int64_t lda_, const T* Fb_, int64_t nb_, int64_t ldb_, int64_t d_,
                          T alpha_, bool weighted_) {
-  hipStream_t st = ctx().stream;
   what = "jaccard";
   sym = (Fb_ == nullptr);
   Fa = Fa_;
@@ -286,63 +148,19 @@ int JaccardCsr<T>::count(const T* Fa_, int64_t na_, int64_t lda_, const T* Fb_, 
   alpha = alpha_;
   weighted = weighted_;
   if (alpha != alpha) return fail(SS_EINVAL, "jaccard: alpha is NaN");
-  // NaN features: refused before anything (the row pointers included) is written
-  {
-    DevBuf<int> flag;
-    SS_TRY(flag.alloc(1));
-    SS_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-    SS_TRY(launch_feature_nan_scan<T>(Fa, na_, lda, d, flag.p));
-    if (!sym) SS_TRY(launch_feature_nan_scan<T>(Fb, nb_, ldb, d, flag.p));
-    int bad = 0;
-    SS_HIP(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    SS_HIP(hipStreamSynchronize(st));
-    if (bad) return fail(SS_EINVAL, "jaccard: the features hold a NaN");
-  }
-  SS_TRY(this->begin(na_, sym ? na_ : nb_, TILE));
+  SS_TRY(this->refuse_nan_features(Fa, na_, lda, Fb, nb_, ldb, d));
+  SS_TRY(this->begin_tiles(na_, sym ? na_ : nb_, TILE, true));
   if (na == 0 || nb == 0) return SS_OK;
-  const int64_t nti = ceil_div(na, TILE);
-  const int64_t nblocks = sym ? nti * (nti + 1) / 2 : nti * ntj;
-  if (sym ? nblocks >= (1LL << 31) : (ntj >= (1LL << 31) || nti > 65535))
-    return fail(SS_EUNSUPPORTED, "jaccard: %lld x %lld pairs need more tiles than one launch holds", (long long)na,
-                (long long)nb);
-  SS_TRY(counts.alloc((size_t)ntj * (size_t)na));
-  SS_TRY(tile_nz.alloc((size_t)nblocks));
-  if (sym) {
-    hipLaunchKernelGGL((jaccard_tile_kernel<T, true, false>), dim3((unsigned)nblocks), dim3(threads<T>()), 0, st, Fa,
-                       na, lda, Fb, nb, ldb, d, alpha, weighted ? 1 : 0, nti, counts.p, tile_nz.p,
-                       (const int64_t*)nullptr, (int*)nullptr, (T*)nullptr, (int*)nullptr);
-  } else {
-    hipLaunchKernelGGL((jaccard_tile_kernel<T, false, false>), dim3((unsigned)ntj, (unsigned)nti), dim3(threads<T>()), 0,
-                       st, Fa, na, lda, Fb, nb, ldb, d, alpha, weighted ? 1 : 0, ntj, counts.p, tile_nz.p,
-                       (const int64_t*)nullptr, (int*)nullptr, (T*)nullptr, (int*)nullptr);
-  }
-  SS_LAUNCH_CHECK();
-  return this->scan();
+  return this->count_pass();
 }
 
 template <class T>
-int JaccardCsr<T>::fill(int* idx, T* val, bool* binary) {
-  hipStream_t st = ctx().stream;
-  if (binary) *binary = true;
-  if (nnz == 0) return SS_OK;
-  DevBuf<int> flag;
-  SS_TRY(flag.alloc(1));
-  SS_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-  const int64_t nti = ceil_div(na, TILE);
-  if (sym) {
-    hipLaunchKernelGGL((jaccard_tile_kernel<T, true, true>), dim3((unsigned)(nti * (nti + 1) / 2)), dim3(threads<T>()),
-                       0, st, Fa, na, lda, Fb, nb, ldb, d, alpha, weighted ? 1 : 0, nti, counts.p, tile_nz.p, ptr.p, idx,
-                       val, flag.p);
-  } else {
-    hipLaunchKernelGGL((jaccard_tile_kernel<T, false, true>), dim3((unsigned)ntj, (unsigned)nti), dim3(threads<T>()), 0,
-                       st, Fa, na, lda, Fb, nb, ldb, d, alpha, weighted ? 1 : 0, ntj, counts.p, tile_nz.p, ptr.p, idx,
-                       val, flag.p);
-  }
+int JaccardCsr<T>::launch(bool fill, int* idx, T* val, int* flag) {
+  auto* kernel = sym ? (fill ? jaccard_tile_kernel<T, true, true> : jaccard_tile_kernel<T, true, false>)
+                     : (fill ? jaccard_tile_kernel<T, false, true> : jaccard_tile_kernel<T, false, false>);
+  hipLaunchKernelGGL(kernel, this->tile_grid(), dim3(threads<T>()), 0, ctx().stream, Fa, na, lda, Fb, nb, ldb, d, alpha,
+                     weighted ? 1 : 0, nti, counts.p, tile_nz.p, ptr.p, idx, val, flag);
   SS_LAUNCH_CHECK();
-  int notbin = 0;
-  SS_HIP(hipMemcpyAsync(&notbin, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-  SS_HIP(hipStreamSynchronize(st));
-  if (binary) *binary = (notbin == 0);
   return SS_OK;
 }
 

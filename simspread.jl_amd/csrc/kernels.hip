@@ -26,13 +26,6 @@ static inline int grid_1d(int64_t work, int block, int cap = 256 * 16) {
   return (int)g;
 }
 
-#define SS_LAUNCH_CHECK()                                                             \
-  do {                                                                                \
-    hipError_t _e = hipGetLastError();                                                \
-    if (_e != hipSuccess)                                                             \
-      return fail(SS_EHIP, "%s:%d kernel launch: %s", __FILE__, __LINE__, hipGetErrorString(_e)); \
-  } while (0)
-
 // ============================================================== element-wise
 template <class T>
 __global__ void cutoff_kernel(const T* __restrict__ X, int64_t rows, int64_t cols, int64_t ld, T alpha,

@@ -17,13 +17,6 @@
 
 namespace ss {
 
-#define SS_LAUNCH_CHECK()                                                                              \
-  do {                                                                                                 \
-    hipError_t _e = hipGetLastError();                                                                 \
-    if (_e != hipSuccess)                                                                              \
-      return fail(SS_EHIP, "%s:%d kernel launch: %s", __FILE__, __LINE__, hipGetErrorString(_e));      \
-  } while (0)
-
 namespace {
 
 // blockIdx.y: row of the launch; nvec 16-byte vectors per row when vec, else ncols elements

@@ -18,13 +18,6 @@
 
 namespace ss {
 
-#define SS_LAUNCH_CHECK()                                                             \
-  do {                                                                                \
-    hipError_t _e = hipGetLastError();                                                \
-    if (_e != hipSuccess)                                                             \
-      return fail(SS_EHIP, "%s:%d kernel launch: %s", __FILE__, __LINE__, hipGetErrorString(_e)); \
-  } while (0)
-
 __global__ void iota_kernel(unsigned* __restrict__ v, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     v[i] = (unsigned)i;

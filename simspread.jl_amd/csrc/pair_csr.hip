@@ -1,7 +1,11 @@
-// Host skeleton of the fused thresholded-similarity producers (fingerprint.hip, jaccard_csr.hip): a producer's count
-// pass leaves the kept entries of every (column tile, row) slot in counts[jt * rows + i]; scan() turns them into
-// exclusive in-row offsets and takes a 64-bit scan of the row totals into ptr, so that nnz >= 2^31 is seen (and
-// refused by the caller) before any output exists.  Positions come from scans, never from atomics.
+// Host skeleton of the fused thresholded-similarity producers (fingerprint.hip, jaccard_csr.hip, dot_csr.hip; their
+// tiles and emit epilogue are pair_tile.hpp) and of the streaming cutoff (recut.hip).  A producer's count pass leaves
+// the kept entries of every (column tile, row) slot in counts[jt * rows + i]; scan() turns them into exclusive in-row
+// offsets and takes a 64-bit scan of the row totals into ptr, so that nnz >= 2^31 is seen (and refused by the caller)
+// before any output exists; fill() runs the producer's fill pass.  Positions come from scans, never from atomics.
+// What every tiled producer does around its kernel lives here too: the refusal of NaN features and of more tiles than
+// one launch holds, the counts / tile_nz buffers and the launch grid.
+#include <algorithm>
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
@@ -9,13 +13,6 @@
 #include "graph.hpp"
 
 namespace ss {
-
-#define SS_LAUNCH_CHECK()                                                                              \
-  do {                                                                                                 \
-    hipError_t _e = hipGetLastError();                                                                 \
-    if (_e != hipSuccess)                                                                              \
-      return fail(SS_EHIP, "%s:%d kernel launch: %s", __FILE__, __LINE__, hipGetErrorString(_e));      \
-  } while (0)
 
 namespace {
 
@@ -34,6 +31,28 @@ __global__ void pair_row_offsets_kernel(int* __restrict__ counts, int64_t rows, 
 }
 
 __global__ void ptr_tail_kernel(const int* in, int64_t* out, int64_t n) { out[n] = n ? out[n - 1] + in[n - 1] : 0; }
+
+template <class T>
+__global__ void nan_scan_kernel(const T* __restrict__ F, int64_t n, int64_t ld, int64_t d, int* __restrict__ flag) {
+  const int64_t total = n * d;
+  bool bad = false;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t k = e / n, i = e - k * n;
+    const T x = F[i + k * ld];
+    bad |= (x != x);
+  }
+  if (bad) *flag = 1;
+}
+
+// flag[0] = 1 when F (n x d, column-major, ld >= n; padding rows are not read) holds a NaN; enqueued only
+template <class T>
+int launch_feature_nan_scan(const T* F, int64_t n, int64_t ld, int64_t d, int* flag) {
+  if (n == 0 || d == 0) return SS_OK;
+  const int64_t blocks = std::min<int64_t>(ceil_div(n * d, 256), 4096);
+  hipLaunchKernelGGL(nan_scan_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, ctx().stream, F, n, ld, d, flag);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
 
 __global__ void ptr_narrow_kernel(const int64_t* __restrict__ in, int64_t n, int* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -58,6 +77,41 @@ int PairCsr<T>::begin(int64_t na_, int64_t nb_, int64_t tile) {
 }
 
 template <class T>
+int PairCsr<T>::begin_tiles(int64_t na_, int64_t nb_, int64_t tile, bool with_tile_nz) {
+  SS_TRY(begin(na_, nb_, tile));
+  if (na == 0 || nb == 0) return SS_OK;
+  nti = ceil_div(na, tile);
+  const int64_t nblocks = sym ? nti * (nti + 1) / 2 : nti * ntj;
+  if (sym ? nblocks >= (1LL << 31) : (ntj >= (1LL << 31) || nti > 65535))
+    return fail(SS_EUNSUPPORTED, "%s: %lld x %lld pairs need more tiles than one launch holds", what, (long long)na,
+                (long long)nb);
+  SS_TRY(counts.alloc((size_t)ntj * (size_t)na));
+  if (with_tile_nz) SS_TRY(tile_nz.alloc((size_t)nblocks));
+  return SS_OK;
+}
+
+template <class T>
+dim3 PairCsr<T>::tile_grid() const {
+  return sym ? dim3((unsigned)(nti * (nti + 1) / 2)) : dim3((unsigned)ntj, (unsigned)nti);
+}
+
+template <class T>
+int PairCsr<T>::refuse_nan_features(const T* Fa, int64_t na_, int64_t lda, const T* Fb, int64_t nb_, int64_t ldb,
+                                    int64_t d) {
+  hipStream_t st = ctx().stream;
+  DevBuf<int> flag;
+  SS_TRY(flag.alloc(1));
+  SS_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
+  SS_TRY(launch_feature_nan_scan<T>(Fa, na_, lda, d, flag.p));
+  if (!sym) SS_TRY(launch_feature_nan_scan<T>(Fb, nb_, ldb, d, flag.p));
+  int bad = 0;
+  SS_HIP(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  if (bad) return fail(SS_EINVAL, "%s: the features hold a NaN", what);
+  return SS_OK;
+}
+
+template <class T>
 int PairCsr<T>::scan() {
   hipStream_t st = ctx().stream;
   DevBuf<int> rowcnt;
@@ -75,6 +129,22 @@ int PairCsr<T>::scan() {
   SS_LAUNCH_CHECK();
   SS_HIP(hipMemcpyAsync(&nnz, ptr.p + na, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   SS_HIP(hipStreamSynchronize(st));  // tmp, rowcnt are freed on return
+  return SS_OK;
+}
+
+template <class T>
+int PairCsr<T>::fill(int* idx, T* val, bool* binary) {
+  hipStream_t st = ctx().stream;
+  if (binary) *binary = true;
+  if (nnz == 0) return SS_OK;
+  DevBuf<int> flag;
+  SS_TRY(flag.alloc(1));
+  SS_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
+  SS_TRY(launch(true, idx, val, flag.p));
+  int notbin = 0;
+  SS_HIP(hipMemcpyAsync(&notbin, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  if (binary) *binary = (notbin == 0);
   return SS_OK;
 }
 

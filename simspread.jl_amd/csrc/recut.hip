@@ -19,13 +19,6 @@
 
 namespace ss {
 
-#define SS_LAUNCH_CHECK()                                                                              \
-  do {                                                                                                 \
-    hipError_t _e = hipGetLastError();                                                                 \
-    if (_e != hipSuccess)                                                                              \
-      return fail(SS_EHIP, "%s:%d kernel launch: %s", __FILE__, __LINE__, hipGetErrorString(_e));      \
-  } while (0)
-
 namespace {
 
 // FILL = false: counts[r] = kept entries of row r.  FILL = true: the kept entries of row r go to optr[r] ... in order.
@@ -133,28 +126,15 @@ int CutCsr<T>::count(const DevCsr<T>& in_, T alpha_, bool weighted_) {
     SS_HIP(hipStreamSynchronize(st));
   }
   gshift = group_shift(in_.nnz, na, longest);
-  hipLaunchKernelGGL((cut_rows_kernel<T, false>), dim3(cut_grid(na, gshift)), dim3(256), 0, st, in_.ptr.p, in_.idx.p,
-                     in_.val.p, na, alpha, weighted ? 1 : 0, gshift, counts.p, (const int64_t*)nullptr, (int*)nullptr,
-                     (T*)nullptr, (int*)nullptr);
-  SS_LAUNCH_CHECK();
-  return this->scan();
+  return this->count_pass();
 }
 
 template <class T>
-int CutCsr<T>::fill(int* idx, T* val, bool* binary) {
-  hipStream_t st = ctx().stream;
-  if (binary) *binary = true;
-  if (nnz == 0) return SS_OK;
-  DevBuf<int> flag;
-  SS_TRY(flag.alloc(1));
-  SS_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-  hipLaunchKernelGGL((cut_rows_kernel<T, true>), dim3(cut_grid(na, gshift)), dim3(256), 0, st, in->ptr.p, in->idx.p,
-                     in->val.p, na, alpha, weighted ? 1 : 0, gshift, (int*)nullptr, ptr.p, idx, val, flag.p);
+int CutCsr<T>::launch(bool fill, int* idx, T* val, int* flag) {
+  auto* kernel = fill ? cut_rows_kernel<T, true> : cut_rows_kernel<T, false>;
+  hipLaunchKernelGGL(kernel, dim3(cut_grid(na, gshift)), dim3(256), 0, ctx().stream, in->ptr.p, in->idx.p, in->val.p, na,
+                     alpha, weighted ? 1 : 0, gshift, counts.p, ptr.p, idx, val, flag);
   SS_LAUNCH_CHECK();
-  int notbin = 0;
-  SS_HIP(hipMemcpyAsync(&notbin, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-  SS_HIP(hipStreamSynchronize(st));
-  if (binary) *binary = (notbin == 0);
   return SS_OK;
 }
 

@@ -23,13 +23,6 @@
 
 namespace ss {
 
-#define SS_LAUNCH_CHECK()                                                             \
-  do {                                                                                \
-    hipError_t _e = hipGetLastError();                                                \
-    if (_e != hipSuccess)                                                             \
-      return fail(SS_EHIP, "%s:%d kernel launch: %s", __FILE__, __LINE__, hipGetErrorString(_e)); \
-  } while (0)
-
 template <class T>
 struct CsArgs {
   const int2* desc;              // [nblocks + 1] {first pair, steps}; the last entry is an empty block
