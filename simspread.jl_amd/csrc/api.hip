@@ -708,59 +708,134 @@ static int graph_set_cutoff_impl(ss_graph* h, T alpha, int weighted) {
   return dense_degrees(*g);  // kf, ks, their reciprocals and 1/(kf-1); synchronises
 }
 
+// SELL chunk of the stage-2 operands for tile width qt; SS_SELL_CHUNK lowers it
+template <class T>
+static int sell_chunk(int qt) {
+  const int kcmax = sell_max_chunk<T>(qt);
+  return (int)env_int_in("SS_SELL_CHUNK", 64, kcmax, kcmax);
+}
+
 // stage-2 operand of a graph: W = Ys' cut for the tile width of this precision
 template <class T>
 static int graph_sell(Graph<T>& g) {
   const int qt = sell_tile_width<T>();
   if (g.W_qt == qt) return SS_OK;
-  int kcmax = sell_max_chunk<T>(qt);
-  if (const char* e = getenv("SS_SELL_CHUNK")) {
-    const int v = atoi(e);
-    if (v >= 64 && v < kcmax) kcmax = v;
-  }
-  SS_TRY(sell_build<T>(g.YsT, kcmax, g.W));
+  SS_TRY(sell_build<T>(g.YsT, sell_chunk<T>(qt), g.W));
   g.W_qt = qt;
   return SS_OK;
 }
 
-// stage-1 operands: X' (and Y' for source rows) cut into column chunks.  The chunk is sized so that an
-// average sub-row fills one 64-lane load (SC ~ 64 * ns / mean row length), the chunk count is a multiple
-// of 8 so that chunk c always meets the same XCD's L2.
+// Column chunk of a stage-1 operand mT (ns columns): sized so that an average sub-row fills one 64-lane load
+// (SC ~ 64 * ns / mean row length), the chunk count a multiple of 8 so that chunk c always meets the same XCD's L2.
+// honour_switch: SS_TRANSFER_CHUNK replaces the size before it is rounded.
+template <class T>
+static int transfer_chunk_cols(const DevCsr<T>& mT, int64_t ns, bool honour_switch) {
+  if (ns < 1) ns = 1;
+  const double mean_len = mT.rows > 0 ? (double)mT.nnz / (double)mT.rows : 0.0;
+  int64_t sc = mean_len > 1.0 ? (int64_t)(64.0 * (double)ns / mean_len) : ns;
+  // keep >= 8 single-wave workgroups per CU: (SC + 64) * sizeof(T) <= 20 KiB (measured at 100k x 100k, 1 %:
+  // SC 6250 -> 7.7 ms, 4167 -> 4.5 ms, 3200 -> 5.9 ms for 2048 folds)
+  const int64_t sc_max = (20 * 1024) / (int64_t)sizeof(T) - 64;
+  if (sc > sc_max) sc = sc_max;
+  if (sc < 256) sc = 256;
+  if (honour_switch) sc = env_int_in("SS_TRANSFER_CHUNK", 16, 8193, sc);
+  int64_t nch = ceil_div(ns, sc);
+  if (nch > 1) nch = ceil_div(nch, 8) * 8;
+  return (int)(ceil_div(ceil_div(ns, nch), 4) * 4);
+}
+
+// stage-1 operands cut into column chunks: Xs' of a sparse graph, and for source rows (need_y) Ys' with the same chunk.
+// A dense-similarity graph has no Xs': the Ys' of its sparse target path is sized by itself (and never honoured
+// SS_TRANSFER_CHUNK).
 template <class T>
 static int graph_chunked(Graph<T>& g, bool need_y) {
-  if (g.XsTc.SC == 0) {
-    const int64_t ns = g.ns > 0 ? g.ns : 1;
-    const double mean_len = g.XsT.rows > 0 ? (double)g.XsT.nnz / (double)g.XsT.rows : 0.0;
-    int64_t sc = mean_len > 1.0 ? (int64_t)(64.0 * (double)ns / mean_len) : ns;
-    // keep >= 8 single-wave workgroups per CU: (SC + 64) * sizeof(T) <= 20 KiB (measured at 100k x 100k, 1 %:
-    // SC 6250 -> 7.7 ms, 4167 -> 4.5 ms, 3200 -> 5.9 ms for 2048 folds)
-    const int64_t sc_max = (20 * 1024) / (int64_t)sizeof(T) - 64;
-    if (sc > sc_max) sc = sc_max;
-    if (sc < 256) sc = 256;
-    if (const char* e = getenv("SS_TRANSFER_CHUNK")) {
-      const long long v = atoll(e);
-      if (v >= 16 && v <= 8192) sc = v;
-    }
-    int64_t nch = ceil_div(ns, sc);
-    if (nch > 1) nch = ceil_div(nch, 8) * 8;
-    sc = ceil_div(ceil_div(ns, nch), 4) * 4;
-    SS_TRY(chunked_build<T>(g.XsT, (int)sc, 1, g.XsTc));
-  }
-  if (need_y && g.YsTc.SC == 0) SS_TRY(chunked_build<T>(g.YsT, g.XsTc.SC, 1, g.YsTc));
+  if (!g.dense.on && g.XsTc.SC == 0)
+    SS_TRY(chunked_build<T>(g.XsT, transfer_chunk_cols(g.XsT, g.ns, true), 1, g.XsTc));
+  if (need_y && g.YsTc.SC == 0)
+    SS_TRY(chunked_build<T>(g.YsT, g.dense.on ? transfer_chunk_cols(g.YsT, g.ns, false) : g.XsTc.SC, 1, g.YsTc));
   return SS_OK;
 }
 
 // rows of T held at once (stage-1 output, stage-2 input)
 static int64_t transfer_batch_rows(int64_t nrows, int64_t nj, size_t elem) {
-  int64_t cap_bytes = 2LL << 30;
-  if (const char* e = getenv("SS_TRANSFER_BYTES")) {
-    const long long v = atoll(e);
-    if (v >= (1 << 20)) cap_bytes = v;
-  }
+  int64_t cap_bytes = env_int("SS_TRANSFER_BYTES", 0);
+  if (cap_bytes < (1 << 20)) cap_bytes = 2LL << 30;
   int64_t rb = cap_bytes / ((nj > 0 ? nj : 1) * (int64_t)elem);
   rb &= ~7LL;
   if (rb < 8) rb = 8;
   return rb < nrows ? rb : nrows;
+}
+
+// Dense-similarity stage 1 of rows [r0, r0 + nb) -- of members[] when that is given -- into dst.  fp64: the fp64 matrix
+// instruction (dense_f64.hip, the reference's default precision).  fp32: the bf16 matrix cores on exact bf16 planes of
+// the operands (dense_bf16.hip: 1.5x weighted, 3.2x unweighted at 50k); SS_DENSE_BF16=0 selects the fp32-input MFMA
+// kernel of dense.hip, which gathers no member rows: the k-fold calls (members != NULL) never take it.
+template <class T>
+static int dense_transfer(Graph<T>& g, bool loo, const T* inv_kf, const T* inv_ks, const int* ks, int64_t r0, int64_t nb,
+                          T* dst, int64_t ld, bool srcrows, const int* members) {
+  if constexpr (std::is_same<T, float>::value) {
+    if (!members && env_off("SS_DENSE_BF16"))
+      return launch_transfer_dense(g.dense, loo, inv_kf, inv_ks, ks, r0, nb, dst, ld, srcrows);
+    return launch_transfer_dense_bf16(g.dense, loo, inv_kf, inv_ks, ks, r0, nb, dst, ld, srcrows, members);
+  } else {
+    return launch_transfer_dense_f64(g.dense, loo, inv_kf, inv_ks, ks, r0, nb, dst, ld, srcrows, members);
+  }
+}
+
+// Where stage 2 puts the score rows of a batch.  Row q of the batch goes to row
+//   o + q              of dst: contiguous rows (row_map and host_rows NULL)
+//   row_map[o + q]     device row map: fused into the SELL launch when the operand is unsorted, launch_scatter_rows
+//                      after launch_unpermute when it is length-sorted
+//   host_rows[o + q]   the same rows on the host, given next to row_map: a length-sorted operand's rows are then put in
+//                      place by one copy each instead of the scatter (ss_predict_kfold_*: few folds x rows)
+template <class T>
+struct ScoreDest {
+  T* dst;
+  int64_t ld, o;
+  const int* row_map;
+  const int* host_rows;
+};
+
+// Stage 2 of nb score rows: F = R W' with the SELL operand W (ncols score columns), R row-major with leading dimension
+// ldr.  A length-sorted operand gives its scores in sorted target order into the scratch buffer ws (sized for batches of
+// rb rows, plus rb packed rows when the destination rows are not contiguous); launch_unpermute puts them back (+ clean!).
+template <class T>
+static int sell_rows(const DevSell<T>& W, const T* R, int64_t ldr, int64_t ncols, DevBuf<T>& ws, int64_t rb, int64_t nb,
+                     const int* kt_clean, const ScoreDest<T>& d) {
+  const int* rows = d.row_map ? d.row_map + d.o : nullptr;
+  T* out = rows ? d.dst : d.dst + d.o * d.ld;
+  if (!W.sorted) {
+    StageTimer t2(ST_SPMM);
+    SS_TRY(launch_spmm_sell<T>(W, R, ldr, nb, out, d.ld, kt_clean, rows));
+    timing_count(ST_NSPMM, 1);
+    return SS_OK;
+  }
+  const size_t nsorted = (size_t)rb * (size_t)W.vrows;
+  const size_t need_s = nsorted + (rows ? (size_t)rb * (size_t)ncols : 0);
+  if (ws.n < need_s) SS_TRY(ws.alloc(need_s));
+  {
+    StageTimer t2(ST_SPMM);
+    SS_TRY(launch_spmm_sell<T>(W, R, ldr, nb, ws.p, W.vrows, nullptr));
+    timing_count(ST_NSPMM, 1);
+  }
+  StageTimer t3(ST_EPILOGUE);
+  T* packed = ws.p + nsorted;  // rows in batch order before they go to their places
+  SS_TRY(launch_unpermute<T>(ws.p, W.vrows, nb, ncols, W.vfirst.p, W.inv.p, kt_clean, rows ? packed : out,
+                             rows ? ncols : d.ld));
+  if (d.host_rows) {
+    for (int64_t q = 0; q < nb; ++q)
+      SS_HIP(hipMemcpyAsync(d.dst + (int64_t)d.host_rows[d.o + q] * d.ld, packed + q * ncols, ncols * sizeof(T),
+                            hipMemcpyDeviceToDevice, ctx().stream));
+  } else if (rows) {
+    SS_TRY(launch_scatter_rows<T>(packed, ncols, nb, ncols, rows, d.dst, d.ld));
+  }
+  return SS_OK;
+}
+
+// stage 2 of a graph's score rows: the nb rows of the transfer block g.Tws (batches of at most rb rows) through W = Ys'
+template <class T>
+static int stage2_rows(Graph<T>& g, int64_t rb, int64_t nb, const int* kt_clean, const ScoreDest<T>& d) {
+  return sell_rows<T>(g.W, g.Tws.p, g.ns, g.nt, g.Sws, rb, nb, kt_clean, d);
 }
 
 // run stage 1 + stage 2 over [row_begin, row_end) into dev_out (row-major nrows x nt, ld = ldo)
@@ -770,20 +845,7 @@ static int predict_rows_device(Graph<T>& g, int kind, int64_t row_begin, int64_t
   const int64_t nrows = row_end - row_begin;
   const int64_t nj = g.ns;
   SS_TRY(graph_sell(g));
-  if (!g.dense.on) SS_TRY(graph_chunked(g, kind == SS_ROWS_SOURCE));
-  if (g.dense.on && kind == SS_ROWS_SOURCE && g.YsTc.SC == 0) {
-    // the sparse target path needs Ys' cut into column chunks (same sizing rule as graph_chunked)
-    const int64_t ns = g.ns > 0 ? g.ns : 1;
-    const double mean_len = g.YsT.rows > 0 ? (double)g.YsT.nnz / (double)g.YsT.rows : 0.0;
-    int64_t sc = mean_len > 1.0 ? (int64_t)(64.0 * (double)ns / mean_len) : ns;
-    const int64_t sc_max = (20 * 1024) / (int64_t)sizeof(T) - 64;
-    if (sc > sc_max) sc = sc_max;
-    if (sc < 256) sc = 256;
-    int64_t nch = ceil_div(ns, sc);
-    if (nch > 1) nch = ceil_div(nch, 8) * 8;
-    sc = ceil_div(ceil_div(ns, nch), 4) * 4;
-    SS_TRY(chunked_build<T>(g.YsT, (int)sc, 1, g.YsTc));
-  }
+  SS_TRY(graph_chunked(g, kind == SS_ROWS_SOURCE));
   const int64_t rb = transfer_batch_rows(nrows, nj, sizeof(T));
   // the transfer block lives in the handle so that repeated predictions do not re-allocate
   const size_t need = (size_t)rb * (size_t)(nj > 0 ? nj : 1);
@@ -794,47 +856,30 @@ static int predict_rows_device(Graph<T>& g, int kind, int64_t row_begin, int64_t
     {
       StageTimer t1(ST_TRANSFER);
       if (g.dense.on) {
-        {
-          const bool loo = (kind == 2);
-          const bool srcrows = (kind == SS_ROWS_SOURCE);  // feature path here, target path added below
-          if constexpr (std::is_same<T, float>::value) {
-            // default: bf16 matrix cores on exact bf16 planes of the operands (dense_bf16.hip: 1.5x weighted, 3.2x
-            // unweighted at 50k); SS_DENSE_BF16=0: the fp32-input MFMA kernel of dense.hip
-            const bool use_bf16 = !(getenv("SS_DENSE_BF16") && atoi(getenv("SS_DENSE_BF16")) == 0);
-            if (use_bf16)
-              SS_TRY(launch_transfer_dense_bf16(g.dense, loo, loo ? g.dense.inv_kf_m1.p : g.inv_kf.p, g.inv_ks.p, g.ks.p,
-                                                row_begin + r0, nb, Tbuf.p, nj, srcrows));
-            else
-              SS_TRY(launch_transfer_dense(g.dense, loo, loo ? g.dense.inv_kf_m1.p : g.inv_kf.p, g.inv_ks.p, g.ks.p,
-                                           row_begin + r0, nb, Tbuf.p, nj, srcrows));
-          } else {
-            // fp64 (the reference's default precision): the fp64 matrix instruction, dense_f64.hip
-            SS_TRY(launch_transfer_dense_f64(g.dense, loo, loo ? g.dense.inv_kf_m1.p : g.inv_kf.p, g.inv_ks.p, g.ks.p,
-                                             row_begin + r0, nb, Tbuf.p, nj, srcrows));
-          }
-          if (srcrows) {
-            // target path (Ys D_t^-1) Ys' D_s^-1 of the source rows: sparse, added to T
-            const DevCsr<T>* L[2] = {&g.Ys, nullptr};
-            const DevChunked<T>* M[2] = {&g.YsTc, nullptr};
-            const T* inv1[2] = {g.inv_kt.p, nullptr};
-            SS_TRY(launch_transfer<T>(1, L, inv1, M, g.inv_ks.p, row_begin + r0, nb, nj, Tbuf.p, nj, nullptr, true));
-          }
+        const bool loo = (kind == 2);
+        const bool srcrows = (kind == SS_ROWS_SOURCE);  // feature path here, target path added below
+        SS_TRY(dense_transfer<T>(g, loo, loo ? g.dense.inv_kf_m1.p : g.inv_kf.p, g.inv_ks.p, g.ks.p, row_begin + r0, nb,
+                                 Tbuf.p, nj, srcrows, nullptr));
+        if (srcrows) {
+          // target path (Ys D_t^-1) Ys' D_s^-1 of the source rows: sparse, added to T
+          const DevCsr<T>* L[2] = {&g.Ys, nullptr};
+          const DevChunked<T>* M[2] = {&g.YsTc, nullptr};
+          const T* inv1[2] = {g.inv_kt.p, nullptr};
+          SS_TRY(launch_transfer<T>(1, L, inv1, M, g.inv_ks.p, row_begin + r0, nb, nj, Tbuf.p, nj, nullptr, true));
         }
       } else if (kind == 2) {
         SS_TRY(launch_transfer_loo<T>(g.Xs, g.XsTc, g.kf.p, g.ks.p, row_begin + r0, nb, Tbuf.p, nj));
       } else if (kind == SS_ROWS_QUERY) {
         // query rows: SS_TRANSFER_V=2 selects the query-block kernels (measured variants of round 3)
         // when the chunk's sub-row offsets fit in LDS next to >= 8 waves of accumulators; default: the single-wave kernel
-        const char* ev = getenv("SS_TRANSFER_V");
-        const bool want_block = (ev && atoi(ev) >= 2) && transfer_block_fits<T>(g.XsT.rows, g.XsTc.SC);
+        const bool want_block = env_int("SS_TRANSFER_V", 0) >= 2 && transfer_block_fits<T>(g.XsT.rows, g.XsTc.SC);
         if (want_block) {
           if (g.XsTb.SC == 0) {
-            int al = 32;
-            if (const char* e = getenv("SS_TRANSFER_ALIGN")) al = atoi(e) == 1 ? 1 : 32;
+            const int al = env_int("SS_TRANSFER_ALIGN", 32) == 1 ? 1 : 32;
             SS_TRY(chunked_build<T>(g.XsT, g.XsTc.SC, al, g.XsTb));
           }
           if (g.Cq.n < (size_t)(g.Xq.nnz > 0 ? g.Xq.nnz : 1)) SS_TRY(g.Cq.alloc((size_t)(g.Xq.nnz > 0 ? g.Xq.nnz : 1)));
-          const bool fixed = !(getenv("SS_TRANSFER_FIX") && atoi(getenv("SS_TRANSFER_FIX")) == 0);
+          const bool fixed = !env_off("SS_TRANSFER_FIX");
           SS_TRY(launch_transfer_block<T>(g.Xq, g.inv_kf.p, g.XsTb, g.inv_ks.p, row_begin + r0, nb, nj, Tbuf.p, nj, g.Cq.p,
                                           g.XsTb.vmax, fixed));
         } else {
@@ -852,23 +897,7 @@ static int predict_rows_device(Graph<T>& g, int kind, int64_t row_begin, int64_t
       }
       timing_count(ST_NTRANSFER, 1);
     }
-    if (!g.W.sorted) {
-      StageTimer t2(ST_SPMM);
-      SS_TRY(launch_spmm_sell<T>(g.W, Tbuf.p, nj, nb, dev_out + r0 * ldo, ldo, clean ? g.kt.p : nullptr));
-      timing_count(ST_NSPMM, 1);
-    } else {
-      // skew-sorted operand: scores come out in sorted target order, then go back through inv[] (+ clean!)
-      const size_t need_s = (size_t)rb * (size_t)g.W.vrows;
-      if (g.Sws.n < need_s) SS_TRY(g.Sws.alloc(need_s));
-      {
-        StageTimer t2(ST_SPMM);
-        SS_TRY(launch_spmm_sell<T>(g.W, Tbuf.p, nj, nb, g.Sws.p, g.W.vrows, nullptr));
-        timing_count(ST_NSPMM, 1);
-      }
-      StageTimer t3(ST_EPILOGUE);
-      SS_TRY(launch_unpermute<T>(g.Sws.p, g.W.vrows, nb, g.nt, g.W.vfirst.p, g.W.inv.p, clean ? g.kt.p : nullptr,
-                                 dev_out + r0 * ldo, ldo));
-    }
+    SS_TRY(stage2_rows<T>(g, rb, nb, clean ? g.kt.p : nullptr, ScoreDest<T>{dev_out, ldo, r0, nullptr, nullptr}));
   }
   if (kind == 2 && clean) {
     StageTimer t3(ST_EPILOGUE);
@@ -883,6 +912,65 @@ static int loo_graph_check(const Graph<T>& g) {
     return fail(SS_EINVAL, "leave-one-out needs a graph with nq == 0 and ns == nf (feature j named after source j)");
   return SS_OK;
 }
+
+// How score rows reach the caller.  begin() opens the call's timing and its ST_TOTAL span and yields the row-major device
+// block the scores are computed into (dev_rm, ld_rm): the caller's own buffer when that is on the device and row-major,
+// else a block this owns.  deliver() transposes for a column-major caller, closes the span and copies to a host caller.
+// The copies are asynchronous and the staging buffers live as long as this does: a call that is not direct()
+// synchronises the stream before it returns.
+template <class T>
+struct ScoreOut {
+  T* out = nullptr;
+  int64_t ld = 0, nrows = 0, nt = 0;
+  int layout = SS_LAYOUT_ROWMAJOR, mem = SS_MEM_DEVICE;
+  T* dev_rm = nullptr;
+  int64_t ld_rm = 0;
+  hipEvent_t e_begin = nullptr;
+  DevBuf<T> scores;  // row-major nrows x nt
+  DevBuf<T> cm;      // column-major staging when the caller is on the host
+
+  bool direct() const { return mem == SS_MEM_DEVICE && layout == SS_LAYOUT_ROWMAJOR; }
+  int begin(T* out_, int64_t ld_, int layout_, int mem_, int64_t nrows_, int64_t nt_) {
+    out = out_; ld = ld_; layout = layout_; mem = mem_; nrows = nrows_; nt = nt_;
+    timing_begin_call();
+    SS_TRY(timing_mark(&e_begin));
+    dev_rm = out;
+    ld_rm = ld;
+    if (!direct()) {
+      SS_TRY(scores.alloc((size_t)nrows * nt));
+      dev_rm = scores.p;
+      ld_rm = nt;
+    }
+    return SS_OK;
+  }
+  int deliver() {
+    if (layout == SS_LAYOUT_COLMAJOR) {
+      StageTimer t3(ST_EPILOGUE);
+      T* dst = out;
+      int64_t dld = ld;
+      if (mem == SS_MEM_HOST) {
+        SS_TRY(cm.alloc((size_t)nrows * nt));
+        dst = cm.p;
+        dld = nrows;
+      }
+      SS_TRY(launch_transpose<T>(dev_rm, nrows, nt, ld_rm, dst, dld));
+    }
+    hipEvent_t e_end;
+    SS_TRY(timing_mark(&e_end));
+    timing_span(ST_TOTAL, e_begin, e_end);
+    if (mem == SS_MEM_HOST) {
+      StageTimer t5(ST_D2H);
+      if (layout == SS_LAYOUT_ROWMAJOR) {
+        SS_HIP(hipMemcpy2DAsync(out, ld * sizeof(T), dev_rm, ld_rm * sizeof(T), nt * sizeof(T), nrows,
+                                hipMemcpyDeviceToHost, ctx().stream));
+      } else {
+        SS_HIP(hipMemcpy2DAsync(out, ld * sizeof(T), cm.p, nrows * sizeof(T), nrows * sizeof(T), nt,
+                                hipMemcpyDeviceToHost, ctx().stream));
+      }
+    }
+    return SS_OK;
+  }
+};
 
 // kind: SS_ROWS_QUERY, SS_ROWS_SOURCE, or 2 = leave-one-out
 template <class T>
@@ -911,52 +999,15 @@ static int predict_impl(ss_graph* h, int kind, int64_t row_begin, int64_t row_en
   if (!out) return fail(SS_EINVAL, "output buffer is NULL");
   const int64_t need_ld = (layout == SS_LAYOUT_ROWMAJOR) ? nt : nrows;
   if (ld < need_ld) return fail(SS_EINVAL, "leading dimension %lld < %lld", (long long)ld, (long long)need_ld);
-  hipStream_t st = ctx().stream;
-  timing_begin_call();
-  hipEvent_t e_begin, e_end;
-  SS_TRY(timing_mark(&e_begin));
-
-  const bool direct = (mem == SS_MEM_DEVICE && layout == SS_LAYOUT_ROWMAJOR);
-  DevBuf<T> scores;  // row-major nrows x nt
-  T* dev_rm = out;
-  int64_t ld_rm = ld;
-  if (!direct) {
-    SS_TRY(scores.alloc((size_t)nrows * nt));
-    dev_rm = scores.p;
-    ld_rm = nt;
-  }
-  SS_TRY(predict_rows_device<T>(g, kind, row_begin, row_end, clean, dev_rm, ld_rm));
-
-  DevBuf<T> cm;  // column-major staging when the caller is on the host
-  if (layout == SS_LAYOUT_COLMAJOR) {
-    StageTimer t3(ST_EPILOGUE);
-    T* dst = out;
-    int64_t dld = ld;
-    if (mem == SS_MEM_HOST) {
-      SS_TRY(cm.alloc((size_t)nrows * nt));
-      dst = cm.p;
-      dld = nrows;
-    }
-    SS_TRY(launch_transpose<T>(dev_rm, nrows, nt, ld_rm, dst, dld));
-  }
-  SS_TRY(timing_mark(&e_end));
-  timing_span(ST_TOTAL, e_begin, e_end);
-  if (mem == SS_MEM_HOST) {
-    StageTimer t5(ST_D2H);
-    if (layout == SS_LAYOUT_ROWMAJOR) {
-      SS_HIP(hipMemcpy2DAsync(out, ld * sizeof(T), dev_rm, ld_rm * sizeof(T), nt * sizeof(T), nrows,
-                              hipMemcpyDeviceToHost, st));
-    } else {
-      SS_HIP(hipMemcpy2DAsync(out, ld * sizeof(T), cm.p, nrows * sizeof(T), nrows * sizeof(T), nt,
-                              hipMemcpyDeviceToHost, st));
-    }
-    t5.stop();
-  }
+  ScoreOut<T> so;
+  SS_TRY(so.begin(out, ld, layout, mem, nrows, nt));
+  SS_TRY(predict_rows_device<T>(g, kind, row_begin, row_end, clean, so.dev_rm, so.ld_rm));
+  SS_TRY(so.deliver());
   // Staging buffers are released on return and host results must be complete: wait for the stream.  With the
   // scores written straight into the caller's device buffer there is nothing to release (the transfer block
   // lives in the handle), so the call returns as soon as the work is enqueued -- stream order, like a kernel
   // launch; ss_synchronize() or the caller's own stream synchronisation waits for it.
-  if (!direct) SS_HIP(hipStreamSynchronize(st));
+  if (!so.direct()) SS_HIP(hipStreamSynchronize(ctx().stream));
   return SS_OK;
 }
 
@@ -1243,6 +1294,59 @@ static int evaluate_loo_binary_impl(ss_graph* h, int64_t i_begin, int64_t i_end,
   return SS_OK;
 }
 
+// device side of a k-fold call: the assignment, the selected members, their output rows and one fold's degrees
+template <class T>
+struct KfoldWork {
+  DevBuf<int> d_fold, d_order, d_sel, d_map, kf, ks, kt;
+  DevBuf<T> inv_kf, inv_ks;
+  int cur_seg = -1;  // segment whose degrees kf / ks / kt / inv_* hold
+};
+
+// the part every k-fold call needs: fold[i] of each source, the sources in fold order, room for one fold's degrees
+template <class T>
+static int kfold_work_folds(const Graph<T>& g, const int32_t* fold, const int* order, KfoldWork<T>& w) {
+  hipStream_t st = ctx().stream;
+  const int64_t ns = g.ns;
+  SS_TRY(w.d_fold.alloc(ns)); SS_TRY(w.d_order.alloc(ns));
+  SS_TRY(w.kf.alloc(g.nf)); SS_TRY(w.ks.alloc(ns)); SS_TRY(w.kt.alloc(g.nt));
+  SS_TRY(w.inv_kf.alloc(g.nf)); SS_TRY(w.inv_ks.alloc(ns));
+  SS_HIP(hipMemcpyAsync(w.d_fold.p, fold, ns * sizeof(int), hipMemcpyHostToDevice, st));
+  SS_HIP(hipMemcpyAsync(w.d_order.p, order, ns * sizeof(int), hipMemcpyHostToDevice, st));
+  w.cur_seg = -1;
+  return SS_OK;
+}
+
+// Degrees of the graph without fold fold_id, whose n members are members[]: w.kf / ks / kt recounted from the graph's
+// own, and the reciprocals stage 1 multiplies by (0 on the members' own feature columns and for the members as sources).
+template <class T>
+static int fold_degrees(const Graph<T>& g, KfoldWork<T>& w, const int* members, int64_t n, int fold_id) {
+  hipStream_t st = ctx().stream;
+  SS_HIP(hipMemcpyAsync(w.kf.p, g.kf.p, g.nf * sizeof(int), hipMemcpyDeviceToDevice, st));
+  SS_HIP(hipMemcpyAsync(w.ks.p, g.ks.p, g.ns * sizeof(int), hipMemcpyDeviceToDevice, st));
+  SS_HIP(hipMemcpyAsync(w.kt.p, g.kt.p, g.nt * sizeof(int), hipMemcpyDeviceToDevice, st));
+  if (g.dense.on) SS_TRY(dense_fold_degrees<T>(g, members, n, w.kf.p, w.ks.p, w.kt.p));
+  else SS_TRY(launch_fold_degrees<T>(g.Xs, g.XsT, g.Ys, members, n, w.kf.p, w.ks.p, w.kt.p));
+  return launch_fold_inverse<T>(w.kf.p, w.ks.p, w.d_fold.p, fold_id, g.nf, g.ns, w.inv_kf.p, w.inv_ks.p);
+}
+
+// stage 1 of a fold's members [r0, r0 + nb) into the transfer block g.Tws, with the fold's degrees in w
+template <class T>
+static int kfold_transfer(Graph<T>& g, KfoldWork<T>& w, const int* members, int64_t r0, int64_t nb) {
+  StageTimer t1(ST_TRANSFER);
+  const int64_t ns = g.ns;
+  if (g.dense.on) {
+    // members' rows gathered into the query planes
+    SS_TRY(dense_transfer<T>(g, false, w.inv_kf.p, w.inv_ks.p, nullptr, r0, nb, g.Tws.p, ns, false, members));
+  } else {
+    const DevCsr<T>* L[2] = {&g.Xs, nullptr};
+    const DevChunked<T>* M[2] = {&g.XsTc, nullptr};
+    const T* inv1[2] = {w.inv_kf.p, nullptr};
+    SS_TRY(launch_transfer<T>(1, L, inv1, M, w.inv_ks.p, r0, nb, ns, g.Tws.p, ns, members));
+  }
+  timing_count(ST_NTRANSFER, 1);
+  return SS_OK;
+}
+
 // k-fold: all folds of construct(y, X, members) + predict (+ clean!) from the resident graph
 template <class T>
 static int predict_kfold_impl(ss_graph* h, const int32_t* fold_of_source, int nfolds, int clean, T* out, int64_t ld,
@@ -1276,109 +1380,30 @@ static int predict_kfold_impl(ss_graph* h, const int32_t* fold_of_source, int nf
     std::vector<int> cur(start.begin(), start.end() - 1);
     for (int64_t i = 0; i < ns; ++i) order[cur[fold[i]]++] = (int)i;
   }
-  DevBuf<int> d_fold, d_order, kf, ks, kt;
-  DevBuf<T> inv_kf, inv_ks;
-  SS_TRY(d_fold.alloc(ns)); SS_TRY(d_order.alloc(ns));
-  SS_TRY(kf.alloc(g.nf)); SS_TRY(ks.alloc(ns)); SS_TRY(kt.alloc(nt));
-  SS_TRY(inv_kf.alloc(g.nf)); SS_TRY(inv_ks.alloc(ns));
-  SS_HIP(hipMemcpyAsync(d_fold.p, fold.data(), ns * sizeof(int), hipMemcpyHostToDevice, st));
-  SS_HIP(hipMemcpyAsync(d_order.p, order.data(), ns * sizeof(int), hipMemcpyHostToDevice, st));
+  KfoldWork<T> w;
+  SS_TRY(kfold_work_folds<T>(g, fold.data(), order.data(), w));
   SS_TRY(graph_sell(g));
-  if (!g.dense.on) SS_TRY(graph_chunked(g, false));
+  SS_TRY(graph_chunked(g, false));
 
-  timing_begin_call();
-  hipEvent_t e_begin, e_end;
-  SS_TRY(timing_mark(&e_begin));
-  const bool direct = (mem == SS_MEM_DEVICE && layout == SS_LAYOUT_ROWMAJOR);
-  DevBuf<T> scores;
-  T* dev_rm = out;
-  int64_t ld_rm = ld;
-  if (!direct) {
-    SS_TRY(scores.alloc((size_t)ns * nt));
-    dev_rm = scores.p;
-    ld_rm = nt;
-  }
-  DevBuf<T> sorted_tmp;
+  ScoreOut<T> so;
+  SS_TRY(so.begin(out, ld, layout, mem, ns, nt));
   for (int phi = 0; phi < nfolds; ++phi) {
     const int64_t nm = start[phi + 1] - start[phi];
     if (nm == 0) continue;
-    const int* members = d_order.p + start[phi];
-    SS_HIP(hipMemcpyAsync(kf.p, g.kf.p, g.nf * sizeof(int), hipMemcpyDeviceToDevice, st));
-    SS_HIP(hipMemcpyAsync(ks.p, g.ks.p, ns * sizeof(int), hipMemcpyDeviceToDevice, st));
-    SS_HIP(hipMemcpyAsync(kt.p, g.kt.p, nt * sizeof(int), hipMemcpyDeviceToDevice, st));
-    if (g.dense.on) {
-      SS_TRY(dense_fold_degrees<T>(g, members, nm, kf.p, ks.p, kt.p));
-    } else {
-      SS_TRY(launch_fold_degrees<T>(g.Xs, g.XsT, g.Ys, members, nm, kf.p, ks.p, kt.p));
-    }
-    SS_TRY(launch_fold_inverse<T>(kf.p, ks.p, d_fold.p, phi, g.nf, ns, inv_kf.p, inv_ks.p));
+    const int* members = w.d_order.p + start[phi];
+    SS_TRY(fold_degrees<T>(g, w, members, nm, phi));
     const int64_t rb = transfer_batch_rows(nm, ns, sizeof(T));
     const size_t need = (size_t)rb * (size_t)ns;
     if (g.Tws.n < need) SS_TRY(g.Tws.alloc(need));
     for (int64_t r0 = 0; r0 < nm; r0 += rb) {
       const int64_t nb = (nm - r0 < rb) ? (nm - r0) : rb;
-      {
-        StageTimer t1(ST_TRANSFER);
-        if (g.dense.on) {
-          // members' rows gathered into the query planes with this fold's 1/kf (0 on the members' own feature
-          // columns); the epilogue multiplies by this fold's 1/ks (0 for the members as sources)
-          if constexpr (std::is_same<T, float>::value)
-            SS_TRY(launch_transfer_dense_bf16(g.dense, false, inv_kf.p, inv_ks.p, nullptr, r0, nb, g.Tws.p, ns, false,
-                                              members));
-          else
-            SS_TRY(launch_transfer_dense_f64(g.dense, false, inv_kf.p, inv_ks.p, nullptr, r0, nb, g.Tws.p, ns, false,
-                                             members));
-        } else {
-          const DevCsr<T>* L[2] = {&g.Xs, nullptr};
-          const DevChunked<T>* M[2] = {&g.XsTc, nullptr};
-          const T* inv1[2] = {inv_kf.p, nullptr};
-          SS_TRY(launch_transfer<T>(1, L, inv1, M, inv_ks.p, r0, nb, ns, g.Tws.p, ns, members));
-        }
-        timing_count(ST_NTRANSFER, 1);
-      }
-      if (!g.W.sorted) {
-        StageTimer t2(ST_SPMM);
-        SS_TRY(launch_spmm_sell<T>(g.W, g.Tws.p, ns, nb, dev_rm, ld_rm, clean ? kt.p : nullptr, members + r0));
-        timing_count(ST_NSPMM, 1);
-      } else {
-        const size_t need_s = (size_t)rb * (size_t)g.W.vrows + (size_t)rb * (size_t)nt;
-        if (g.Sws.n < need_s) SS_TRY(g.Sws.alloc(need_s));
-        T* packed = g.Sws.p + (size_t)rb * (size_t)g.W.vrows;  // member-ordered rows before the scatter
-        {
-          StageTimer t2(ST_SPMM);
-          SS_TRY(launch_spmm_sell<T>(g.W, g.Tws.p, ns, nb, g.Sws.p, g.W.vrows, nullptr));
-          timing_count(ST_NSPMM, 1);
-        }
-        StageTimer t3(ST_EPILOGUE);
-        SS_TRY(launch_unpermute<T>(g.Sws.p, g.W.vrows, nb, nt, g.W.vfirst.p, g.W.inv.p, clean ? kt.p : nullptr, packed, nt));
-        for (int64_t q = 0; q < nb; ++q)  // few folds x rows: row copies to the members' source rows
-          SS_HIP(hipMemcpyAsync(dev_rm + (int64_t)order[start[phi] + r0 + q] * ld_rm, packed + q * nt, nt * sizeof(T),
-                                hipMemcpyDeviceToDevice, st));
-      }
+      SS_TRY(kfold_transfer<T>(g, w, members, r0, nb));
+      // a member's scores go to its source row: on a length-sorted operand by row copies addressed from order[]
+      SS_TRY(stage2_rows<T>(g, rb, nb, clean ? w.kt.p : nullptr,
+                            ScoreDest<T>{so.dev_rm, so.ld_rm, start[phi] + r0, w.d_order.p, order.data()}));
     }
   }
-  DevBuf<T> cm;
-  if (layout == SS_LAYOUT_COLMAJOR) {
-    StageTimer t3(ST_EPILOGUE);
-    T* dst = out;
-    int64_t dld = ld;
-    if (mem == SS_MEM_HOST) {
-      SS_TRY(cm.alloc((size_t)ns * nt));
-      dst = cm.p;
-      dld = ns;
-    }
-    SS_TRY(launch_transpose<T>(dev_rm, ns, nt, ld_rm, dst, dld));
-  }
-  SS_TRY(timing_mark(&e_end));
-  timing_span(ST_TOTAL, e_begin, e_end);
-  if (mem == SS_MEM_HOST) {
-    StageTimer t5(ST_D2H);
-    if (layout == SS_LAYOUT_ROWMAJOR)
-      SS_HIP(hipMemcpy2DAsync(out, ld * sizeof(T), dev_rm, ld_rm * sizeof(T), nt * sizeof(T), ns, hipMemcpyDeviceToHost, st));
-    else
-      SS_HIP(hipMemcpy2DAsync(out, ld * sizeof(T), cm.p, ns * sizeof(T), ns * sizeof(T), nt, hipMemcpyDeviceToHost, st));
-    t5.stop();
-  }
+  SS_TRY(so.deliver());
   SS_HIP(hipStreamSynchronize(st));
   return SS_OK;
 }
@@ -1442,30 +1467,16 @@ static void kfold_range(const KfoldPlan& p, int64_t i_begin, int64_t i_end, Kfol
   }
 }
 
-// device side of a k-fold call: the assignment, the selected members, their output rows and one fold's degrees
-template <class T>
-struct KfoldWork {
-  DevBuf<int> d_fold, d_order, d_sel, d_map, kf, ks, kt;
-  DevBuf<T> inv_kf, inv_ks;
-  int cur_seg = -1;  // segment whose degrees kf / ks / kt / inv_* hold
-};
-
 // map[p]: output row of the p-th selected member (its source row relative to i_begin)
 template <class T>
 static int kfold_work_init(const Graph<T>& g, const KfoldPlan& p, const KfoldRange& r, const std::vector<int>& map,
                            KfoldWork<T>& w) {
   hipStream_t st = ctx().stream;
-  const int64_t ns = g.ns;
-  SS_TRY(w.d_fold.alloc(ns)); SS_TRY(w.d_order.alloc(ns));
+  SS_TRY(kfold_work_folds<T>(g, p.fold.data(), p.order.data(), w));
   SS_TRY(w.d_sel.alloc(r.sel.size())); SS_TRY(w.d_map.alloc(map.size()));
-  SS_TRY(w.kf.alloc(g.nf)); SS_TRY(w.ks.alloc(ns)); SS_TRY(w.kt.alloc(g.nt));
-  SS_TRY(w.inv_kf.alloc(g.nf)); SS_TRY(w.inv_ks.alloc(ns));
-  SS_HIP(hipMemcpyAsync(w.d_fold.p, p.fold.data(), ns * sizeof(int), hipMemcpyHostToDevice, st));
-  SS_HIP(hipMemcpyAsync(w.d_order.p, p.order.data(), ns * sizeof(int), hipMemcpyHostToDevice, st));
   if (!r.sel.empty())
     SS_HIP(hipMemcpyAsync(w.d_sel.p, r.sel.data(), r.sel.size() * sizeof(int), hipMemcpyHostToDevice, st));
   if (!map.empty()) SS_HIP(hipMemcpyAsync(w.d_map.p, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  w.cur_seg = -1;
   return SS_OK;
 }
 
@@ -1476,21 +1487,14 @@ static int kfold_work_init(const Graph<T>& g, const KfoldPlan& p, const KfoldRan
 template <class T>
 static int kfold_rows_device(Graph<T>& g, KfoldWork<T>& w, const KfoldPlan& plan, const KfoldRange& rg, int64_t p0,
                              int64_t p1, int clean, T* dst, int64_t ld, const int* row_map) {
-  hipStream_t st = ctx().stream;
-  const int64_t ns = g.ns, nt = g.nt;
+  const int64_t ns = g.ns;
   for (size_t k = 0; k < rg.seg.size(); ++k) {
     const int64_t a = rg.pos[k] > p0 ? rg.pos[k] : p0, b = rg.pos[k + 1] < p1 ? rg.pos[k + 1] : p1;
     if (a >= b) continue;
     const int s = rg.seg[k];
     if (w.cur_seg != s) {
-      const int* all = w.d_order.p + plan.seg_start[s];
-      const int64_t nall = plan.seg_start[s + 1] - plan.seg_start[s];
-      SS_HIP(hipMemcpyAsync(w.kf.p, g.kf.p, g.nf * sizeof(int), hipMemcpyDeviceToDevice, st));
-      SS_HIP(hipMemcpyAsync(w.ks.p, g.ks.p, ns * sizeof(int), hipMemcpyDeviceToDevice, st));
-      SS_HIP(hipMemcpyAsync(w.kt.p, g.kt.p, nt * sizeof(int), hipMemcpyDeviceToDevice, st));
-      if (g.dense.on) SS_TRY(dense_fold_degrees<T>(g, all, nall, w.kf.p, w.ks.p, w.kt.p));
-      else SS_TRY(launch_fold_degrees<T>(g.Xs, g.XsT, g.Ys, all, nall, w.kf.p, w.ks.p, w.kt.p));
-      SS_TRY(launch_fold_inverse<T>(w.kf.p, w.ks.p, w.d_fold.p, plan.seg_fold[s], g.nf, ns, w.inv_kf.p, w.inv_ks.p));
+      SS_TRY(fold_degrees<T>(g, w, w.d_order.p + plan.seg_start[s], plan.seg_start[s + 1] - plan.seg_start[s],
+                             plan.seg_fold[s]));
       w.cur_seg = s;
     }
     const int* members = w.d_sel.p + a;
@@ -1500,47 +1504,9 @@ static int kfold_rows_device(Graph<T>& g, KfoldWork<T>& w, const KfoldPlan& plan
     if (g.Tws.n < need) SS_TRY(g.Tws.alloc(need));
     for (int64_t r0 = 0; r0 < nm; r0 += rb) {
       const int64_t nb = (nm - r0 < rb) ? (nm - r0) : rb;
-      const int64_t o = a - p0 + r0;  // block row of the batch's first member
-      {
-        StageTimer t1(ST_TRANSFER);
-        if (g.dense.on) {
-          if constexpr (std::is_same<T, float>::value)
-            SS_TRY(launch_transfer_dense_bf16(g.dense, false, w.inv_kf.p, w.inv_ks.p, nullptr, r0, nb, g.Tws.p, ns,
-                                              false, members));
-          else
-            SS_TRY(launch_transfer_dense_f64(g.dense, false, w.inv_kf.p, w.inv_ks.p, nullptr, r0, nb, g.Tws.p, ns,
-                                             false, members));
-        } else {
-          const DevCsr<T>* L[2] = {&g.Xs, nullptr};
-          const DevChunked<T>* M[2] = {&g.XsTc, nullptr};
-          const T* inv1[2] = {w.inv_kf.p, nullptr};
-          SS_TRY(launch_transfer<T>(1, L, inv1, M, w.inv_ks.p, r0, nb, ns, g.Tws.p, ns, members));
-        }
-        timing_count(ST_NTRANSFER, 1);
-      }
-      const int* kt_clean = clean ? w.kt.p : nullptr;
-      if (!g.W.sorted) {
-        StageTimer t2(ST_SPMM);
-        if (row_map) SS_TRY(launch_spmm_sell<T>(g.W, g.Tws.p, ns, nb, dst, ld, kt_clean, row_map + o));
-        else SS_TRY(launch_spmm_sell<T>(g.W, g.Tws.p, ns, nb, dst + o * ld, ld, kt_clean));
-        timing_count(ST_NSPMM, 1);
-      } else {
-        const size_t need_s = (size_t)rb * (size_t)g.W.vrows + (row_map ? (size_t)rb * (size_t)nt : 0);
-        if (g.Sws.n < need_s) SS_TRY(g.Sws.alloc(need_s));
-        {
-          StageTimer t2(ST_SPMM);
-          SS_TRY(launch_spmm_sell<T>(g.W, g.Tws.p, ns, nb, g.Sws.p, g.W.vrows, nullptr));
-          timing_count(ST_NSPMM, 1);
-        }
-        StageTimer t3(ST_EPILOGUE);
-        if (row_map) {
-          T* packed = g.Sws.p + (size_t)rb * (size_t)g.W.vrows;  // member-ordered rows before the scatter
-          SS_TRY(launch_unpermute<T>(g.Sws.p, g.W.vrows, nb, nt, g.W.vfirst.p, g.W.inv.p, kt_clean, packed, nt));
-          SS_TRY(launch_scatter_rows<T>(packed, nt, nb, nt, row_map + o, dst, ld));
-        } else {
-          SS_TRY(launch_unpermute<T>(g.Sws.p, g.W.vrows, nb, nt, g.W.vfirst.p, g.W.inv.p, kt_clean, dst + o * ld, ld));
-        }
-      }
+      SS_TRY(kfold_transfer<T>(g, w, members, r0, nb));
+      // a - p0 + r0: block row of the batch's first member
+      SS_TRY(stage2_rows<T>(g, rb, nb, clean ? w.kt.p : nullptr, ScoreDest<T>{dst, ld, a - p0 + r0, row_map, nullptr}));
     }
   }
   return SS_OK;
@@ -1586,7 +1552,7 @@ static int kfold_blocks(Graph<T>& g, const KfoldPlan& plan, int64_t i_begin, int
   SS_TRY(scores.alloc((size_t)rb * nt));
   SS_HIP(hipMemcpyAsync(d_pptr.p, pptr.data(), pptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
   SS_TRY(graph_sell(g));
-  if (!g.dense.on) SS_TRY(graph_chunked(g, false));
+  SS_TRY(graph_chunked(g, false));
   timing_begin_call();
   hipEvent_t e_begin, e_end;
   SS_TRY(timing_mark(&e_begin));
@@ -1624,7 +1590,6 @@ static int predict_kfold_rows_impl(ss_graph* h, const int32_t* fold_of_source, i
   if (!out) return fail(SS_EINVAL, "output buffer is NULL");
   const int64_t need_ld = (layout == SS_LAYOUT_ROWMAJOR) ? nt : nrows;
   if (ld < need_ld) return fail(SS_EINVAL, "leading dimension %lld < %lld", (long long)ld, (long long)need_ld);
-  hipStream_t st = ctx().stream;
   KfoldRange rg;
   kfold_range(plan, i_begin, i_end, rg);
   std::vector<int> map(rg.sel.size());
@@ -1632,47 +1597,14 @@ static int predict_kfold_rows_impl(ss_graph* h, const int32_t* fold_of_source, i
   KfoldWork<T> w;
   SS_TRY(kfold_work_init<T>(g, plan, rg, map, w));
   SS_TRY(graph_sell(g));
-  if (!g.dense.on) SS_TRY(graph_chunked(g, false));
+  SS_TRY(graph_chunked(g, false));
 
-  timing_begin_call();
-  hipEvent_t e_begin, e_end;
-  SS_TRY(timing_mark(&e_begin));
-  const bool direct = (mem == SS_MEM_DEVICE && layout == SS_LAYOUT_ROWMAJOR);
-  DevBuf<T> scores;
-  T* dev_rm = out;
-  int64_t ld_rm = ld;
-  if (!direct) {
-    SS_TRY(scores.alloc((size_t)nrows * nt));
-    dev_rm = scores.p;
-    ld_rm = nt;
-  }
-  SS_TRY(kfold_rows_device<T>(g, w, plan, rg, 0, nrows, clean, dev_rm, ld_rm, w.d_map.p));
-  DevBuf<T> cm;
-  if (layout == SS_LAYOUT_COLMAJOR) {
-    StageTimer t3(ST_EPILOGUE);
-    T* dst = out;
-    int64_t dld = ld;
-    if (mem == SS_MEM_HOST) {
-      SS_TRY(cm.alloc((size_t)nrows * nt));
-      dst = cm.p;
-      dld = nrows;
-    }
-    SS_TRY(launch_transpose<T>(dev_rm, nrows, nt, ld_rm, dst, dld));
-  }
-  SS_TRY(timing_mark(&e_end));
-  timing_span(ST_TOTAL, e_begin, e_end);
-  if (mem == SS_MEM_HOST) {
-    StageTimer t5(ST_D2H);
-    if (layout == SS_LAYOUT_ROWMAJOR)
-      SS_HIP(hipMemcpy2DAsync(out, ld * sizeof(T), dev_rm, ld_rm * sizeof(T), nt * sizeof(T), nrows,
-                              hipMemcpyDeviceToHost, st));
-    else
-      SS_HIP(hipMemcpy2DAsync(out, ld * sizeof(T), cm.p, nrows * sizeof(T), nrows * sizeof(T), nt,
-                              hipMemcpyDeviceToHost, st));
-    t5.stop();
-  }
+  ScoreOut<T> so;
+  SS_TRY(so.begin(out, ld, layout, mem, nrows, nt));
+  SS_TRY(kfold_rows_device<T>(g, w, plan, rg, 0, nrows, clean, so.dev_rm, so.ld_rm, w.d_map.p));
+  SS_TRY(so.deliver());
   // the member lists and degree buffers of the call are released on return
-  SS_HIP(hipStreamSynchronize(st));
+  SS_HIP(hipStreamSynchronize(ctx().stream));
   return SS_OK;
 }
 
@@ -2324,6 +2256,96 @@ static int spmat_create_impl(int64_t rows, int64_t cols, const int64_t* ptr, con
   return SS_OK;
 }
 
+// Which kernel serves a W*R of width B, and on which lazily built operand of the matrix handle.
+enum WrFamily { WR_CSELL, WR_COLGROUP, WR_NARROW, WR_SELL };
+struct WrRoute {
+  WrFamily family;
+  int slot;           // m.csell[slot], m.col[slot] or m.narrow[slot]; unused for WR_SELL
+  int cols;           // columns of R per tile row (the padded width the operand is cut for)
+  WrFamily fallback;  // WR_CSELL only: the family that serves B when the compact operand cannot hold the matrix
+};
+
+// the 2-D kernel (spmm_colgroup.hip): tile rows of 64 / 128 / 256 bytes in m.col[0..2]
+template <class T>
+static WrRoute colgroup_route(int64_t B) {
+  const int64_t bytes = B * (int64_t)sizeof(T);
+  const int rowb = bytes <= 64 ? 64 : (bytes <= 128 ? 128 : 256);
+  return {WR_COLGROUP, rowb == 64 ? 0 : (rowb == 128 ? 1 : 2), rowb / (int)sizeof(T), WR_COLGROUP};
+}
+// the narrow kernel: B <= 1, 2, 4 in m.narrow[0..2]
+template <class T>
+static WrRoute narrow_route(int64_t B) {
+  int slot = 0, bv = 1;
+  while (bv < B) { bv <<= 1; ++slot; }
+  return {WR_NARROW, slot, bv, WR_NARROW};
+}
+
+// Routing by width, row-major operands (measured at 100k x 100k / 1 %):
+//   B <= 4                          narrow kernel: W streamed once, the chunk of R in LDS, lanes of a row folded -- the
+//                                   HBM-bound regime (B = 1 0.13 ms = 4.6 TB/s of the 6 B/nnz operand).  B = 3, 4: the
+//                                   lane-per-row kernel (spmm_csell.hip) with four columns per tile row (16 bytes in fp32:
+//                                   0.136 vs 0.150 ms at B = 4; 32 bytes in fp64), m.csell[4].  fp64 B = 2: the same on
+//                                   16-byte tile rows, m.csell[5]: 0.199 vs 0.234 ms (measured also: fp64 B = 1 0.204 vs
+//                                   0.200, fp32 B = 1 / 2 0.138 / 0.139 vs 0.112 / 0.116 -- those stay narrow)
+//   5 <= B, B*sizeof(T) <= 256 B    the lane-per-row kernel on the compact sliced-ELL operand, m.csell[0..2] by tile row of
+//                                   64 / 128 / 256 bytes, fp32 B <= 8 on 32-byte tile rows (two pieces) in m.csell[3]
+//                                   instead of half-empty 64-byte ones (fp32 B = 8 / 16 / 32 / 64 0.19 / 0.18 / 0.35 /
+//                                   0.70 ms); SS_CSELL=0 or an operand that does not fit: the 2-D kernel
+//                                   (spmm_colgroup.hip); fp32 B = 5..16 0.22-0.24 ms, 32 0.44, 64 0.9
+//   wider, and pattern-only W (every value 1) above 128-byte tile rows: the SELL kernel of stage 2, which re-streams only
+//                                   the 2-byte indices (B = 64: 0.61 vs 0.82 ms); column-major operands always
+// SS_COL=0: no 2-D kernel (SELL instead); SS_COL_FROM: its first B, pattern-only wide cases included (comparisons, tests);
+// SS_CSELL_ROW32 / SS_CSELL_ROW16 / SS_CSELL_B12 = 0: without the 32-byte / four-column / fp64 B = 2 operands
+template <class T>
+static WrRoute wr_route(int64_t B, bool rowmajor, bool binary) {
+  const int64_t bytes = B * (int64_t)sizeof(T);
+  if (rowmajor && B >= env_int("SS_COL_FROM", 5) && bytes <= 256 && (!(binary && bytes > 128) || env_set("SS_COL_FROM")) &&
+      !env_off("SS_COL")) {
+    const WrRoute col = colgroup_route<T>(B);
+    if (env_off("SS_CSELL")) return col;
+    if (sizeof(T) == 4 && B <= 8 && !env_off("SS_CSELL_ROW32")) return {WR_CSELL, 3, 32 / (int)sizeof(T), WR_COLGROUP};
+    return {WR_CSELL, col.slot, col.cols, WR_COLGROUP};
+  }
+  if (rowmajor && B <= 4) {
+    if (sizeof(T) == 8 && B == 2 && !env_off("SS_CSELL_B12") && !env_off("SS_CSELL"))
+      return {WR_CSELL, 5, 16 / (int)sizeof(T), WR_NARROW};
+    if (B >= 3 && !env_off("SS_CSELL_ROW16") && !env_off("SS_CSELL")) return {WR_CSELL, 4, 4, WR_NARROW};
+    return narrow_route<T>(B);
+  }
+  return {WR_SELL, 0, 0, WR_SELL};
+}
+
+// SS_NARROW_CHUNK lowers the column chunk of a W*R operand (comparisons, tests)
+static int wr_chunk_cols(int kc) { return (int)env_int_in("SS_NARROW_CHUNK", 16, kc, kc); }
+
+// The lazily built operands of a route; *op is NULL when the slot cannot serve (csell only: take the fallback).
+// soft (the csell operands of B <= 4): a failed build is no error and is tried again by the next call, and the chunk
+// does not follow SS_NARROW_CHUNK; otherwise a failed build is the call's error.  A slot that built but cannot hold the
+// matrix (!ok) is remembered and never serves.
+template <class T>
+static int csell_operand(SpMat<T>& m, const WrRoute& r, bool soft, DevCsell<T>** op) {
+  DevCsell<T>& cs = m.csell[r.slot];
+  *op = nullptr;
+  if (!m.csell_tried[r.slot]) {
+    const int kc = csell_chunk_cols(r.cols * (int)sizeof(T));
+    const int rc = csell_build<T>(m.csr, soft ? kc : wr_chunk_cols(kc), r.cols, cs);
+    if (rc != SS_OK) return soft ? SS_OK : rc;
+    m.csell_tried[r.slot] = true;
+  }
+  if (cs.ok) *op = &cs;
+  return SS_OK;
+}
+template <class T>
+static int chunked_operand(SpMat<T>& m, const WrRoute& r, DevChunked<T>** op) {
+  DevChunked<T>& c = r.family == WR_COLGROUP ? m.col[r.slot] : m.narrow[r.slot];
+  if (c.SC == 0) {
+    const int kc = r.family == WR_COLGROUP ? colgroup_chunk_cols<T>(r.cols) : narrow_chunk_cols<T>(r.cols);
+    SS_TRY(chunked_build<T>(m.csr, wr_chunk_cols(kc), 4, c));
+  }
+  *op = &c;
+  return SS_OK;
+}
+
 template <class T>
 static int spmm_impl(ss_spmat* h, const T* R, int64_t B, int64_t ldr, int r_layout, T* F, int64_t ldf, int f_layout,
                      int mem) {
@@ -2364,116 +2386,39 @@ static int spmm_impl(ss_spmat* h, const T* R, int64_t B, int64_t ldr, int r_layo
   }
   hipEvent_t e_begin, e_end;
   SS_TRY(timing_mark(&e_begin));
-  // Routing by width, row-major operands (measured at 100k x 100k / 1 %):
-  //   B <= 4                          narrow kernel (fp32 B = 3, 4: spmm_csell.hip on 16-byte tile rows): W streamed once, the chunk of R in LDS, lanes of a row folded -- the
-  //                                   HBM-bound regime (B = 1 0.13 ms = 4.6 TB/s of the 6 B/nnz operand)
-  //   5 <= B, B*sizeof(T) <= 256 B    fp32: lane-per-row kernel on the compact sliced-ELL operand (spmm_csell.hip; B = 8 / 16 / 32 / 64
-  //                                   0.19 / 0.18 / 0.35 / 0.70 ms); fp64 (and SS_CSELL=0): 2-D kernel (spmm_colgroup.hip), tile rows
-  //                                   of 64 / 128 / 256 bytes; fp32 B = 5..16 0.22-0.24 ms, 32 0.44, 64 0.9
-  //   wider, and pattern-only W (every value 1) above 128-byte tile rows: the SELL kernel of stage 2, which re-streams only
-  //                                   the 2-byte indices (B = 64: 0.61 vs 0.82 ms); column-major operands always
-  // SS_COL=0: no 2-D kernel (SELL instead); SS_COL_FROM: its first B, pattern-only wide cases included (comparisons, tests)
   const bool rowmajor = r_layout == SS_LAYOUT_ROWMAJOR && f_layout == SS_LAYOUT_ROWMAJOR;
-  int col_from = 5;
-  if (const char* e = getenv("SS_COL_FROM")) col_from = atoi(e);
-  const bool col_wide_ok = !(m.csr.binary && B * (int64_t)sizeof(T) > 128) || getenv("SS_COL_FROM") != nullptr;
-  const bool col = rowmajor && B >= col_from && B * (int64_t)sizeof(T) <= 256 && col_wide_ok &&
-                   !(getenv("SS_COL") && atoi(getenv("SS_COL")) == 0);
-  const bool narrow = rowmajor && B <= 4;
+  WrRoute route = wr_route<T>(B, rowmajor, m.csr.binary);
+  DevCsell<T>* cs = nullptr;
+  if (route.family == WR_CSELL) {
+    SS_TRY(csell_operand<T>(m, route, route.fallback == WR_NARROW, &cs));
+    if (!cs) route = route.fallback == WR_NARROW ? narrow_route<T>(B) : colgroup_route<T>(B);
+  }
+  DevChunked<T>* op = nullptr;
+  if (route.family == WR_COLGROUP || route.family == WR_NARROW) SS_TRY(chunked_operand<T>(m, route, &op));
   DevBuf<T> Rt, Ft;
-  if (col) {
-    const int rowb = B * (int64_t)sizeof(T) <= 64 ? 64 : (B * (int64_t)sizeof(T) <= 128 ? 128 : 256);
-    const int slot = rowb == 64 ? 0 : (rowb == 128 ? 1 : 2);
-    const int bv = rowb / (int)sizeof(T);
-    // the lane-per-row kernel on the compact sliced-ELL operand (spmm_csell.hip, round 3); SS_CSELL=0: the 2-D kernel
-    bool done = false;
-    if (!(getenv("SS_CSELL") && atoi(getenv("SS_CSELL")) == 0)) {
-      // fp32 B <= 8: 32-byte tile rows (two pieces) instead of half-empty 64-byte ones
-      const bool half = sizeof(T) == 4 && B <= 8 && !(getenv("SS_CSELL_ROW32") && atoi(getenv("SS_CSELL_ROW32")) == 0);
-      const int crowb = half ? 32 : rowb, cslot = half ? 3 : slot, cbv = crowb / (int)sizeof(T);
-      DevCsell<T>& cs = m.csell[cslot];
-      if (!m.csell_tried[cslot]) {
-        int kc = csell_chunk_cols(crowb);
-        if (const char* e = getenv("SS_NARROW_CHUNK")) {
-          const int v = atoi(e);
-          if (v >= 16 && v < kc) kc = v;
-        }
-        SS_TRY(csell_build<T>(m.csr, kc, cbv, cs));
-        m.csell_tried[cslot] = true;
-      }
-      if (cs.ok) {
-        StageTimer t2(ST_SPMM);
-        SS_TRY(launch_spmm_csell<T>(cs, Rd, ldr_d, (int)B, Fd, ldf_d, m.partial));
-        timing_count(ST_NSPMM, 1);
-        done = true;
-      }
-    }
-    DevChunked<T>& op = m.col[slot];
-    if (!done && op.SC == 0) {
-      int kc = colgroup_chunk_cols<T>(bv);
-      if (const char* e = getenv("SS_NARROW_CHUNK")) {
-        const int v = atoi(e);
-        if (v >= 16 && v < kc) kc = v;
-      }
-      SS_TRY(chunked_build<T>(m.csr, kc, 4, op));
-    }
-    if (!done) {
-      StageTimer t2(ST_SPMM);
-      SS_TRY(launch_spmm_colgroup<T>(op, bv, Rd, ldr_d, (int)B, Fd, ldf_d, m.partial));
-      timing_count(ST_NSPMM, 1);
-    }
-  } else if (narrow && sizeof(T) == 8 && B == 2 && !(getenv("SS_CSELL_B12") && atoi(getenv("SS_CSELL_B12")) == 0) &&
-             !(getenv("SS_CSELL") && atoi(getenv("SS_CSELL")) == 0) &&
-             [&]() -> bool {   // fp64 B = 2 on 16-byte tile rows: 0.199 vs 0.234 ms for the narrow kernel (measured also: fp64
-                               // B = 1 0.204 vs 0.200, fp32 B = 1 / 2 0.138 / 0.139 vs 0.112 / 0.116 -- those stay narrow)
-               DevCsell<T>& cs = m.csell[5];
-               if (!m.csell_tried[5]) {
-                 if (csell_build<T>(m.csr, csell_chunk_cols(16), 16 / (int)sizeof(T), cs) != SS_OK) return false;
-                 m.csell_tried[5] = true;
-               }
-               return cs.ok;
-             }()) {
+  switch (route.family) {
+  case WR_CSELL: {
     StageTimer t2(ST_SPMM);
-    SS_TRY(launch_spmm_csell<T>(m.csell[5], Rd, ldr_d, (int)B, Fd, ldf_d, m.partial));
+    SS_TRY(launch_spmm_csell<T>(*cs, Rd, ldr_d, (int)B, Fd, ldf_d, m.partial));
     timing_count(ST_NSPMM, 1);
-  } else if (narrow && B >= 3 && !(getenv("SS_CSELL_ROW16") && atoi(getenv("SS_CSELL_ROW16")) == 0) &&
-             !(getenv("SS_CSELL") && atoi(getenv("SS_CSELL")) == 0) &&
-             [&]() -> bool {   // B = 3, 4: the lane-per-row kernel with four columns per tile row (16 bytes in fp32: 0.136
-                               // vs 0.150 ms at B = 4; 32 bytes in fp64)
-               DevCsell<T>& cs = m.csell[4];
-               if (!m.csell_tried[4]) {
-                 if (csell_build<T>(m.csr, csell_chunk_cols(4 * (int)sizeof(T)), 4, cs) != SS_OK) return false;
-                 m.csell_tried[4] = true;
-               }
-               return cs.ok;
-             }()) {
+    break;
+  }
+  case WR_COLGROUP: {
     StageTimer t2(ST_SPMM);
-    SS_TRY(launch_spmm_csell<T>(m.csell[4], Rd, ldr_d, (int)B, Fd, ldf_d, m.partial));
+    SS_TRY(launch_spmm_colgroup<T>(*op, route.cols, Rd, ldr_d, (int)B, Fd, ldf_d, m.partial));
     timing_count(ST_NSPMM, 1);
-  } else if (narrow) {
-    int slot = 0, bv = 1;
-    while (bv < B) { bv <<= 1; ++slot; }
-    DevChunked<T>& op = m.narrow[slot];
-    if (op.SC == 0) {
-      int kc = narrow_chunk_cols<T>(bv);
-      if (const char* e = getenv("SS_NARROW_CHUNK")) {
-        const int v = atoi(e);
-        if (v >= 16 && v < kc) kc = v;
-      }
-      SS_TRY(chunked_build<T>(m.csr, kc, 4, op));
-    }
+    break;
+  }
+  case WR_NARROW: {
     StageTimer t2(ST_SPMM);
-    SS_TRY(launch_spmm_chunked_narrow<T>(op, bv, Rd, ldr_d, (int)B, Fd, ldf_d, m.partial));
+    SS_TRY(launch_spmm_chunked_narrow<T>(*op, route.cols, Rd, ldr_d, (int)B, Fd, ldf_d, m.partial));
     timing_count(ST_NSPMM, 1);
-  } else {
+    break;
+  }
+  case WR_SELL: {
     const int qt = sell_tile_width<T>();
     if (m.sell_qt != qt) {
-      int kcmax = sell_max_chunk<T>(qt);
-      if (const char* e = getenv("SS_SELL_CHUNK")) {
-        const int v = atoi(e);
-        if (v >= 64 && v < kcmax) kcmax = v;
-      }
-      SS_TRY(sell_build<T>(m.csr, kcmax, m.sell));
+      SS_TRY(sell_build<T>(m.csr, sell_chunk<T>(qt), m.sell));
       m.sell_qt = qt;
     }
     const T* Rc = Rd;   // column-major view: R(k,b) at Rc[b*ldrc + k]
@@ -2492,25 +2437,14 @@ static int spmm_impl(ss_spmat* h, const T* R, int64_t B, int64_t ldr, int r_layo
       Fc = Ft.p;
       ldfc = M;
     }
-    DevBuf<T> Fs;  // skew-sorted operand: sorted-order result, put back through inv[]
-    if (!m.sell.sorted) {
-      StageTimer t2(ST_SPMM);
-      SS_TRY(launch_spmm_sell<T>(m.sell, Rc, ldrc, B, Fc, ldfc, nullptr));
-      timing_count(ST_NSPMM, 1);
-    } else {
-      SS_TRY(Fs.alloc((size_t)B * m.sell.vrows));
-      {
-        StageTimer t2(ST_SPMM);
-        SS_TRY(launch_spmm_sell<T>(m.sell, Rc, ldrc, B, Fs.p, m.sell.vrows, nullptr));
-        timing_count(ST_NSPMM, 1);
-      }
-      StageTimer t3(ST_EPILOGUE);
-      SS_TRY(launch_unpermute<T>(Fs.p, m.sell.vrows, B, M, m.sell.vfirst.p, m.sell.inv.p, nullptr, Fc, ldfc));
-    }
+    DevBuf<T> Fs;  // length-sorted operand: the sorted-order result
+    SS_TRY(sell_rows<T>(m.sell, Rc, ldrc, M, Fs, B, B, nullptr, ScoreDest<T>{Fc, ldfc, 0, nullptr, nullptr}));
     if (f_layout == SS_LAYOUT_ROWMAJOR) {
       StageTimer t3(ST_EPILOGUE);
       SS_TRY(launch_transpose<T>(Fc, B, M, ldfc, Fd, ldf_d));
     }
+    break;
+  }
   }
   SS_TRY(timing_mark(&e_end));
   timing_span(ST_TOTAL, e_begin, e_end);
@@ -2604,7 +2538,7 @@ int ss_init(int device) {
   c.num_cu = prop.multiProcessorCount;
   // binary_rows.hip's LDS-path row limit, lowered only (tests drive both paths over the same rows with it)
   c.binary_lds_cols = -1;
-  if (const char* e = getenv("SS_BINARY_LDS_COLS")) c.binary_lds_cols = atoi(e) < 0 ? 0 : atoi(e);
+  if (env_set("SS_BINARY_LDS_COLS")) c.binary_lds_cols = (int)std::max<int64_t>(0, env_int("SS_BINARY_LDS_COLS", 0));
   SS_HIP(hipStreamCreateWithFlags(&c.own_stream, hipStreamNonBlocking));
   c.stream = c.own_stream;
   c.device = device;

@@ -652,12 +652,12 @@ int sell_build(const DevCsr<T>& in, int KCmax, DevSell<T>& out, int qt) {
   out.vrows = in.rows;
   // padded storage well above nnz means skewed row lengths inside slices: split the longest rows into
   // virtual rows of bounded length and sort all (virtual) rows by length before cutting slices
-  const char* force = getenv("SS_SELL_SORT");
   // (the rounding of every slice to whole quads adds ~0.4 quads per slice and is not skew)
-  const bool want_sort = force ? atoi(force) != 0 : (((double)nq - 0.4 * (double)nws) * 256.0 > 1.3 * (double)in.nnz + 65536.0);
+  const bool skewed = ((double)nq - 0.4 * (double)nws) * 256.0 > 1.3 * (double)in.nnz + 65536.0;
+  const bool want_sort = env_set("SS_SELL_SORT") ? env_int("SS_SELL_SORT", 0) != 0 : skewed;
   if (want_sort && in.rows > 64) {
-    int64_t lmax = in.nnz / 4096;  // a slice of full-length virtual rows is ~1/4 of one wave's share of a workgroup
-    if (const char* e = getenv("SS_SELL_LMAX")) lmax = atoll(e);
+    // a slice of full-length virtual rows is ~1/4 of one wave's share of a workgroup
+    int64_t lmax = env_int("SS_SELL_LMAX", in.nnz / 4096);
     if (lmax < 256) lmax = 256;
     if (lmax > 65536) lmax = 65536;
     lmax &= ~3LL;
@@ -716,7 +716,7 @@ int sell_build(const DevCsr<T>& in, int KCmax, DevSell<T>& out, int qt) {
   } else {
     out.val.release();
   }
-  if (getenv("SS_SELL_PLAIN")) {
+  if (env_set("SS_SELL_PLAIN")) {
     hipLaunchKernelGGL(sell_fill_kernel<T>, dim3((unsigned)ceil_div(nws_f * 64, 256)), dim3(256), 0, st, in.ptr.p,
                        in.idx.p, in.val.p, out.vrows, out.KC, out.nslices, out.nchunks, out.off.p,
                        out.sorted ? (const int*)out.vs.p : (const int*)nullptr,
@@ -1150,7 +1150,7 @@ int chunked_build(const DevCsr<T>& in, int SC, int align, DevChunked<T>& out) {
   SS_HIP(hipMemsetAsync(out.idx.p + out.stored, 0, 256 * sizeof(unsigned short), st));
   SS_HIP(hipMemsetAsync(out.val.p + out.stored, 0, 256 * sizeof(T), st));
   // entry order inside a sub-row: bank-scheduled for the stage-1 operands (align 1 or 32) unless SS_CHUNK_SCHED=0
-  const int sched = ((align == 1 || align == 32) && !(getenv("SS_CHUNK_SCHED") && atoi(getenv("SS_CHUNK_SCHED")) == 0)) ? 1 : 0;
+  const int sched = ((align == 1 || align == 32) && !env_off("SS_CHUNK_SCHED")) ? 1 : 0;
   hipLaunchKernelGGL(chunk_fill_kernel<T>, dim3(grid_for(total * 64, 256)), dim3(256), 0, st, in.ptr.p, in.idx.p,
                      in.val.p, in.rows, SC, out.nchunks, align, sched, out.off.p, out.idx.p, out.val.p);
   SS_LAUNCH_CHECK();

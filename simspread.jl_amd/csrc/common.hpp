@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <atomic>
 #include <cstring>
 #include <string>
@@ -130,5 +131,22 @@ int upload(T* dst, const T* src, size_t count, int mem) {
 }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// ---------------------------------------------------------------- switches (SS_* environment variables)
+// Read where they are used and never cached: operands read them when they are built, and tests set them between
+// handles of one process.
+inline bool env_set(const char* k) { return getenv(k) != nullptr; }  // present, whatever its value
+inline bool env_off(const char* k) {                                 // set to 0, as in SS_CSELL=0
+  const char* e = getenv(k);
+  return e && atoi(e) == 0;
+}
+inline int64_t env_int(const char* k, int64_t dflt) {                // integer switch, dflt when unset
+  const char* e = getenv(k);
+  return e ? (int64_t)atoll(e) : dflt;
+}
+inline int64_t env_int_in(const char* k, int64_t lo, int64_t hi, int64_t dflt) {  // accepted inside [lo, hi) only
+  const int64_t v = env_int(k, lo - 1);
+  return v >= lo && v < hi ? v : dflt;
+}
 
 }  // namespace ss

@@ -255,8 +255,7 @@ int launch_transfer_dense(const DenseSim<float>& d, bool loo, const float* inv_k
   a.ldo = ldo;
   // 128 x 128 tiles (2 waves per SIMD).  SS_DENSE_TILE=256 selects the 256 x 128 variant: less L2 traffic per flop
   // but 128 accumulator + 200 other registers leave one wave per SIMD -- measured 87 vs 99 TFLOP/s at 50k
-  int tm = 128;
-  if (const char* e = getenv("SS_DENSE_TILE")) tm = atoi(e) == 256 ? 256 : 128;
+  const int tm = env_int("SS_DENSE_TILE", 128) == 256 ? 256 : 128;
   path_add(tm == 256 ? "transfer_dense_f32_mfma_256" : "transfer_dense_f32_mfma");
   a.gx = (int)ceil_div(d.ns, 128);
   a.gy = (int)ceil_div(nrows, tm);

@@ -439,8 +439,8 @@ int launch_transfer_dense_bf16(DenseSim<float>& d, bool loo, const float* inv_k,
   // enough 256 x 256 tiles to fill the chip: one workgroup per CU (measured at 50k, unweighted: 44.6 ms; the
   // 128 x 128 kernel with two workgroups per CU 65).  SS_DENSE_RING=0 / 1 forces the choice.
   const bool ring_ok = (Mp / RING_TM) * (Np / 256) >= ctx().num_cu;
-  const char* ring_env = getenv("SS_DENSE_RING");  // 0: never, 1: always, unset: by size
-  if (ring_env ? atoi(ring_env) != 0 : ring_ok) {
+  // 0: never, 1: always, unset: by size
+  if (env_set("SS_DENSE_RING") ? env_int("SS_DENSE_RING", 0) != 0 : ring_ok) {
     path_add("transfer_dense_bf16_ring");
     return loo ? launch_ring<true, 256, 64>(a, Mp, Np) : launch_ring<false, 256, 64>(a, Mp, Np);
   }

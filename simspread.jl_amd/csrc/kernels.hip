@@ -434,17 +434,13 @@ __global__ void __launch_bounds__(TRANSFER_THREADS) transfer_kernel(TransferArgs
 constexpr int TRANSFER_U = 8;
 
 // SS_TRANSFER_DUAL=0/1: one or two copies of the LDS accumulators (see subrows_fold)
-static bool transfer_dual() {
-  const char* e = getenv("SS_TRANSFER_DUAL");
-  return e ? atoi(e) != 0 : false;
-}
+static bool transfer_dual() { return env_int("SS_TRANSFER_DUAL", 0) != 0; }
 
 // sub-rows in flight per wave.  Default 8; 4 (55 instead of 90 registers: 30 instead of 20 single-wave workgroups per CU)
 // where it measured faster: weighted operands that stay in L2 (C2: 1.46 vs 1.51 ms; pattern-only operands 1.24 vs
 // 1.19 ms and the 600 MB operand of C3 5.1 vs 4.6 ms go the other way).  SS_TRANSFER_U overrides.
 static int transfer_u(bool small_weighted = false) {
-  const char* e = getenv("SS_TRANSFER_U");
-  const int u = e ? atoi(e) : (small_weighted ? 4 : TRANSFER_U);
+  const int u = (int)env_int("SS_TRANSFER_U", small_weighted ? 4 : TRANSFER_U);
   return (u == 4 || u == 16) ? u : 8;
 }
 
@@ -1059,10 +1055,7 @@ static int transfer_block_waves(int64_t mrows, int SC, int* offs_bytes) {
   int64_t nw = ((int64_t)ctx().lds_per_block - ob) / per_wave;
   if (ob >= (int64_t)ctx().lds_per_block) nw = 0;
   if (nw > 16) nw = 16;
-  if (const char* e = getenv("SS_TRANSFER_NW")) {
-    const int v = atoi(e);
-    if (v >= 1 && v < nw) nw = v;
-  }
+  nw = env_int_in("SS_TRANSFER_NW", 1, nw, nw);
   *offs_bytes = (int)ob;
   return nw >= 8 ? (int)nw : 0;
 }
@@ -1098,8 +1091,8 @@ int launch_transfer_block(const DevCsr<T>& L, const T* inv1, const DevChunked<T>
   if (fx) path_add("fixed_point");
   if constexpr (std::is_same<T, float>::value) {
     // the fixed-point kernels with 16 bytes per lane: they walk exact sub-row lengths (operand cut with align 32)
-    auto envi = [](const char* k) { const char* e = getenv(k); return e ? atoi(e) : 0; };
-    const int wide2 = envi("SS_TRANSFER_WIDE2"), wide = envi("SS_TRANSFER_WIDE"), qflat = envi("SS_TRANSFER_QFLAT");
+    const int wide2 = (int)env_int("SS_TRANSFER_WIDE2", 0), wide = (int)env_int("SS_TRANSFER_WIDE", 0),
+              qflat = (int)env_int("SS_TRANSFER_QFLAT", 0);
     if ((wide2 > 0 || wide > 0 || qflat > 0) && fixed && Mt.align == 32 && Mt.len_ok) {
       const int64_t lens_bytes = ((Mt.rows * 2 + 15) / 16) * 16;
       const int64_t accb = ((((int64_t)p.SC + 4) * 4 + 15) / 16) * 16;
@@ -1108,7 +1101,7 @@ int launch_transfer_block(const DevCsr<T>& L, const T* inv1, const DevChunked<T>
       const int64_t fixed_bytes = (int64_t)offs_bytes + lens_bytes + (wide > 0 && wide2 == 0 ? 64 : 0);
       int64_t nwf = ((int64_t)ctx().lds_per_block - fixed_bytes) / per_wave;
       if (nwf > 16) nwf = 16;
-      if (const int v = envi("SS_TRANSFER_NW"); v >= 1 && v < nwf) nwf = v;
+      nwf = env_int_in("SS_TRANSFER_NW", 1, nwf, nwf);
       if (nwf >= 8) {
         const int64_t fgrid = ceil_div(nrows, nwf) * p.nchunks;
         const size_t flds = (size_t)fixed_bytes + (size_t)nwf * (size_t)per_wave;
@@ -1181,10 +1174,9 @@ static int launch_transfer_variant(const TransferArgs<T>& p, unsigned grid, size
     else { if (dual) SS_TRANSFER_LAUNCH(U, false, true); else SS_TRANSFER_LAUNCH(U, false, false); }    \
   } while (0)
   if constexpr (std::is_same<T, float>::value && !LOO) {
-    const char* eb = getenv("SS_TRANSFER_LD");
-    if (eb && atoi(eb) == 1 && !dual) {
+    if (env_int("SS_TRANSFER_LD", 0) == 1 && !dual) {
       path_add("buffer_loads");
-      const bool fx = getenv("SS_TRANSFER_FIX1") && atoi(getenv("SS_TRANSFER_FIX1")) == 1 && p.nterms == 1 && !p.accumulate;
+      const bool fx = env_int("SS_TRANSFER_FIX1", 0) == 1 && p.nterms == 1 && !p.accumulate;
       if (fx) path_add("fixed_point");
 #define SS_TL(U, BINM, FX) hipLaunchKernelGGL((transfer_kernel<T, LOO, U, BINM, false, FX, true>), dim3(grid), dim3(TRANSFER_THREADS), lds, ctx().stream, p)
       if (transfer_u(p.small_weighted != 0 && !LOO) == 4) {
@@ -1198,8 +1190,7 @@ static int launch_transfer_variant(const TransferArgs<T>& p, unsigned grid, size
       SS_LAUNCH_CHECK();
       return SS_OK;
     }
-    const char* e = getenv("SS_TRANSFER_FIX1");
-    if (e && atoi(e) == 1 && p.nterms == 1 && !dual && !p.accumulate) {
+    if (env_int("SS_TRANSFER_FIX1", 0) == 1 && p.nterms == 1 && !dual && !p.accumulate) {
       path_add("fixed_point");
       if (transfer_u(p.small_weighted != 0 && !LOO) == 4) {
         if (binm) hipLaunchKernelGGL((transfer_kernel<T, LOO, 4, true, false, true>), dim3(grid), dim3(TRANSFER_THREADS), lds, ctx().stream, p);
@@ -1256,7 +1247,7 @@ int launch_transfer(int nterms, const DevCsr<T>* L[2], const T* inv1[2], const D
     }
     p.small_weighted = (weighted && bytes <= (32LL << 20)) ? 1 : 0;
   }
-  p.chunk_interleave = (getenv("SS_TRANSFER_ORDER") && atoi(getenv("SS_TRANSFER_ORDER")) == 0) ? 1 : 0;
+  p.chunk_interleave = env_off("SS_TRANSFER_ORDER") ? 1 : 0;
   const int64_t grid = nrows * p.nchunks;
   if (grid >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "transfer grid too large; lower SS_TRANSFER_BYTES");
   bool binm = true;
@@ -1284,7 +1275,7 @@ int launch_transfer_loo(const DevCsr<T>& X, const DevChunked<T>& XT, const int* 
   p.nchunks = XT.nchunks;
   p.out = out;
   p.ld = ld;
-  p.chunk_interleave = (getenv("SS_TRANSFER_ORDER") && atoi(getenv("SS_TRANSFER_ORDER")) == 0) ? 1 : 0;
+  p.chunk_interleave = env_off("SS_TRANSFER_ORDER") ? 1 : 0;
   const int64_t grid = nrows * p.nchunks;
   if (grid >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "transfer grid too large; lower SS_TRANSFER_BYTES");
   const bool dual = transfer_dual();
@@ -1521,10 +1512,8 @@ __global__ void __launch_bounds__(SELL_THREADS) spmm_sell_kernel(SellArgs<T> a) 
 
 // fp32: 8 columns per tile row since round 3 (SS_SELL_QT=4: the 16-byte rows of rounds 1-2)
 template <> int sell_tile_width<float>() {
-  if (const char* e = getenv("SS_SELL_QT")) {
-    const int v = atoi(e);
-    if (v == 4 || v == 8) return v;
-  }
+  const int v = (int)env_int("SS_SELL_QT", 0);
+  if (v == 4 || v == 8) return v;
   return SELL_QT_F32_DEFAULT;
 }
 template <> int sell_tile_width<double>() { return 2; }
@@ -2285,7 +2274,7 @@ __global__ void __launch_bounds__(TOPL2_THREADS) topl_bound_kernel(const float* 
 int launch_topl(const float* scores, int64_t nrows, int64_t ncols, int64_t ld, int L, int* oidx, float* oval) {
   if (nrows <= 0) return SS_OK;
   if (L < 1 || L > TOPL_MAX || L > ncols) return fail(SS_EINVAL, "top-L needs 1 <= L <= min(%d, ncols)", TOPL_MAX);
-  const bool fast = !(getenv("SS_TOPL_BOUND") && atoi(getenv("SS_TOPL_BOUND")) == 0);
+  const bool fast = !env_off("SS_TOPL_BOUND");
   for (int64_t r0 = 0; r0 < nrows; r0 += (1 << 30)) {
     const int64_t nb = nrows - r0 < (1 << 30) ? nrows - r0 : (1 << 30);
     if (fast) {

@@ -391,10 +391,7 @@ int launch_spmm_colgroup(const DevChunked<T>& W, int bv, const T* R, int64_t ldr
   if (cgn < 1) cgn = 1;
   if (cgn > W.nchunks) cgn = W.nchunks;
   if (cgn > 16) cgn = 16;
-  if (const char* e = getenv("SS_COL_CG")) {
-    const int v = atoi(e);
-    if (v >= 1 && v <= W.nchunks) cgn = v;
-  }
+  cgn = (int)env_int_in("SS_COL_CG", 1, (int64_t)W.nchunks + 1, cgn);
   a.CG = cgn;
   a.P = nullptr;
   // scratch: the CG partial sums, then (rows of R not movable in 16-byte pieces) the padded copy of R
@@ -413,7 +410,7 @@ int launch_spmm_colgroup(const DevChunked<T>& W, int bv, const T* R, int64_t ldr
     a.R = rp; a.ldr = bv; a.BR = bv;
   }
   const unsigned grid = (unsigned)(a.RBn * a.CG);
-  if (getenv("SS_COL_DEBUG"))
+  if (env_set("SS_COL_DEBUG"))
     fprintf(stderr, "colgroup: rowb %d KC %d chunks %d RB %d CG %d np %d rows/wg %d grid %u\n", rowb, a.KC, a.nchunks, a.RBn,
             a.CG, a.np_used, a.rows_per_wg, grid);
   const size_t lds = (size_t)(W.SC + 1) * rowb + 2 * (((size_t)(a.rows_per_wg + 1) * 4 + 15) / 16 * 16);

@@ -334,7 +334,7 @@ int launch_spmm_csell(const DevCsell<T>& W, const T* R, int64_t ldr, int B, T* F
   }
   const int64_t grid = (int64_t)a.RBn * a.CG;
   if (grid >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "spmm_csell: grid too large");
-  if (getenv("SS_COL_DEBUG"))
+  if (env_set("SS_COL_DEBUG"))
     fprintf(stderr, "csell: rowb %d QT %d KC %d chunks %d slices %d spw %d RB %d CG %d grid %lld\n", rowb, QT, a.KC, a.nchunks,
             a.S, a.spw, a.RBn, a.CG, (long long)grid);
   const size_t lds = (size_t)(W.KC + 1) * rowb;

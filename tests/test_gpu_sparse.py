@@ -57,6 +57,10 @@ STAGE2 = {
     "SELL chunk 128": ({"SS_SELL_CHUNK": "128"}, "random", "spmm_sell"),
     "QT=8": ({"SS_SELL_QT": "8"}, "random", "spmm_sell"),
     "sorted": ({"SS_SELL_SORT": "1", "SS_SELL_LMAX": "256"}, "hub", "spmm_sell_sorted"),
+    # the length-sorted operand over several batches of T: the scratch rows, the packed rows and the row maps of the
+    # stage-2 step together (the batches are counted in _assert_batches; 2^20 is the library's floor)
+    "sorted, transfer batches": ({"SS_SELL_SORT": "1", "SS_SELL_LMAX": "256", "SS_TRANSFER_BYTES": str(1 << 20)}, "hub",
+                                 "spmm_sell_sorted"),
 }
 DTYPES = [np.float32, np.float64]
 
@@ -108,6 +112,14 @@ def _tags(stage1, stage2="spmm_sell", loo=False):
     assert path & STAGE1_TAGS == want, (want, path)
     assert stage2 is None or path & {"spmm_sell", "spmm_sell_sorted"} == {stage2}, (stage2, path)
     assert not (FIXED_POINT_TAGS & path), path
+
+
+def _batches(env, nrows, ns, dtype):
+    """Transfer batches nrows rows take: rb = max(8, (bytes / (ns * itemsize)) & ~7) rows each, one without the switch."""
+    if "SS_TRANSFER_BYTES" not in env:
+        return 1
+    rb = S.transfer_batch_rows(nrows, ns, np.dtype(dtype).itemsize, int(env["SS_TRANSFER_BYTES"]))
+    return -(-nrows // rb)
 
 
 def _graph(Xq, Xs, Ys, dtype):
@@ -239,7 +251,9 @@ def _loo_case(weighted):
 @pytest.mark.parametrize("weighted", WEIGHTED, ids=W_IDS)
 @pytest.mark.parametrize("dtype,kind,name", _params([s for s in FOLD_SWITCHES if s[0] == "stage2" or STAGE1[s[1]][3]]))
 def test_leave_one_out_exact_under_every_switch(dtype, kind, name, weighted, switches):
-    """predict_loo on blocks of 2^j + 1 sources: whole, with clean!, a sub-range and a column-major one."""
+    """predict_loo on blocks of 2^j + 1 sources: whole, with clean!, a sub-range and a column-major one.  Under
+    SS_TRANSFER_BYTES = 2^20 the 488 rows take two batches of 264 in fp64 and one of 488 in fp32 (536 would fit); the
+    band graph's 608 rows take at least two in both precisions, asserted there."""
     env, tags, stage2 = _fold_env(kind, name, "loo")
     switches(env)
     inp, want = _loo_case(weighted)
@@ -269,7 +283,11 @@ def _kfold_case(weighted):
 @pytest.mark.parametrize("weighted", WEIGHTED, ids=W_IDS)
 @pytest.mark.parametrize("dtype,kind,name", _params([s for s in FOLD_SWITCHES if s[1] != "block kernel"]))
 def test_kfold_exact_under_every_switch(dtype, kind, name, weighted, switches):
-    """predict_kfold and predict_kfold_rows (a sub-range, one column-major) on blocks of 36 = 9 folds x 4."""
+    """predict_kfold and predict_kfold_rows (a sub-range, one column-major) on blocks of 36 = 9 folds x 4.  A fold has
+    28 members and SS_TRANSFER_BYTES cannot go below 2^20, which holds 520 (fp64) or 1040 (fp32) rows of 252 sources:
+    no fold of these inputs, nor of the band graph's five (122 members, 208 or 424 rows), takes a second batch.  Several
+    batches are asserted for the leave-one-out sweep and the source rows of the band graph, and
+    test_kfold_of_one_large_fold_in_several_sorted_batches gives the band graph a fold that needs them."""
     env, tags, stage2 = _fold_env(kind, name, "kfold")
     switches(env)
     inp, want = _kfold_case(weighted)
@@ -412,6 +430,8 @@ def test_every_score_within_its_band_under_every_switch(dtype, kind, name, weigh
                  parts=S.parts_of_targets(Y, 256) if stage2 == "spmm_sell_sorted" else 0)
     loo_ok = kind == "stage2" or STAGE1[name][3]
     query_only = kind == "stage1" and name == "block kernel"
+    if "SS_TRANSFER_BYTES" in env:      # the source rows and the leave-one-out sweep really take several batches
+        assert _batches(env, ns, ns, dtype) >= 2
 
     def check(got, mode, rows=slice(None)):
         want, (chain, addends) = ref[mode]
@@ -443,3 +463,41 @@ def test_every_score_within_its_band_under_every_switch(dtype, kind, name, weigh
         check(g.predict_kfold_rows(fold, inp["nfolds"], 13, 99), "kfold", slice(13, 99))
         g.close()
     print(f"[sparse] worst so far: {WORST}")
+
+
+@functools.lru_cache(maxsize=None)
+def _large_fold_case(weighted):
+    inp, _ = _band_case(weighted)
+    X, Y = inp["X"], inp["Y"]
+    fold = (np.arange(X.shape[0]) % 8 == 0).astype(np.int32)       # fold 0: 532 of the 608 sources, fold 1: 76
+    want, counts = S.oracle_kfold(X, Y, fold), S.counts_kfold(X, Y, fold)
+    want.setflags(write=False)
+    return X, Y, fold, want, counts
+
+
+@pytest.mark.parametrize("weighted", WEIGHTED, ids=W_IDS)
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
+def test_kfold_of_one_large_fold_in_several_sorted_batches(dtype, weighted, switches):
+    """Where the length-sorted operand, several batches of one fold and a row map meet: a fold of 532 members under
+    SS_TRANSFER_BYTES = 2^20 (batches of 424 rows in fp32, 208 in fp64).  predict_kfold (row copies from the host's
+    order) and predict_kfold_rows (device row map; all rows and a sub-range) stay within the oracle's bands, and equal
+    bit for bit what a handle without the switch gives in one batch per fold: a row's sums do not depend on its batch."""
+    X, Y, fold, want, (chain, addends) = _large_fold_case(weighted)
+    ns = X.shape[0]
+    env = dict(STAGE2["sorted, transfer batches"][0])
+    assert _batches(env, int((fold == 0).sum()), ns, dtype) >= 2
+    got = {}
+    for batched in (False, True):
+        switches(env if batched else STAGE2["sorted"][0])
+        g = _graph(None, X, Y, dtype)
+        got[batched] = (g.predict_kfold(fold, 2), g.predict_kfold_rows(fold, 2), g.predict_kfold_rows(fold, 2, 13, 599),
+                        g.predict_kfold(fold, 2, clean=True))
+        _tags(("transfer",), "spmm_sell_sorted")
+        g.close()
+    band = S.band_graph_scores(want, chain, addends, dtype, sell_chunks=1, parts=S.parts_of_targets(Y, 256))
+    S.assert_band(got[True][0], want, band, f"k-fold, one large fold, {np.dtype(dtype).name}")
+    for one, several, what in zip(got[False], got[True], ("k-fold", "k-fold rows", "k-fold rows [13,599)", "clean")):
+        np.testing.assert_array_equal(several, one, err_msg=what)
+    np.testing.assert_array_equal(got[True][1], got[True][0])
+    np.testing.assert_array_equal(got[True][2], got[True][0][13:599])
+    assert (got[True][3] == -99).any()       # (without 532 sources some targets have none left)
