@@ -131,6 +131,13 @@ int upload(T* dst, const T* src, size_t count, int mem) {
 }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// blocks of a grid-stride launch over `work` items
+inline int grid_1d(int64_t work, int block, int cap = 256 * 16) {
+  int64_t g = ceil_div(work, block);
+  if (g < 1) g = 1;
+  if (g > cap) g = cap;
+  return (int)g;
+}
 
 // ---------------------------------------------------------------- switches (SS_* environment variables)
 // Read where they are used and never cached: operands read them when they are built, and tests set them between

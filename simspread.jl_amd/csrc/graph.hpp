@@ -161,7 +161,7 @@ int graph_finalize_general(Graph<T>& g);  // degrees = row counts of B (held in 
 template <class T>
 int graph_finalize_general_targets(Graph<T>& g);  // kt / inv_kt from YsT only
 
-// ---- kernels.hip (launch wrappers; everything is enqueued on ctx().stream)
+// ---- kernels.hip, transfer.hip (launch wrappers; everything is enqueued on ctx().stream)
 template <class T>
 struct CsrView {
   const int* ptr;

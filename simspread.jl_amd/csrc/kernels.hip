@@ -1,8 +1,5 @@
-// Hand-written gfx950 kernels of the SimSpread resource-spreading pass.
+// Hand-written gfx950 kernels of the SimSpread resource-spreading pass (stage 1, the transfer rows, is transfer.hip).
 //
-//   transfer_kernel      stage 1: one row of the transfer block T = (L D1^-1) Mt D2^-1 per
-//                        workgroup, accumulated in LDS (the sparse x sparse -> dense product
-//                        hidden in the reference's W*W, src/core.jl:413)
 //   spmm_sell_kernel     stage 2, wide: F = W*R with an LDS-resident tile of QT columns of R,
 //                        one lane per row of W, chunk-local 16-bit indices (the A*W^2 row
 //                        gather of src/core.jl:413,421 restricted to the Nq x Nt corner)
@@ -13,18 +10,9 @@
 //
 // Wavefront = 64 lanes everywhere.  No float atomics anywhere: every sum has a fixed order, so
 // results are bitwise reproducible from run to run.
-#include <type_traits>
-
 #include "graph.hpp"
 
 namespace ss {
-
-static inline int grid_1d(int64_t work, int block, int cap = 256 * 16) {
-  int64_t g = ceil_div(work, block);
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return (int)g;
-}
 
 // ============================================================== element-wise
 template <class T>
@@ -87,1201 +75,6 @@ int launch_spread_dense(const T* G, int64_t rows, int64_t cols, int64_t ld, cons
   hipLaunchKernelGGL(spread_dense_kernel<T>, dim3(grid_1d(rows * cols, 256)), dim3(256), 0, ctx().stream, G,
                      rows, cols, ld, deg, W, ldw);
   SS_LAUNCH_CHECK();
-  return SS_OK;
-}
-
-// ============================================================== stage 1: transfer rows
-template <class T>
-struct ChunkedView {
-  const int* off;            // [nchunks*rows + 1]
-  const unsigned short* idx; // chunk-local column
-  const T* val;
-  int64_t rows;
-};
-template <class T>
-static inline ChunkedView<T> view(const DevChunked<T>& m) {
-  return ChunkedView<T>{m.off.p, m.idx.p, m.val.p, m.rows};
-}
-
-template <class T>
-struct TransferArgs {
-  int nterms;
-  CsrView<T> L[2];
-  const T* inv1[2];
-  ChunkedView<T> M[2];
-  const T* inv2;
-  const int* kf;  // LOO: integer degrees
-  const int* ks;
-  int64_t row_begin;
-  const int* row_ids;  // optional: row of L handled by workgroup-row r is row_ids[row_begin + r] (k-fold members)
-  int64_t nj;
-  int SC;       // columns of T per workgroup (= chunk of the Mt operands)
-  int nchunks;
-  T* out;
-  int64_t ld;
-  int accumulate;  // add to what `out` already holds (dense regime: the feature path came from the GEMM)
-  float xmax;      // FIX: largest |value| of the Mt operand
-  int small_weighted;  // host only: weighted operand of at most 32 MiB (picks the default batch size)
-  int chunk_interleave;  // SS_TRANSFER_ORDER=0: rows take all their chunks in turn (the order of rounds 1-2)
-};
-template <class T>
-__device__ __forceinline__ bool getenv_chunk_interleave(const TransferArgs<T>& p) { return p.chunk_interleave != 0; }
-
-// One single-wave workgroup per (row r of L, column chunk c of T); c = blockIdx % nchunks so that,
-// with the dispatcher dealing workgroups round-robin over the 8 XCDs, chunk c is always served by
-// the same XCD and the sub-rows of Mt it touches stay in that XCD's L2 (speed only -- any placement
-// is correct).  acc[j] (LDS, owned by this one wave) collects sum_a L[r,a]*inv1[a]*Mt[a][c*SC + j].
-// The wave takes U neighbours a of r at a time, issues all their global loads, then folds the
-// sub-rows in one after the other with plain LDS read-add-write: the columns inside one sub-row are
-// distinct and LDS operations of one wave execute in order, so no atomics are needed and the sum
-// order is fixed (bitwise reproducible).  Measured on MI355X: ds_add_f32 costs ~193 clk per
-// wave-instruction (lanes serialised), ds_add_f64 ~27, a plain read-add-write pair ~17
-// (tools/lds_atomic_bench.hip) -- which is why this is not an LDS-atomic kernel.
-constexpr int TRANSFER_THREADS = 64;
-
-template <class T> struct BitsOf;
-template <> struct BitsOf<float> {
-  static __device__ __forceinline__ float bcast(float v, int src) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
-  }
-};
-template <> struct BitsOf<double> {
-  static __device__ __forceinline__ double bcast(double v, int src) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), src);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-  }
-};
-
-// U sub-rows: scalar bounds + coefficient, and the (unconditional) loads of their first 64 entries.
-// The operand arrays carry 64 entries of slack, so lanes past the end of a sub-row read valid memory;
-// such lanes are steered to a per-lane dummy accumulator behind the chunk.
-template <class T, int U>
-struct SubRows {
-  int n[U];
-  unsigned b[U];
-  T cf[U];
-  unsigned short j[U];
-  T v[U];
-  unsigned short j2[U];  // entries 64..127 of the sub-row, fetched only when it is that long (wave-uniform)
-  T v2[U];
-};
-
-// The same loads as buffer instructions: resource descriptor (SGPRs) + scalar byte offset of the sub-row + a 32-bit lane
-// offset.  A global_load with per-lane 64-bit addresses hands the texture addresser 512 bytes of address per
-// wave-instruction, the buffer form 256; stage 1 is bound by that unit (TA busy 92 % of the kernel at ~7 clk per load,
-// profiles/r03_stage1_mem_pmc.txt).
-template <int U, bool BINM>
-__device__ __forceinline__ void subrows_load_buf(SubRows<float, U>& s, int first, int b_l, int n_l, float cf_l,
-                                                 __amdgpu_buffer_rsrc_t ridx, __amdgpu_buffer_rsrc_t rval, int lane) {
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const int src = first + u;
-    s.b[u] = (unsigned)__builtin_amdgcn_readlane(b_l, src);
-    s.n[u] = __builtin_amdgcn_readlane(n_l, src);
-    s.cf[u] = BitsOf<float>::bcast(cf_l, src);
-    s.j[u] = __builtin_amdgcn_raw_buffer_load_b16(ridx, lane * 2, (int)(s.b[u] * 2u), 0);
-    s.v[u] = BINM ? 1.f : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rval, lane * 4, (int)(s.b[u] * 4u), 0));
-    if (s.n[u] > 64) {
-      s.j2[u] = __builtin_amdgcn_raw_buffer_load_b16(ridx, lane * 2, (int)(s.b[u] * 2u + 128u), 0);
-      s.v2[u] = BINM ? 1.f : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rval, lane * 4, (int)(s.b[u] * 4u + 256u), 0));
-    }
-  }
-}
-
-template <class T, int U, bool BINM>
-__device__ __forceinline__ void subrows_load(SubRows<T, U>& s, int first, int b_l, int n_l, T cf_l,
-                                             const unsigned short* __restrict__ midx, const T* __restrict__ mval,
-                                             int lane) {
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const int src = first + u;  // < 64 by construction
-    s.b[u] = (unsigned)__builtin_amdgcn_readlane(b_l, src);
-    s.n[u] = __builtin_amdgcn_readlane(n_l, src);
-    s.cf[u] = BitsOf<T>::bcast(cf_l, src);
-    const unsigned short* pi = midx + s.b[u];
-    const T* pv = mval + s.b[u];
-    s.j[u] = pi[lane];
-    s.v[u] = BINM ? T(1) : pv[lane];  // unweighted features: every stored value is 1, two thirds of the bytes vanish
-    // With the chunk sized for a mean sub-row of ~60 entries, ~40 % of the sub-rows are longer than one
-    // wave: their second half must be prefetched like the first (a dependent load inside the fold
-    // stalls the whole batch), so it is issued here under a wave-uniform branch.
-    if (s.n[u] > 64) {
-      s.j2[u] = pi[64 + lane];
-      s.v2[u] = BINM ? T(1) : pv[64 + lane];
-    }
-  }
-}
-
-// DUAL: two copies of the accumulators (acc and acc + astride); sub-rows 2i and 2i+1 of a batch go to different
-// copies, so their read-add-write pairs are independent and both LDS reads are in flight together (with one copy
-// every pair waits for the previous pair's LDS round trip).  The copies are added when T is written out: the sum
-// order is still fixed.
-template <class T, int U, bool DUAL>
-__device__ __forceinline__ void subrows_fold(const SubRows<T, U>& s, int first, int b_l, int n_l, T cf_l,
-                                             T* __restrict__ acc, int astride, int dummy,
-                                             const unsigned short* __restrict__ midx, const T* __restrict__ mval,
-                                             int lane) {
-  int nmax = 0;
-  if constexpr (DUAL) {
-    T* __restrict__ acc1 = acc + astride;
-#pragma unroll
-    for (int u = 0; u < U; u += 2) {
-      const int ja = lane < s.n[u] ? (int)s.j[u] : dummy;
-      const int jb = lane < s.n[u + 1] ? (int)s.j[u + 1] : dummy;
-      const T ra = acc[ja], rb = acc1[jb];
-      acc[ja] = fma(s.cf[u], s.v[u], ra);
-      acc1[jb] = fma(s.cf[u + 1], s.v[u + 1], rb);
-      if (s.n[u] > 64 || s.n[u + 1] > 64) {
-        const int ka = (s.n[u] > 64 && 64 + lane < s.n[u]) ? (int)s.j2[u] : dummy;
-        const int kb = (s.n[u + 1] > 64 && 64 + lane < s.n[u + 1]) ? (int)s.j2[u + 1] : dummy;
-        const T va = s.n[u] > 64 ? s.v2[u] : T(0), vb = s.n[u + 1] > 64 ? s.v2[u + 1] : T(0);
-        const T qa = acc[ka], qb = acc1[kb];
-        acc[ka] = fma(s.cf[u], va, qa);
-        acc1[kb] = fma(s.cf[u + 1], vb, qb);
-      }
-      nmax = s.n[u] > nmax ? s.n[u] : nmax;
-      nmax = s.n[u + 1] > nmax ? s.n[u + 1] : nmax;
-    }
-  } else {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int j = lane < s.n[u] ? (int)s.j[u] : dummy;
-      acc[j] = fma(s.cf[u], s.v[u], acc[j]);
-      if (s.n[u] > 64) {
-        const int k = 64 + lane < s.n[u] ? (int)s.j2[u] : dummy;
-        acc[k] = fma(s.cf[u], s.v2[u], acc[k]);
-      }
-      nmax = s.n[u] > nmax ? s.n[u] : nmax;
-    }
-  }
-  if (nmax > 128) {  // rare: a sub-row longer than two waves (bounds re-read by lane index, no register arrays)
-#pragma unroll 1
-    for (int u = 0; u < U; ++u) {
-      const int n = __builtin_amdgcn_readlane(n_l, first + u);
-      const unsigned b = (unsigned)__builtin_amdgcn_readlane(b_l, first + u);
-      const T cf = BitsOf<T>::bcast(cf_l, first + u);
-      for (int x = 128 + lane; x < n; x += 64) {
-        const int j = midx[b + x];
-        acc[j] = fma(cf, mval[b + x], acc[j]);
-      }
-    }
-  }
-}
-
-// Fixed-point fold (fp32 graphs): the product cf * v is scaled by 2^k (k per row of L, see transfer_block_kernel),
-// rounded to an integer and added with ds_add_u32.  An LDS integer atomic costs ~8 clk per wave-instruction on random
-// addresses where the plain read-add-write pair costs ~15 (tools/lds_atomic_bench.hip) -- and stage 1 runs at exactly
-// the LDS rate of its scatter -- it returns nothing (no wait, no dependent chain through the LDS round trip) and integer
-// addition commutes: the sums do not depend on any order, so the result is bitwise reproducible by construction.
-// Lanes past the end of a sub-row add 0 to whatever valid column they happened to read.
-__device__ __forceinline__ int cvt_rpi(float x) {
-  int r;
-  asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(x));   // floor(x + 0.5)
-  return r;
-}
-template <int U>
-__device__ __forceinline__ void subrows_fold_fixed(const SubRows<float, U>& s, int first, int b_l, int n_l, float cf_l,
-                                                   unsigned* __restrict__ acc, const unsigned short* __restrict__ midx,
-                                                   const float* __restrict__ mval, int lane) {
-  int nmax = 0;
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const float v = lane < s.n[u] ? s.v[u] : 0.f;
-    atomicAdd(&acc[s.j[u]], (unsigned)cvt_rpi(s.cf[u] * v));
-    if (s.n[u] > 64) {
-      const float v2 = 64 + lane < s.n[u] ? s.v2[u] : 0.f;
-      atomicAdd(&acc[s.j2[u]], (unsigned)cvt_rpi(s.cf[u] * v2));
-    }
-    nmax = s.n[u] > nmax ? s.n[u] : nmax;
-  }
-  if (nmax > 128) {
-#pragma unroll 1
-    for (int u = 0; u < U; ++u) {
-      const int n = __builtin_amdgcn_readlane(n_l, first + u);
-      const unsigned b = (unsigned)__builtin_amdgcn_readlane(b_l, first + u);
-      const float cf = BitsOf<float>::bcast(cf_l, first + u);
-      for (int x = 128 + lane; x < n; x += 64) atomicAdd(&acc[midx[b + x]], (unsigned)cvt_rpi(cf * mval[b + x]));
-    }
-  }
-}
-
-template <class T, bool LOO, int U, bool BINM, bool DUAL, bool FIX = false, bool BUF = false>
-__global__ void __launch_bounds__(TRANSFER_THREADS) transfer_kernel(TransferArgs<T> p) {
-  static_assert(64 % (2 * U) == 0, "U must divide 32");
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  T* acc = reinterpret_cast<T*>(smem_raw);                        // [SC] sums + [64] per-lane dummies (x2 when DUAL)
-  const int astride = p.SC + 64;
-  constexpr int NCOPY = DUAL ? 2 : 1;
-  unsigned* bits = reinterpret_cast<unsigned*>(acc + NCOPY * astride);  // LOO only: source owns the dropped feature
-  const int lane = threadIdx.x;
-  // Workgroup i runs on XCD i % 8 and chunk c on XCD c % 8 (the chunk count is a multiple of 8).  With more than 8
-  // chunks the groups of 8 chunks are walked ONE AFTER THE OTHER over all rows (round 3; before: every row took all its
-  // chunks in turn): what the 8 XCDs re-read from row to row is then 8 chunk slices of X' instead of all of it -- at
-  // C3 200 MB instead of 600 MB, i.e. inside the 256 MB Infinity Cache instead of in HBM.  8 chunks (C2): same order as before.
-  int c;
-  int64_t r;
-  if (p.nchunks > 8 && p.nchunks % 8 == 0 && !getenv_chunk_interleave(p)) {
-    const int64_t nrows = (int64_t)gridDim.x / p.nchunks, per = nrows * 8;
-    const int64_t grp = blockIdx.x / per, rem = blockIdx.x - grp * per;
-    r = rem >> 3;
-    c = (int)(grp * 8 + (rem & 7));
-  } else {
-    c = blockIdx.x % p.nchunks;
-    r = blockIdx.x / p.nchunks;
-  }
-  const int64_t gr = p.row_ids ? (int64_t)p.row_ids[p.row_begin + r] : p.row_begin + r;
-  const int64_t j0 = (int64_t)c * p.SC;
-  const int jn = (int)((p.nj - j0 < p.SC) ? (p.nj - j0) : p.SC);
-  const int dummy = p.SC + lane;
-
-  for (int j = lane; j < NCOPY * astride; j += 64) acc[j] = T(0);
-  if (LOO)
-    for (int j = lane; j < (p.SC + 31) / 32; j += 64) bits[j] = 0u;
-  __syncthreads();
-
-  float fix_unscale = 1.f;
-  for (int t = 0; t < p.nterms; ++t) {
-    const CsrView<T> L = p.L[t];
-    const ChunkedView<T> M = p.M[t];
-    const int* __restrict__ off = M.off + (int64_t)c * M.rows;
-    const unsigned short* __restrict__ midx = M.idx;
-    const T* __restrict__ mval = M.val;
-    const int lb = L.ptr[gr], le = L.ptr[gr + 1];
-    float scale = 1.f;
-    if constexpr (FIX) {   // (experiment: fixed-point sums in the single-wave kernel; one term, not LOO)
-      float sabs = 0.f;
-      for (int q = lb + lane; q < le; q += 64) sabs += fabsf((float)(L.val[q] * p.inv1[t][L.idx[q]]));
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) sabs += __shfl_xor(sabs, o);
-      int e = 0;
-      (void)frexpf(sabs * p.xmax, &e);
-      if (!(sabs * p.xmax > 0.f)) e = 0;
-      e = e < -90 ? -90 : (e > 120 ? 120 : e);
-      scale = ldexpf(1.f, 30 - e);
-      fix_unscale = ldexpf(1.f, e - 30);
-    }
-    for (int g0 = lb; g0 < le; g0 += 64) {
-      // ---- the next 64 neighbours a of r, one per lane: coefficient and sub-row bounds
-      const int q = g0 + lane;
-      int b_l = 0, n_l = 0;
-      T cf_l = T(0);
-      if (q < le) {
-        const int a = L.idx[q];
-        const T lv = L.val[q];
-        if (LOO) {
-          const int d = p.kf[a] - 1;  // the query leaves every feature column it touched
-          cf_l = (a != (int)gr && d > 0) ? lv * (T(1) / T(d)) : T(0);  // a == gr: the dropped feature
-        } else {
-          cf_l = lv * p.inv1[t][a];
-          if constexpr (FIX) cf_l = (T)((float)cf_l * scale);
-        }
-        if (cf_l != T(0)) { b_l = off[a]; n_l = off[a + 1] - b_l; }
-      }
-      const int cnt = __builtin_amdgcn_readfirstlane((le - g0 < 64) ? (le - g0) : 64);
-      // ---- fold the sub-rows in, U at a time; the loads of the next U are in flight meanwhile
-      SubRows<T, U> A, B;
-      auto load = [&](SubRows<T, U>& sr, int first) __attribute__((always_inline)) {
-        if constexpr (BUF) {
-          const __amdgpu_buffer_rsrc_t ridx = __builtin_amdgcn_make_buffer_rsrc((void*)midx, 0, -1, 0x00020000);
-          const __amdgpu_buffer_rsrc_t rval = __builtin_amdgcn_make_buffer_rsrc((void*)mval, 0, -1, 0x00020000);
-          subrows_load_buf<U, BINM>(sr, first, b_l, n_l, cf_l, ridx, rval, lane);
-        } else {
-          subrows_load<T, U, BINM>(sr, first, b_l, n_l, cf_l, midx, mval, lane);
-        }
-      };
-      load(A, 0);
-      for (int u0 = 0; u0 < cnt; u0 += 2 * U) {
-        if (u0 + U < cnt) load(B, u0 + U);
-        if constexpr (FIX) subrows_fold_fixed<U>(A, u0, b_l, n_l, cf_l, reinterpret_cast<unsigned*>(acc), midx, mval, lane);
-        else subrows_fold<T, U, DUAL>(A, u0, b_l, n_l, cf_l, acc, astride, dummy, midx, mval, lane);
-        if (u0 + U < cnt) {
-          if (u0 + 2 * U < cnt) load(A, u0 + 2 * U);
-          if constexpr (FIX) subrows_fold_fixed<U>(B, u0 + U, b_l, n_l, cf_l, reinterpret_cast<unsigned*>(acc), midx, mval, lane);
-          else subrows_fold<T, U, DUAL>(B, u0 + U, b_l, n_l, cf_l, acc, astride, dummy, midx, mval, lane);
-        }
-      }
-    }
-  }
-  if (LOO) {
-    // sources that own the dropped feature column f_i: their degree is one lower in this fold
-    const ChunkedView<T> M = p.M[0];
-    const int* off = M.off + (int64_t)c * M.rows;
-    for (int x = off[gr] + lane; x < off[gr + 1]; x += 64) {
-      const int j = M.idx[x];
-      atomicOr(&bits[j >> 5], 1u << (j & 31));
-    }
-  }
-  __syncthreads();
-
-  T* orow = p.out + r * p.ld + j0;
-  for (int j = lane; j < jn; j += 64) {
-    T z;
-    T sum = DUAL ? acc[j] + acc[astride + j] : acc[j];
-    if constexpr (FIX) sum = (T)((float)reinterpret_cast<const int*>(acc)[j] * fix_unscale);
-    if (LOO) {
-      const int d = p.ks[j0 + j] - (int)((bits[j >> 5] >> (j & 31)) & 1u);
-      z = (d > 0 && (j0 + j) != gr) ? sum * (T(1) / T(d)) : T(0);
-    } else {
-      z = sum * p.inv2[j0 + j];
-      if (p.accumulate) z += orow[j];
-    }
-    orow[j] = z;
-  }
-}
-
-constexpr int TRANSFER_U = 8;
-
-// SS_TRANSFER_DUAL=0/1: one or two copies of the LDS accumulators (see subrows_fold)
-static bool transfer_dual() { return env_int("SS_TRANSFER_DUAL", 0) != 0; }
-
-// sub-rows in flight per wave.  Default 8; 4 (55 instead of 90 registers: 30 instead of 20 single-wave workgroups per CU)
-// where it measured faster: weighted operands that stay in L2 (C2: 1.46 vs 1.51 ms; pattern-only operands 1.24 vs
-// 1.19 ms and the 600 MB operand of C3 5.1 vs 4.6 ms go the other way).  SS_TRANSFER_U overrides.
-static int transfer_u(bool small_weighted = false) {
-  const int u = (int)env_int("SS_TRANSFER_U", small_weighted ? 4 : TRANSFER_U);
-  return (u == 4 || u == 16) ? u : 8;
-}
-
-// ---------------------------------------------------------------- stage 1, query-block workgroups (round 3)
-// Same product, same per-wave loop (U sub-rows in flight, plain LDS read-add-write), different workgroup: NW waves,
-// one row of L per wave, all on chunk c.  What the single-wave kernel fetched per (row, feature) from L2 besides the
-// sub-row itself -- off[a], off[a+1] (one 64-byte sector for 8 bytes) and inv1[a] (another sector for 4 bytes), i.e.
-// ~130 of the ~600 bytes of L2 -> L1 traffic per sub-row visit -- is gone: the chunk's sub-row offsets ((rows+1) ints)
-// are staged once per workgroup in LDS and read from there, and the coefficients L[r,a] * inv1[a] come from a
-// coalesced array written by transfer_coef_kernel (one pass over L per launch).  The operand may be cut with
-// sub-rows padded to 32 entries (64-byte index runs, 128-byte value runs: every sub-row starts on an L2 sector).
-template <class T>
-__global__ void transfer_coef_kernel(const int* __restrict__ ptr, const int* __restrict__ idx, const T* __restrict__ val,
-                                     const T* __restrict__ inv1, int64_t row_begin, int64_t nrows, T* __restrict__ coef) {
-  const int lo = ptr[row_begin], hi = ptr[row_begin + nrows];
-  for (int64_t e = (int64_t)lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < hi; e += (int64_t)gridDim.x * blockDim.x)
-    coef[e] = val[e] * inv1[idx[e]];
-}
-
-template <class T, int U, bool BINM, bool FIX>
-__global__ void __launch_bounds__(1024) transfer_block_kernel(TransferArgs<T> p, const T* __restrict__ coef, int64_t nrows,
-                                                              int align, int offs_bytes, float xmax) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  int* offs = reinterpret_cast<int*>(smem_raw);                               // [rows + 1] sub-row offsets of chunk c
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  const int astride = p.SC + 64;
-  T* acc = reinterpret_cast<T*>(smem_raw + offs_bytes) + (size_t)wave * astride;  // this wave's sums + per-lane dummies
-  const int c = blockIdx.x % p.nchunks;
-  const int64_t r = (int64_t)(blockIdx.x / p.nchunks) * nw + wave;
-  const ChunkedView<T> M = p.M[0];
-  const CsrView<T> L = p.L[0];
-  {
-    const int* __restrict__ off = M.off + (int64_t)c * M.rows;
-    for (int64_t i = threadIdx.x; i <= M.rows; i += blockDim.x) offs[i] = off[i];
-  }
-  for (int j = lane; j < astride; j += 64) acc[j] = T(0);
-  __syncthreads();
-  if (r >= nrows) return;   // (after the only barrier)
-  const int64_t gr = p.row_begin + r;
-  const int64_t j0 = (int64_t)c * p.SC;
-  const int jn = (int)((p.nj - j0 < p.SC) ? (p.nj - j0) : p.SC);
-  const int dummy = p.SC + lane;
-  const unsigned short* __restrict__ midx = M.idx;
-  const T* __restrict__ mval = M.val;
-  const int lb = L.ptr[gr], le = L.ptr[gr + 1];
-  // FIX: scale 2^k of this row's fixed-point sums.  Every sum is bounded by bound = (sum_a |coef[a]|) * xmax
-  // (xmax = largest |value| of the operand); bound < 2^e, so with k = 30 - e all sums stay below 2^30, the roundings
-  // (one unit per term at most) below 2^24: no overflow in 32 bits, resolution bound * 2^-30.
-  float scale = 1.f, unscale = 1.f;
-  if constexpr (FIX) {
-    float sabs = 0.f;
-    for (int q = lb + lane; q < le; q += 64) sabs += fabsf((float)coef[q]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sabs += __shfl_xor(sabs, o);
-    int e = 0;
-    (void)frexpf(sabs * xmax, &e);
-    if (!(sabs * xmax > 0.f)) e = 0;
-    e = e < -90 ? -90 : (e > 120 ? 120 : e);
-    scale = ldexpf(1.f, 30 - e);
-    unscale = ldexpf(1.f, e - 30);
-  }
-  for (int g0 = lb; g0 < le; g0 += 64) {
-    const int q = g0 + lane;
-    int b_l = 0, n_l = 0;
-    T cf_l = T(0);
-    if (q < le) {
-      const int a = L.idx[q];
-      cf_l = coef[q];
-      if constexpr (FIX) cf_l = (T)((float)cf_l * scale);   // exact: a power of two
-      if (cf_l != T(0)) {
-        const int o0 = offs[a], o1 = offs[a + 1];
-        b_l = o0 * align;
-        n_l = (o1 - o0) * align;
-      }
-    }
-    const int cnt = __builtin_amdgcn_readfirstlane((le - g0 < 64) ? (le - g0) : 64);
-    SubRows<T, U> A, B;
-    subrows_load<T, U, BINM>(A, 0, b_l, n_l, cf_l, midx, mval, lane);
-    for (int u0 = 0; u0 < cnt; u0 += 2 * U) {
-      if (u0 + U < cnt) subrows_load<T, U, BINM>(B, u0 + U, b_l, n_l, cf_l, midx, mval, lane);
-      if constexpr (FIX) subrows_fold_fixed<U>(A, u0, b_l, n_l, cf_l, reinterpret_cast<unsigned*>(acc), midx, mval, lane);
-      else subrows_fold<T, U, false>(A, u0, b_l, n_l, cf_l, acc, astride, dummy, midx, mval, lane);
-      if (u0 + U < cnt) {
-        if (u0 + 2 * U < cnt) subrows_load<T, U, BINM>(A, u0 + 2 * U, b_l, n_l, cf_l, midx, mval, lane);
-        if constexpr (FIX) subrows_fold_fixed<U>(B, u0 + U, b_l, n_l, cf_l, reinterpret_cast<unsigned*>(acc), midx, mval, lane);
-        else subrows_fold<T, U, false>(B, u0 + U, b_l, n_l, cf_l, acc, astride, dummy, midx, mval, lane);
-      }
-    }
-  }
-  // the wave's own LDS operations execute in order: no barrier needed before it reads its sums back
-  T* orow = p.out + r * p.ld + j0;
-  if constexpr (FIX) {
-    const int* iacc = reinterpret_cast<const int*>(acc);
-    for (int j = lane; j < jn; j += 64) orow[j] = (T)((float)iacc[j] * unscale) * p.inv2[j0 + j];
-  } else {
-    for (int j = lane; j < jn; j += 64) orow[j] = acc[j] * p.inv2[j0 + j];
-  }
-}
-
-// ---------------------------------------------------------------- stage 1, flat stream of quads (round 3, measured variant)
-// Workgroup as in transfer_block_kernel (NW waves = NW rows of L on chunk c; the chunk's sub-row offsets AND exact
-// sub-row lengths staged in LDS; coefficients precomputed).  The entries of the 64 sub-rows of a feature group are walked
-// as ONE stream of QUADS (4 consecutive entries of a sub-row, the last quad of a sub-row padded with zero entries) in
-// steps of 64 quads = 256 entries ~ four 62-entry sub-rows: lane l of step t takes stream position 64 t + l, whichever
-// sub-row it falls into -- no half-empty second halves.  One global_load_dwordx4 (values) + one global_load_dwordx2
-// (indices) per step; a step holds entries of several features, whose columns can coincide: only safe because the sums
-// are integer atomics (ds_add_u32 on 2^k-scaled fixed-point products, see subrows_fold_fixed).  Per step: the owner of
-// the first lane (popcount of a ballot), then one select per sub-row boundary inside the step, all from wave-uniform
-// broadcasts.  Steps run through a ring of D slots, every load unconditional.  Measured (C2): 2.04 ms -- the boundary
-// loop's readlane -> scalar -> select chains make a step ~1900 clk per wave.
-template <class T, int D, bool BINM>
-__global__ void __launch_bounds__(1024) transfer_qflat_kernel(TransferArgs<T> p, const T* __restrict__ coef, int64_t nrows,
-                                                             int align, int offs_bytes, int lens_bytes, float xmax,
-                                                             const unsigned short* __restrict__ glen) {
-  static_assert(std::is_same<T, float>::value, "fixed-point sums: fp32 graphs only");
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  int* offs = reinterpret_cast<int*>(smem_raw);                                        // [rows + 1], units of `align`
-  unsigned short* lens = reinterpret_cast<unsigned short*>(smem_raw + offs_bytes);     // [rows] exact entries
-  const int lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int astride = p.SC + 64;
-  unsigned* acc = reinterpret_cast<unsigned*>(smem_raw + offs_bytes + lens_bytes) + (size_t)wave * astride;
-  const int c = blockIdx.x % p.nchunks;
-  const int64_t r = (int64_t)(blockIdx.x / p.nchunks) * nw + wave;
-  const ChunkedView<T> M = p.M[0];
-  const CsrView<T> L = p.L[0];
-  {
-    const int* __restrict__ off = M.off + (int64_t)c * M.rows;
-    const unsigned short* __restrict__ gl = glen + (int64_t)c * M.rows;
-    for (int64_t i = threadIdx.x; i <= M.rows; i += blockDim.x) offs[i] = off[i];
-    for (int64_t i = threadIdx.x; i < M.rows; i += blockDim.x) lens[i] = gl[i];
-  }
-  for (int j = lane; j < astride; j += 64) acc[j] = 0u;
-  __syncthreads();
-  if (r >= nrows) return;
-  const int64_t gr = p.row_begin + r;
-  const int64_t j0 = (int64_t)c * p.SC;
-  const int jn = (int)((p.nj - j0 < p.SC) ? (p.nj - j0) : p.SC);
-  const unsigned short* __restrict__ midx = M.idx;
-  const T* __restrict__ mval = M.val;
-  const int lb = __builtin_amdgcn_readfirstlane(L.ptr[gr]), le = __builtin_amdgcn_readfirstlane(L.ptr[gr + 1]);
-  // scale 2^k of the row's sums: bound = (sum |coef|) * xmax < 2^e, k = 30 - e (see transfer_block_kernel)
-  float scale, unscale;
-  {
-    float sabs = 0.f;
-    for (int q = lb + lane; q < le; q += 64) sabs += fabsf(coef[q]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sabs += __shfl_xor(sabs, o);
-    int e = 0;
-    (void)frexpf(sabs * xmax, &e);
-    if (!(sabs * xmax > 0.f)) e = 0;
-    e = e < -90 ? -90 : (e > 120 ? 120 : e);
-    scale = ldexpf(1.f, 30 - e);
-    unscale = ldexpf(1.f, e - 30);
-  }
-  const int ngroups = (le - lb + 63) >> 6;
-  auto raw_load = [&](int g, int& a, float& cf) __attribute__((always_inline)) {
-    const int q = lb + g * 64 + lane;
-    a = 0;
-    cf = 0.f;
-    if (q < le) { a = L.idx[q]; cf = coef[q]; }
-  };
-  // sub-row of feature a in this chunk: start (entries) and exact length, from LDS; nothing for a zero coefficient
-  auto meta = [&](int a, float cf, int& b_l, int& n_l, float& cf_l) __attribute__((always_inline)) {
-    cf_l = cf * scale;   // exact: a power of two
-    b_l = 0;
-    n_l = 0;
-    if (cf_l != 0.f) {
-      b_l = (offs[a] * align) >> 2;        // start in quads (sub-rows start on 32-entry boundaries)
-      n_l = ((int)lens[a] + 3) >> 2;       // length in quads; the last quad is padded with zero entries
-    }
-  };
-  // current group: per lane i the stream start P_i of its sub-row, delta_i = start in memory - P_i, coefficient
-  int Pc = 0, dc = 0, ra, bn, nn;
-  float cc = 0.f, cn, rc;
-  int total = 0, nst = 0, t = 0, gcur = -1;
-  raw_load(0, ra, rc); meta(ra, rc, bn, nn, cn);
-  raw_load(1, ra, rc);
-  bool done = false;
-  auto switch_group = [&]() __attribute__((always_inline)) {
-    // the prepared next group becomes current: exclusive prefix sum of the lengths over the 64 lanes
-    ++gcur;
-    int incl = nn;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int up = __shfl_up(incl, o);
-      if (lane >= o) incl += up;
-    }
-    Pc = incl - nn;
-    dc = bn - Pc;
-    cc = cn;
-    total = __builtin_amdgcn_readlane(incl, 63);
-    nst = (total + 63) >> 6;
-    t = 0;
-    meta(ra, rc, bn, nn, cn);            // group gcur + 1 (its raw pairs were requested a group ago)
-    raw_load(gcur + 2, ra, rc);
-  };
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  typedef unsigned u2 __attribute__((ext_vector_type(2)));
-  u2 sj[D];
-  f4 sv[D];
-  float sc[D];
-  const f4* __restrict__ mval4 = reinterpret_cast<const f4*>(mval);
-  const u2* __restrict__ midx4 = reinterpret_cast<const u2*>(midx);
-  auto next_step = [&](u2& oj, f4& ov, float& ocf) __attribute__((always_inline)) {
-    if (t >= nst) {
-      if (gcur + 1 < ngroups) switch_group();   // (may land on a group without entries: a null step, next call moves on)
-      else done = true;
-    }
-    float cfv = 0.f;
-    int addr = lane;   // lanes without work add 0 to different columns (same-address atomics serialise)
-    if (t < nst) {
-      const int lo = t << 6;
-      const int pos = lo + lane;
-      const unsigned long long le_mask = __ballot(Pc <= lo);
-      const int own0 = __builtin_popcountll(le_mask) - 1;                 // last sub-row that starts at or before lo
-      unsigned long long m = __ballot(Pc > lo && Pc <= lo + 63);          // sub-rows that start inside the step
-      cfv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cc), own0));
-      int dlv = __builtin_amdgcn_readlane(dc, own0);
-      while (m != 0ull) {
-        const int i = __builtin_ctzll(m);
-        m &= m - 1ull;
-        const int Pi = __builtin_amdgcn_readlane(Pc, i);
-        const float cfi = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cc), i));
-        const int dli = __builtin_amdgcn_readlane(dc, i);
-        const bool in = pos >= Pi;
-        cfv = in ? cfi : cfv;
-        dlv = in ? dli : dlv;
-      }
-      const bool valid = pos < total;
-      cfv = valid ? cfv : 0.f;
-      addr = valid ? pos + dlv : lane;
-      ++t;
-    }
-    ocf = cfv;
-    oj = midx4[addr];
-    if constexpr (BINM) ov = f4{1.f, 1.f, 1.f, 1.f};
-    else ov = mval4[addr];
-  };
-  auto fold = [&](u2 j, f4 v, float cf) __attribute__((always_inline)) {
-    atomicAdd(acc + (j.x & 0xffffu), (unsigned)cvt_rpi(cf * v.x));
-    atomicAdd(acc + (j.x >> 16), (unsigned)cvt_rpi(cf * v.y));
-    atomicAdd(acc + (j.y & 0xffffu), (unsigned)cvt_rpi(cf * v.z));
-    atomicAdd(acc + (j.y >> 16), (unsigned)cvt_rpi(cf * v.w));
-  };
-#pragma unroll
-  for (int i = 0; i < D; ++i) next_step(sj[i], sv[i], sc[i]);
-  while (!done) {
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-      fold(sj[i], sv[i], sc[i]);
-      next_step(sj[i], sv[i], sc[i]);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < D; ++i) fold(sj[i], sv[i], sc[i]);
-  T* orow = p.out + r * p.ld + j0;
-  const int* iacc = reinterpret_cast<const int*>(acc);
-  for (int j = lane; j < jn; j += 64) orow[j] = ((float)iacc[j] * unscale) * p.inv2[j0 + j];
-}
-
-// ---------------------------------------------------------------- stage 1, wide loads + fixed-point sums (round 3)
-// What the counters of the single-wave kernel say (profiles/r03_stage1_mem_pmc.txt): its 2- and 4-byte-per-lane loads
-// cost the vector L1 ~6 accesses each (TCP_TOTAL_CACHE_ACCESSES ~0.8 per cycle and CU, TA busy 92 %), its LDS
-// read-add-write pairs keep the LDS 64 % busy, and a wave needs ~400 clk per sub-row (readlane -> scalar -> address
-// chains, one LDS round trip per fold).  This kernel removes all three:
-//  * 16 bytes per lane: 16 lanes share a sub-row, lane e takes its entries 4e .. 4e+3 -- ONE global_load_dwordx4
-//    (values) + ONE global_load_dwordx2 (indices) fetch the first 64 entries of FOUR sub-rows;
-//  * sums are 2^k-scaled integers added with ds_add_u32 (half the LDS cycles of the pair, no return value, no wait;
-//    columns of different sub-rows may coincide inside one instruction, which only atomics get right; integer sums do
-//    not depend on any order);
-//  * no per-sub-row scalar work: a wave writes (start, length, coefficient) of its 64 current features to a small LDS
-//    table once per group and every lane reads its sub-row's triple from there (one ds_read per step).
-// Entries past the first 64 of a sub-row (40 % of the sub-rows have some, ~8 on average) are taken afterwards, 4 lanes
-// (16 entries) per sub-row and step, through a list of the features that still have entries left.
-// Workgroup = NW waves = NW rows of L on chunk c; sub-row offsets and exact lengths of the chunk staged in LDS;
-// coefficients precomputed (transfer_coef_kernel); steps run through a ring of D slots, every load unconditional.
-constexpr int WIDE_META = 64 * 12;   // bytes per wave: (start quad, length, coefficient) of 64 features
-constexpr int WIDE_LIST = 64;        // bytes per wave: features with entries left (one byte each)
-template <int D, bool BINM>
-__global__ void __launch_bounds__(1024) transfer_wide_kernel(TransferArgs<float> p, const float* __restrict__ coef,
-                                                             int64_t nrows, int align, int offs_bytes, int lens_bytes,
-                                                             float xmax, const unsigned short* __restrict__ glen) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  int* offs = reinterpret_cast<int*>(smem_raw);
-  unsigned short* lens = reinterpret_cast<unsigned short*>(smem_raw + offs_bytes);
-  unsigned char* ident = smem_raw + offs_bytes + lens_bytes;                 // [64] identity list (first 64 entries: all features)
-  const int lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int accb = (((p.SC + 4) * 4 + 15) / 16) * 16;   // + the padding column SC (zero entries point at it)
-  unsigned char* mine = smem_raw + offs_bytes + lens_bytes + 64 + (size_t)wave * (size_t)(accb + WIDE_META + WIDE_LIST);
-  unsigned* acc = reinterpret_cast<unsigned*>(mine);
-  unsigned char* metab = mine + accb;                                        // [64][12]
-  unsigned char* list = metab + WIDE_META;                                   // [64]
-  const int c = blockIdx.x % p.nchunks;
-  const int64_t r = (int64_t)(blockIdx.x / p.nchunks) * nw + wave;
-  const ChunkedView<float> M = p.M[0];
-  const CsrView<float> L = p.L[0];
-  {
-    const int* __restrict__ off = M.off + (int64_t)c * M.rows;
-    const unsigned short* __restrict__ gl = glen + (int64_t)c * M.rows;
-    for (int64_t i = threadIdx.x; i <= M.rows; i += blockDim.x) offs[i] = off[i];
-    for (int64_t i = threadIdx.x; i < M.rows; i += blockDim.x) lens[i] = gl[i];
-    if (threadIdx.x < 64) ident[threadIdx.x] = (unsigned char)threadIdx.x;
-  }
-  for (int j = lane; j < p.SC; j += 64) acc[j] = 0u;
-  __syncthreads();
-  if (r >= nrows) return;
-  const int64_t gr = p.row_begin + r;
-  const int64_t j0 = (int64_t)c * p.SC;
-  const int jn = (int)((p.nj - j0 < p.SC) ? (p.nj - j0) : p.SC);
-  const int lb = __builtin_amdgcn_readfirstlane(L.ptr[gr]), le = __builtin_amdgcn_readfirstlane(L.ptr[gr + 1]);
-  float scale, unscale;
-  {
-    float sabs = 0.f;
-    for (int q = lb + lane; q < le; q += 64) sabs += fabsf(coef[q]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sabs += __shfl_xor(sabs, o);
-    int e = 0;
-    (void)frexpf(sabs * xmax, &e);
-    if (!(sabs * xmax > 0.f)) e = 0;
-    e = e < -90 ? -90 : (e > 120 ? 120 : e);
-    scale = ldexpf(1.f, 30 - e);
-    unscale = ldexpf(1.f, e - 30);
-  }
-  const int ngroups = (le - lb + 63) >> 6;
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  typedef unsigned u2 __attribute__((ext_vector_type(2)));
-  const f4* __restrict__ mval4 = reinterpret_cast<const f4*>(M.val);
-  const u2* __restrict__ midx4 = reinterpret_cast<const u2*>(M.idx);
-  auto raw_load = [&](int g, int& a, float& cf) __attribute__((always_inline)) {
-    const int q = lb + g * 64 + lane;
-    a = 0;
-    cf = 0.f;
-    if (q < le) { a = L.idx[q]; cf = coef[q]; }
-  };
-  // ---- generator state (wave-uniform): group, level (0: entries 0..63, 16 lanes per sub-row; h >= 1: entries
-  // 64 + 16 (h-1) .. +15, 4 lanes per sub-row), step inside the level
-  int gcur = -1, level = 0, st = 0, nst = 0, nlist = 0, qoff = 0;
-  int ncur = 0;            // lane i: length of the sub-row of feature i of the current group
-  int ra;
-  float rc;
-  raw_load(0, ra, rc);
-  bool done = false;
-  auto open_group = [&]() __attribute__((always_inline)) {
-    // the raw (feature, coefficient) pairs of this group are here; those of the next group are requested now
-    ++gcur;
-    const float cf = rc * scale;   // exact: a power of two
-    int b = 0, n = 0;
-    if (cf != 0.f) { b = (offs[ra] * align) >> 2; n = (int)lens[ra]; }
-    raw_load(gcur + 1, ra, rc);
-    ncur = n;
-    unsigned* m = reinterpret_cast<unsigned*>(metab + lane * 12);
-    m[0] = (unsigned)b; m[1] = (unsigned)n; m[2] = __float_as_uint(cf);
-    level = 0;
-    st = 0;
-    qoff = 0;
-    const int cnt = (le - lb - gcur * 64 < 64) ? (le - lb - gcur * 64) : 64;
-    nlist = cnt;
-    nst = (cnt + 3) >> 2;          // four sub-rows per step
-  };
-  auto next_level = [&]() __attribute__((always_inline)) {
-    // features that still have entries: level 1 starts at entry 64, each further level 16 entries on
-    const int covered = 64 + 16 * level;
-    ++level;
-    qoff = covered >> 2;
-    const bool more = ncur > covered;
-    const unsigned long long mk = __ballot(more);
-    nlist = __builtin_popcountll(mk);
-    if (more) list[__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0u))] = (unsigned char)lane;
-    st = 0;
-    nst = (nlist + 15) >> 4;       // sixteen sub-rows per step
-  };
-  u2 sj[D];
-  f4 sv[D];
-  float sc[D];
-  auto next_step = [&](u2& oj, f4& ov, float& ocf) __attribute__((always_inline)) {
-    if (st >= nst) {
-      if (gcur >= 0 && nlist > 0) next_level();          // (an empty level: nst = 0, handled by the next call)
-      else if (gcur + 1 < ngroups) open_group();
-      else done = true;
-    }
-    float cfv = 0.f;
-    int quad = lane;   // lanes without work add 0 to 64 DIFFERENT columns (64 lanes adding to one LDS word serialise)
-    int rem = 0;       // entries of the sub-row in this lane's quad (the last quad of a sub-row ends in padding)
-    if (st < nst) {
-      const int sh = level == 0 ? 4 : 2;                 // log2(lanes per sub-row)
-      const int pos = (st << (6 - sh)) + (lane >> sh);   // position in the list of features of this level
-      const int e = lane & ((1 << sh) - 1);
-      const unsigned char* lst = level == 0 ? ident : list;
-      const int fi = pos < nlist ? (int)lst[pos] : 0;
-      const unsigned* m = reinterpret_cast<const unsigned*>(metab + fi * 12);
-      const int b = (int)m[0], n = (int)m[1];
-      const float cf = __uint_as_float(m[2]);
-      const int qe = qoff + e;                           // quad of the sub-row this lane takes
-      const bool valid = pos < nlist && 4 * qe < n;
-      cfv = valid ? cf : 0.f;
-      quad = valid ? b + qe : lane;
-      rem = n - 4 * qe;
-      ++st;
-    }
-    ocf = cfv;
-    oj = midx4[quad];
-    // pattern-only operand: the values are not read, so the padding of a sub-row's last quad must be masked here (a
-    // stored padding value is 0, an implied one would be 1 -- added to the padding's column SC)
-    if constexpr (BINM) ov = f4{rem > 0 ? 1.f : 0.f, rem > 1 ? 1.f : 0.f, rem > 2 ? 1.f : 0.f, rem > 3 ? 1.f : 0.f};
-    else ov = mval4[quad];
-  };
-  auto fold = [&](u2 j, f4 v, float cf) __attribute__((always_inline)) {
-    atomicAdd(acc + (j.x & 0xffffu), (unsigned)cvt_rpi(cf * v.x));
-    atomicAdd(acc + (j.x >> 16), (unsigned)cvt_rpi(cf * v.y));
-    atomicAdd(acc + (j.y & 0xffffu), (unsigned)cvt_rpi(cf * v.z));
-    atomicAdd(acc + (j.y >> 16), (unsigned)cvt_rpi(cf * v.w));
-  };
-#pragma unroll
-  for (int i = 0; i < D; ++i) next_step(sj[i], sv[i], sc[i]);
-  while (!done) {
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-      fold(sj[i], sv[i], sc[i]);
-      next_step(sj[i], sv[i], sc[i]);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < D; ++i) fold(sj[i], sv[i], sc[i]);
-  float* orow = p.out + r * p.ld + j0;
-  const int* iacc = reinterpret_cast<const int*>(acc);
-  for (int j = lane; j < jn; j += 64) orow[j] = ((float)iacc[j] * unscale) * p.inv2[j0 + j];
-}
-
-// ---------------------------------------------------------------- stage 1, wide loads, static schedule (round 3)
-// transfer_wide_kernel without its step generator (whose scalar control flow cost ~45 instructions and two dependent LDS
-// reads per step: 1.2 ms of the 1.8 ms with loads and atomics removed).  A group of 64 features is ALWAYS 20 steps:
-//   steps  0..15  entries  0..63 of features 4s .. 4s+3        (16 lanes x 4 entries per sub-row)
-//   steps 16..18  entries 64..79 of the features that have them (4 lanes per sub-row, 16 features per step, from list 1)
-//   step  19      entries 80..95 of the features that have them (list 2)
-// so the whole row is one straight-line software pipeline: the loop body is one group, completely unrolled, LDS table
-// reads use immediate offsets, a ring of 4 slots carries the loads across steps and across groups (the table of the
-// next group is written -- into the other of two buffers -- four steps before the current group ends), every load is
-// unconditional and the waits are exact counts.  What the 20 steps cannot hold (a 49th feature longer than 64 entries,
-// a 17th longer than 80, entries past 96; ~1e-4 of the sub-rows at a mean of 62) is added by the owning lane itself,
-// entry by entry, when the table is written.
-constexpr int W2_TBL = 64 * 12;
-constexpr int W2_STEPS = 20;
-constexpr int W2_D = 4;
-template <bool BINM>
-__global__ void __launch_bounds__(1024) transfer_wide2_kernel(TransferArgs<float> p, const float* __restrict__ coef,
-                                                              int64_t nrows, int align, int offs_bytes, int lens_bytes,
-                                                              float xmax, const unsigned short* __restrict__ glen) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  int* offs = reinterpret_cast<int*>(smem_raw);
-  unsigned short* lens = reinterpret_cast<unsigned short*>(smem_raw + offs_bytes);
-  const int lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int accb = (((p.SC + 4) * 4 + 15) / 16) * 16;   // + the padding column SC (zero entries point at it)
-  const int per_wave = accb + 2 * W2_TBL + 4 * 64;
-  unsigned char* mine = smem_raw + offs_bytes + lens_bytes + (size_t)wave * (size_t)per_wave;
-  unsigned* acc = reinterpret_cast<unsigned*>(mine);
-  unsigned char* tbl0 = mine + accb;                      // two tables [64][12]: (start quad, length, coefficient)
-  unsigned char* lst0 = tbl0 + 2 * W2_TBL;                // two x (list 1 [64], list 2 [64])
-  const int c = blockIdx.x % p.nchunks;
-  const int64_t r = (int64_t)(blockIdx.x / p.nchunks) * nw + wave;
-  const ChunkedView<float> M = p.M[0];
-  const CsrView<float> L = p.L[0];
-  {
-    const int* __restrict__ off = M.off + (int64_t)c * M.rows;
-    const unsigned short* __restrict__ gl = glen + (int64_t)c * M.rows;
-    for (int64_t i = threadIdx.x; i <= M.rows; i += blockDim.x) offs[i] = off[i];
-    for (int64_t i = threadIdx.x; i < M.rows; i += blockDim.x) lens[i] = gl[i];
-  }
-  for (int j = lane; j < p.SC; j += 64) acc[j] = 0u;
-  __syncthreads();
-  if (r >= nrows) return;
-  const int64_t gr = p.row_begin + r;
-  const int64_t j0 = (int64_t)c * p.SC;
-  const int jn = (int)((p.nj - j0 < p.SC) ? (p.nj - j0) : p.SC);
-  const int lb = __builtin_amdgcn_readfirstlane(L.ptr[gr]), le = __builtin_amdgcn_readfirstlane(L.ptr[gr + 1]);
-  float scale, unscale;
-  {
-    float sabs = 0.f;
-    for (int q = lb + lane; q < le; q += 64) sabs += fabsf(coef[q]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sabs += __shfl_xor(sabs, o);
-    int e = 0;
-    (void)frexpf(sabs * xmax, &e);
-    if (!(sabs * xmax > 0.f)) e = 0;
-    e = e < -90 ? -90 : (e > 120 ? 120 : e);
-    scale = ldexpf(1.f, 30 - e);
-    unscale = ldexpf(1.f, e - 30);
-  }
-  const int ngroups = (le - lb + 63) >> 6;
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  typedef unsigned u2 __attribute__((ext_vector_type(2)));
-  const f4* __restrict__ mval4 = reinterpret_cast<const f4*>(M.val);
-  const u2* __restrict__ midx4 = reinterpret_cast<const u2*>(M.idx);
-  const unsigned short* __restrict__ midx = M.idx;
-  const float* __restrict__ mval = M.val;
-  const int lastq = le > lb ? le - 1 : lb;   // (an empty row never dereferences: ngroups == 0)
-  // raw (feature, coefficient) pair of this lane in group g; lanes past the end of the row get coefficient 0.
-  // Unconditional loads from a clamped position: no branch, exact wait counts.
-  auto raw_load = [&](int g, int& a, float& cf) __attribute__((always_inline)) {
-    const int q = lb + g * 64 + lane;
-    const int qc = q < le ? q : lastq;
-    a = L.idx[qc];
-    const float x = coef[qc];
-    cf = q < le ? x : 0.f;
-  };
-  // write the table + lists of group g (its raw pair is in (ra, rc)) into buffer g & 1; request the raw pair of g + 1
-  int ra = 0;
-  float rc = 0.f;
-  auto open_group = [&](int g) __attribute__((always_inline)) {
-    unsigned char* tb = tbl0 + (g & 1) * W2_TBL;
-    unsigned char* l1 = lst0 + (g & 1) * 128;
-    unsigned char* l2 = l1 + 64;
-    const float cf = (g < ngroups) ? rc * scale : 0.f;   // exact: a power of two
-    int b = 0, n = 0;
-    if (cf != 0.f) { b = (offs[ra] * align) >> 2; n = (int)lens[ra]; }
-    raw_load(g + 1, ra, rc);                            // (clamped past the end of the row: always safe, never a branch)
-    unsigned* m = reinterpret_cast<unsigned*>(tb + lane * 12);
-    m[0] = (unsigned)b; m[1] = (unsigned)n; m[2] = __float_as_uint(cf);
-    // list 1 holds the first 48 features longer than 64 entries (steps 16..18), list 2 the first 16 of THOSE that are
-    // longer than 80 (step 19): a feature that found no place in list 1 must not appear in list 2 -- its owner adds
-    // everything past entry 64 itself, and step 19 would add entries 80..95 a second time
-    const unsigned long long m1 = __ballot(n > 64);
-    const int r1 = __builtin_amdgcn_mbcnt_hi((unsigned)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m1, 0u));
-    const bool in1 = n > 64 && r1 < 48;
-    const unsigned long long m2 = __ballot(in1 && n > 80);
-    const int r2 = __builtin_amdgcn_mbcnt_hi((unsigned)(m2 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m2, 0u));
-    const bool in2 = in1 && n > 80 && r2 < 16;
-    l1[lane] = 255; l2[lane] = 255;                      // 255 = no feature at this list position
-    if (in1) l1[r1] = (unsigned char)lane;
-    if (in2) l2[r2] = (unsigned char)lane;
-    // the rare rest: entries the 20 steps do not reach, added by the owning lane
-    const int cov = in2 ? 96 : (in1 ? 80 : 64);
-    if (__ballot(n > cov) != 0ull) {
-      for (int x = cov; x < n; ++x) {
-        const int at = 4 * b + x;
-        atomicAdd(acc + midx[at], (unsigned)cvt_rpi(cf * (BINM ? 1.f : mval[at])));
-      }
-    }
-  };
-  // ---- the ring
-  u2 sj[W2_D];
-  f4 sv[W2_D];
-  float sc[W2_D];
-  auto fetch = [&](int quad, float cfv, int rem, u2& oj, f4& ov, float& ocf) __attribute__((always_inline)) {
-    ocf = cfv;
-    oj = midx4[quad];
-    // pattern-only operand: the values are not read, so the padding of a sub-row's last quad is masked here
-    if constexpr (BINM) ov = f4{rem > 0 ? 1.f : 0.f, rem > 1 ? 1.f : 0.f, rem > 2 ? 1.f : 0.f, rem > 3 ? 1.f : 0.f};
-    else ov = mval4[quad];
-  };
-  // step s (compile-time after unrolling) of the group whose table sits in buffer `par`
-  auto gen = [&](int s, int par, u2& oj, f4& ov, float& ocf) __attribute__((always_inline)) {
-    const unsigned char* tb = tbl0 + par * W2_TBL;
-    int fi, e, qoff;
-    bool have = true;
-    if (s < 16) {
-      fi = 4 * s + (lane >> 4);
-      e = lane & 15;
-      qoff = 0;
-    } else {
-      const unsigned char* lst = lst0 + par * 128 + (s < 19 ? 0 : 64);
-      const int pos = (s < 19 ? 16 * (s - 16) : 0) + (lane >> 2);
-      fi = (int)lst[pos];
-      have = fi != 255;
-      fi = have ? fi : 0;
-      e = lane & 3;
-      qoff = s < 19 ? 16 : 20;
-    }
-    const unsigned* m = reinterpret_cast<const unsigned*>(tb + fi * 12);
-    const int b = (int)m[0], n = (int)m[1];
-    const float cf = __uint_as_float(m[2]);
-    const int qe = qoff + e;
-    const bool valid = have && 4 * qe < n;
-    // lanes without work add 0 to 64 DIFFERENT columns (many lanes adding to one LDS word serialise)
-    fetch(valid ? b + qe : lane, valid ? cf : 0.f, n - 4 * qe, oj, ov, ocf);
-  };
-  auto fold = [&](u2 j, f4 v, float cf) __attribute__((always_inline)) {
-    atomicAdd(acc + (j.x & 0xffffu), (unsigned)cvt_rpi(cf * v.x));
-    atomicAdd(acc + (j.x >> 16), (unsigned)cvt_rpi(cf * v.y));
-    atomicAdd(acc + (j.y & 0xffffu), (unsigned)cvt_rpi(cf * v.z));
-    atomicAdd(acc + (j.y >> 16), (unsigned)cvt_rpi(cf * v.w));
-  };
-  if (ngroups > 0) {
-    raw_load(0, ra, rc);
-    open_group(0);
-#pragma unroll
-    for (int i = 0; i < W2_D; ++i) gen(i, 0, sj[i], sv[i], sc[i]);
-    for (int g = 0; g < ngroups; ++g) {
-      const int par = g & 1;
-#pragma unroll
-      for (int s = 0; s < W2_STEPS; ++s) {
-        if (s == W2_STEPS - W2_D) open_group(g + 1);     // (past the last group: an empty table, all steps idle)
-        fold(sj[s % W2_D], sv[s % W2_D], sc[s % W2_D]);
-        if (s + W2_D < W2_STEPS) gen(s + W2_D, par, sj[s % W2_D], sv[s % W2_D], sc[s % W2_D]);
-        else gen(s + W2_D - W2_STEPS, par ^ 1, sj[s % W2_D], sv[s % W2_D], sc[s % W2_D]);
-      }
-    }
-    // the ring now holds the first steps of the (empty) group past the end: nothing left to add
-  }
-  float* orow = p.out + r * p.ld + j0;
-  const int* iacc = reinterpret_cast<const int*>(acc);
-  for (int j = lane; j < jn; j += 64) orow[j] = ((float)iacc[j] * unscale) * p.inv2[j0 + j];
-}
-
-// waves per workgroup of the block kernel that fit next to the offsets: 0 = does not fit (fall back)
-template <class T>
-static int transfer_block_waves(int64_t mrows, int SC, int* offs_bytes) {
-  const int64_t ob = (((mrows + 1) * 4 + 15) / 16) * 16;
-  const int64_t per_wave = (int64_t)(SC + 64) * (int64_t)sizeof(T);
-  int64_t nw = ((int64_t)ctx().lds_per_block - ob) / per_wave;
-  if (ob >= (int64_t)ctx().lds_per_block) nw = 0;
-  if (nw > 16) nw = 16;
-  nw = env_int_in("SS_TRANSFER_NW", 1, nw, nw);
-  *offs_bytes = (int)ob;
-  return nw >= 8 ? (int)nw : 0;
-}
-
-template <class T>
-int launch_transfer_block(const DevCsr<T>& L, const T* inv1, const DevChunked<T>& Mt, const T* inv2, int64_t row_begin,
-                          int64_t nrows, int64_t nj, T* out, int64_t ld, T* coef, float xmax, bool fixed) {
-  if (nrows <= 0 || nj <= 0) return SS_OK;
-  int offs_bytes = 0;
-  const int nw = transfer_block_waves<T>(Mt.rows, Mt.SC, &offs_bytes);
-  if (nw == 0) return fail(SS_EUNSUPPORTED, "transfer_block: offsets + accumulators do not fit in LDS");
-  TransferArgs<T> p{};
-  p.nterms = 1;
-  p.L[0] = view(L);
-  p.M[0] = view(Mt);
-  p.inv2 = inv2;
-  p.row_begin = row_begin;
-  p.nj = nj;
-  p.SC = Mt.SC;
-  p.nchunks = Mt.nchunks;
-  p.out = out;
-  p.ld = ld;
-  const int64_t groups = ceil_div(nrows, (int64_t)nw);
-  const int64_t grid = groups * p.nchunks;
-  if (grid >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "transfer grid too large; lower SS_TRANSFER_BYTES");
-  path_add("transfer_block");
-  hipLaunchKernelGGL(transfer_coef_kernel<T>, dim3(grid_1d(L.nnz > 0 ? L.nnz : 1, 256, 256 * 8)), dim3(256), 0, ctx().stream,
-                     L.ptr.p, L.idx.p, L.val.p, inv1, row_begin, nrows, coef);
-  SS_LAUNCH_CHECK();
-  const size_t lds = (size_t)offs_bytes + (size_t)nw * (size_t)(p.SC + 64) * sizeof(T);
-  constexpr bool CANFIX = std::is_same<T, float>::value;
-  const bool fx = CANFIX && fixed;
-  if (fx) path_add("fixed_point");
-  if constexpr (std::is_same<T, float>::value) {
-    // the fixed-point kernels with 16 bytes per lane: they walk exact sub-row lengths (operand cut with align 32)
-    const int wide2 = (int)env_int("SS_TRANSFER_WIDE2", 0), wide = (int)env_int("SS_TRANSFER_WIDE", 0),
-              qflat = (int)env_int("SS_TRANSFER_QFLAT", 0);
-    if ((wide2 > 0 || wide > 0 || qflat > 0) && fixed && Mt.align == 32 && Mt.len_ok) {
-      const int64_t lens_bytes = ((Mt.rows * 2 + 15) / 16) * 16;
-      const int64_t accb = ((((int64_t)p.SC + 4) * 4 + 15) / 16) * 16;
-      const int64_t per_wave = wide2 > 0 ? accb + 2 * W2_TBL + 4 * 64
-                               : wide > 0 ? accb + WIDE_META + WIDE_LIST : (int64_t)(p.SC + 64) * 4;
-      const int64_t fixed_bytes = (int64_t)offs_bytes + lens_bytes + (wide > 0 && wide2 == 0 ? 64 : 0);
-      int64_t nwf = ((int64_t)ctx().lds_per_block - fixed_bytes) / per_wave;
-      if (nwf > 16) nwf = 16;
-      nwf = env_int_in("SS_TRANSFER_NW", 1, nwf, nwf);
-      if (nwf >= 8) {
-        const int64_t fgrid = ceil_div(nrows, nwf) * p.nchunks;
-        const size_t flds = (size_t)fixed_bytes + (size_t)nwf * (size_t)per_wave;
-        const unsigned short* glen = Mt.len.p;
-#define SS_TX_LAUNCH(KERNEL)                                                                                          \
-  do {                                                                                                                \
-    static std::atomic<bool> attr_done{false};                                                                        \
-    if (!attr_done) {                                                                                                 \
-      SS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                 160 * 1024));                                                                        \
-      attr_done = true;                                                                                               \
-    }                                                                                                                 \
-    hipLaunchKernelGGL(KERNEL, dim3((unsigned)fgrid), dim3(64 * (int)nwf), flds, ctx().stream, p, (const float*)coef,  \
-                       nrows, Mt.align, offs_bytes, (int)lens_bytes, xmax, glen);                                     \
-  } while (0)
-        if (wide2 > 0) {
-          path_add("wide2");
-          if (Mt.binary) SS_TX_LAUNCH((transfer_wide2_kernel<true>)); else SS_TX_LAUNCH((transfer_wide2_kernel<false>));
-        } else if (wide > 0) {
-          path_add("wide");
-          if (wide == 2) { if (Mt.binary) SS_TX_LAUNCH((transfer_wide_kernel<2, true>)); else SS_TX_LAUNCH((transfer_wide_kernel<2, false>)); }
-          else { if (Mt.binary) SS_TX_LAUNCH((transfer_wide_kernel<4, true>)); else SS_TX_LAUNCH((transfer_wide_kernel<4, false>)); }
-        } else {
-          path_add("qflat");
-          if (Mt.binary) SS_TX_LAUNCH((transfer_qflat_kernel<float, 4, true>)); else SS_TX_LAUNCH((transfer_qflat_kernel<float, 4, false>));
-        }
-#undef SS_TX_LAUNCH
-        SS_LAUNCH_CHECK();
-        return SS_OK;
-      }
-    }
-  }
-  const int pu = transfer_u() == 4 ? 4 : 8;
-#define SS_TB_LAUNCH(U, BINM, FIX)                                                                                    \
-  do {                                                                                                                \
-    static std::atomic<bool> attr_done{false};                                                                        \
-    if (!attr_done) {                                                                                                 \
-      SS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&transfer_block_kernel<T, U, BINM, FIX>),              \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                            \
-      attr_done = true;                                                                                               \
-    }                                                                                                                 \
-    hipLaunchKernelGGL((transfer_block_kernel<T, U, BINM, FIX>), dim3((unsigned)grid), dim3(64 * nw), lds,            \
-                       ctx().stream, p, (const T*)coef, nrows, Mt.align, offs_bytes, xmax);                           \
-  } while (0)
-#define SS_TB_BIN(U, FIX) do { if (Mt.binary) SS_TB_LAUNCH(U, true, FIX); else SS_TB_LAUNCH(U, false, FIX); } while (0)
-#define SS_TB_FIX(U) do { if (fx) SS_TB_BIN(U, CANFIX); else SS_TB_BIN(U, false); } while (0)
-  if (pu == 4) SS_TB_FIX(4);
-  else SS_TB_FIX(8);
-#undef SS_TB_FIX
-#undef SS_TB_BIN
-#undef SS_TB_LAUNCH
-  SS_LAUNCH_CHECK();
-  return SS_OK;
-}
-
-template <class T>
-bool transfer_block_fits(int64_t mrows, int SC) {
-  int ob = 0;
-  return transfer_block_waves<T>(mrows, SC, &ob) > 0;
-}
-
-template <class T, bool LOO>
-static int launch_transfer_variant(const TransferArgs<T>& p, unsigned grid, size_t lds, bool binm, bool dual) {
-#define SS_TRANSFER_LAUNCH(U, BINM, DUAL)                                                               \
-  hipLaunchKernelGGL((transfer_kernel<T, LOO, U, BINM, DUAL>), dim3(grid), dim3(TRANSFER_THREADS), lds, \
-                     ctx().stream, p)
-#define SS_TRANSFER_U(U)                                                                      \
-  do {                                                                                        \
-    if (binm) { if (dual) SS_TRANSFER_LAUNCH(U, true, true); else SS_TRANSFER_LAUNCH(U, true, false); } \
-    else { if (dual) SS_TRANSFER_LAUNCH(U, false, true); else SS_TRANSFER_LAUNCH(U, false, false); }    \
-  } while (0)
-  if constexpr (std::is_same<T, float>::value && !LOO) {
-    if (env_int("SS_TRANSFER_LD", 0) == 1 && !dual) {
-      path_add("buffer_loads");
-      const bool fx = env_int("SS_TRANSFER_FIX1", 0) == 1 && p.nterms == 1 && !p.accumulate;
-      if (fx) path_add("fixed_point");
-#define SS_TL(U, BINM, FX) hipLaunchKernelGGL((transfer_kernel<T, LOO, U, BINM, false, FX, true>), dim3(grid), dim3(TRANSFER_THREADS), lds, ctx().stream, p)
-      if (transfer_u(p.small_weighted != 0 && !LOO) == 4) {
-        if (binm) { if (fx) SS_TL(4, true, true); else SS_TL(4, true, false); }
-        else { if (fx) SS_TL(4, false, true); else SS_TL(4, false, false); }
-      } else {
-        if (binm) { if (fx) SS_TL(8, true, true); else SS_TL(8, true, false); }
-        else { if (fx) SS_TL(8, false, true); else SS_TL(8, false, false); }
-      }
-#undef SS_TL
-      SS_LAUNCH_CHECK();
-      return SS_OK;
-    }
-    if (env_int("SS_TRANSFER_FIX1", 0) == 1 && p.nterms == 1 && !dual && !p.accumulate) {
-      path_add("fixed_point");
-      if (transfer_u(p.small_weighted != 0 && !LOO) == 4) {
-        if (binm) hipLaunchKernelGGL((transfer_kernel<T, LOO, 4, true, false, true>), dim3(grid), dim3(TRANSFER_THREADS), lds, ctx().stream, p);
-        else hipLaunchKernelGGL((transfer_kernel<T, LOO, 4, false, false, true>), dim3(grid), dim3(TRANSFER_THREADS), lds, ctx().stream, p);
-      } else {
-        if (binm) hipLaunchKernelGGL((transfer_kernel<T, LOO, 8, true, false, true>), dim3(grid), dim3(TRANSFER_THREADS), lds, ctx().stream, p);
-        else hipLaunchKernelGGL((transfer_kernel<T, LOO, 8, false, false, true>), dim3(grid), dim3(TRANSFER_THREADS), lds, ctx().stream, p);
-      }
-      SS_LAUNCH_CHECK();
-      return SS_OK;
-    }
-  }
-  switch (transfer_u(p.small_weighted != 0 && !LOO)) {
-    case 4: SS_TRANSFER_U(4); break;
-    case 16: SS_TRANSFER_U(16); break;
-    default: SS_TRANSFER_U(8); break;
-  }
-#undef SS_TRANSFER_U
-#undef SS_TRANSFER_LAUNCH
-  SS_LAUNCH_CHECK();
-  return SS_OK;
-}
-
-template <class T>
-int launch_transfer(int nterms, const DevCsr<T>* L[2], const T* inv1[2], const DevChunked<T>* Mt[2],
-                    const T* inv2, int64_t row_begin, int64_t nrows, int64_t nj, T* out, int64_t ld,
-                    const int* row_ids, bool accumulate) {
-  if (nrows <= 0 || nj <= 0) return SS_OK;
-  TransferArgs<T> p{};
-  p.nterms = nterms;
-  for (int t = 0; t < nterms; ++t) {
-    p.L[t] = view(*L[t]);
-    p.M[t] = view(*Mt[t]);
-    p.inv1[t] = inv1[t];
-    if (Mt[t]->SC != Mt[0]->SC || Mt[t]->nchunks != Mt[0]->nchunks)
-      return fail(SS_EINVAL, "transfer operands were cut with different chunk sizes");
-  }
-  p.inv2 = inv2;
-  p.row_begin = row_begin;
-  p.row_ids = row_ids;
-  p.nj = nj;
-  p.SC = Mt[0]->SC;
-  p.nchunks = Mt[0]->nchunks;
-  p.out = out;
-  p.ld = ld;
-  p.accumulate = accumulate ? 1 : 0;
-  p.xmax = 1.0f;
-  {
-    int64_t bytes = 0;
-    bool weighted = false;
-    for (int t = 0; t < nterms; ++t) {
-      bytes += Mt[t]->stored * (int64_t)(2 + sizeof(T));
-      weighted = weighted || !Mt[t]->binary;
-    }
-    p.small_weighted = (weighted && bytes <= (32LL << 20)) ? 1 : 0;
-  }
-  p.chunk_interleave = env_off("SS_TRANSFER_ORDER") ? 1 : 0;
-  const int64_t grid = nrows * p.nchunks;
-  if (grid >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "transfer grid too large; lower SS_TRANSFER_BYTES");
-  bool binm = true;
-  for (int t = 0; t < nterms; ++t) binm = binm && Mt[t]->binary;
-  const bool dual = transfer_dual();
-  path_add("transfer");
-  const size_t lds = (size_t)(p.SC + 64) * sizeof(T) * (dual ? 2 : 1);
-  SS_TRY((launch_transfer_variant<T, false>(p, (unsigned)grid, lds, binm, dual)));
-  return SS_OK;
-}
-
-template <class T>
-int launch_transfer_loo(const DevCsr<T>& X, const DevChunked<T>& XT, const int* kf, const int* ks,
-                        int64_t i_begin, int64_t nrows, T* out, int64_t ld) {
-  if (nrows <= 0) return SS_OK;
-  TransferArgs<T> p{};
-  p.nterms = 1;
-  p.L[0] = view(X);
-  p.M[0] = view(XT);
-  p.kf = kf;
-  p.ks = ks;
-  p.row_begin = i_begin;
-  p.nj = X.rows;
-  p.SC = XT.SC;
-  p.nchunks = XT.nchunks;
-  p.out = out;
-  p.ld = ld;
-  p.chunk_interleave = env_off("SS_TRANSFER_ORDER") ? 1 : 0;
-  const int64_t grid = nrows * p.nchunks;
-  if (grid >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "transfer grid too large; lower SS_TRANSFER_BYTES");
-  const bool dual = transfer_dual();
-  path_add("transfer_loo");
-  const size_t lds = (size_t)(p.SC + 64) * sizeof(T) * (dual ? 2 : 1) + (size_t)((p.SC + 31) / 32) * 4;
-  SS_TRY((launch_transfer_variant<T, true>(p, (unsigned)grid, lds, XT.binary, dual)));
   return SS_OK;
 }
 
@@ -2386,16 +1179,9 @@ int launch_jaccard(const T* F, int64_t n, int64_t d, int64_t ld, T* S, int64_t l
   template int launch_jaccard<T>(const T*, int64_t, int64_t, int64_t, T*, int64_t);                        \
   template int launch_row_degree<T>(const T*, int64_t, int64_t, int64_t, int*);                             \
   template int launch_spread_dense<T>(const T*, int64_t, int64_t, int64_t, const int*, T*, int64_t);        \
-  template int launch_transfer<T>(int, const DevCsr<T>*[2], const T*[2], const DevChunked<T>*[2], const T*, \
-                                  int64_t, int64_t, int64_t, T*, int64_t, const int*, bool);                      \
   template int launch_fold_degrees<T>(const DevCsr<T>&, const DevCsr<T>&, const DevCsr<T>&, const int*,     \
                                       int64_t, int*, int*, int*);                                           \
   template int launch_fold_inverse<T>(const int*, const int*, const int*, int, int64_t, int64_t, T*, T*);   \
-  template int launch_transfer_block<T>(const DevCsr<T>&, const T*, const DevChunked<T>&, const T*, int64_t, int64_t, \
-                                        int64_t, T*, int64_t, T*, float, bool);                               \
-  template bool transfer_block_fits<T>(int64_t, int);                                                        \
-  template int launch_transfer_loo<T>(const DevCsr<T>&, const DevChunked<T>&, const int*, const int*,       \
-                                      int64_t, int64_t, T*, int64_t);                                                \
   template int sell_max_chunk<T>(int);                                                                      \
   template int launch_spmm_sell<T>(const DevSell<T>&, const T*, int64_t, int64_t, T*, int64_t, const int*,  \
                                    const int*);                                                             \

@@ -414,7 +414,7 @@ def gamma(k, u):
 def band_graph_scores(want, chain, addends, dtype, sell_chunks=1, parts=0, dual=False):
     """|got - oracle| <= band for every score of a graph prediction with non-negative inputs: band = gamma(k) * score,
     k the largest number of roundings any term x_qa (1/kf_a) x_sa (1/ks_s) y_st of the score passes through, counted in
-    simspread.jl_amd/csrc/kernels.hip:
+    simspread.jl_amd/csrc/transfer.hip (stage 1) and kernels.hip (stage 2):
       1  fl(1/kf): degree_kernel (assemble.hip), fold_inverse for k-fold; leave-one-out: T(1) / T(kf - 1) in
          transfer_kernel; the target path of source rows: fl(1/kt)
       1  the coefficient cf = L[r,a] * inv1[a] (transfer_kernel, transfer_coef_kernel)

@@ -1133,3 +1133,50 @@ def test_stage1_variants_match_the_oracle(variant, chunk, dx, monkeypatch):
         assert_close(got, want, np.float32)
         assert (got[5] == 0).all()
         g.close()
+
+
+# the fixed-point stage-1 kernels: (switches, tags the path must hold, tags it must not hold)
+FIXED_POINT_STAGE1 = {
+    "block": ({"SS_TRANSFER_V": "2"}, ("transfer_block", "fixed_point"), ("qflat", "wide", "wide2")),
+    "qflat": ({"SS_TRANSFER_V": "2", "SS_TRANSFER_QFLAT": "4"}, ("transfer_block", "fixed_point", "qflat"), ("wide", "wide2")),
+    "wide D=2": ({"SS_TRANSFER_V": "2", "SS_TRANSFER_WIDE": "2"}, ("transfer_block", "fixed_point", "wide"), ("qflat", "wide2")),
+    "wide D=4": ({"SS_TRANSFER_V": "2", "SS_TRANSFER_WIDE": "4"}, ("transfer_block", "fixed_point", "wide"), ("qflat", "wide2")),
+    "wide2": ({"SS_TRANSFER_V": "2", "SS_TRANSFER_WIDE2": "1"}, ("transfer_block", "fixed_point", "wide2"), ("qflat", "wide")),
+    "single-wave FIX1": ({"SS_TRANSFER_V": "1", "SS_TRANSFER_FIX1": "1"}, ("transfer", "fixed_point"),
+                         ("transfer_block", "buffer_loads")),
+}
+
+
+@pytest.mark.parametrize("chunk,dx", [(None, 0.05), ("3000", 0.05), ("500", 0.2)])
+def test_stage1_fixed_point_kernels_give_the_same_bits(chunk, dx, monkeypatch):
+    """The fixed-point stage-1 kernels add integers, so their sums do not depend on any order, and all of them round
+    the same products cvt_rpi(coef * 2^k * value) with the same per-row k: block + FIX, qflat, wide (D = 2 and 4), wide2
+    and the single-wave FIX1 kernel must give the same bits, not only scores within a tolerance.  Inputs are those of
+    test_stage1_variants_match_the_oracle (waves without a row, a partial last chunk, sub-rows past 64 / 80 / 96
+    entries, both lists of wide2 overflowing in every group, an empty query, zero-degree features, weighted and
+    pattern-only).  Every variant's path tags are asserted, so none falls back silently.
+    "The same k" holds for these inputs, not for every input: k comes from (sum |coef|) * xmax, and the block family
+    takes xmax = the operand's largest |value| where the single-wave kernel takes xmax = 1.  synth_bipartite puts 1.0 on
+    the diagonal of Xs when sources and features are equally many, as here, so the largest value is exactly 1 in the
+    weighted case too.  With a weighted operand whose largest value is below 1 the exponent of some rows can differ by
+    one between the single-wave kernel and the others, and then so do the bits (within the fixed-point resolution)."""
+    if chunk:
+        monkeypatch.setenv("SS_TRANSFER_CHUNK", chunk)
+    for weighted in (True, False):
+        Xq, Xs, Ys = O.synth_bipartite(257, 3000, 3000, 200, dx, 0.03, seed=11, weighted=weighted, dtype=np.float32)
+        Xq = Xq.tolil(); Xq[5, :] = 0; Xq = Xq.tocsr()
+        Xs = Xs.tolil(); Xs[:, 17] = 0; Xs[:, 18] = 0; Xs = Xs.tocsr()
+        got = {}
+        for name, (env, tags, not_tags) in FIXED_POINT_STAGE1.items():
+            with monkeypatch.context() as m:
+                for k, v in env.items():
+                    m.setenv(k, v)
+                g = ss.DeviceGraph.from_sparse(Xq, Xs, Ys, dtype=np.float32)
+                got[name] = g.predict("query").copy()
+                path = ss.path_last()
+                g.close()
+            assert all(t in path for t in tags) and not any(t in path for t in not_tags), (name, path)
+        ref = got["block"]
+        for name, s in got.items():
+            assert np.array_equal(s, ref), (name, weighted, f"{int((s != ref).sum())} scores differ from block + FIX, by at "
+                                            f"most {float(np.abs(s - ref).max() / np.abs(ref).max()):.3e} of the largest")
