@@ -55,12 +55,13 @@ enum {
 };
 
 enum { SS_MEM_HOST = 0, SS_MEM_DEVICE = 1 };
-enum { SS_ROWS_QUERY = 0, SS_ROWS_SOURCE = 1 };
+enum { SS_ROWS_QUERY = 0, SS_ROWS_SOURCE = 1, SS_ROWS_LOO = 2 /* leave-one-out folds: ss_support_* only */ };
 enum { SS_LAYOUT_ROWMAJOR = 0, SS_LAYOUT_COLMAJOR = 1 };
 enum { SS_SIM_COSINE = 0, SS_SIM_TANIMOTO = 1, SS_SIM_DICE = 2 }; /* `metric` of ss_similarity_dot_csr_* */
 
 typedef struct ss_graph ss_graph; /* tri-partite query/source/feature/target graph, device resident */
 typedef struct ss_spmat ss_spmat; /* one sparse operand W of F = W*R, device resident            */
+typedef struct ss_queries ss_queries; /* a block of query rows bound to one graph, device resident */
 
 /* ---------------------------------------------------------------- runtime ---- */
 int ss_version(void);
@@ -86,7 +87,7 @@ int ss_synchronize(void);
  * [6] number of SpMM launches, [7] number of stage-1 launches.  Writes min(n,8) values. */
 int ss_timing_last(double* ms, int n);
 /* Which kernels the last predict / spmm / fingerprint call of this host thread went through: a comma-separated list of tags
- * ("tanimoto_csr_sym", "tanimoto_csr_cross", "jaccard_csr_sym", "jaccard_csr_cross", "dot_csr_sym", "dot_csr_cross", "cutoff_csr", "recut", "transfer", "transfer_loo", "transfer_dense_bf16_ring", "transfer_dense_bf16_128", "transfer_dense_f32_mfma", "transfer_dense_f32_mfma_256",
+ * ("tanimoto_csr_sym", "tanimoto_csr_cross", "jaccard_csr_sym", "jaccard_csr_cross", "dot_csr_sym", "dot_csr_cross", "cutoff_csr", "recut", "support", "transfer", "transfer_loo", "transfer_dense_bf16_ring", "transfer_dense_bf16_128", "transfer_dense_f32_mfma", "transfer_dense_f32_mfma_256",
  * "spmm_sell", "spmm_sell_sorted", "spmm_csell", "spmm_colgroup", "spmm_chunked_narrow", ...), NUL-terminated, truncated
  * to n - 1 characters.  Lets a caller (and the parity tests) assert that a size-dependent routing decision was the one
  * expected.  Has no counterpart in the reference (its only switch is GPU::Bool, src/core.jl:402,404). */
@@ -670,6 +671,9 @@ int ss_target_topl_import_f64(ss_target_topl* h, const double* vals, const int64
  * (the reference's `length(y) > L` assertion). */
 int ss_target_topl_metrics(ss_target_topl* h, int64_t* hits, int64_t* npos, double out[4], int mem);
 
+/* Query sets (ss_queries_*, ss_predict_queries_*) and support lists (ss_support_*) -- prospective screening on a resident
+ * graph -- are declared in simspread_hip_screening.h, which this header includes at its end. */
+
 /* -------------------------------------------------------------- raw W*R SpMM --- */
 /* The resource-spreading product F = W * R on its own (kernel unit tests and the
  * roofline benchmark; inside predict W = Ys' and R = the transfer block, src/core.jl:413).
@@ -694,4 +698,7 @@ int ss_spmat_cost(const ss_spmat* w, int64_t B, double* bytes, double* flops);
 #ifdef __cplusplus
 }
 #endif
+
+#include "simspread_hip_screening.h"
+
 #endif /* SIMSPREAD_HIP_H */

@@ -13,10 +13,11 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SS_LIB_PATH") or os.path.join(_HERE, "libsimspread_hip.so")   # SS_LIB_PATH: A/B builds of the same ABI
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip.h")
+SCREENING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_screening.h")   # included by it
 
 SS_OK = 0
 SS_MEM_HOST, SS_MEM_DEVICE = 0, 1
-SS_ROWS_QUERY, SS_ROWS_SOURCE = 0, 1
+SS_ROWS_QUERY, SS_ROWS_SOURCE, SS_ROWS_LOO = 0, 1, 2
 SS_LAYOUT_ROWMAJOR, SS_LAYOUT_COLMAJOR = 0, 1
 
 _ERR_NAMES = {-1: "SS_EINVAL", -2: "SS_ENOMEM", -3: "SS_EHIP", -4: "SS_ENODEV", -5: "SS_EUNSUPPORTED"}
@@ -129,12 +130,38 @@ def _sigs():
 SIGNATURES = _sigs()
 
 
-def header_symbols():
+def _screening_sigs():
+    """include/simspread_hip_screening.h: query sets and support lists"""
+    s = {
+        "ss_queries_destroy": ([_vp], _int),
+        "ss_queries_info": ([_vp, _vp], _int),
+        "ss_queries_degrees": ([_vp, _vp, _int], _int),
+    }
+    for suf, ft in (("f32", C.c_float), ("f64", C.c_double)):
+        s[f"ss_queries_create_csr_{suf}"] = ([_vp, _i64, _vp, _vp, _vp, _int, _int, _vp], _int)
+        s[f"ss_queries_create_fingerprint_{suf}"] = ([_vp, _i64, _i64, _i64, _vp, _vp, ft, _int, _int, _vp], _int)
+        s[f"ss_queries_create_features_{suf}"] = ([_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, ft, _int, _int, _vp], _int)
+        s[f"ss_queries_create_vectors_{suf}"] = ([_vp, _i64, _i64, _i64, _int, _vp, _i64, _vp, _i64, ft, _int, _int, _vp],
+                                                 _int)
+        s[f"ss_predict_queries_{suf}"] = ([_vp, _vp, _i64, _i64, _int, _vp, _i64, _int, _int], _int)
+        s[f"ss_support_{suf}"] = ([_vp, _vp, _int, _i64, _vp, _vp, _int, _vp, _vp, _vp, _int], _int)
+    return s
+
+
+SCREENING_SIGNATURES = _screening_sigs()
+
+
+def header_symbols(path=HEADER_PATH):
     """Every function the C header declares (used by the symbol-export test)."""
-    with open(HEADER_PATH) as f:
+    with open(path) as f:
         text = f.read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(ss_[a-z0-9_]+)\s*\(", text)))
+
+
+def screening_header_symbols():
+    """Every function include/simspread_hip_screening.h declares."""
+    return header_symbols(SCREENING_HEADER_PATH)
 
 
 def load():
@@ -147,7 +174,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(make -C simspread.jl_amd/csrc).  There is no CPU fallback for the HIP path.")
     lib = C.CDLL(LIB_PATH)
-    for name, (args, res) in SIGNATURES.items():
+    for name, (args, res) in list(SIGNATURES.items()) + list(SCREENING_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res

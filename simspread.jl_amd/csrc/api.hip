@@ -230,9 +230,21 @@ struct HandleHead {
   int dtype;  // 4 or 8 = sizeof(T), guards against mixing _f32/_f64 entry points
   std::mutex mu;
 };
+// every graph box carries an identity of its own (never reused, unlike its address): what a query set is bound to
+static uint64_t next_graph_id() {
+  static std::atomic<uint64_t> n{0};
+  return ++n;
+}
 template <class T>
 struct GraphBox : HandleHead {
+  uint64_t id = next_graph_id();
   Graph<T> g;
+};
+// a query set: an nq x nf block of query rows that belongs to the graph with identity graph_id
+template <class T>
+struct QueriesBox : HandleHead {
+  uint64_t graph_id = 0;
+  DevCsr<T> Xq;
 };
 template <class T>
 struct SpMatBox : HandleHead {
@@ -245,6 +257,17 @@ static int graph_check(const void* h, Graph<T>** out) {
   GraphBox<T>* b = const_cast<GraphBox<T>*>(reinterpret_cast<const GraphBox<T>*>(h));
   if (b->dtype != (int)sizeof(T)) return fail(SS_EINVAL, "graph handle was created with the other precision");
   *out = &b->g;
+  return SS_OK;
+}
+
+// a query set used with the graph handle h (already checked): its precision, and that it was created for that graph
+template <class T>
+static int queries_check(const void* qh, const void* h, const DevCsr<T>** out) {
+  const QueriesBox<T>* q = reinterpret_cast<const QueriesBox<T>*>(qh);
+  if (q->dtype != (int)sizeof(T)) return fail(SS_EINVAL, "query set was created with the other precision");
+  if (q->graph_id != reinterpret_cast<const GraphBox<T>*>(h)->id)
+    return fail(SS_EINVAL, "query set was created for another graph");
+  *out = &q->Xq;
   return SS_OK;
 }
 
@@ -838,10 +861,11 @@ static int stage2_rows(Graph<T>& g, int64_t rb, int64_t nb, const int* kt_clean,
   return sell_rows<T>(g.W, g.Tws.p, g.ns, g.nt, g.Sws, rb, nb, kt_clean, d);
 }
 
-// run stage 1 + stage 2 over [row_begin, row_end) into dev_out (row-major nrows x nt, ld = ldo)
+// run stage 1 + stage 2 over [row_begin, row_end) into dev_out (row-major nrows x nt, ld = ldo); Xq: the query block
+// SS_ROWS_QUERY rows of a sparse graph are taken from (the graph's own, or a query set's)
 template <class T>
-static int predict_rows_device(Graph<T>& g, int kind, int64_t row_begin, int64_t row_end, int clean, T* dev_out,
-                               int64_t ldo) {
+static int predict_rows_device(Graph<T>& g, const DevCsr<T>& Xq, int kind, int64_t row_begin, int64_t row_end, int clean,
+                               T* dev_out, int64_t ldo) {
   const int64_t nrows = row_end - row_begin;
   const int64_t nj = g.ns;
   SS_TRY(graph_sell(g));
@@ -878,12 +902,12 @@ static int predict_rows_device(Graph<T>& g, int kind, int64_t row_begin, int64_t
             const int al = env_int("SS_TRANSFER_ALIGN", 32) == 1 ? 1 : 32;
             SS_TRY(chunked_build<T>(g.XsT, g.XsTc.SC, al, g.XsTb));
           }
-          if (g.Cq.n < (size_t)(g.Xq.nnz > 0 ? g.Xq.nnz : 1)) SS_TRY(g.Cq.alloc((size_t)(g.Xq.nnz > 0 ? g.Xq.nnz : 1)));
+          if (g.Cq.n < (size_t)(Xq.nnz > 0 ? Xq.nnz : 1)) SS_TRY(g.Cq.alloc((size_t)(Xq.nnz > 0 ? Xq.nnz : 1)));
           const bool fixed = !env_off("SS_TRANSFER_FIX");
-          SS_TRY(launch_transfer_block<T>(g.Xq, g.inv_kf.p, g.XsTb, g.inv_ks.p, row_begin + r0, nb, nj, Tbuf.p, nj, g.Cq.p,
+          SS_TRY(launch_transfer_block<T>(Xq, g.inv_kf.p, g.XsTb, g.inv_ks.p, row_begin + r0, nb, nj, Tbuf.p, nj, g.Cq.p,
                                           g.XsTb.vmax, fixed));
         } else {
-          const DevCsr<T>* L[2] = {&g.Xq, nullptr};
+          const DevCsr<T>* L[2] = {&Xq, nullptr};
           const DevChunked<T>* M[2] = {&g.XsTc, nullptr};
           const T* inv1[2] = {g.inv_kf.p, nullptr};
           SS_TRY(launch_transfer<T>(1, L, inv1, M, g.inv_ks.p, row_begin + r0, nb, nj, Tbuf.p, nj));
@@ -972,17 +996,20 @@ struct ScoreOut {
   }
 };
 
-// kind: SS_ROWS_QUERY, SS_ROWS_SOURCE, or 2 = leave-one-out
+// kind: SS_ROWS_QUERY, SS_ROWS_SOURCE, or 2 (SS_ROWS_LOO) = leave-one-out; qh: the query set SS_ROWS_QUERY rows are taken
+// from instead of the graph's own (ss_predict_queries_*)
 template <class T>
 static int predict_impl(ss_graph* h, int kind, int64_t row_begin, int64_t row_end, int clean, T* out, int64_t ld,
-                        int layout, int mem) {
+                        int layout, int mem, const ss_queries* qh = nullptr) {
   SS_TRY(require_init());
   SS_TRY(check_mem(mem));
   SS_TRY(check_layout(layout));
   Graph<T>* gp = nullptr;
   SS_TRY(graph_check<T>(h, &gp));
   Graph<T>& g = *gp;
-  const int64_t limit = (kind == SS_ROWS_QUERY) ? g.nq : g.ns;
+  const DevCsr<T>* xq = &g.Xq;
+  if (qh) SS_TRY(queries_check<T>(qh, h, &xq));
+  const int64_t limit = (kind == SS_ROWS_QUERY) ? (qh ? xq->rows : g.nq) : g.ns;
   if (g.general && kind != SS_ROWS_QUERY)
     return fail(SS_EINVAL, "a general graph serves SS_ROWS_QUERY only");
   if (kind == 2) {
@@ -1001,7 +1028,7 @@ static int predict_impl(ss_graph* h, int kind, int64_t row_begin, int64_t row_en
   if (ld < need_ld) return fail(SS_EINVAL, "leading dimension %lld < %lld", (long long)ld, (long long)need_ld);
   ScoreOut<T> so;
   SS_TRY(so.begin(out, ld, layout, mem, nrows, nt));
-  SS_TRY(predict_rows_device<T>(g, kind, row_begin, row_end, clean, so.dev_rm, so.ld_rm));
+  SS_TRY(predict_rows_device<T>(g, *xq, kind, row_begin, row_end, clean, so.dev_rm, so.ld_rm));
   SS_TRY(so.deliver());
   // Staging buffers are released on return and host results must be complete: wait for the stream.  With the
   // scores written straight into the caller's device buffer there is nothing to release (the transfer block
@@ -1142,7 +1169,7 @@ static int loo_blocks(Graph<T>& g, int64_t i_begin, int64_t i_end, int clean, in
   SS_TRY(begin());
   for (int64_t r0 = 0; r0 < nrows; r0 += rb) {
     const int64_t nb = nrows - r0 < rb ? nrows - r0 : rb;
-    SS_TRY(predict_rows_device<T>(g, 2, i_begin + r0, i_begin + r0 + nb, clean, scores.p, nt));
+    SS_TRY(predict_rows_device<T>(g, g.Xq, 2, i_begin + r0, i_begin + r0 + nb, clean, scores.p, nt));
     StageTimer t3(ST_EPILOGUE);
     SS_TRY(each(SweepBlock<T, int>{g.Ys.ptr.p + i_begin + r0, 0, g.Ys.idx.p, (int64_t)(hp[r0 + nb] - hp[r0]),
                                    hp.data() + r0, scores.p, nb, nt, r0, i_begin + r0, nullptr, nullptr}));
@@ -2459,6 +2486,269 @@ static int spmm_impl(ss_spmat* h, const T* R, int64_t B, int64_t ldr, int r_layo
   return SS_OK;
 }
 
+// ------------------------------------------------------------------ query sets
+// the common head of the query-set constructors: the library and `mem` are usable, *out is cleared, the path note is
+// emptied, gh is a graph of this precision that holds CSR blocks
+template <class T>
+static int queries_begin(const ss_graph* gh, int64_t nq, int mem, ss_queries** out, Graph<T>** gp) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  if (!out) return fail(SS_EINVAL, "out handle pointer is NULL");
+  *out = nullptr;
+  path_note().clear();
+  SS_TRY(graph_check<T>(gh, gp));
+  if ((*gp)->general) return fail(SS_EUNSUPPORTED, "query sets: a general graph takes its rows when it is created");
+  if ((*gp)->dense.on)
+    return fail(SS_EUNSUPPORTED, "query sets: a dense-similarity graph holds no CSR query block");
+  if (nq < 0) return fail(SS_EINVAL, "query sets: negative query count");
+  return SS_OK;
+}
+
+// a new query set bound to gh whose block fill(Xq) produces
+template <class T, class Fill>
+static int queries_finish(const ss_graph* gh, Fill fill, ss_queries** out) {
+  QueriesBox<T>* box = new (std::nothrow) QueriesBox<T>();
+  if (!box) return fail(SS_ENOMEM, "host allocation failed");
+  box->dtype = (int)sizeof(T);
+  box->graph_id = reinterpret_cast<const GraphBox<T>*>(gh)->id;
+  const int rc = fill(box->Xq);
+  if (rc != SS_OK) { delete box; return rc; }
+  *out = reinterpret_cast<ss_queries*>(box);
+  return SS_OK;
+}
+
+template <class T>
+static int queries_create_csr_impl(const ss_graph* gh, int64_t nq, const int64_t* ptr, const int32_t* idx, const T* val,
+                                   int index_base, int mem, ss_queries** out) {
+  Graph<T>* g = nullptr;
+  SS_TRY(queries_begin<T>(gh, nq, mem, out, &g));
+  return queries_finish<T>(
+      gh, [&](DevCsr<T>& Xq) { return csr_from_user<T>(nq, g->nf, ptr, idx, val, index_base, mem, Xq); }, out);
+}
+
+// the sources a cross block is cut against are the graph's: features named after the sources, ns of them
+template <class T>
+static int queries_check_sources(const Graph<T>& g, int64_t ns) {
+  if (g.nf != g.ns)
+    return fail(SS_EINVAL, "query sets from raw data need a graph with nf == ns (features named after the sources)");
+  if (ns != g.ns)
+    return fail(SS_EINVAL, "query sets: Fs has %lld rows, the graph has %lld sources", (long long)ns, (long long)g.ns);
+  return SS_OK;
+}
+
+// the cross block of producer Prod, counted by count(p), into a new query set; tag: its ss_path_last tag
+template <class T, class Prod, class Count>
+static int queries_from_producer(const ss_graph* gh, int64_t nq, int64_t ns, Count count, const char* tag,
+                                 ss_queries** out) {
+  return queries_finish<T>(
+      gh,
+      [&](DevCsr<T>& Xq) -> int {
+        if (ns == 0) {  // no sources: an nq x 0 block (a producer given no second side would pair the queries with themselves)
+          const std::vector<int64_t> zeros((size_t)nq + 1, 0);
+          return csr_from_user<T>(nq, 0, zeros.data(), nullptr, nullptr, 0, SS_MEM_HOST, Xq);
+        }
+        Prod p;
+        int rc = count(p);
+        if (rc == SS_OK) rc = p.to_dev_csr(Xq);
+        if (nq > 0) path_add(tag);
+        return rc;
+      },
+      out);
+}
+
+template <class T>
+static int queries_create_fingerprint_impl(const ss_graph* gh, int64_t nq, int64_t ns, int64_t nwords,
+                                           const uint64_t* Fq, const uint64_t* Fs, T alpha, int weighted, int mem,
+                                           ss_queries** out) {
+  Graph<T>* g = nullptr;
+  SS_TRY(queries_begin<T>(gh, nq, mem, out, &g));
+  SS_TRY(queries_check_sources(*g, ns));
+  SS_TRY(check_nwords(nwords));
+  SS_TRY(check_fingerprints("Fq", Fq, nq, nwords));
+  SS_TRY(check_fingerprints("Fs", Fs, ns, nwords));
+  DevBuf<uint64_t> bq, bs;
+  const uint64_t *dq = nullptr, *ds = nullptr;
+  SS_TRY(stage_fingerprints(Fs, ns, nwords, mem, bs, &ds));
+  SS_TRY(stage_fingerprints(Fq, nq, nwords, mem, bq, &dq));
+  return queries_from_producer<T, TanimotoCsr<T>>(
+      gh, nq, ns, [&](TanimotoCsr<T>& p) { return p.count(dq, nq, ds, ns, nwords, alpha, weighted != 0); },
+      "tanimoto_csr_cross", out);
+}
+
+template <class T, class Prod, class Check, class Count>
+static int features_queries_impl(const FeatureNames& nm, Check check, Count count, const ss_graph* gh, int64_t nq,
+                                 int64_t ns, int64_t d, const T* Fq, int64_t ldq, const T* Fs, int64_t lds_, T alpha,
+                                 int mem, ss_queries** out) {
+  Graph<T>* g = nullptr;
+  SS_TRY(queries_begin<T>(gh, nq, mem, out, &g));
+  SS_TRY(queries_check_sources(*g, ns));
+  SS_TRY(check_feature_args(nm, check, d, alpha));
+  SS_TRY(check_features("Fq", Fq, nq, ldq, d));
+  SS_TRY(check_features("Fs", Fs, ns, lds_, d));
+  DevBuf<T> bq, bs;
+  const T *dq = nullptr, *ds = nullptr;
+  int64_t lq = 0, ls = 0;
+  SS_TRY(stage_features(Fs, ns, lds_, d, mem, bs, &ds, &ls));
+  SS_TRY(stage_features(Fq, nq, ldq, d, mem, bq, &dq, &lq));
+  return queries_from_producer<T, Prod>(
+      gh, nq, ns, [&](Prod& p) { return count(p, dq, nq, lq, ds, ns, ls); }, nm.tag_cross, out);
+}
+
+template <class T>
+static int queries_degrees_impl(const ss_queries* qh, int64_t* kq, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  const QueriesBox<T>* q = reinterpret_cast<const QueriesBox<T>*>(qh);
+  const int64_t nq = q->Xq.rows;
+  if (nq == 0) return SS_OK;
+  if (!kq) return fail(SS_EINVAL, "ss_queries_degrees: kq is NULL");
+  hipStream_t st = ctx().stream;
+  std::vector<int> hp((size_t)nq + 1);
+  SS_HIP(hipMemcpyAsync(hp.data(), q->Xq.ptr.p, hp.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  if (mem == SS_MEM_HOST) {
+    for (int64_t r = 0; r < nq; ++r) kq[r] = hp[r + 1] - hp[r];
+    return SS_OK;
+  }
+  std::vector<int64_t> k((size_t)nq);
+  for (int64_t r = 0; r < nq; ++r) k[r] = hp[r + 1] - hp[r];
+  SS_HIP(hipMemcpyAsync(kq, k.data(), (size_t)nq * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
+}
+
+// ------------------------------------------------------------------ support lists (support.hip)
+template <class T>
+static int support_impl(ss_graph* h, const ss_queries* qh, int kind, int64_t npairs, const int64_t* rows,
+                        const int32_t* targets, int M, int32_t* src, T* contrib, int32_t* nsupp, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  Graph<T>* gp = nullptr;
+  SS_TRY(graph_check<T>(h, &gp));
+  Graph<T>& g = *gp;
+  if (g.general || g.dense.on)
+    return fail(SS_EUNSUPPORTED, "support: only a graph that holds CSR blocks has a sparse transfer row");
+  if (kind == SS_ROWS_SOURCE)
+    return fail(SS_EUNSUPPORTED, "support: the transfer row of a source row mixes the feature and the target path");
+  if (kind != SS_ROWS_QUERY && kind != SS_ROWS_LOO)
+    return fail(SS_EINVAL, "support: rows_kind must be SS_ROWS_QUERY or SS_ROWS_LOO");
+  const DevCsr<T>* xq = &g.Xq;
+  int64_t limit = g.nq;
+  if (kind == SS_ROWS_LOO) {
+    if (qh) return fail(SS_EINVAL, "support: SS_ROWS_LOO takes the graph's own sources, q must be NULL");
+    SS_TRY(loo_graph_check(g));
+    limit = g.ns;
+  } else if (qh) {
+    SS_TRY(queries_check<T>(qh, h, &xq));
+    limit = xq->rows;
+  }
+  if (npairs < 0) return fail(SS_EINVAL, "support: negative pair count");
+  if (M < 1 || M > 64) return fail(SS_EINVAL, "support: M = %d outside 1..64", M);
+  if (npairs == 0) return SS_OK;
+  if (npairs >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "support: %lld pairs (>= 2^31)", (long long)npairs);
+  if (!rows || !targets || !src || !contrib || !nsupp) return fail(SS_EINVAL, "support: NULL buffer");
+  hipStream_t st = ctx().stream;
+  // the pair list on the host (it is small), checked whole before anything is written
+  std::vector<int64_t> hr((size_t)npairs);
+  std::vector<int32_t> ht((size_t)npairs);
+  if (mem == SS_MEM_HOST) {
+    memcpy(hr.data(), rows, hr.size() * sizeof(int64_t));
+    memcpy(ht.data(), targets, ht.size() * sizeof(int32_t));
+  } else {
+    SS_HIP(hipMemcpyAsync(hr.data(), rows, hr.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    SS_HIP(hipMemcpyAsync(ht.data(), targets, ht.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    SS_HIP(hipStreamSynchronize(st));
+  }
+  for (int64_t p = 0; p < npairs; ++p) {
+    if (hr[p] < 0 || hr[p] >= limit)
+      return fail(SS_EINVAL, "support: rows[%lld] = %lld outside 0..%lld", (long long)p, (long long)hr[p],
+                  (long long)limit - 1);
+    if (ht[p] < 0 || (int64_t)ht[p] >= g.nt)
+      return fail(SS_EINVAL, "support: targets[%lld] = %d outside 0..%lld", (long long)p, ht[p], (long long)g.nt - 1);
+  }
+  timing_begin_call();
+  path_add("support");
+  // pairs grouped by row: the distinct rows in ascending order take one slot of the transfer block each, batch by batch
+  std::vector<int> order((size_t)npairs);
+  for (int64_t p = 0; p < npairs; ++p) order[p] = (int)p;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return hr[a] < hr[b]; });
+  const int64_t ns = g.ns;
+  std::vector<int> drow;                                   // distinct rows
+  std::vector<int> hs((size_t)npairs * 3);                 // slot, target, position of every pair in row order
+  std::vector<int64_t> first;                              // first pair (in row order) of every distinct row
+  for (int64_t k = 0; k < npairs; ++k) {
+    const int p = order[k];
+    if (k == 0 || hr[p] != hr[order[k - 1]]) {
+      drow.push_back((int)hr[p]);
+      first.push_back(k);
+    }
+    hs[(size_t)npairs + k] = ht[p];
+    hs[(size_t)npairs * 2 + k] = p;
+  }
+  const int64_t nd = (int64_t)drow.size();
+  first.push_back(npairs);
+  const int64_t rb = transfer_batch_rows(nd, ns, sizeof(T));
+  for (int64_t d = 0; d < nd; ++d)
+    for (int64_t k = first[d]; k < first[d + 1]; ++k) hs[k] = (int)(d % rb);
+  SS_TRY(graph_chunked(g, false));
+  const size_t need = (size_t)rb * (size_t)(ns > 0 ? ns : 1);
+  if (g.Tws.n < need) SS_TRY(g.Tws.alloc(need));
+  DevBuf<int> d_rows, d_pairs, d_src, d_nsupp;
+  DevBuf<T> d_contrib;
+  SS_TRY(d_rows.alloc((size_t)nd));
+  SS_TRY(d_pairs.alloc(hs.size()));
+  int* osrc = src;
+  T* ocon = contrib;
+  int* ons = nsupp;
+  if (mem == SS_MEM_HOST) {
+    SS_TRY(d_src.alloc((size_t)npairs * M));
+    SS_TRY(d_contrib.alloc((size_t)npairs * M));
+    SS_TRY(d_nsupp.alloc((size_t)npairs));
+    osrc = d_src.p;
+    ocon = d_contrib.p;
+    ons = d_nsupp.p;
+  }
+  SS_TRY(upload<int>(d_rows.p, drow.data(), (size_t)nd, SS_MEM_HOST));
+  SS_TRY(upload<int>(d_pairs.p, hs.data(), hs.size(), SS_MEM_HOST));
+  hipEvent_t e_begin, e_end;
+  SS_TRY(timing_mark(&e_begin));
+  for (int64_t d0 = 0; d0 < nd; d0 += rb) {
+    const int64_t nb = nd - d0 < rb ? nd - d0 : rb;
+    {
+      StageTimer t1(ST_TRANSFER);
+      if (kind == SS_ROWS_LOO) {
+        // one launch per run of consecutive folds
+        for (int64_t a = d0; a < d0 + nb;) {
+          int64_t b = a + 1;
+          while (b < d0 + nb && drow[b] == drow[b - 1] + 1) ++b;
+          SS_TRY(launch_transfer_loo<T>(g.Xs, g.XsTc, g.kf.p, g.ks.p, drow[a], b - a, g.Tws.p + (a - d0) * ns, ns));
+          a = b;
+        }
+      } else {
+        const DevCsr<T>* L[2] = {xq, nullptr};
+        const DevChunked<T>* Mt[2] = {&g.XsTc, nullptr};
+        const T* inv1[2] = {g.inv_kf.p, nullptr};
+        SS_TRY(launch_transfer<T>(1, L, inv1, Mt, g.inv_ks.p, d0, nb, ns, g.Tws.p, ns, d_rows.p));
+      }
+      timing_count(ST_NTRANSFER, 1);
+    }
+    StageTimer t3(ST_EPILOGUE);
+    const int64_t k0 = first[d0], k1 = first[d0 + nb];
+    SS_TRY(launch_support<T>(g.YsT, g.Tws.p, ns, d_pairs.p + k0, d_pairs.p + npairs + k0, d_pairs.p + 2 * npairs + k0,
+                             k1 - k0, M, osrc, ocon, ons));
+  }
+  SS_TRY(timing_mark(&e_end));
+  timing_span(ST_TOTAL, e_begin, e_end);
+  if (mem == SS_MEM_HOST) {
+    StageTimer t5(ST_D2H);
+    SS_HIP(hipMemcpyAsync(src, d_src.p, (size_t)npairs * M * sizeof(int), hipMemcpyDeviceToHost, st));
+    SS_HIP(hipMemcpyAsync(contrib, d_contrib.p, (size_t)npairs * M * sizeof(T), hipMemcpyDeviceToHost, st));
+    SS_HIP(hipMemcpyAsync(nsupp, d_nsupp.p, (size_t)npairs * sizeof(int), hipMemcpyDeviceToHost, st));
+  }
+  SS_HIP(hipStreamSynchronize(st));  // the pair list and the staging buffers are released on return
+  return SS_OK;
+}
+
 }  // namespace ss
 
 // ==================================================================== extern "C"
@@ -2978,6 +3268,149 @@ int ss_predict_loo_f64(ss_graph* g, int64_t i_begin, int64_t i_end, int clean, d
   if (!g) return fail(SS_EINVAL, "handle is NULL");
   SS_HANDLE_LOCK(g);
   return predict_impl<double>(g, 2, i_begin, i_end, clean, out, ld, layout, mem);
+}
+
+// a graph and a query set: the graph's lock first, always
+#define SS_QUERIES_LOCK(q) \
+  std::unique_lock<std::mutex> _ss_queries_guard(reinterpret_cast<HandleHead*>(const_cast<ss_queries*>(q))->mu)
+
+int ss_queries_create_csr_f32(const ss_graph* g, int64_t nq, const int64_t* ptr, const int32_t* idx, const float* val,
+                              int index_base, int mem, ss_queries** out) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  return queries_create_csr_impl<float>(g, nq, ptr, idx, val, index_base, mem, out);
+}
+int ss_queries_create_csr_f64(const ss_graph* g, int64_t nq, const int64_t* ptr, const int32_t* idx, const double* val,
+                              int index_base, int mem, ss_queries** out) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  return queries_create_csr_impl<double>(g, nq, ptr, idx, val, index_base, mem, out);
+}
+int ss_queries_create_fingerprint_f32(const ss_graph* g, int64_t nq, int64_t ns, int64_t nwords, const uint64_t* Fq,
+                                      const uint64_t* Fs, float alpha, int weighted, int mem, ss_queries** out) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  return queries_create_fingerprint_impl<float>(g, nq, ns, nwords, Fq, Fs, alpha, weighted, mem, out);
+}
+int ss_queries_create_fingerprint_f64(const ss_graph* g, int64_t nq, int64_t ns, int64_t nwords, const uint64_t* Fq,
+                                      const uint64_t* Fs, double alpha, int weighted, int mem, ss_queries** out) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  return queries_create_fingerprint_impl<double>(g, nq, ns, nwords, Fq, Fs, alpha, weighted, mem, out);
+}
+int ss_queries_create_features_f32(const ss_graph* g, int64_t nq, int64_t ns, int64_t d, const float* Fq, int64_t ldq,
+                                   const float* Fs, int64_t lds, float alpha, int weighted, int mem, ss_queries** out) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  return features_queries_impl<float, JaccardCsr<float>>(jaccard_names, no_check, jaccard_count<float>(d, alpha, weighted),
+                                                         g, nq, ns, d, Fq, ldq, Fs, lds, alpha, mem, out);
+}
+int ss_queries_create_features_f64(const ss_graph* g, int64_t nq, int64_t ns, int64_t d, const double* Fq, int64_t ldq,
+                                   const double* Fs, int64_t lds, double alpha, int weighted, int mem,
+                                   ss_queries** out) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  return features_queries_impl<double, JaccardCsr<double>>(jaccard_names, no_check,
+                                                           jaccard_count<double>(d, alpha, weighted), g, nq, ns, d, Fq,
+                                                           ldq, Fs, lds, alpha, mem, out);
+}
+int ss_queries_create_vectors_f32(const ss_graph* g, int64_t nq, int64_t ns, int64_t d, int metric, const float* Fq,
+                                  int64_t ldq, const float* Fs, int64_t lds, float alpha, int weighted, int mem,
+                                  ss_queries** out) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  return features_queries_impl<float, DotCsr<float>>(
+      dot_names, [=] { return check_sim_metric(metric); }, dot_count<float>(d, metric, alpha, weighted), g, nq, ns, d, Fq,
+      ldq, Fs, lds, alpha, mem, out);
+}
+int ss_queries_create_vectors_f64(const ss_graph* g, int64_t nq, int64_t ns, int64_t d, int metric, const double* Fq,
+                                  int64_t ldq, const double* Fs, int64_t lds, double alpha, int weighted, int mem,
+                                  ss_queries** out) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  return features_queries_impl<double, DotCsr<double>>(
+      dot_names, [=] { return check_sim_metric(metric); }, dot_count<double>(d, metric, alpha, weighted), g, nq, ns, d,
+      Fq, ldq, Fs, lds, alpha, mem, out);
+}
+
+int ss_queries_destroy(ss_queries* q) {
+  SS_API_LOCK();
+  if (!q) return SS_OK;
+  const int dtype = *reinterpret_cast<int*>(q);
+  if (dtype != 4 && dtype != 8) return fail(SS_EINVAL, "not a query-set handle");
+  {  // wait for a call that still works on the handle, then for the device (a prediction may still read the block)
+    SS_QUERIES_LOCK(q);
+    if (ctx().inited) (void)hipStreamSynchronize(ctx().stream);
+  }
+  if (dtype == 4) delete reinterpret_cast<QueriesBox<float>*>(q);
+  else delete reinterpret_cast<QueriesBox<double>*>(q);
+  return SS_OK;
+}
+
+int ss_queries_info(const ss_queries* q, int64_t sizes[3]) {
+  SS_API_LOCK();
+  if (!q || !sizes) return fail(SS_EINVAL, "NULL argument");
+  SS_QUERIES_LOCK(q);
+  const int dtype = *reinterpret_cast<const int*>(q);
+  auto fill = [&](auto* b) { sizes[0] = b->Xq.rows; sizes[1] = b->Xq.cols; sizes[2] = b->Xq.nnz; };
+  if (dtype == 4) fill(reinterpret_cast<const QueriesBox<float>*>(q));
+  else if (dtype == 8) fill(reinterpret_cast<const QueriesBox<double>*>(q));
+  else return fail(SS_EINVAL, "not a query-set handle");
+  return SS_OK;
+}
+
+int ss_queries_degrees(const ss_queries* q, int64_t* kq, int mem) {
+  SS_API_LOCK();
+  if (!q) return fail(SS_EINVAL, "handle is NULL");
+  SS_QUERIES_LOCK(q);
+  const int dtype = *reinterpret_cast<const int*>(q);
+  if (dtype == 4) return queries_degrees_impl<float>(q, kq, mem);
+  if (dtype == 8) return queries_degrees_impl<double>(q, kq, mem);
+  return fail(SS_EINVAL, "not a query-set handle");
+}
+
+int ss_predict_queries_f32(ss_graph* g, const ss_queries* q, int64_t row_begin, int64_t row_end, int clean, float* out,
+                           int64_t ld, int layout, int mem) {
+  SS_API_LOCK();
+  if (!g || !q) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  SS_QUERIES_LOCK(q);
+  return predict_impl<float>(g, SS_ROWS_QUERY, row_begin, row_end, clean, out, ld, layout, mem, q);
+}
+int ss_predict_queries_f64(ss_graph* g, const ss_queries* q, int64_t row_begin, int64_t row_end, int clean, double* out,
+                           int64_t ld, int layout, int mem) {
+  SS_API_LOCK();
+  if (!g || !q) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  SS_QUERIES_LOCK(q);
+  return predict_impl<double>(g, SS_ROWS_QUERY, row_begin, row_end, clean, out, ld, layout, mem, q);
+}
+
+int ss_support_f32(ss_graph* g, const ss_queries* q, int rows_kind, int64_t npairs, const int64_t* rows,
+                   const int32_t* targets, int M, int32_t* src, float* contrib, int32_t* nsupp, int mem) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  std::unique_lock<std::mutex> _ss_queries_guard;
+  if (q) _ss_queries_guard = std::unique_lock<std::mutex>(reinterpret_cast<HandleHead*>(const_cast<ss_queries*>(q))->mu);
+  return support_impl<float>(g, q, rows_kind, npairs, rows, targets, M, src, contrib, nsupp, mem);
+}
+int ss_support_f64(ss_graph* g, const ss_queries* q, int rows_kind, int64_t npairs, const int64_t* rows,
+                   const int32_t* targets, int M, int32_t* src, double* contrib, int32_t* nsupp, int mem) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  std::unique_lock<std::mutex> _ss_queries_guard;
+  if (q) _ss_queries_guard = std::unique_lock<std::mutex>(reinterpret_cast<HandleHead*>(const_cast<ss_queries*>(q))->mu);
+  return support_impl<double>(g, q, rows_kind, npairs, rows, targets, M, src, contrib, nsupp, mem);
 }
 
 int ss_predict_kfold_f32(ss_graph* g, const int32_t* fold_of_source, int nfolds, int clean, float* out, int64_t ld,

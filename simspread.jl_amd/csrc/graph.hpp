@@ -344,6 +344,13 @@ int tl_export_table(const TlTable<pool_key_t<T>>& t, int64_t nt, int L, int64_t 
 // hits[t] = positives among target t's entries (device)
 template <class K>
 int tl_hits(const TlTable<K>& t, int64_t nt, int L, int64_t fill, int64_t* hits);
+// ---- support.hip: support lists.  Pair p reads transfer row slot[p] of Trows (row-major, leading dimension ldt) and row
+// tgt[p] of Ys' and writes entry pos[p] of src / contrib (M slots each) and nsupp: the sources s with
+// Trows[slot][s] * Ys'[t][s] != 0 under (product descending by isless, s ascending), the first M of them and their count.
+// All arrays on the device, enqueued on the stream; 1 <= M <= 64.
+template <class T>
+int launch_support(const DevCsr<T>& YsT, const T* Trows, int64_t ldt, const int* slot, const int* tgt, const int* pos,
+                   int64_t npairs, int M, int* src, T* contrib, int* nsupp);
 // ---- dense.hip (fp32 only: fp32-input MFMA)
 int launch_transfer_dense(const DenseSim<float>& d, bool loo, const float* inv_k, const float* inv_n, const int* ks,
                           int64_t row_begin, int64_t nrows, float* out, int64_t ldo, bool source_rows = false);

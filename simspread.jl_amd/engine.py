@@ -363,9 +363,17 @@ class DeviceGraph:
         return out
 
     def predict(self, rows: str = "query", row_begin: int = 0, row_end: Optional[int] = None, clean: bool = False,
-                out=None, layout: str = "row"):
+                out=None, layout: str = "row", queries: Optional["DeviceQueries"] = None):
         """Scores of rows [row_begin,row_end) of the query (or source) nodes against all targets
-        (predict, src/core.jl:402-425,446-466; clean! fused, src/core.jl:478-484)."""
+        (predict, src/core.jl:402-425,446-466; clean! fused, src/core.jl:478-484).  queries: a ``DeviceQueries`` bound
+        to this graph whose rows are scored instead of the graph's own query block (ss_predict_queries_*): bitwise what
+        the graph built with those queries gives."""
+        if queries is not None:
+            if rows != "query":
+                raise ValueError("a query set has query rows only")
+            row_end = queries.nq if row_end is None else row_end
+            return self._run("ss_predict_queries", (queries._h, row_begin, row_end), row_end - row_begin, clean, out,
+                             layout)
         kind = {"query": L.SS_ROWS_QUERY, "source": L.SS_ROWS_SOURCE}[rows]
         limit = self.nq if rows == "query" else self.ns
         row_end = limit if row_end is None else row_end
@@ -499,6 +507,44 @@ class DeviceGraph:
         finally:
             p.close()
 
+    def support(self, rows, targets, M: int = 16, queries: Optional["DeviceQueries"] = None, loo: bool = False):
+        """Which sources carry the scores of the (row, target) pairs ``zip(rows, targets)`` (ss_support_*): returns
+        ``(src, contrib, nsupp)`` with src, contrib of shape (npairs, M) -- the sources s with the largest contributions
+        ``T[r,s] * Ys[s,t]`` in descending order (ties by ascending s; unused slots -1 / 0) -- and nsupp[p] the number of
+        sources that contribute at all.  rows are query rows of ``queries`` (a ``DeviceQueries`` of this graph), of the
+        graph's own query block, or with ``loo=True`` leave-one-out folds.  numpy in, numpy out; CUDA tensors (int64
+        rows, int32 targets) in, CUDA tensors out."""
+        lib = L.lib()
+        kind = L.SS_ROWS_LOO if loo else L.SS_ROWS_QUERY
+        qh = None if queries is None else queries._h
+        fn = getattr(lib, f"ss_support_{self._suf}")
+        M = int(M)
+        if _is_torch(rows):
+            import torch
+            r = rows.to(torch.int64).contiguous()
+            t = targets.to(torch.int32).contiguous()
+            if r.ndim != 1 or r.shape != t.shape or not (r.is_cuda and t.is_cuda):
+                raise ValueError("rows and targets must be 1-D CUDA tensors of one length")
+            n = int(r.numel())
+            m = max(M, 1)
+            src = torch.empty((n, m), dtype=torch.int32, device=r.device)
+            con = torch.empty((n, m), dtype=torch.float32 if self._suf == "f32" else torch.float64, device=r.device)
+            cnt = torch.empty(n, dtype=torch.int32, device=r.device)
+            L.check(fn(self._h, qh, kind, n, r.data_ptr(), t.data_ptr(), M, src.data_ptr(), con.data_ptr(),
+                       cnt.data_ptr(), L.SS_MEM_DEVICE))
+            return src, con, cnt
+        r = np.ascontiguousarray(rows, dtype=np.int64)
+        t = np.ascontiguousarray(targets, dtype=np.int32)
+        if r.ndim != 1 or r.shape != t.shape:
+            raise ValueError("rows and targets must be 1-D arrays of one length")
+        n = r.shape[0]
+        m = max(M, 1)
+        src = np.empty((n, m), np.int32)
+        con = np.empty((n, m), self.dtype)
+        cnt = np.empty(n, np.int32)
+        L.check(fn(self._h, qh, kind, n, _ptr(r), _ptr(t), M, _ptr(src), _ptr(con), _ptr(cnt), L.SS_MEM_HOST))
+        return src, con, cnt
+
     # ---------------------------------------------------------------- cutoff sweeps
     def _ctype(self):
         return C.c_float if self.dtype == np.float32 else C.c_double
@@ -525,6 +571,130 @@ class DeviceGraph:
     def close(self):
         if self._h is not None and self._h.value:
             L.load().ss_graph_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceQueries:
+    """A block of query rows bound to one resident ``DeviceGraph`` (ss_queries_*): screen new batches on the graph that
+    was built and cross-validated once.  ``g.predict(queries=q)`` gives bitwise the scores of the graph built with these
+    queries; creating, using and closing query sets leaves every result of the graph itself unchanged.  The
+    constructors mirror the graph's: ``from_sparse`` takes the (nq, nf) block itself, the others cut the cross block of
+    raw query data against the sources ``Fs`` -- pass the Fs, alpha, weighted (and metric) the graph was built with."""
+
+    def __init__(self, handle, graph: DeviceGraph):
+        self._h = handle
+        self.dtype = graph.dtype
+        info = (C.c_int64 * 3)()
+        L.check(L.load().ss_queries_info(self._h, info))
+        self.nq, self.nf, self.nnz = [int(v) for v in info]
+
+    @classmethod
+    def from_sparse(cls, graph: DeviceGraph, Xq, index_base: int = 0):
+        """Xq: a scipy matrix (nq, nf) (converted to ``index_base``), or a (ptr int64, idx int32, val, nq) CSR tuple of
+        numpy arrays or CUDA tensors that already has that base (val None: all ones)."""
+        lib = L.lib()
+        dt = graph.dtype.type
+        keep = []
+        if isinstance(Xq, tuple):
+            ptr, idx, val, nq = Xq
+            if _is_torch(ptr):
+                import torch
+                want = torch.float32 if dt == np.float32 else torch.float64
+                ptr, idx = ptr.to(torch.int64).contiguous(), idx.to(torch.int32).contiguous()
+                val = None if val is None else val.to(want).contiguous()
+                keep.extend([ptr, idx, val])
+                args = (ptr.data_ptr(), idx.data_ptr(), None if val is None else val.data_ptr())
+                mem = L.SS_MEM_DEVICE
+            else:
+                parts = (np.ascontiguousarray(ptr, dtype=np.int64), np.ascontiguousarray(idx, dtype=np.int32),
+                         None if val is None else np.ascontiguousarray(val, dtype=dt))
+                keep.append(parts)
+                args = (_ptr(parts[0]), _ptr(parts[1]), _ptr(parts[2]))
+                mem = L.SS_MEM_HOST
+        else:
+            import scipy.sparse as sp
+            Xq = sp.csr_matrix(Xq)
+            if Xq.shape[1] != graph.nf:
+                raise AssertionError("Number of features between test and training sets doesn't match")
+            nq = Xq.shape[0]
+            parts = _csr_parts(Xq, dt)
+            if index_base:
+                parts = (parts[0] + index_base, parts[1] + np.int32(index_base), parts[2])
+            keep.append(parts)
+            args = (_ptr(parts[0]), _ptr(parts[1]), _ptr(parts[2]))
+            mem = L.SS_MEM_HOST
+        h = C.c_void_p()
+        fn = getattr(lib, f"ss_queries_create_csr_{_suffix(dt)}")
+        L.check(fn(graph._h, int(nq), *args, int(index_base), mem, C.byref(h)))
+        if mem == L.SS_MEM_DEVICE:
+            L.check(lib.ss_synchronize())
+        del keep
+        return cls(h, graph)
+
+    @classmethod
+    def from_fingerprints(cls, graph: DeviceGraph, Fq, Fs, alpha: float, weighted: bool = True):
+        """Xq = cut(Tanimoto(Fq, Fs)) as ``DeviceGraph.from_fingerprints`` stores it; inputs as there."""
+        lib = L.lib()
+        dt = graph.dtype.type
+        dev = _is_torch(Fs)
+        keep = []
+        fq, nq, nwq = _fingerprints(Fq, dev, keep)
+        fs, ns, nwords = _fingerprints(Fs, dev, keep)
+        if Fq is not None and nwq != nwords:
+            raise ValueError("Fq and Fs have different fingerprint widths")
+        h = C.c_void_p()
+        fn = getattr(lib, f"ss_queries_create_fingerprint_{_suffix(dt)}")
+        L.check(fn(graph._h, nq, ns, nwords, fq, fs, graph._ctype()(alpha), 1 if weighted else 0,
+                   L.SS_MEM_DEVICE if dev else L.SS_MEM_HOST, C.byref(h)))
+        if dev:
+            L.check(lib.ss_synchronize())
+        del keep
+        return cls(h, graph)
+
+    @classmethod
+    def _from_rows(cls, name, graph, Fq, Fs, mid, alpha, weighted):
+        lib = L.lib()
+        dt = graph.dtype.type
+        dev = _is_torch(Fs)
+        keep = []
+        fq, nq, dq, ldq = _features(Fq, dt, dev, keep)
+        fs, ns, d, lds = _features(Fs, dt, dev, keep)
+        if Fq is not None and dq != d:
+            raise ValueError("Fq and Fs have different numbers of features")
+        h = C.c_void_p()
+        fn = getattr(lib, f"ss_queries_create_{name}_{_suffix(dt)}")
+        L.check(fn(graph._h, nq, ns, d, *mid, fq, ldq, fs, lds, graph._ctype()(alpha), 1 if weighted else 0,
+                   L.SS_MEM_DEVICE if dev else L.SS_MEM_HOST, C.byref(h)))
+        if dev:
+            L.check(lib.ss_synchronize())
+        del keep
+        return cls(h, graph)
+
+    @classmethod
+    def from_features(cls, graph: DeviceGraph, Fq, Fs, alpha: float, weighted: bool = True):
+        """Xq = cut(J(Fq, Fs)), the weighted Jaccard block of ``DeviceGraph.from_features``; inputs as there."""
+        return cls._from_rows("features", graph, Fq, Fs, (), alpha, weighted)
+
+    @classmethod
+    def from_vectors(cls, graph: DeviceGraph, Fq, Fs, alpha: float, metric="cosine", weighted: bool = True):
+        """Xq = cut(S(Fq, Fs)), the inner-product block of ``DeviceGraph.from_vectors``; inputs as there."""
+        return cls._from_rows("vectors", graph, Fq, Fs, (_sim_metric(metric),), alpha, weighted)
+
+    def degrees(self) -> np.ndarray:
+        """Stored entries of every query row: 0 = no source is similar enough (outside the applicability domain)."""
+        kq = np.zeros(self.nq, np.int64)
+        L.check(L.lib().ss_queries_degrees(self._h, _ptr(kq), L.SS_MEM_HOST))
+        return kq
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            L.load().ss_queries_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -1134,14 +1304,15 @@ class TargetTopL:
         return self
 
     def add_predict(self, g: "DeviceGraph", rows: str = "query", begin: int = 0, end: Optional[int] = None,
-                    clean: bool = False, y=None, block_rows: int = 0):
+                    clean: bool = False, y=None, block_rows: int = 0, queries: Optional["DeviceQueries"] = None):
         """Virtual screening: the scores of rows [begin, end) of the query (or source) nodes, predicted block by block
         into a device buffer (DeviceGraph.predict(..., out=tensor)) and added with row ids begin..end-1.  `y`: labels
         of those rows (scipy / dense 0/1, shape (end - begin, nt)) or None -- unlabelled rows count as negatives.
-        block_rows: rows per block (0: about 1 GiB of scores)."""
+        block_rows: rows per block (0: about 1 GiB of scores).  queries: a ``DeviceQueries`` of `g` whose rows are
+        screened instead of the graph's own."""
         import scipy.sparse as sp
         import torch
-        limit = g.nq if rows == "query" else g.ns
+        limit = queries.nq if queries is not None else (g.nq if rows == "query" else g.ns)
         end = limit if end is None else end
         n = end - begin
         if n <= 0:
@@ -1159,7 +1330,7 @@ class TargetTopL:
         for r0 in range(0, n, rb):
             nb = min(rb, n - r0)
             out = buf[:nb]
-            g.predict(rows, begin + r0, begin + r0 + nb, clean=clean, out=out)
+            g.predict(rows, begin + r0, begin + r0 + nb, clean=clean, out=out, queries=queries)
             self.add_rows(Y[r0:r0 + nb], out, row_begin=begin + r0)
         return self
 
