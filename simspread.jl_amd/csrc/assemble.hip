@@ -419,6 +419,78 @@ __global__ void sell_width_kernel(const int* __restrict__ ptr, const int* __rest
   if (lane == 0) widthq[wave] = (n + 3) >> 2;
 }
 
+// Slot lending (DevSell, graph.hpp): one wave per (chunk, slice) chooses the slice's length Q2 (-> widthq) and the
+// boundary Q1 (-> q1).  For a given Q1 (a multiple of SELL_Q1_STEP) the receivers are the lanes with at most 4*Q1
+// entries -- lanes past the last row are empty rows -- and a receiver offers cap = 4*(Q2 - Q1) slots to one donor; a row
+// with e = n - 4*Q2 > 0 entries too many needs ceil(e / cap) <= SELL_LEND_R receivers.  (Q1, Q2) is valid when the
+// donors' needs fit the receivers; that is monotone in Q2, so the smallest valid Q2 of every Q1 is found by bisection.
+// The smallest Q2 wins (ties: the largest Q1); none below the longest row: Q1 = Q2 = longest row, the plain layout.
+__global__ void sell_plan_kernel(const int* __restrict__ ptr, const int* __restrict__ idx, int64_t rows, int KC,
+                                 int nslices, int nchunks, int* __restrict__ widthq, int* __restrict__ q1,
+                                 int* __restrict__ nlend) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (wave >= (int64_t)nslices * nchunks) return;
+  const int c = (int)(wave / nslices), s = (int)(wave % nslices);
+  const int64_t pos = (int64_t)s * 64 + lane;
+  int n = 0;
+  if (pos < rows) {
+    const int lo = ptr[pos], hi = ptr[pos + 1];
+    const int64_t k0 = (int64_t)c * KC, k1 = k0 + KC;
+    int a = lo, b = hi;
+    while (a < b) { const int m = (a + b) >> 1; if (idx[m] < k0) a = m + 1; else b = m; }
+    const int first = a;
+    b = hi;
+    while (a < b) { const int m = (a + b) >> 1; if (idx[m] < k1) a = m + 1; else b = m; }
+    n = a - first;
+  }
+  int nmax = n, tot = n;
+  for (int o = 32; o > 0; o >>= 1) {
+    const int t = __shfl_xor(nmax, o);
+    nmax = t > nmax ? t : nmax;
+    tot += __shfl_xor(tot, o);
+  }
+  const int qmax = (nmax + 3) >> 2;
+  auto valid = [&](int Q1, int Q2, int nrecv) {
+    const int cap = 4 * (Q2 - Q1);
+    const int e = n > 4 * Q2 ? n - 4 * Q2 : 0;
+    const int need = (e + cap - 1) / cap;
+    if (__ballot(need > SELL_LEND_R) != 0ull) return false;
+    const int sum = __popcll(__ballot(need >= 1)) + __popcll(__ballot(need >= 2)) + __popcll(__ballot(need >= 3));
+    return sum <= nrecv;
+  };
+  static_assert(SELL_LEND_R == 3, "the sum of the needs above counts up to three receivers per donor");
+  int bq1 = qmax, bq2 = qmax;
+  const int qmin = (tot + 255) >> 8;   // the entries of the slice need that many quads whoever holds them
+  for (int Q1 = 0; Q1 < qmax - 1; Q1 += SELL_Q1_STEP) {
+    const int nrecv = __popcll(__ballot(n <= 4 * Q1));
+    if (nrecv == 0) continue;
+    int lo = Q1 + 1 > qmin ? Q1 + 1 : qmin;
+    int hi = bq2 < qmax - 1 ? bq2 : qmax - 1;
+    if (lo > hi || !valid(Q1, hi, nrecv)) continue;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (valid(Q1, mid, nrecv)) hi = mid; else lo = mid + 1;
+    }
+    bq1 = Q1;
+    bq2 = hi;
+  }
+  if (lane == 0) {
+    widthq[wave] = bq2;
+    q1[wave] = bq1;
+    if (bq1 < bq2) atomicAdd(nlend, 1);
+  }
+}
+
+// the plain layout's metadata: nothing lent
+__global__ void sell_meta_plain_kernel(const int* __restrict__ off, int64_t nws, int* __restrict__ q1,
+                                       unsigned* __restrict__ rec) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nws * 64; i += (int64_t)gridDim.x * blockDim.x) {
+    rec[i] = SELL_REC_NONE;
+    if ((i & 63) == 0) q1[i >> 6] = off[(i >> 6) + 1] - off[i >> 6];
+  }
+}
+
 template <class T>
 __global__ void sell_fill_kernel(const int* __restrict__ ptr, const int* __restrict__ idx, const T* __restrict__ val,
                                  int64_t rows, int KC, int nslices, int nchunks, const int* __restrict__ off,
@@ -486,12 +558,15 @@ __global__ void __launch_bounds__(64) sell_fill_sched_kernel(const int* __restri
                                                              int nslices, int nchunks, const int* __restrict__ off,
                                                              const int* __restrict__ vs, const int* __restrict__ ve,
                                                              int* __restrict__ perm, unsigned short* __restrict__ sidx,
-                                                             T* __restrict__ sval, int ncls, int npid) {
+                                                             T* __restrict__ sval, int ncls, int npid,
+                                                             const int* __restrict__ q1, unsigned* __restrict__ rec) {
   // ncls slot classes (tile rows per 256-byte LDS line: 16 for 16-byte rows, 8 for 32-byte rows), npid pieces per tile
   // row: a lane reads piece r ^ (lane & (npid - 1)) in read r, so only lanes with the same lane & (npid - 1) compete for
   // a class (claim bit = pid * ncls + class)
   __shared__ unsigned short cnt[64][17];
   __shared__ int cur[64][17];
+  __shared__ int sh_exc[64], sh_start[64];
+  __shared__ unsigned char sh_recv[64][4];
   const int lane = threadIdx.x;
   const int64_t wave = blockIdx.x;
   const int c = (int)(wave / nslices), s = (int)(wave % nslices);
@@ -529,10 +604,10 @@ __global__ void __launch_bounds__(64) sell_fill_sched_kernel(const int* __restri
   // row with the fewest slots that are still free picks next (ties: the longer rest), and takes the free slot it has the
   // most entries in.  On Poisson(100) rows this leaves 1.10 LDS cycles per group and position instead of 1.23 (simulated;
   // the kernel counters agree).  A row whose slots are all taken adds a conflict wherever it goes.
-  for (int p = 0; p < (oe - o) * 4; ++p) {
-    unsigned claimed = 0;
+  // `claimed`: the slots taken before the first pick; `done`: this lane does not pick; `may_wait`: when all its slots are
+  // taken the lane passes (it has positions to spare) instead of adding a conflict.  Returns the lane's slot or -1.
+  auto pick = [&](unsigned& claimed, bool done, bool may_wait) {
     int mine = -1;
-    bool done = left == 0;
     for (int it = 0; it < 16; ++it) {
       if (__ballot(!done) == 0ull) break;
       const int rest = left > 4095 ? 4095 : left;
@@ -551,7 +626,7 @@ __global__ void __launch_bounds__(64) sell_fill_sched_kernel(const int* __restri
           const int cq = cnt[lane][q];
           if (cq > bestc && !((claimed >> (psh + q)) & 1u)) { best = q; bestc = cq; }
         }
-        if (best < 0)
+        if (best < 0 && !may_wait)
           for (int q = 0; q < ncls; ++q) {
             const int cq = cnt[lane][q];
             if (cq > bestc) { best = q; bestc = cq; }
@@ -564,23 +639,101 @@ __global__ void __launch_bounds__(64) sell_fill_sched_kernel(const int* __restri
       const int ch = __shfl(choice, wl);
       if (any && ch >= 0) claimed |= 1u << ((wl & (npid - 1)) * ncls + ch);
     }
+    return mine;
+  };
+  // the entry of slot `mine` goes to `base`; a lane's entries of one slot lie `step` apart in perm
+  auto place = [&](int64_t base, int mine, int step) {
+    const int e = perm[cur[lane][mine]];
+    cur[lane][mine] += step;
+    cnt[lane][mine]--;
+    if (cnt[lane][mine] == 0) have &= ~(1u << mine);
+    --left;
+    sidx[base] = (unsigned short)(idx[e] - k0);
+    if (sval) sval[base] = val[e];
+  };
+  // padding: one of the 16 zero rows behind the tile (KC .. KC+15, spmm_sell_kernel), the one whose 16-byte slot no
+  // active lane of this LDS cycle reads (the lowest free one; padding lanes of a group share it: same address)
+  auto pad = [&](int64_t base, unsigned claimed) {
+    int q = 0;
+    while (q < ncls - 1 && ((claimed >> (psh + q)) & 1u)) ++q;
+    sidx[base] = (unsigned short)(KC + ((q - KC) & (ncls - 1)));
+    if (sval) sval[base] = T(0);
+  };
+  // A slice that lends (q1[wave] < its quads, DevSell) ends below its longest rows: their first entries stay, in the
+  // order and at the positions they have in the plain layout, and what is left over when the slice ends is lent below.
+  for (int p = 0; p < (oe - o) * 4; ++p) {
+    unsigned claimed = 0;
+    const int mine = pick(claimed, left == 0, false);
     const int64_t base = ((int64_t)(o + (p >> 2)) * 64 + lane) * 4 + (p & 3);
-    if (mine >= 0) {
-      const int e = perm[cur[lane][mine]];
-      cur[lane][mine]++;
-      cnt[lane][mine]--;
-      if (cnt[lane][mine] == 0) have &= ~(1u << mine);
-      --left;
-      sidx[base] = (unsigned short)(idx[e] - k0);
-      if (sval) sval[base] = val[e];
-    } else {
-      // padding: one of the 16 zero rows behind the tile (KC .. KC+15, spmm_sell_kernel), the one whose 16-byte slot no
-      // active lane of this LDS cycle reads (the lowest free one; padding lanes of a group share it: same address)
-      int q = 0;
-      while (q < ncls - 1 && ((claimed >> (psh + q)) & 1u)) ++q;
-      sidx[base] = (unsigned short)(KC + ((q - KC) & (ncls - 1)));
-      if (sval) sval[base] = T(0);
+    if (mine >= 0) place(base, mine, 1);
+    else pad(base, claimed);
+  }
+  const int Q2 = oe - o, Q1 = q1 ? q1[wave] : Q2;
+  if (!rec) return;
+  if (Q1 >= Q2) {
+    rec[wave * 64 + lane] = SELL_REC_NONE;
+    return;
+  }
+  // Donors in the order (excess descending, lane ascending) take the receivers in ascending lane order, as many as their
+  // excess needs at cap entries each (sell_plan_kernel saw that they suffice)
+  const int cap = 4 * (Q2 - Q1);
+  const int exc = left;
+  sh_exc[lane] = exc;
+  sh_recv[lane][0] = sh_recv[lane][1] = sh_recv[lane][2] = 0xff;
+  __syncthreads();
+  int start = -1;
+  if (exc > 0) {
+    start = 0;
+    for (int l = 0; l < 64; ++l) {
+      const int ol = sh_exc[l];
+      if (ol > exc || (ol == exc && l < lane)) start += (ol + cap - 1) / cap;
     }
+  }
+  sh_start[lane] = start;
+  __syncthreads();
+  const bool can_recv = n <= 4 * Q1;
+  const int ridx = __popcll(__ballot(can_recv) & ((1ull << lane) - 1ull));
+  int donor = -1, part = 0, parts = 1;
+  if (can_recv)
+    for (int l = 0; l < 64; ++l) {
+      const int need = (sh_exc[l] + cap - 1) / cap;
+      if (need > 0 && ridx >= sh_start[l] && ridx < sh_start[l] + need) { donor = l; part = ridx - sh_start[l]; parts = need; }
+    }
+  if (donor >= 0 && part < SELL_LEND_R) sh_recv[donor][part] = (unsigned char)lane;
+  __syncthreads();
+  rec[wave * 64 + lane] = (unsigned)sh_recv[lane][0] | ((unsigned)sh_recv[lane][1] << 8) | ((unsigned)sh_recv[lane][2] << 16) |
+                          (donor >= 0 ? 1u << 24 : 0u);
+  // receiver `part` of `parts` takes every parts-th of its donor's left-over entries, counted through the donor's slot
+  // buckets: a mix of slots, and nobody else's entries
+  left = 0;
+  have = 0;
+  if (donor >= 0) {
+    int pre = 0;
+    for (int q = 0; q < ncls; ++q) {
+      const int cd = cnt[donor][q];
+      const int f = pre + (((part - pre) % parts) + parts) % parts;
+      const int cq = f < pre + cd ? (pre + cd - 1 - f) / parts + 1 : 0;
+      cnt[lane][q] = (unsigned short)cq;
+      cur[lane][q] = cur[donor][q] + (f - pre);
+      if (cq > 0) have |= 1u << q;
+      left += cq;
+      pre += cd;
+    }
+  }
+  __syncthreads();
+  // quads Q1 .. Q2-1: what stands there stays and keeps its slot; the receivers pick among the slots that are left -- one
+  // that finds them all taken waits for a later position as long as it has more positions than entries left -- and the
+  // padding lanes then move to a zero row that is still free
+  for (int p = Q1 * 4; p < Q2 * 4; ++p) {
+    const int64_t base = ((int64_t)(o + (p >> 2)) * 64 + lane) * 4 + (p & 3);
+    const unsigned short held = sidx[base];
+    const bool fixed = held < KC;
+    unsigned claimed = fixed ? 1u << (psh + (held & (ncls - 1))) : 0u;
+#pragma unroll
+    for (int m2 = 1; m2 < 16; m2 <<= 1) claimed |= (unsigned)__shfl((int)claimed, b128_lane_of_group(grp, gi ^ m2));
+    const int mine = pick(claimed, !(donor >= 0 && left > 0), left < Q2 * 4 - p);
+    if (mine >= 0) place(base, mine, parts);
+    else if (!fixed) pad(base, claimed);
   }
 }
 
@@ -704,6 +857,38 @@ int sell_build(const DevCsr<T>& in, int KCmax, DevSell<T>& out, int qt) {
     SS_HIP(hipStreamSynchronize(st));
   }
   const int64_t nws_f = (int64_t)out.nslices * out.nchunks;
+  // slot lending (DevSell): the kernel reads q1 / rec for 16-byte tile rows, so they exist for every such operand
+  out.lends = false;
+  const bool plain = env_set("SS_SELL_PLAIN");
+  if (rowb == 16) {
+    SS_TRY(out.q1.alloc(nws_f + 1));   // [nws_f]: the number of slices that lend
+    SS_TRY(out.rec.alloc(nws_f * 64));
+    if (!out.sorted && !plain && env_int("SS_SELL_LEND", 1) != 0) {
+      SS_HIP(hipMemsetAsync(out.q1.p + nws_f, 0, sizeof(int), st));
+      hipLaunchKernelGGL(sell_plan_kernel, dim3((unsigned)ceil_div(nws_f * 64, 256)), dim3(256), 0, st, in.ptr.p, in.idx.p,
+                         in.rows, out.KC, out.nslices, out.nchunks, widthq.p, out.q1.p, out.q1.p + nws_f);
+      SS_LAUNCH_CHECK();
+      int nlend = 0;
+      SS_TRY(read_int(out.q1.p + nws_f, &nlend));
+      if (nlend > 0) {
+        out.lends = true;
+        SS_TRY(exclusive_scan_int(widthq.p, out.off.p, nws_f));
+        SS_TRY(read_int(out.off.p + nws_f, &nq));
+      }
+    }
+    if (!out.lends) {
+      hipLaunchKernelGGL(sell_meta_plain_kernel, dim3(grid_for(nws_f * 64, 256)), dim3(256), 0, st, (const int*)out.off.p,
+                         nws_f, out.q1.p, out.rec.p);
+      SS_LAUNCH_CHECK();
+    }
+  } else {
+    out.q1.release();
+    out.rec.release();
+  }
+  if (env_int("SS_SELL_STATS", 0) != 0)
+    fprintf(stderr, "sell_build: rows %lld cols %lld nnz %lld chunks %d slices %d quads %d slots_per_nnz %.4f lend %d sorted %d\n",
+            (long long)in.rows, (long long)in.cols, (long long)in.nnz, out.nchunks, out.nslices, nq,
+            in.nnz > 0 ? (double)nq * 256.0 / (double)in.nnz : 0.0, out.lends ? 1 : 0, out.sorted ? 1 : 0);
   if (nq < 0 || (int64_t)nq * 256 >= (1LL << 40)) return fail(SS_EUNSUPPORTED, "SELL storage too large");
   out.nquads = nq;
   // two groups of four quads of slack: the SpMM kernel loads (and ignores) up to that much past the last slice
@@ -730,7 +915,7 @@ int sell_build(const DevCsr<T>& in, int KCmax, DevSell<T>& out, int qt) {
                        out.vrows, out.KC, out.nslices, out.nchunks, out.off.p,
                        out.sorted ? (const int*)out.vs.p : (const int*)nullptr,
                        out.sorted ? (const int*)out.ve.p : (const int*)nullptr, perm.p, out.idx.p,
-                       out.binary ? (T*)nullptr : out.val.p, ncls, npid);
+                       out.binary ? (T*)nullptr : out.val.p, ncls, npid, (const int*)out.q1.p, out.rec.p);
     SS_LAUNCH_CHECK();
     SS_HIP(hipStreamSynchronize(st));
   }

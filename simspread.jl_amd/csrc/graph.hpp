@@ -22,6 +22,10 @@ struct DevCsr {
   bool binary = false;  // every stored value == 1
 };
 
+constexpr int SELL_Q1_STEP = 8;   // = 2 * SELL_NB (kernels.hip): the quads of one turn of spmm_sell_kernel's gather loop
+constexpr int SELL_LEND_R = 3;    // receivers per donor row: their lanes fit bytes 0-2 of a lane's record
+constexpr unsigned SELL_REC_NONE = 0x00ffffffu;
+
 template <class T>
 struct DevSell {
   int64_t rows = 0, cols = 0;
@@ -34,6 +38,17 @@ struct DevSell {
   DevBuf<int> off;              // [nchunks*nslices + 1] quad offsets, chunk-major
   DevBuf<unsigned short> idx;   // [nquads][64][4]
   DevBuf<T> val;                // [nquads][64][4] unless binary
+  // Slot lending (16-byte tile rows, not sorted; SS_SELL_LEND=0: off).  A slice is as long as its longest row, so short
+  // rows pad it.  Slice (chunk, slice) = w is cut at Q2 = off[w+1] - off[w] quads, below its longest row, when the rows
+  // longer than 4*Q2 ("donors") can park their excess in the quads q1[w] .. Q2-1 of rows with at most 4*q1[w] entries
+  // ("receivers": one donor each, at most SELL_LEND_R receivers per donor).  q1[w] is a multiple of SELL_Q1_STEP, the
+  // unit in which the kernel consumes quads; q1[w] == Q2: nothing is lent in the slice.  rec[w*64 + lane]: bytes 0-2 =
+  // the lanes whose partial sums this lane adds to its own, in that order (0xFF: none); bit 24: this lane is a receiver
+  // (its own sum ends at quad q1[w], what follows belongs to its donor).  Every row stays on its lane: the store and the
+  // row order are those of the plain layout, and the entries a lane keeps sit where the plain layout puts them.
+  DevBuf<int> q1;               // [nchunks*nslices] (16-byte tile rows only)
+  DevBuf<unsigned> rec;         // [nchunks*nslices][64]
+  bool lends = false;           // at least one slice lends
   // skewed row lengths (power-law graphs): rows are sorted by length before they are cut into slices so
   // that the 64 rows of a slice are equally long; results then come out in sorted order and are put back
   // by unpermute_kernel.  perm[sorted position] = row, inv[row] = sorted position.

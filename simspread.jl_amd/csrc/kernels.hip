@@ -97,10 +97,13 @@ struct SellArgs {
   int64_t ldf;
   const int* clean_deg;
   const int* out_rows;  // optional: column b of R goes to row out_rows[b] of F (k-fold members -> source rows)
+  const int* q1;        // 16-byte tile rows: slot lending (DevSell), per (chunk, slice) the quads before the lent ones ...
+  const unsigned* rec;  // ... and per lane whose partial sums it collects, and whether it is a receiver
 };
 
 constexpr int SELL_THREADS = 1024;
 constexpr int SELL_NB = 4;  // quads of W in flight per lane ahead of the gathers
+static_assert(SELL_Q1_STEP == 2 * SELL_NB, "a lending slice's first part must end with a turn of the gather loop");
 constexpr int SELL_QT_F32_DEFAULT = 4;
 constexpr int SELL_ZERO_ROWS = 16;  // zero rows behind the tile: one per 16-byte slot class of the 256-byte LDS line
 constexpr int SELL_STAGE_IT = 5;  // passes of SELL_THREADS per staging round (the largest tile, 10240 rows, takes two rounds)
@@ -198,6 +201,13 @@ __global__ void __launch_bounds__(SELL_THREADS) spmm_sell_kernel(SellArgs<T> a) 
         if (NP == 1 && c && m < a.M && b0 + q < a.B)   // (two-piece rows: read when the slice is done -- registers)
           fprev[q] = a.F[(a.out_rows ? (int64_t)a.out_rows[b0 + q] : b0 + q) * a.ldf + m];
       }
+      // slot lending (DevSell): quads q1 .. nq-1 of a receiver lane hold entries of another row of the slice
+      int q1 = oe - o;
+      unsigned rec = SELL_REC_NONE;
+      if (NP == 1) {
+        q1 = __builtin_amdgcn_readfirstlane(a.q1[(int64_t)c * a.nslices + s]);
+        rec = a.rec[((int64_t)c * a.nslices + s) * 64 + lane];
+      }
       const ushort4* ip = reinterpret_cast<const ushort4*>(a.idx) + (int64_t)o * 64 + lane;
       const Vec<T, 4>* vp = reinterpret_cast<const Vec<T, 4>*>(a.val) + (int64_t)o * 64 + lane;
       // NB quads of indices (and values) are fetched ahead of the LDS gathers they feed: the index stream comes
@@ -272,19 +282,54 @@ __global__ void __launch_bounds__(SELL_THREADS) spmm_sell_kernel(SellArgs<T> a) 
       // Two register sets, both requested before the first gather; a slice is a whole number of QUADS (not of groups, since
       // round 3): the last one or two groups are consumed quad by quad under wave-uniform conditions, outside the loop.
       // Requests run up to two groups past the slice (the next slice, or the slack behind the last one).
+      //
+      // A slice that lends (q1 < nq; q1 is a multiple of 2 * NBQ, so it ends a turn of the loop): where its first part
+      // ends the receivers put their own sums aside and start from zero -- one wave-uniform test per turn, away from the
+      // loads and the gathers; every other lane carries on in one chain, so its sums are those of the plain layout.  After
+      // the last quad a lane adds the partial sums of the lanes its record lists (ds_bpermute: the LDS crossbar, no LDS
+      // storage), in list order, and the receivers take their own sums back.  (q1 == 0: the receivers' own sums are 0.)
       fetch(ia, wa, 0);
       fetch(ib, wb, NBQ);
+      const bool recv = NP == 1 && ((rec >> 24) & 1u);
+      T own[QT];
+#pragma unroll
+      for (int q = 0; q < QT; ++q) own[q] = T(0);
       int u = 0;
       for (; u + 2 * NBQ <= nq; u += 2 * NBQ) {
         gather(ia, wa, NBQ);
         fetch(ia, wa, u + 2 * NBQ);
         gather(ib, wb, NBQ);
         fetch(ib, wb, u + 3 * NBQ);
+        if (NP == 1 && u + 2 * NBQ == q1) {
+#pragma unroll
+          for (int q = 0; q < QT; ++q) { own[q] = recv ? acc[q] : own[q]; acc[q] = recv ? T(0) : acc[q]; }
+        }
       }
       {
         const int rest = nq - u;   // 0 .. 2 * NBQ - 1 quads; ia holds quads u .., ib quads u + NBQ ..
         if (rest > 0) gather(ia, wa, rest < NBQ ? rest : NBQ);
         if (rest > NBQ) gather(ib, wb, rest - NBQ);
+      }
+      if (NP == 1 && q1 < nq) {
+        constexpr int NW = (int)(sizeof(T) * QT / 4);
+        int lent[NW];
+        __builtin_memcpy(lent, acc, sizeof(lent));
+#pragma unroll
+        for (int r = 0; r < SELL_LEND_R; ++r) {
+          const unsigned src = (rec >> (8 * r)) & 0xffu;
+          if (__ballot(src != 0xffu) == 0ull) break;   // (the lists are filled from byte 0 on)
+          // a lane with nothing to collect reads itself: every lane reading one lane would serialise in the crossbar
+          const int from = (int)((src != 0xffu ? src : (unsigned)lane) << 2);
+          int got[NW];
+#pragma unroll
+          for (int w = 0; w < NW; ++w) got[w] = __builtin_amdgcn_ds_bpermute(from, lent[w]);
+          T add[QT];
+          __builtin_memcpy(add, got, sizeof(got));
+#pragma unroll
+          for (int q = 0; q < QT; ++q) acc[q] = src != 0xffu ? acc[q] + add[q] : acc[q];
+        }
+#pragma unroll
+        for (int q = 0; q < QT; ++q) acc[q] = recv ? own[q] : acc[q];
       }
       if (m < a.M) {
         const bool flag = last && a.clean_deg != nullptr && a.clean_deg[m] == 0;
@@ -341,6 +386,9 @@ int launch_spmm_sell(const DevSell<T>& W, const T* R, int64_t ldr, int64_t B, T*
   a.ldf = ldf;
   a.clean_deg = clean_deg;
   a.out_rows = out_rows;
+  a.q1 = W.q1.p;
+  a.rec = W.rec.p;
+  if (W.lends) path_add("sell_lend");
   const size_t lds = (size_t)(W.KC + SELL_ZERO_ROWS) * QT * sizeof(T);
   if (lds > (size_t)160 * 1024) return fail(SS_EINVAL, "SELL chunk does not fit the LDS tile of %d columns", QT);
   const unsigned gx = (unsigned)ceil_div(B, QT);
