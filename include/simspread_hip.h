@@ -672,7 +672,10 @@ int ss_target_topl_import_f64(ss_target_topl* h, const double* vals, const int64
 int ss_target_topl_metrics(ss_target_topl* h, int64_t* hits, int64_t* npos, double out[4], int mem);
 
 /* Query sets (ss_queries_*, ss_predict_queries_*) and support lists (ss_support_*) -- prospective screening on a resident
- * graph -- are declared in simspread_hip_screening.h, which this header includes at its end. */
+ * graph -- are declared in simspread_hip_screening.h, which this header includes at its end.  The neighbour floor of the
+ * fingerprint producer (ss_similarity_tanimoto_kth_*, ss_similarity_tanimoto_floor_csr_*, ss_graph_create_fingerprint_floor_*,
+ * ss_queries_create_fingerprint_floor_*: "at least the k nearest sources, whatever alpha says") is declared in
+ * simspread_hip_neighbours.h, included there too. */
 
 /* -------------------------------------------------------------- raw W*R SpMM --- */
 /* The resource-spreading product F = W * R on its own (kernel unit tests and the
@@ -700,5 +703,6 @@ int ss_spmat_cost(const ss_spmat* w, int64_t B, double* bytes, double* flops);
 #endif
 
 #include "simspread_hip_screening.h"
+#include "simspread_hip_neighbours.h"
 
 #endif /* SIMSPREAD_HIP_H */

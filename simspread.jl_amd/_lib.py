@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SS_LIB_PATH") or os.path.join(_HERE, "libsimspread_hip.so")   # SS_LIB_PATH: A/B builds of the same ABI
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip.h")
 SCREENING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_screening.h")   # included by it
+NEIGHBOURS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_neighbours.h")  # included by it
 
 SS_OK = 0
 SS_MEM_HOST, SS_MEM_DEVICE = 0, 1
@@ -151,6 +152,22 @@ def _screening_sigs():
 SCREENING_SIGNATURES = _screening_sigs()
 
 
+def _neighbour_sigs():
+    """include/simspread_hip_neighbours.h: the neighbour floor of the fingerprint producer"""
+    s = {}
+    for suf, ft in (("f32", C.c_float), ("f64", C.c_double)):
+        s[f"ss_similarity_tanimoto_kth_{suf}"] = ([_vp, _i64, _vp, _i64, _i64, _int, _vp, _int], _int)
+        s[f"ss_similarity_tanimoto_floor_csr_{suf}"] = ([_vp, _i64, _vp, _i64, _i64, ft, _int, _int, _vp, _vp, _vp, _i64,
+                                                         _vp, _int], _int)
+        s[f"ss_graph_create_fingerprint_floor_{suf}"] = ([_i64] * 4 + [_vp] * 5 + [_int, ft, _int, _int, _int, _vp], _int)
+        s[f"ss_queries_create_fingerprint_floor_{suf}"] = ([_vp, _i64, _i64, _i64, _vp, _vp, ft, _int, _int, _int, _vp],
+                                                           _int)
+    return s
+
+
+NEIGHBOUR_SIGNATURES = _neighbour_sigs()
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function the C header declares (used by the symbol-export test)."""
     with open(path) as f:
@@ -164,6 +181,11 @@ def screening_header_symbols():
     return header_symbols(SCREENING_HEADER_PATH)
 
 
+def neighbours_header_symbols():
+    """Every function include/simspread_hip_neighbours.h declares."""
+    return header_symbols(NEIGHBOURS_HEADER_PATH)
+
+
 def load():
     """dlopen the library (no GPU needed for this step)."""
     global _lib
@@ -174,7 +196,8 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(make -C simspread.jl_amd/csrc).  There is no CPU fallback for the HIP path.")
     lib = C.CDLL(LIB_PATH)
-    for name, (args, res) in list(SIGNATURES.items()) + list(SCREENING_SIGNATURES.items()):
+    for name, (args, res) in (list(SIGNATURES.items()) + list(SCREENING_SIGNATURES.items())
+                              + list(NEIGHBOUR_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res

@@ -484,10 +484,24 @@ static int graph_from_producers(int64_t nq, int64_t ns, int64_t nt, CountS count
   return SS_OK;
 }
 
+// The neighbour floor (include/simspread_hip_neighbours.h): k > 0 adds the per-row cut tau = tanimoto_kth(k) to the
+// producer (TanimotoCsr::count); k == 0 is the plain producer, its kernels and its tags.
+static const char* tanimoto_tag(bool sym, int k) {
+  if (k > 0) return sym ? "tanimoto_csr_floor_sym" : "tanimoto_csr_floor_cross";
+  return sym ? "tanimoto_csr_sym" : "tanimoto_csr_cross";
+}
+// what the floor entry points refuse before anything is written
+template <class T>
+static int check_floor(int k, T alpha) {
+  if (k < 0 || k > NEIGHBOUR_K_MAX) return fail(SS_EINVAL, "neighbour floor: k = %d outside 0..%d", k, NEIGHBOUR_K_MAX);
+  if (alpha != alpha) return fail(SS_EINVAL, "neighbour floor: alpha is NaN");
+  return SS_OK;
+}
+
 template <class T>
 static int tanimoto_csr_impl(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords, T alpha,
                              int weighted, int64_t* ptr, int32_t* idx, T* val, int64_t capacity, int64_t* nnz,
-                             int mem) {
+                             int mem, int k = 0) {
   SS_TRY(require_init());
   SS_TRY(check_mem(mem));
   path_note().clear();
@@ -502,9 +516,42 @@ static int tanimoto_csr_impl(const uint64_t* Fa, int64_t na, const uint64_t* Fb,
   SS_TRY(stage_fingerprints(Fa, na, nwords, mem, ba, &da));
   if (!sym) SS_TRY(stage_fingerprints(Fb, nb, nwords, mem, bb, &db));
   TanimotoCsr<T> tc;
-  SS_TRY(tc.count(da, na, sym ? nullptr : db, nb, nwords, alpha, weighted != 0));
-  path_add(sym ? "tanimoto_csr_sym" : "tanimoto_csr_cross");
+  SS_TRY(tc.count(da, na, sym ? nullptr : db, nb, nwords, alpha, weighted != 0, k));
+  path_add(tanimoto_tag(sym, k));
   return emit_pair_csr<T>(tc, na, ptr, idx, val, capacity, nnz, mem);
+}
+
+// tau[na]: the k-th largest positive similarity of every row (neighbour_floor.hip)
+template <class T>
+static int tanimoto_kth_impl(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords, int k,
+                             T* tau, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  path_note().clear();
+  const bool sym = (Fb == nullptr);
+  if (sym) nb = na;
+  if (k < 1 || k > NEIGHBOUR_K_MAX) return fail(SS_EINVAL, "tanimoto kth: k = %d outside 1..%d", k, NEIGHBOUR_K_MAX);
+  SS_TRY(check_nwords(nwords));
+  SS_TRY(check_fingerprints("Fa", Fa, na, nwords));
+  if (!sym) SS_TRY(check_fingerprints("Fb", Fb, nb, nwords));
+  if (na > 0 && !tau) return fail(SS_EINVAL, "tanimoto kth: tau must not be NULL");
+  path_add("tanimoto_kth");
+  if (na == 0) return SS_OK;
+  DevBuf<uint64_t> ba, bb;
+  const uint64_t *da = nullptr, *db = nullptr;
+  SS_TRY(stage_fingerprints(Fa, na, nwords, mem, ba, &da));
+  if (!sym) SS_TRY(stage_fingerprints(Fb, nb, nwords, mem, bb, &db));
+  hipStream_t st = ctx().stream;
+  DevBuf<T> dt;
+  T* dtau = tau;
+  if (mem == SS_MEM_HOST) {
+    SS_TRY(dt.alloc(na));
+    dtau = dt.p;
+  }
+  SS_TRY(tanimoto_kth<T>(da, na, sym ? nullptr : db, nb, nwords, nullptr, nullptr, k, dtau));
+  if (mem == SS_MEM_HOST) SS_HIP(hipMemcpyAsync(tau, dtau, (size_t)na * sizeof(T), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
 }
 
 // construct(y, X, ...) with X = featurize(Tanimoto(F), alpha, weighted): Xs = cut(T(Fs, Fs)), Xq = cut(T(Fq, Fs)),
@@ -513,7 +560,7 @@ template <class T>
 static int graph_create_fingerprint_impl(int64_t nq, int64_t ns, int64_t nt, int64_t nwords, const uint64_t* Fq,
                                          const uint64_t* Fs, const int64_t* y_ptr, const int32_t* y_idx,
                                          const T* y_val, int index_base, T alpha, int weighted, int mem,
-                                         ss_graph** out) {
+                                         ss_graph** out, int k = 0) {
   SS_TRY(graph_create_begin(mem, nt, out));
   SS_TRY(check_nwords(nwords));
   SS_TRY(check_fingerprints("Fq", Fq, nq, nwords));
@@ -524,9 +571,9 @@ static int graph_create_fingerprint_impl(int64_t nq, int64_t ns, int64_t nt, int
   SS_TRY(stage_fingerprints(Fq, nq, nwords, mem, bq, &dq));
   const bool wgt = weighted != 0;
   return graph_from_producers<T, TanimotoCsr<T>>(
-      nq, ns, nt, [&](TanimotoCsr<T>& p) { return p.count(ds, ns, nullptr, ns, nwords, alpha, wgt); },
-      [&](TanimotoCsr<T>& p) { return p.count(dq, nq, ds, ns, nwords, alpha, wgt); }, "tanimoto_csr_sym",
-      "tanimoto_csr_cross", y_ptr, y_idx, y_val, index_base, mem, out);
+      nq, ns, nt, [&](TanimotoCsr<T>& p) { return p.count(ds, ns, nullptr, ns, nwords, alpha, wgt, k); },
+      [&](TanimotoCsr<T>& p) { return p.count(dq, nq, ds, ns, nwords, alpha, wgt, k); }, tanimoto_tag(true, k),
+      tanimoto_tag(false, k), y_ptr, y_idx, y_val, index_base, mem, out);
 }
 
 // ------------------- real-valued rows -> thresholded weighted Jaccard CSR, or cosine / Tanimoto / Dice CSR (MFMA)
@@ -2559,7 +2606,7 @@ static int queries_from_producer(const ss_graph* gh, int64_t nq, int64_t ns, Cou
 template <class T>
 static int queries_create_fingerprint_impl(const ss_graph* gh, int64_t nq, int64_t ns, int64_t nwords,
                                            const uint64_t* Fq, const uint64_t* Fs, T alpha, int weighted, int mem,
-                                           ss_queries** out) {
+                                           ss_queries** out, int k = 0) {
   Graph<T>* g = nullptr;
   SS_TRY(queries_begin<T>(gh, nq, mem, out, &g));
   SS_TRY(queries_check_sources(*g, ns));
@@ -2571,8 +2618,8 @@ static int queries_create_fingerprint_impl(const ss_graph* gh, int64_t nq, int64
   SS_TRY(stage_fingerprints(Fs, ns, nwords, mem, bs, &ds));
   SS_TRY(stage_fingerprints(Fq, nq, nwords, mem, bq, &dq));
   return queries_from_producer<T, TanimotoCsr<T>>(
-      gh, nq, ns, [&](TanimotoCsr<T>& p) { return p.count(dq, nq, ds, ns, nwords, alpha, weighted != 0); },
-      "tanimoto_csr_cross", out);
+      gh, nq, ns, [&](TanimotoCsr<T>& p) { return p.count(dq, nq, ds, ns, nwords, alpha, weighted != 0, k); },
+      tanimoto_tag(false, k), out);
 }
 
 template <class T, class Prod, class Check, class Count>
@@ -3287,6 +3334,70 @@ int ss_queries_create_csr_f64(const ss_graph* g, int64_t nq, const int64_t* ptr,
   if (!g) return fail(SS_EINVAL, "handle is NULL");
   SS_HANDLE_LOCK(g);
   return queries_create_csr_impl<double>(g, nq, ptr, idx, val, index_base, mem, out);
+}
+int ss_similarity_tanimoto_kth_f32(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords, int k,
+                                   float* tau, int mem) {
+  SS_API_LOCK();
+  return tanimoto_kth_impl<float>(Fa, na, Fb, nb, nwords, k, tau, mem);
+}
+int ss_similarity_tanimoto_floor_csr_f32(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords,
+                                         float alpha, int k, int weighted, int64_t* ptr, int32_t* idx, float* val,
+                                         int64_t capacity, int64_t* nnz, int mem) {
+  SS_API_LOCK();
+  SS_TRY(check_floor<float>(k, alpha));
+  return tanimoto_csr_impl<float>(Fa, na, Fb, nb, nwords, alpha, weighted, ptr, idx, val, capacity, nnz, mem, k);
+}
+int ss_graph_create_fingerprint_floor_f32(int64_t nq, int64_t ns, int64_t nt, int64_t nwords, const uint64_t* Fq,
+                                          const uint64_t* Fs, const int64_t* y_ptr, const int32_t* y_idx,
+                                          const float* y_val, int index_base, float alpha, int k, int weighted, int mem,
+                                          ss_graph** out) {
+  SS_API_LOCK();
+  if (out) *out = nullptr;
+  SS_TRY(check_floor<float>(k, alpha));
+  return graph_create_fingerprint_impl<float>(nq, ns, nt, nwords, Fq, Fs, y_ptr, y_idx, y_val, index_base, alpha,
+                                            weighted, mem, out, k);
+}
+int ss_queries_create_fingerprint_floor_f32(const ss_graph* g, int64_t nq, int64_t ns, int64_t nwords,
+                                            const uint64_t* Fq, const uint64_t* Fs, float alpha, int k, int weighted,
+                                            int mem, ss_queries** out) {
+  SS_API_LOCK();
+  if (out) *out = nullptr;
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  SS_TRY(check_floor<float>(k, alpha));
+  return queries_create_fingerprint_impl<float>(g, nq, ns, nwords, Fq, Fs, alpha, weighted, mem, out, k);
+}
+int ss_similarity_tanimoto_kth_f64(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords, int k,
+                                   double* tau, int mem) {
+  SS_API_LOCK();
+  return tanimoto_kth_impl<double>(Fa, na, Fb, nb, nwords, k, tau, mem);
+}
+int ss_similarity_tanimoto_floor_csr_f64(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords,
+                                         double alpha, int k, int weighted, int64_t* ptr, int32_t* idx, double* val,
+                                         int64_t capacity, int64_t* nnz, int mem) {
+  SS_API_LOCK();
+  SS_TRY(check_floor<double>(k, alpha));
+  return tanimoto_csr_impl<double>(Fa, na, Fb, nb, nwords, alpha, weighted, ptr, idx, val, capacity, nnz, mem, k);
+}
+int ss_graph_create_fingerprint_floor_f64(int64_t nq, int64_t ns, int64_t nt, int64_t nwords, const uint64_t* Fq,
+                                          const uint64_t* Fs, const int64_t* y_ptr, const int32_t* y_idx,
+                                          const double* y_val, int index_base, double alpha, int k, int weighted, int mem,
+                                          ss_graph** out) {
+  SS_API_LOCK();
+  if (out) *out = nullptr;
+  SS_TRY(check_floor<double>(k, alpha));
+  return graph_create_fingerprint_impl<double>(nq, ns, nt, nwords, Fq, Fs, y_ptr, y_idx, y_val, index_base, alpha,
+                                            weighted, mem, out, k);
+}
+int ss_queries_create_fingerprint_floor_f64(const ss_graph* g, int64_t nq, int64_t ns, int64_t nwords,
+                                            const uint64_t* Fq, const uint64_t* Fs, double alpha, int k, int weighted,
+                                            int mem, ss_queries** out) {
+  SS_API_LOCK();
+  if (out) *out = nullptr;
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  SS_TRY(check_floor<double>(k, alpha));
+  return queries_create_fingerprint_impl<double>(g, nq, ns, nwords, Fq, Fs, alpha, weighted, mem, out, k);
 }
 int ss_queries_create_fingerprint_f32(const ss_graph* g, int64_t nq, int64_t ns, int64_t nwords, const uint64_t* Fq,
                                       const uint64_t* Fs, float alpha, int weighted, int mem, ss_queries** out) {

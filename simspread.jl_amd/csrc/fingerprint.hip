@@ -15,7 +15,11 @@
 //    nnz >= 2^31 refusal happens there, before any output exists)
 //   fill   the same tiles again (every one: this producer keeps no per-tile flag), each slot written at ptr[i] + its
 //          offset in column order.
-// This file holds what is the producer's own: the row popcounts, the staging, the AND-popcount sums and the keep rule.
+// This file holds what is the producer's own: the keep rule and the host side.  The row popcounts, the staging and the
+// AND-popcount sums are tanimoto_tile.hpp, shared with the selection pass of the neighbour floor (neighbour_floor.hip):
+// with k > 0, count() first asks it for tau[na], the k-th largest positive similarity of every row, and the tile kernel
+// keeps (i, j) iff v != 0 and (s >= alpha or (s > 0 and s >= tau[i])).  That rule is not symmetric, so the floor case
+// runs the full (ntj, nti) grid with Fb = Fa instead of the triangle: twice the pair work of the symmetric mode.
 #include <cstdlib>
 #include <cstring>
 #include <hip/hip_runtime.h>
@@ -23,39 +27,42 @@
 
 #include "graph.hpp"
 #include "pair_tile.hpp"
+#include "tanimoto_tile.hpp"
 
 namespace ss {
 
 namespace {
 
-constexpr int TILE = 128;  // rows and columns per workgroup tile
-constexpr int BK = 16;     // 32-bit fingerprint words staged per step (8 uint64 words)
-constexpr int RB = 8;      // rows / columns per thread
-
-__global__ void popcount_rows_kernel(const uint64_t* __restrict__ F, int64_t n, int64_t nwords, int* __restrict__ pop) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint64_t* row = F + i * nwords;
-  int c = 0;
-  for (int64_t w = 0; w < nwords; ++w) c += __popcll(row[w]);
-  pop[i] = c;
-}
+using fptile::BK;
+using fptile::RB;
+using fptile::TILE;
+using fptile::popcount_rows_kernel;
 
 template <class T>
 __device__ __forceinline__ bool tanimoto_keep(int c, int pa, int pb, T alpha, bool weighted, T& v) {
-  const int u = pa + pb - c;
-  const T s = u == 0 ? T(1) : T(c) / T(u);
+  const T s = fptile::tanimoto_similarity<T>(c, pa, pb);
   v = weighted ? s : T(1);
   return s >= alpha && v != T(0);
 }
 
+// the neighbour floor (neighbour_floor.hip): row i also keeps its positive similarities >= tau = tau[i], the k-th
+// largest of them (+0 when it has fewer than k: all of them stay)
+template <class T>
+__device__ __forceinline__ bool tanimoto_keep_floor(int c, int pa, int pb, T alpha, T tau, bool weighted, T& v) {
+  const T s = fptile::tanimoto_similarity<T>(c, pa, pb);
+  v = weighted ? s : T(1);
+  return v != T(0) && (s >= alpha || (s > T(0) && s >= tau));
+}
+
 // FILL == false: write the per-(tile, row) counts.  FILL == true: write the entries (counts then hold in-row offsets).
-template <class T, bool SYM, bool FILL>
+// FLOOR: the per-row cut tau[na] next to alpha; a pair is then decided by its row alone, so there is no mirror (!SYM).
+template <class T, bool SYM, bool FILL, bool FLOOR>
 __global__ void __launch_bounds__(256) tanimoto_tile_kernel(
     const uint64_t* __restrict__ Fa, int64_t na, const uint64_t* __restrict__ Fb, int64_t nb, int64_t nwords,
-    const int* __restrict__ pop_a, const int* __restrict__ pop_b, T alpha, int weighted, int64_t nti,
-    int* __restrict__ counts, const int64_t* __restrict__ ptr, int* __restrict__ oidx, T* __restrict__ oval,
-    int* __restrict__ not_binary) {
+    const int* __restrict__ pop_a, const int* __restrict__ pop_b, T alpha, const T* __restrict__ tau, int weighted,
+    int64_t nti, int* __restrict__ counts, const int64_t* __restrict__ ptr, int* __restrict__ oidx,
+    T* __restrict__ oval, int* __restrict__ not_binary) {
+  static_assert(!(SYM && FLOOR), "a per-row cut decides (i, j) and (j, i) separately");
   __shared__ __attribute__((aligned(16))) uint32_t As[BK][TILE];
   __shared__ __attribute__((aligned(16))) uint32_t Bs[BK][TILE];
 
@@ -64,41 +71,7 @@ __global__ void __launch_bounds__(256) tanimoto_tile_kernel(
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
 
   uint32_t acc[RB][RB];
-#pragma unroll
-  for (int a = 0; a < RB; ++a)
-#pragma unroll
-    for (int b = 0; b < RB; ++b) acc[a][b] = 0;
-
-  for (int64_t w0 = 0; w0 < nwords; w0 += BK / 2) {
-    // stage 8 uint64 words of 128 rows of each side: consecutive threads read consecutive words of a row
-#pragma unroll
-    for (int e = tid; e < TILE * (BK / 2); e += 256) {
-      const int r = e >> 3, w = e & 7;
-      const int64_t k = w0 + w;
-      const int64_t ia = i0 + r, jb = j0 + r;
-      const uint64_t x = (k < nwords && ia < na) ? Fa[ia * nwords + k] : 0ull;
-      const uint64_t y = (k < nwords && jb < nb) ? Fb[jb * nwords + k] : 0ull;
-      As[2 * w][r] = (uint32_t)x;
-      As[2 * w + 1][r] = (uint32_t)(x >> 32);
-      Bs[2 * w][r] = (uint32_t)y;
-      Bs[2 * w + 1][r] = (uint32_t)(y >> 32);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < BK; ++kk) {
-      const uint4 a0 = *reinterpret_cast<const uint4*>(&As[kk][RB * ty]);
-      const uint4 a1 = *reinterpret_cast<const uint4*>(&As[kk][RB * ty + 4]);
-      const uint4 b0 = *reinterpret_cast<const uint4*>(&Bs[kk][RB * tx]);
-      const uint4 b1 = *reinterpret_cast<const uint4*>(&Bs[kk][RB * tx + 4]);
-      const uint32_t av[RB] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-      const uint32_t bv[RB] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-      for (int a = 0; a < RB; ++a)
-#pragma unroll
-        for (int b = 0; b < RB; ++b) acc[a][b] += __popc(av[a] & bv[b]);
-    }
-    __syncthreads();
-  }
+  fptile::tanimoto_tile_counts(As, Bs, Fa, na, Fb, nb, nwords, i0, j0, acc);
 
   // popcounts of the thread's rows and columns; those past the last row / column are never used
   int pa[RB], pb[RB];
@@ -113,44 +86,68 @@ __global__ void __launch_bounds__(256) tanimoto_tile_kernel(
     pb[b] = j < nb ? pop_b[j] : 0;
   }
   const bool wgt = weighted != 0;
-  pair_tile_emit<T, TILE, RB, RB, SYM, FILL, false>(
-      t, na, nb, [&](int a, int b, T& v) { return tanimoto_keep<T>((int)acc[a][b], pa[a], pb[b], alpha, wgt, v); },
-      counts, nullptr, ptr, oidx, oval, not_binary);
+  if constexpr (FLOOR) {
+    T ta[RB];
+#pragma unroll
+    for (int a = 0; a < RB; ++a) {
+      const int64_t i = i0 + RB * ty + a;
+      ta[a] = i < na ? tau[i] : T(0);
+    }
+    pair_tile_emit<T, TILE, RB, RB, false, FILL, false>(
+        t, na, nb,
+        [&](int a, int b, T& v) {
+          return tanimoto_keep_floor<T>((int)acc[a][b], pa[a], pb[b], alpha, ta[a], wgt, v);
+        },
+        counts, nullptr, ptr, oidx, oval, not_binary);
+  } else {
+    pair_tile_emit<T, TILE, RB, RB, SYM, FILL, false>(
+        t, na, nb, [&](int a, int b, T& v) { return tanimoto_keep<T>((int)acc[a][b], pa[a], pb[b], alpha, wgt, v); },
+        counts, nullptr, ptr, oidx, oval, not_binary);
+  }
 }
 
 }  // namespace
 
 template <class T>
 int TanimotoCsr<T>::count(const uint64_t* Fa_, int64_t na_, const uint64_t* Fb_, int64_t nb_, int64_t nwords_, T alpha_,
-                          bool weighted_) {
+                          bool weighted_, int k) {
   hipStream_t st = ctx().stream;
-  what = "tanimoto";
-  sym = (Fb_ == nullptr);
+  self = (Fb_ == nullptr);
+  what = k > 0 ? "tanimoto floor" : "tanimoto";
+  sym = self && k == 0;  // a per-row cut has no mirror: the full grid
   Fa = Fa_;
-  Fb = sym ? Fa_ : Fb_;
+  Fb = self ? Fa_ : Fb_;
   nwords = nwords_;
   alpha = alpha_;
   weighted = weighted_;
-  SS_TRY(this->begin_tiles(na_, sym ? na_ : nb_, TILE, false));
+  tau = nullptr;
+  SS_TRY(this->begin_tiles(na_, self ? na_ : nb_, TILE, false));
   if (na == 0 || nb == 0) return SS_OK;
   SS_TRY(pop_a.alloc(na));
   hipLaunchKernelGGL(popcount_rows_kernel, dim3((unsigned)ceil_div(na, 256)), dim3(256), 0, st, Fa, na, nwords, pop_a.p);
   SS_LAUNCH_CHECK();
-  if (!sym) {
+  if (!self) {
     SS_TRY(pop_b.alloc(nb));
     hipLaunchKernelGGL(popcount_rows_kernel, dim3((unsigned)ceil_div(nb, 256)), dim3(256), 0, st, Fb, nb, nwords,
                        pop_b.p);
     SS_LAUNCH_CHECK();
+  }
+  if (k > 0) {
+    SS_TRY(tau_buf.alloc(na));
+    SS_TRY(tanimoto_kth<T>(Fa, na, Fb, nb, nwords, pop_a.p, self ? pop_a.p : pop_b.p, k, tau_buf.p));
+    tau = tau_buf.p;
   }
   return this->count_pass();
 }
 
 template <class T>
 int TanimotoCsr<T>::launch(bool fill, int* idx, T* val, int* flag) {
-  auto* kernel = sym ? (fill ? tanimoto_tile_kernel<T, true, true> : tanimoto_tile_kernel<T, true, false>)
-                     : (fill ? tanimoto_tile_kernel<T, false, true> : tanimoto_tile_kernel<T, false, false>);
+  auto* kernel = tau   ? (fill ? tanimoto_tile_kernel<T, false, true, true> : tanimoto_tile_kernel<T, false, false, true>)
+                 : sym ? (fill ? tanimoto_tile_kernel<T, true, true, false> : tanimoto_tile_kernel<T, true, false, false>)
+                       : (fill ? tanimoto_tile_kernel<T, false, true, false>
+                               : tanimoto_tile_kernel<T, false, false, false>);
   hipLaunchKernelGGL(kernel, this->tile_grid(), dim3(256), 0, ctx().stream, Fa, na, Fb, nb, nwords, pop_a.p,
-                     sym ? pop_a.p : pop_b.p, alpha, weighted ? 1 : 0, nti, counts.p, ptr.p, idx, val, flag);
+                     self ? pop_a.p : pop_b.p, alpha, tau, weighted ? 1 : 0, nti, counts.p, ptr.p, idx, val, flag);
   SS_LAUNCH_CHECK();
   return SS_OK;
 }

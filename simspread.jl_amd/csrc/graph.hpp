@@ -452,12 +452,26 @@ struct TanimotoCsr : PairCsr<T> {
   const uint64_t* Fa = nullptr;
   const uint64_t* Fb = nullptr;
   int64_t nwords = 0;
-  DevBuf<int> pop_a, pop_b;  // popcount of every row (pop_b unused in symmetric mode)
-  int count(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords, T alpha, bool weighted);
+  DevBuf<int> pop_a, pop_b;  // popcount of every row (pop_b unused when Fb == Fa)
+  bool self = false;         // Fb == Fa (sym says whether the triangle grid runs: not with a per-row cut)
+  const T* tau = nullptr;    // per-row cut of the neighbour floor: entry (i, j) is also kept when 0 < s and s >= tau[i]
+  DevBuf<T> tau_buf;
+  // k > 0: the neighbour floor -- tau = tanimoto_kth(k) first, then the count pass over the full (ntj, nti) grid
+  int count(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords, T alpha, bool weighted,
+            int k = 0);
 
  protected:
   int launch(bool fill, int* idx, T* val, int* flag) override;
 };
+
+// ---- neighbour_floor.hip: tau[i] = the k-th largest of the positive Tanimoto similarities of row i of Fa against the
+// rows of Fb (multiplicity counted), +0 when there are fewer than k; 1 <= k <= NEIGHBOUR_K_MAX.  Device pointers,
+// Fb == nullptr: Fb = Fa; pop_a / pop_b: the row popcounts (pop_a == nullptr: computed here).  Enqueued on the stream;
+// the scratch (na * k * column groups values) is freed after a synchronisation.  Bitwise repeatable.
+constexpr int NEIGHBOUR_K_MAX = 64;
+template <class T>
+int tanimoto_kth(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords, const int* pop_a,
+                 const int* pop_b, int k, T* tau);
 
 // ---- jaccard_csr.hip: thresholded weighted Jaccard (Ruzicka) similarity of real-valued feature rows as CSR, bitwise
 // what jaccard_kernel followed by the dense cutoff assembly gives.  Fa (na x d, column-major, lda >= na) against Fb

@@ -230,14 +230,18 @@ class DeviceGraph:
         return cls(h, dt)
 
     @classmethod
-    def from_fingerprints(cls, Fq, Fs, Y, alpha: float, weighted: bool = True, dtype=np.float32, index_base: int = 0):
+    def from_fingerprints(cls, Fq, Fs, Y, alpha: float, weighted: bool = True, dtype=np.float32, index_base: int = 0,
+                          min_neighbours: int = 0):
         """``construct(y, X)`` with ``X = featurize(Tanimoto(F), alpha, weighted)`` for packed binary fingerprints (see
         ``pack_fingerprints``): Xq = cut(T(Fq, Fs)), Xs = cut(T(Fs, Fs)), features named after the sources, produced as
         CSR on the device (the dense similarity never exists).  Fq may be None (3-layer graph: predict_loo /
         predict_kfold).  Fq, Fs: uint64 numpy arrays (n, nwords) with Y a scipy matrix (ns x nt), or int64 torch CUDA
         tensors with Y = (ptr, idx, val, nt) device CSR.  index_base (0 or 1) is the base of the label CSR handed to the
         library: a scipy matrix is converted, a (ptr, idx, val, nt) tuple (numpy arrays on the host) is taken as it
-        is."""
+        is.  min_neighbours = k > 0 (at most 64) adds the neighbour floor of ``tanimoto_csr``: every source and every
+        query also keeps its k nearest sources (ties included), whatever alpha says; alpha = inf gives the pure k-nearest
+        graph.  The graph is an ordinary CSR graph afterwards; in a leave-one-out fold the held-out source's own column
+        is dropped as always, so pass k + 1 for k neighbours in every fold."""
         lib = L.lib()
         dt = np.dtype(dtype).type
         if dt not in (np.float32, np.float64):
@@ -251,9 +255,14 @@ class DeviceGraph:
         yptr, yidx, yval, nt, mem = _source_labels(Y, ns, dt, dev, keep, index_base)
         h = C.c_void_p()
         ctype = C.c_float if dt == np.float32 else C.c_double
-        fn = getattr(lib, f"ss_graph_create_fingerprint_{_suffix(dt)}")
-        L.check(fn(nq, ns, nt, nwords, fq, fs, yptr, yidx, yval, index_base, ctype(alpha), 1 if weighted else 0, mem,
-                   C.byref(h)))
+        if min_neighbours:
+            fn = getattr(lib, f"ss_graph_create_fingerprint_floor_{_suffix(dt)}")
+            L.check(fn(nq, ns, nt, nwords, fq, fs, yptr, yidx, yval, index_base, ctype(alpha), int(min_neighbours),
+                       1 if weighted else 0, mem, C.byref(h)))
+        else:
+            fn = getattr(lib, f"ss_graph_create_fingerprint_{_suffix(dt)}")
+            L.check(fn(nq, ns, nt, nwords, fq, fs, yptr, yidx, yval, index_base, ctype(alpha), 1 if weighted else 0, mem,
+                       C.byref(h)))
         if dev:
             L.check(lib.ss_synchronize())
         del keep
@@ -638,8 +647,10 @@ class DeviceQueries:
         return cls(h, graph)
 
     @classmethod
-    def from_fingerprints(cls, graph: DeviceGraph, Fq, Fs, alpha: float, weighted: bool = True):
-        """Xq = cut(Tanimoto(Fq, Fs)) as ``DeviceGraph.from_fingerprints`` stores it; inputs as there."""
+    def from_fingerprints(cls, graph: DeviceGraph, Fq, Fs, alpha: float, weighted: bool = True, min_neighbours: int = 0):
+        """Xq = cut(Tanimoto(Fq, Fs)) as ``DeviceGraph.from_fingerprints`` stores it; inputs as there.  min_neighbours =
+        k > 0: every query also keeps its k nearest sources (ties included), so ``degrees()`` is at least k for a query
+        with k positive similarities; the graph may be a plain or a floor graph."""
         lib = L.lib()
         dt = graph.dtype.type
         dev = _is_torch(Fs)
@@ -649,9 +660,14 @@ class DeviceQueries:
         if Fq is not None and nwq != nwords:
             raise ValueError("Fq and Fs have different fingerprint widths")
         h = C.c_void_p()
-        fn = getattr(lib, f"ss_queries_create_fingerprint_{_suffix(dt)}")
-        L.check(fn(graph._h, nq, ns, nwords, fq, fs, graph._ctype()(alpha), 1 if weighted else 0,
-                   L.SS_MEM_DEVICE if dev else L.SS_MEM_HOST, C.byref(h)))
+        mem = L.SS_MEM_DEVICE if dev else L.SS_MEM_HOST
+        if min_neighbours:
+            fn = getattr(lib, f"ss_queries_create_fingerprint_floor_{_suffix(dt)}")
+            L.check(fn(graph._h, nq, ns, nwords, fq, fs, graph._ctype()(alpha), int(min_neighbours), 1 if weighted else 0,
+                       mem, C.byref(h)))
+        else:
+            fn = getattr(lib, f"ss_queries_create_fingerprint_{_suffix(dt)}")
+            L.check(fn(graph._h, nq, ns, nwords, fq, fs, graph._ctype()(alpha), 1 if weighted else 0, mem, C.byref(h)))
         if dev:
             L.check(lib.ss_synchronize())
         del keep
@@ -1458,18 +1474,57 @@ def _fingerprints(F, dev, keep):
     return a.ctypes.data, a.shape[0], a.shape[1]
 
 
-def tanimoto_csr(Fa, Fb=None, alpha=None, weighted: bool = True, dtype=np.float32):
+def tanimoto_kth(Fa, Fb=None, k=None, dtype=np.float32):
+    """tau[i] = the k-th largest of the positive Tanimoto similarities of fingerprint Fa[i] against the rows of Fb
+    (multiplicity counted; Fb None: Fb = Fa, the diagonal included), +0 where a row has fewer than k: the per-row cut of
+    ``tanimoto_csr(..., min_neighbours=k)``, computed on the device without the dense similarity.  1 <= k <= 64.  Host
+    input (uint64 numpy) returns a numpy vector, device input (int64 torch CUDA tensors) a CUDA tensor."""
+    if k is None:
+        raise TypeError("tanimoto_kth needs k")
+    lib = L_.lib()
+    dt = np.dtype(dtype).type
+    fn = getattr(lib, f"ss_similarity_tanimoto_kth_{_suffix(dt)}")
+    dev = _is_torch(Fa)
+    keep = []
+    pa, na, nw = _fingerprints(Fa, dev, keep)
+    pb, nb, nwb = _fingerprints(Fb, dev, keep)
+    if Fb is None:
+        nb, nwb = na, nw
+    if nwb != nw:
+        raise ValueError("Fa and Fb have different fingerprint widths")
+    if dev:
+        import torch
+        tau = torch.empty(na, dtype=torch.float32 if dt == np.float32 else torch.float64, device=Fa.device)
+        L_.check(fn(pa, na, pb, nb, nw, int(k), tau.data_ptr(), L_.SS_MEM_DEVICE))
+        return tau
+    tau = np.empty(na, dt)
+    L_.check(fn(pa, na, pb, nb, nw, int(k), tau.ctypes.data, L_.SS_MEM_HOST))
+    del keep
+    return tau
+
+
+def tanimoto_csr(Fa, Fb=None, alpha=None, weighted: bool = True, dtype=np.float32, min_neighbours: int = 0):
     """``featurize(1 .- pairwise(Jaccard(), F, dims=1), alpha, weighted)`` for packed binary fingerprints (see
     ``pack_fingerprints``), produced as CSR on the device without the dense similarity: entry (i, j) = Tanimoto(Fa[i],
     Fb[j]) when it is >= alpha (1 when not weighted).  Fb None: Fb = Fa.  Host input (uint64 numpy) returns a
-    scipy.sparse.csr_matrix; device input (int64 torch CUDA tensors) returns (ptr int64, idx int32, val) tensors."""
+    scipy.sparse.csr_matrix; device input (int64 torch CUDA tensors) returns (ptr int64, idx int32, val) tensors.
+    min_neighbours = k > 0 (at most 64) adds the neighbour floor: row i also keeps every positive similarity >= tau_i,
+    the k-th largest of its positive similarities (``tanimoto_kth``), i.e. at least its k nearest columns whatever alpha
+    says (alpha = inf: exactly those).  Ties at tau_i are all kept, a row with fewer than k positive similarities keeps
+    all of them, and the result is in general not symmetric ((i, j) is decided by tau_i, (j, i) by tau_j)."""
     if alpha is None:
         raise TypeError("tanimoto_csr needs alpha")
     lib = L_.lib()
     dt = np.dtype(dtype).type
     suf = _suffix(dt)
-    fn = getattr(lib, f"ss_similarity_tanimoto_csr_{suf}")
     ctype = C.c_float if dt == np.float32 else C.c_double
+    if min_neighbours:
+        floor = getattr(lib, f"ss_similarity_tanimoto_floor_csr_{suf}")
+
+        def fn(pa, na, pb, nb, nw, a, w, *rest):
+            return floor(pa, na, pb, nb, nw, a, int(min_neighbours), w, *rest)
+    else:
+        fn = getattr(lib, f"ss_similarity_tanimoto_csr_{suf}")
     dev = _is_torch(Fa)
     keep = []
     pa, na, nw = _fingerprints(Fa, dev, keep)
