@@ -4,7 +4,7 @@
 // block family (transfer_block / _qflat / _wide / _wide2_kernel: NW rows of L per workgroup on one chunk, opt-in with
 // SS_TRANSFER_V=2) is the measured record behind DESIGN.md 4.1.  Shared: BlockLayout, quad_fetch, quad_fold (all that
 // have them), block_prologue (block, qflat), block_row (qflat), fixed_scale (block, wide, wide2), fixed_store (block, qflat,
-// wide2), raw_load (wide), subrows_fold_any.  A piece is used only where the kernel's loop compiles to the parent
+// wide2), raw_load (wide), subrows_fold_any, tails_begin / tails_finish (single-wave, block).  A piece is used only where the kernel's loop compiles to the parent
 // layout's instructions with it; where it did not, the kernel keeps its own text and says so.
 // Wavefront = 64 lanes.  No float atomics: every sum has a fixed order or is an integer sum, so results are bitwise
 // reproducible from run to run.
@@ -95,18 +95,36 @@ template <> struct BitsOf<float> {
   static __device__ __forceinline__ float bcast(float v, int src) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
   }
+  // lane i's value goes to lane to4 / 4; lane i takes the value of lane from4 / 4
+  static __device__ __forceinline__ float push(int to4, float v) {
+    return __int_as_float(__builtin_amdgcn_ds_permute(to4, __float_as_int(v)));
+  }
+  static __device__ __forceinline__ float pull(int from4, float v) {
+    return __int_as_float(__builtin_amdgcn_ds_bpermute(from4, __float_as_int(v)));
+  }
 };
 template <> struct BitsOf<double> {
+  static __device__ __forceinline__ double join(int lo, int hi) {
+    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+  }
   static __device__ __forceinline__ double bcast(double v, int src) {
     const long long b = __double_as_longlong(v);
     const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), src);
     const int hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+    return join(lo, hi);
+  }
+  static __device__ __forceinline__ double push(int to4, double v) {
+    const long long b = __double_as_longlong(v);
+    return join(__builtin_amdgcn_ds_permute(to4, (int)(b & 0xffffffffll)), __builtin_amdgcn_ds_permute(to4, (int)(b >> 32)));
+  }
+  static __device__ __forceinline__ double pull(int from4, double v) {
+    const long long b = __double_as_longlong(v);
+    return join(__builtin_amdgcn_ds_bpermute(from4, (int)(b & 0xffffffffll)), __builtin_amdgcn_ds_bpermute(from4, (int)(b >> 32)));
   }
 };
 
-// U sub-rows: scalar bounds + coefficient, and the (unconditional) loads of their first 64 entries.
-// The operand arrays carry 64 entries of slack, so lanes past the end of a sub-row read valid memory;
+// U sub-rows: scalar bounds + coefficient, and the (unconditional) loads of their first 64 entries (the heads).
+// The operand arrays carry 256 entries of slack, so lanes past the end of a sub-row read valid memory;
 // such lanes are steered to a per-lane dummy accumulator behind the chunk.
 template <class T, int U>
 struct SubRows {
@@ -115,8 +133,6 @@ struct SubRows {
   T cf[U];
   unsigned short j[U];
   T v[U];
-  unsigned short j2[U];  // entries 64..127 of the sub-row, fetched only when it is that long (wave-uniform)
-  T v2[U];
 };
 
 // The same loads as buffer instructions: resource descriptor (SGPRs) + scalar byte offset of the sub-row + a 32-bit lane
@@ -134,10 +150,7 @@ __device__ __forceinline__ void subrows_load_buf(SubRows<float, U>& s, int first
     s.cf[u] = BitsOf<float>::bcast(cf_l, src);
     s.j[u] = __builtin_amdgcn_raw_buffer_load_b16(ridx, lane * 2, (int)(s.b[u] * 2u), 0);
     s.v[u] = BINM ? 1.f : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rval, lane * 4, (int)(s.b[u] * 4u), 0));
-    if (s.n[u] > 64) {
-      s.j2[u] = __builtin_amdgcn_raw_buffer_load_b16(ridx, lane * 2, (int)(s.b[u] * 2u + 128u), 0);
-      s.v2[u] = BINM ? 1.f : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rval, lane * 4, (int)(s.b[u] * 4u + 256u), 0));
-    }
+    __builtin_amdgcn_sched_barrier(0);
   }
 }
 
@@ -155,26 +168,18 @@ __device__ __forceinline__ void subrows_load(SubRows<T, U>& s, int first, int b_
     const T* pv = mval + s.b[u];
     s.j[u] = pi[lane];
     s.v[u] = BINM ? T(1) : pv[lane];  // unweighted features: every stored value is 1, two thirds of the bytes vanish
-    // With the chunk sized for a mean sub-row of ~60 entries, ~40 % of the sub-rows are longer than one
-    // wave: their second half must be prefetched like the first (a dependent load inside the fold
-    // stalls the whole batch), so it is issued here under a wave-uniform branch.
-    if (s.n[u] > 64) {
-      s.j2[u] = pi[64 + lane];
-      s.v2[u] = BINM ? T(1) : pv[64 + lane];
-    }
+    // the loads leave in the order the fold takes them (it waits for them one by one): without the fence the
+    // scheduler is free to issue sub-row 0 last, and the fold of a batch then waits for all of it
+    __builtin_amdgcn_sched_barrier(0);
   }
 }
 
 // DUAL: two copies of the accumulators (acc and acc + astride); sub-rows 2i and 2i+1 of a batch go to different
 // copies, so their read-add-write pairs are independent and both LDS reads are in flight together (with one copy
 // every pair waits for the previous pair's LDS round trip).  The copies are added when T is written out: the sum
-// order is still fixed.
+// order is still fixed.  (Tails and rests go to the first copy.)
 template <class T, int U, bool DUAL>
-__device__ __forceinline__ void subrows_fold(const SubRows<T, U>& s, int first, int b_l, int n_l, T cf_l,
-                                             T* __restrict__ acc, int astride, int dummy,
-                                             const unsigned short* __restrict__ midx, const T* __restrict__ mval,
-                                             int lane) {
-  int nmax = 0;
+__device__ __forceinline__ void subrows_fold(const SubRows<T, U>& s, T* __restrict__ acc, int astride, int dummy, int lane) {
   if constexpr (DUAL) {
     T* __restrict__ acc1 = acc + astride;
 #pragma unroll
@@ -184,39 +189,12 @@ __device__ __forceinline__ void subrows_fold(const SubRows<T, U>& s, int first, 
       const T ra = acc[ja], rb = acc1[jb];
       acc[ja] = fma(s.cf[u], s.v[u], ra);
       acc1[jb] = fma(s.cf[u + 1], s.v[u + 1], rb);
-      if (s.n[u] > 64 || s.n[u + 1] > 64) {
-        const int ka = (s.n[u] > 64 && 64 + lane < s.n[u]) ? (int)s.j2[u] : dummy;
-        const int kb = (s.n[u + 1] > 64 && 64 + lane < s.n[u + 1]) ? (int)s.j2[u + 1] : dummy;
-        const T va = s.n[u] > 64 ? s.v2[u] : T(0), vb = s.n[u + 1] > 64 ? s.v2[u + 1] : T(0);
-        const T qa = acc[ka], qb = acc1[kb];
-        acc[ka] = fma(s.cf[u], va, qa);
-        acc1[kb] = fma(s.cf[u + 1], vb, qb);
-      }
-      nmax = s.n[u] > nmax ? s.n[u] : nmax;
-      nmax = s.n[u + 1] > nmax ? s.n[u + 1] : nmax;
     }
   } else {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int j = lane < s.n[u] ? (int)s.j[u] : dummy;
       acc[j] = fma(s.cf[u], s.v[u], acc[j]);
-      if (s.n[u] > 64) {
-        const int k = 64 + lane < s.n[u] ? (int)s.j2[u] : dummy;
-        acc[k] = fma(s.cf[u], s.v2[u], acc[k]);
-      }
-      nmax = s.n[u] > nmax ? s.n[u] : nmax;
-    }
-  }
-  if (nmax > 128) {  // rare: a sub-row longer than two waves (bounds re-read by lane index, no register arrays)
-#pragma unroll 1
-    for (int u = 0; u < U; ++u) {
-      const int n = __builtin_amdgcn_readlane(n_l, first + u);
-      const unsigned b = (unsigned)__builtin_amdgcn_readlane(b_l, first + u);
-      const T cf = BitsOf<T>::bcast(cf_l, first + u);
-      for (int x = 128 + lane; x < n; x += 64) {
-        const int j = midx[b + x];
-        acc[j] = fma(cf, mval[b + x], acc[j]);
-      }
     }
   }
 }
@@ -233,38 +211,113 @@ __device__ __forceinline__ int cvt_rpi(float x) {
   return r;
 }
 template <int U>
-__device__ __forceinline__ void subrows_fold_fixed(const SubRows<float, U>& s, int first, int b_l, int n_l, float cf_l,
-                                                   unsigned* __restrict__ acc, const unsigned short* __restrict__ midx,
-                                                   const float* __restrict__ mval, int lane) {
-  int nmax = 0;
+__device__ __forceinline__ void subrows_fold_fixed(const SubRows<float, U>& s, unsigned* __restrict__ acc, int lane) {
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const float v = lane < s.n[u] ? s.v[u] : 0.f;
     atomicAdd(&acc[s.j[u]], (unsigned)cvt_rpi(s.cf[u] * v));
-    if (s.n[u] > 64) {
-      const float v2 = 64 + lane < s.n[u] ? s.v2[u] : 0.f;
-      atomicAdd(&acc[s.j2[u]], (unsigned)cvt_rpi(s.cf[u] * v2));
-    }
-    nmax = s.n[u] > nmax ? s.n[u] : nmax;
-  }
-  if (nmax > 128) {
-#pragma unroll 1
-    for (int u = 0; u < U; ++u) {
-      const int n = __builtin_amdgcn_readlane(n_l, first + u);
-      const unsigned b = (unsigned)__builtin_amdgcn_readlane(b_l, first + u);
-      const float cf = BitsOf<float>::bcast(cf_l, first + u);
-      for (int x = 128 + lane; x < n; x += 64) atomicAdd(&acc[midx[b + x]], (unsigned)cvt_rpi(cf * mval[b + x]));
-    }
   }
 }
 
-// one batch into the wave's sums: fixed point or plain read-add-write
+// the heads of one batch into the wave's sums: fixed point or plain read-add-write
 template <class T, int U, bool DUAL, bool FIX>
-__device__ __forceinline__ void subrows_fold_any(const SubRows<T, U>& s, int first, int b_l, int n_l, T cf_l, T* acc,
-                                                 int astride, int dummy, const unsigned short* midx, const T* mval,
-                                                 int lane) {
-  if constexpr (FIX) subrows_fold_fixed<U>(s, first, b_l, n_l, cf_l, reinterpret_cast<unsigned*>(acc), midx, mval, lane);
-  else subrows_fold<T, U, DUAL>(s, first, b_l, n_l, cf_l, acc, astride, dummy, midx, mval, lane);
+__device__ __forceinline__ void subrows_fold_any(const SubRows<T, U>& s, T* acc, int astride, int dummy, int lane) {
+  if constexpr (FIX) subrows_fold_fixed<U>(s, reinterpret_cast<unsigned*>(acc), lane);
+  else subrows_fold<T, U, DUAL>(s, acc, astride, dummy, lane);
+}
+
+// ---------------------------------------------------------------- tails: entries 64.. of the long sub-rows of a group
+// With the chunk sized for a mean sub-row of ~60 entries, ~40 % of the sub-rows are longer than one wave, by ~6 entries.
+// Their entries 64..79 are taken once per group of 64 neighbours, after the heads, FOUR sub-rows to a load pair: the
+// group's long sub-rows are compacted to the low lanes (one lane permutation of start, length and coefficient per
+// group: no scalar work per sub-row), round r serves the long sub-rows 4r .. 4r+3, lane group g = lane >> 4 the
+// sub-row 4r + g with its 16 lanes.  A group without a long sub-row (sub-rows of ~40 entries, C3) pays one ballot and
+// one branch.  The four tails of a round are folded one after the other: the columns inside a sub-row are distinct,
+// those of different sub-rows are not, so tails never share a plain read-add-write (the fixed-point fold adds all four
+// in one integer atomic).  Lanes outside the group, past the end of the tail, or of a slot past the last long sub-row
+// (it holds a short one: nothing past position 64) go to their dummy word.  Entries from position 80 on (~1 % of the
+// sub-rows at 62.5 +- 7.7 entries) take the rest loop, bounds re-read by lane index.
+// Order of a group's sums: heads in neighbour order, tails in neighbour order, rests in neighbour order -- a fixed
+// function of the row's neighbour list.
+// AHEAD rounds are fetched together; the first AHEAD of a group fly while its heads are folded.  Measured at C2
+// (profiles/stage1_tails_time.json): 4 with pattern-only operands (one register a round), 2 with values (4 rounds
+// take the U = 8 kernel from 6 to 5 waves per SIMD: 1.39 instead of 1.33 ms).
+template <class T, int AHEAD>
+struct Tails {
+  static constexpr int TAIL_AHEAD = AHEAD;
+  int nt;      // long sub-rows of the group (wave-uniform)
+  int cb, cn;  // lane i: start and length of the i-th long sub-row, i < nt; the short ones follow
+  T ccf;
+  unsigned short tj[TAIL_AHEAD];
+  T tv[TAIL_AHEAD];
+};
+
+// rounds r0 .. r0 + TAIL_AHEAD - 1 that exist; ld(entry, index&, value&) reads one operand entry
+template <class T, int TAIL_AHEAD, class LD>
+__device__ __forceinline__ void tails_fetch(Tails<T, TAIL_AHEAD>& t, int r0, int lane, LD&& ld) {
+#pragma unroll
+  for (int i = 0; i < TAIL_AHEAD; ++i) {
+    if (4 * (r0 + i) >= t.nt) break;
+    const unsigned b = (unsigned)__builtin_amdgcn_ds_bpermute((4 * (r0 + i) + (lane >> 4)) * 4, t.cb);
+    ld(b + 64u + (unsigned)(lane & 15), t.tj[i], t.tv[i]);   // (any start + 80 is inside the operand and its slack)
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// compaction of the group's long sub-rows, and the loads of the first rounds
+template <class T, int TAIL_AHEAD, class LD>
+__device__ __forceinline__ void tails_begin(Tails<T, TAIL_AHEAD>& t, int b_l, int n_l, T cf_l, int lane, LD&& ld) {
+  const unsigned long long longs = __ballot(n_l > 64);
+  t.nt = __builtin_popcountll(longs);
+  if (t.nt == 0) return;
+  const int k = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(longs >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)longs, 0u));
+  const int to4 = (n_l > 64 ? k : t.nt + lane - k) * 4;   // a permutation of the 64 lanes
+  t.cb = __builtin_amdgcn_ds_permute(to4, b_l);
+  t.cn = __builtin_amdgcn_ds_permute(to4, n_l);
+  t.ccf = BitsOf<T>::push(to4, cf_l);
+  tails_fetch(t, 0, lane, ld);
+}
+
+template <class T, bool BINM, bool FIX, int TAIL_AHEAD, class LD>
+__device__ __forceinline__ void tails_finish(Tails<T, TAIL_AHEAD>& t, int b_l, int n_l, T cf_l, T* __restrict__ acc, int dummy,
+                                             const unsigned short* __restrict__ midx, const T* __restrict__ mval, int lane,
+                                             LD&& ld) {
+  if (t.nt == 0) return;
+  for (int r0 = 0; 4 * r0 < t.nt; r0 += TAIL_AHEAD) {
+    if (r0 > 0) tails_fetch(t, r0, lane, ld);
+#pragma unroll
+    for (int i = 0; i < TAIL_AHEAD; ++i) {
+      if (4 * (r0 + i) >= t.nt) break;
+      const int from4 = (4 * (r0 + i) + (lane >> 4)) * 4;
+      const int tn = __builtin_amdgcn_ds_bpermute(from4, t.cn) - 64;   // entries past position 64 (<= 0: none); may exceed 16
+      const T tcf = BitsOf<T>::pull(from4, t.ccf);
+      const bool live = (lane & 15) < tn;
+      if constexpr (FIX) {
+        atomicAdd(reinterpret_cast<unsigned*>(acc) + (live ? (int)t.tj[i] : dummy),
+                  (unsigned)cvt_rpi(live ? (float)(tcf * t.tv[i]) : 0.f));
+      } else {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int j = (live && (lane >> 4) == g) ? (int)t.tj[i] : dummy;
+          acc[j] = fma(tcf, t.tv[i], acc[j]);
+        }
+      }
+    }
+  }
+  unsigned long long m = __ballot(n_l > 80);
+  while (m != 0ull) {
+    const int src = __builtin_ctzll(m);
+    m &= m - 1ull;
+    const int n = __builtin_amdgcn_readlane(n_l, src);
+    const unsigned b = (unsigned)__builtin_amdgcn_readlane(b_l, src);
+    const T cf = BitsOf<T>::bcast(cf_l, src);
+    for (int x = 80 + lane; x < n; x += 64) {
+      const int j = midx[b + x];
+      const T v = BINM ? T(1) : mval[b + x];
+      if constexpr (FIX) atomicAdd(reinterpret_cast<unsigned*>(acc) + j, (unsigned)cvt_rpi((float)(cf * v)));
+      else acc[j] = fma(cf, v, acc[j]);
+    }
+  }
 }
 
 // Scale 2^k of one row's fixed-point sums.  Every sum is bounded by bound = (sum_a |coef[a]|) * xmax (xmax = largest
@@ -373,15 +426,29 @@ __global__ void __launch_bounds__(TRANSFER_THREADS) transfer_kernel(TransferArgs
           subrows_load<T, U, BINM>(sr, first, b_l, n_l, cf_l, midx, mval, lane);
         }
       };
+      auto tail_ld = [&](unsigned e, unsigned short& j, T& v) __attribute__((always_inline)) {
+        if constexpr (BUF) {
+          const __amdgpu_buffer_rsrc_t ridx = __builtin_amdgcn_make_buffer_rsrc((void*)midx, 0, -1, 0x00020000);
+          const __amdgpu_buffer_rsrc_t rval = __builtin_amdgcn_make_buffer_rsrc((void*)mval, 0, -1, 0x00020000);
+          j = __builtin_amdgcn_raw_buffer_load_b16(ridx, (int)(e * 2u), 0, 0);
+          v = BINM ? 1.f : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rval, (int)(e * 4u), 0, 0));
+        } else {
+          j = midx[e];
+          v = BINM ? T(1) : mval[e];
+        }
+      };
+      Tails<T, (BINM ? 4 : 2)> tails;
+      tails_begin(tails, b_l, n_l, cf_l, lane, tail_ld);
       load(A, 0);
       for (int u0 = 0; u0 < cnt; u0 += 2 * U) {
         if (u0 + U < cnt) load(B, u0 + U);
-        subrows_fold_any<T, U, DUAL, FIX>(A, u0, b_l, n_l, cf_l, acc, astride, dummy, midx, mval, lane);
+        subrows_fold_any<T, U, DUAL, FIX>(A, acc, astride, dummy, lane);
         if (u0 + U < cnt) {
           if (u0 + 2 * U < cnt) load(A, u0 + 2 * U);
-          subrows_fold_any<T, U, DUAL, FIX>(B, u0 + U, b_l, n_l, cf_l, acc, astride, dummy, midx, mval, lane);
+          subrows_fold_any<T, U, DUAL, FIX>(B, acc, astride, dummy, lane);
         }
       }
+      tails_finish<T, BINM, FIX>(tails, b_l, n_l, cf_l, acc, dummy, midx, mval, lane, tail_ld);
     }
   }
   if (LOO) {
@@ -416,11 +483,12 @@ constexpr int TRANSFER_U = 8;
 // SS_TRANSFER_DUAL=0/1: one or two copies of the LDS accumulators (see subrows_fold)
 static bool transfer_dual() { return env_int("SS_TRANSFER_DUAL", 0) != 0; }
 
-// sub-rows in flight per wave.  Default 8; 4 (55 instead of 90 registers: 30 instead of 20 single-wave workgroups per CU)
-// where it measured faster: weighted operands that stay in L2 (C2: 1.46 vs 1.51 ms; pattern-only operands 1.24 vs
-// 1.19 ms and the 600 MB operand of C3 5.1 vs 4.6 ms go the other way).  SS_TRANSFER_U overrides.
-static int transfer_u(bool small_weighted = false) {
-  const int u = (int)env_int("SS_TRANSFER_U", small_weighted ? 4 : TRANSFER_U);
+// sub-rows in flight per wave: 8.  Until the tails left the batch small weighted operands took 4, which
+// reached 30 instead of 20 single-wave workgroups per CU (55 instead of 90 registers); now U = 8 holds 77 registers
+// (24 workgroups per CU) and measures faster everywhere: C2 weighted 1.33 vs 1.37 ms, pattern-only 1.15 vs 1.19 ms
+// (profiles/stage1_tails_time.json).  SS_TRANSFER_U overrides.
+static int transfer_u() {
+  const int u = (int)env_int("SS_TRANSFER_U", TRANSFER_U);
   return (u == 4 || u == 16) ? u : 8;
 }
 
@@ -597,15 +665,22 @@ __global__ void __launch_bounds__(1024) transfer_block_kernel(TransferArgs<T> p,
     auto load = [&](SubRows<T, U>& sr, int first) __attribute__((always_inline)) {
       subrows_load<T, U, BINM>(sr, first, b_l, n_l, cf_l, midx, mval, lane);
     };
+    auto tail_ld = [&](unsigned e, unsigned short& j, T& v) __attribute__((always_inline)) {
+      j = midx[e];
+      v = BINM ? T(1) : mval[e];
+    };
+    Tails<T, (BINM ? 4 : 2)> tails;
+    tails_begin(tails, b_l, n_l, cf_l, lane, tail_ld);
     load(A, 0);
     for (int u0 = 0; u0 < cnt; u0 += 2 * U) {
       if (u0 + U < cnt) load(B, u0 + U);
-      subrows_fold_any<T, U, false, FIX>(A, u0, b_l, n_l, cf_l, acc, astride, dummy, midx, mval, lane);
+      subrows_fold_any<T, U, false, FIX>(A, acc, astride, dummy, lane);
       if (u0 + U < cnt) {
         if (u0 + 2 * U < cnt) load(A, u0 + 2 * U);
-        subrows_fold_any<T, U, false, FIX>(B, u0 + U, b_l, n_l, cf_l, acc, astride, dummy, midx, mval, lane);
+        subrows_fold_any<T, U, false, FIX>(B, acc, astride, dummy, lane);
       }
     }
+    tails_finish<T, BINM, FIX>(tails, b_l, n_l, cf_l, acc, dummy, midx, mval, lane, tail_ld);
   }
   if constexpr (FIX) {
     fixed_store(p, w.r, w.j0, w.jn, lane, acc, unscale);
@@ -1147,14 +1222,13 @@ int launch_transfer_block(const DevCsr<T>& L, const T* inv1, const DevChunked<T>
 // The single-wave kernel, by (U, BINM, DUAL); fp32 query / source rows with one accumulator copy also by FIX
 // (SS_TRANSFER_FIX1=1: a single term that does not accumulate) and BUF (SS_TRANSFER_LD=1), where U is 4 or 8.
 template <class T, bool LOO>
-static int launch_transfer_variant(const TransferArgs<T>& p, unsigned grid, size_t lds, bool binm, bool dual,
-                                   bool small_weighted) {
+static int launch_transfer_variant(const TransferArgs<T>& p, unsigned grid, size_t lds, bool binm, bool dual) {
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(TRANSFER_THREADS), lds, ctx().stream, p);
     SS_LAUNCH_CHECK();
     return (int)SS_OK;
   };
-  const int u = transfer_u(small_weighted && !LOO);
+  const int u = transfer_u();
   if constexpr (std::is_same<T, float>::value && !LOO) {
     const bool buf = !dual && env_int("SS_TRANSFER_LD", 0) == 1;
     const bool fix = !dual && env_int("SS_TRANSFER_FIX1", 0) == 1 && p.nterms == 1 && !p.accumulate;
@@ -1206,21 +1280,14 @@ int launch_transfer(int nterms, const DevCsr<T>* L[2], const T* inv1[2], const D
   p.accumulate = accumulate ? 1 : 0;
   p.xmax = 1.0f;
   p.chunk_interleave = env_off("SS_TRANSFER_ORDER") ? 1 : 0;
-  // weighted operand of at most 32 MiB: picks the default batch size (transfer_u)
-  int64_t bytes = 0;
-  bool weighted = false, binm = true;
-  for (int t = 0; t < nterms; ++t) {
-    bytes += Mt[t]->stored * (int64_t)(2 + sizeof(T));
-    weighted = weighted || !Mt[t]->binary;
-    binm = binm && Mt[t]->binary;
-  }
-  const bool small_weighted = weighted && bytes <= (32LL << 20);
+  bool binm = true;
+  for (int t = 0; t < nterms; ++t) binm = binm && Mt[t]->binary;
   const int64_t grid = nrows * p.nchunks;
   if (grid >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "transfer grid too large; lower SS_TRANSFER_BYTES");
   const bool dual = transfer_dual();
   path_add("transfer");
   const size_t lds = (size_t)(p.SC + 64) * sizeof(T) * (dual ? 2 : 1);
-  return launch_transfer_variant<T, false>(p, (unsigned)grid, lds, binm, dual, small_weighted);
+  return launch_transfer_variant<T, false>(p, (unsigned)grid, lds, binm, dual);
 }
 
 template <class T>
@@ -1245,7 +1312,7 @@ int launch_transfer_loo(const DevCsr<T>& X, const DevChunked<T>& XT, const int* 
   const bool dual = transfer_dual();
   path_add("transfer_loo");
   const size_t lds = (size_t)(p.SC + 64) * sizeof(T) * (dual ? 2 : 1) + (size_t)((p.SC + 31) / 32) * 4;
-  return launch_transfer_variant<T, true>(p, (unsigned)grid, lds, XT.binary, dual, false);
+  return launch_transfer_variant<T, true>(p, (unsigned)grid, lds, XT.binary, dual);
 }
 
 #define SS_INSTANTIATE(T)                                                                                   \
