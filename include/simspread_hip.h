@@ -704,5 +704,6 @@ int ss_spmat_cost(const ss_spmat* w, int64_t B, double* bytes, double* flops);
 
 #include "simspread_hip_screening.h"
 #include "simspread_hip_neighbours.h"
+#include "simspread_hip_neighbours_real.h"
 
 #endif /* SIMSPREAD_HIP_H */

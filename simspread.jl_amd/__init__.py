@@ -13,13 +13,13 @@ from .dist import (comm_destroy, comm_init, comm_unique_id, gather_scores, gathe
 from .engine import (BINARY_ROWS_FIELDS, POOLED_FIELDS, RANK_ROWS_FIELDS, TARGET_TOPL_FIELDS, DeviceGraph, DeviceQueries, DeviceSpMat,
                      Pool,
                      TargetTopL, binary_metrics_rows, cutoff_csr,
-                     dot_csr, jaccard_csr,
+                     dot_csr, dot_kth, jaccard_csr, jaccard_kth,
                      jaccard_similarity, pack_fingerprints, rank_metrics, rank_metrics_rows, tanimoto_csr, tanimoto_kth, topl)
 from .metrics import (AuPRC, AuROC, BEDROC, ROCNums, accuracy, balancedaccuracy, f1score, maxperformance, mcc,
                       meanperformance, meanstdperformance, precision, recall, roc, validity_ratio)
 
 __all__ = ["NamedMatrix", "Network", "DeviceGraph", "DeviceQueries", "DeviceSpMat", "SimSpreadError", "init", "timing_last", "timing_hold", "path_last", "use_torch_stream",
            "shard_range", "pooled_metrics", "Pool", "POOLED_FIELDS", "target_topl", "TargetTopL", "TARGET_TOPL_FIELDS", "gather_scores", "gather_topl", "comm_unique_id", "comm_init", "comm_destroy", "lib_gather_scores", "k", "cutoff", "featurize", "construct", "spread", "predict", "clean", "clean_", "names", "split", "save", "save_loo", "topl", "recallatL", "precisionatL",
-           "read_namedmatrix", "writedlm", "rank_metrics", "rank_metrics_rows", "RANK_ROWS_FIELDS", "binary_metrics_rows", "BINARY_ROWS_FIELDS", "jaccard_similarity", "jaccard_csr", "dot_csr", "cutoff_csr", "pack_fingerprints", "tanimoto_csr", "tanimoto_kth", "AuROC", "AuPRC", "BEDROC", "validity_ratio", "roc", "ROCNums",
+           "read_namedmatrix", "writedlm", "rank_metrics", "rank_metrics_rows", "RANK_ROWS_FIELDS", "binary_metrics_rows", "BINARY_ROWS_FIELDS", "jaccard_similarity", "jaccard_csr", "dot_csr", "cutoff_csr", "pack_fingerprints", "tanimoto_csr", "tanimoto_kth", "jaccard_kth", "dot_kth", "AuROC", "AuPRC", "BEDROC", "validity_ratio", "roc", "ROCNums",
            "f1score", "mcc", "accuracy", "balancedaccuracy", "recall", "precision", "maxperformance", "meanperformance",
            "meanstdperformance"]

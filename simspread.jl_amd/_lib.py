@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("SS_LIB_PATH") or os.path.join(_HERE, "libsimspread_hi
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip.h")
 SCREENING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_screening.h")   # included by it
 NEIGHBOURS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_neighbours.h")  # included by it
+REAL_NEIGHBOURS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_neighbours_real.h")  # too
 
 SS_OK = 0
 SS_MEM_HOST, SS_MEM_DEVICE = 0, 1
@@ -168,6 +169,30 @@ def _neighbour_sigs():
 NEIGHBOUR_SIGNATURES = _neighbour_sigs()
 
 
+def _real_neighbour_sigs():
+    """include/simspread_hip_neighbours_real.h: the neighbour floor of the weighted-Jaccard and inner-product producers"""
+    s = {}
+    for suf, ft in (("f32", C.c_float), ("f64", C.c_double)):
+        rows = [_vp, _i64, _i64, _vp, _i64, _i64, _i64]                 # Fa, na, lda, Fb, nb, ldb, d
+        out = [_vp, _vp, _vp, _i64, _vp, _int]                          # ptr, idx, val, capacity, nnz, mem
+        s[f"ss_similarity_jaccard_kth_{suf}"] = (rows + [_int, _vp, _int], _int)
+        s[f"ss_similarity_jaccard_floor_csr_{suf}"] = (rows + [ft, _int, _int] + out, _int)
+        s[f"ss_similarity_dot_kth_{suf}"] = (rows + [_int, _int, _vp, _int], _int)
+        s[f"ss_similarity_dot_floor_csr_{suf}"] = (rows + [_int, ft, _int, _int] + out, _int)
+        s[f"ss_graph_create_features_floor_{suf}"] = ([_i64] * 4 + [_vp, _i64, _vp, _i64] + [_vp] * 3
+                                                      + [_int, ft, _int, _int, _int, _vp], _int)
+        s[f"ss_graph_create_vectors_floor_{suf}"] = ([_i64] * 4 + [_int, _vp, _i64, _vp, _i64] + [_vp] * 3
+                                                     + [_int, ft, _int, _int, _int, _vp], _int)
+        s[f"ss_queries_create_features_floor_{suf}"] = ([_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, ft, _int, _int, _int,
+                                                         _vp], _int)
+        s[f"ss_queries_create_vectors_floor_{suf}"] = ([_vp, _i64, _i64, _i64, _int, _vp, _i64, _vp, _i64, ft, _int, _int,
+                                                        _int, _vp], _int)
+    return s
+
+
+REAL_NEIGHBOUR_SIGNATURES = _real_neighbour_sigs()
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function the C header declares (used by the symbol-export test)."""
     with open(path) as f:
@@ -186,6 +211,11 @@ def neighbours_header_symbols():
     return header_symbols(NEIGHBOURS_HEADER_PATH)
 
 
+def real_neighbours_header_symbols():
+    """Every function include/simspread_hip_neighbours_real.h declares."""
+    return header_symbols(REAL_NEIGHBOURS_HEADER_PATH)
+
+
 def load():
     """dlopen the library (no GPU needed for this step)."""
     global _lib
@@ -197,7 +227,7 @@ def load():
             "(make -C simspread.jl_amd/csrc).  There is no CPU fallback for the HIP path.")
     lib = C.CDLL(LIB_PATH)
     for name, (args, res) in (list(SIGNATURES.items()) + list(SCREENING_SIGNATURES.items())
-                              + list(NEIGHBOUR_SIGNATURES.items())):
+                              + list(NEIGHBOUR_SIGNATURES.items()) + list(REAL_NEIGHBOUR_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res

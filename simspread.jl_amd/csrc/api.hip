@@ -606,9 +606,16 @@ static int stage_features(const T* F, int64_t n, int64_t ld, int64_t d, int mem,
 // producer p on device rows (Fb == NULL: symmetric).
 struct FeatureNames {
   const char *msg, *tag_sym, *tag_cross;
+  // the neighbour floor (include/simspread_hip_neighbours_real.h): the tags of the floor producer and of its tau
+  const char *tag_floor_sym, *tag_floor_cross, *tag_kth;
+  const char* tag(bool sym, int k) const {
+    return k > 0 ? (sym ? tag_floor_sym : tag_floor_cross) : (sym ? tag_sym : tag_cross);
+  }
 };
-static const FeatureNames jaccard_names = {"jaccard", "jaccard_csr_sym", "jaccard_csr_cross"};
-static const FeatureNames dot_names = {"dot_csr", "dot_csr_sym", "dot_csr_cross"};
+static const FeatureNames jaccard_names = {"jaccard", "jaccard_csr_sym", "jaccard_csr_cross", "jaccard_csr_floor_sym",
+                                           "jaccard_csr_floor_cross", "jaccard_kth"};
+static const FeatureNames dot_names = {"dot_csr", "dot_csr_sym", "dot_csr_cross", "dot_csr_floor_sym",
+                                       "dot_csr_floor_cross", "dot_kth"};
 
 static int check_sim_metric(int metric) {
   if (metric != SS_SIM_COSINE && metric != SS_SIM_TANIMOTO && metric != SS_SIM_DICE)
@@ -616,15 +623,15 @@ static int check_sim_metric(int metric) {
   return SS_OK;
 }
 template <class T>
-static auto jaccard_count(int64_t d, T alpha, int weighted) {
+static auto jaccard_count(int64_t d, T alpha, int weighted, int k = 0) {
   return [=](JaccardCsr<T>& p, const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb) {
-    return p.count(Fa, na, lda, Fb, nb, ldb, d, alpha, weighted != 0);
+    return p.count(Fa, na, lda, Fb, nb, ldb, d, alpha, weighted != 0, k);
   };
 }
 template <class T>
-static auto dot_count(int64_t d, int metric, T alpha, int weighted) {
+static auto dot_count(int64_t d, int metric, T alpha, int weighted, int k = 0) {
   return [=](DotCsr<T>& p, const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb) {
-    return p.count(Fa, na, lda, Fb, nb, ldb, d, metric, alpha, weighted != 0);
+    return p.count(Fa, na, lda, Fb, nb, ldb, d, metric, alpha, weighted != 0, k);
   };
 }
 
@@ -640,7 +647,7 @@ static int check_feature_args(const FeatureNames& nm, Check check, int64_t d, T 
 template <class T, class Prod, class Check, class Count>
 static int features_csr_impl(const FeatureNames& nm, Check check, Count count, const T* Fa, int64_t na, int64_t lda,
                              const T* Fb, int64_t nb, int64_t ldb, int64_t d, T alpha, int64_t* ptr, int32_t* idx,
-                             T* val, int64_t capacity, int64_t* nnz, int mem) {
+                             T* val, int64_t capacity, int64_t* nnz, int mem, int k = 0) {
   SS_TRY(require_init());
   SS_TRY(check_mem(mem));
   path_note().clear();
@@ -660,8 +667,48 @@ static int features_csr_impl(const FeatureNames& nm, Check check, Count count, c
   if (!sym) SS_TRY(stage_features(Fb, nb, ldb, d, mem, bb, &db, &lb));
   Prod p;
   SS_TRY(count(p, da, na, la, sym ? nullptr : db, nb, lb));
-  path_add(sym ? nm.tag_sym : nm.tag_cross);
+  path_add(nm.tag(sym, k));
   return emit_pair_csr<T>(p, na, ptr, idx, val, capacity, nnz, mem);
+}
+
+// tau[na] (in `mem`): the k-th largest positive similarity of every row of Fa against Fb (real_floor.hip);
+// kth(da, na, la, db, nb, lb, dtau) is the producer's selection on device rows (db == NULL: Fa against itself)
+template <class T, class Check, class Kth>
+static int features_kth_impl(const FeatureNames& nm, Check check, Kth kth, const T* Fa, int64_t na, int64_t lda,
+                             const T* Fb, int64_t nb, int64_t ldb, int64_t d, int k, T* tau, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  path_note().clear();
+  const bool sym = (Fb == nullptr);
+  if (sym) {
+    nb = na;
+    ldb = lda;
+  }
+  if (k < 1 || k > NEIGHBOUR_K_MAX) return fail(SS_EINVAL, "%s kth: k = %d outside 1..%d", nm.msg, k, NEIGHBOUR_K_MAX);
+  SS_TRY(check());
+  if (d < 0) return fail(SS_EINVAL, "%s kth: negative feature count", nm.msg);
+  SS_TRY(check_features("Fa", Fa, na, lda, d));
+  if (!sym) SS_TRY(check_features("Fb", Fb, nb, ldb, d));
+  if (na > 0 && !tau) return fail(SS_EINVAL, "%s kth: tau must not be NULL", nm.msg);
+  path_add(nm.tag_kth);
+  if (na == 0) return SS_OK;
+  DevBuf<T> ba, bb;
+  const T *da = nullptr, *db = nullptr;
+  int64_t la = 0, lb = 0;
+  SS_TRY(stage_features(Fa, na, lda, d, mem, ba, &da, &la));
+  if (!sym) SS_TRY(stage_features(Fb, nb, ldb, d, mem, bb, &db, &lb));
+  SS_TRY(refuse_nan_rows<T>(nm.msg, da, na, la, sym ? nullptr : db, nb, lb, d));
+  hipStream_t st = ctx().stream;
+  DevBuf<T> dt;
+  T* dtau = tau;
+  if (mem == SS_MEM_HOST) {
+    SS_TRY(dt.alloc(na));
+    dtau = dt.p;
+  }
+  SS_TRY(kth(da, na, la, sym ? nullptr : db, nb, lb, dtau));
+  if (mem == SS_MEM_HOST) SS_HIP(hipMemcpyAsync(tau, dtau, (size_t)na * sizeof(T), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
 }
 
 // construct(y, X, ...) with X = featurize(S(F), alpha, weighted), S the producer's similarity of the feature rows:
@@ -669,7 +716,8 @@ static int features_csr_impl(const FeatureNames& nm, Check check, Count count, c
 template <class T, class Prod, class Check, class Count>
 static int features_graph_impl(const FeatureNames& nm, Check check, Count count, int64_t nq, int64_t ns, int64_t nt,
                                int64_t d, const T* Fq, int64_t ldq, const T* Fs, int64_t lds_, const int64_t* y_ptr,
-                               const int32_t* y_idx, const T* y_val, int index_base, T alpha, int mem, ss_graph** out) {
+                               const int32_t* y_idx, const T* y_val, int index_base, T alpha, int mem, ss_graph** out,
+                               int k = 0) {
   SS_TRY(graph_create_begin(mem, nt, out));
   SS_TRY(check_feature_args(nm, check, d, alpha));
   SS_TRY(check_features("Fq", Fq, nq, ldq, d));
@@ -681,7 +729,7 @@ static int features_graph_impl(const FeatureNames& nm, Check check, Count count,
   SS_TRY(stage_features(Fq, nq, ldq, d, mem, bq, &dq, &lq));
   return graph_from_producers<T, Prod>(
       nq, ns, nt, [&](Prod& p) { return count(p, ds, ns, ls, nullptr, ns, ls); },
-      [&](Prod& p) { return count(p, dq, nq, lq, ds, ns, ls); }, nm.tag_sym, nm.tag_cross, y_ptr, y_idx, y_val,
+      [&](Prod& p) { return count(p, dq, nq, lq, ds, ns, ls); }, nm.tag(true, k), nm.tag(false, k), y_ptr, y_idx, y_val,
       index_base, mem, out);
 }
 
@@ -690,32 +738,55 @@ static int no_check() { return SS_OK; }
 template <class T>
 static int jaccard_csr_impl(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d,
                             T alpha, int weighted, int64_t* ptr, int32_t* idx, T* val, int64_t capacity, int64_t* nnz,
-                            int mem) {
-  return features_csr_impl<T, JaccardCsr<T>>(jaccard_names, no_check, jaccard_count<T>(d, alpha, weighted), Fa, na, lda,
-                                             Fb, nb, ldb, d, alpha, ptr, idx, val, capacity, nnz, mem);
+                            int mem, int k = 0) {
+  return features_csr_impl<T, JaccardCsr<T>>(jaccard_names, no_check, jaccard_count<T>(d, alpha, weighted, k), Fa, na,
+                                             lda, Fb, nb, ldb, d, alpha, ptr, idx, val, capacity, nnz, mem, k);
+}
+template <class T>
+static int jaccard_kth_impl(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d, int k,
+                            T* tau, int mem) {
+  return features_kth_impl<T>(
+      jaccard_names, no_check,
+      [=](const T* da, int64_t na_, int64_t la, const T* db, int64_t nb_, int64_t lb, T* dtau) {
+        return jaccard_kth<T>(da, na_, la, db, nb_, lb, d, k, dtau);
+      },
+      Fa, na, lda, Fb, nb, ldb, d, k, tau, mem);
 }
 template <class T>
 static int graph_create_features_impl(int64_t nq, int64_t ns, int64_t nt, int64_t d, const T* Fq, int64_t ldq,
                                       const T* Fs, int64_t lds_, const int64_t* y_ptr, const int32_t* y_idx,
-                                      const T* y_val, int index_base, T alpha, int weighted, int mem, ss_graph** out) {
-  return features_graph_impl<T, JaccardCsr<T>>(jaccard_names, no_check, jaccard_count<T>(d, alpha, weighted), nq, ns, nt,
-                                               d, Fq, ldq, Fs, lds_, y_ptr, y_idx, y_val, index_base, alpha, mem, out);
+                                      const T* y_val, int index_base, T alpha, int weighted, int mem, ss_graph** out,
+                                      int k = 0) {
+  return features_graph_impl<T, JaccardCsr<T>>(jaccard_names, no_check, jaccard_count<T>(d, alpha, weighted, k), nq, ns,
+                                               nt, d, Fq, ldq, Fs, lds_, y_ptr, y_idx, y_val, index_base, alpha, mem, out,
+                                               k);
 }
 template <class T>
 static int dot_csr_impl(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d,
                         int metric, T alpha, int weighted, int64_t* ptr, int32_t* idx, T* val, int64_t capacity,
-                        int64_t* nnz, int mem) {
+                        int64_t* nnz, int mem, int k = 0) {
   return features_csr_impl<T, DotCsr<T>>(
-      dot_names, [=] { return check_sim_metric(metric); }, dot_count<T>(d, metric, alpha, weighted), Fa, na, lda, Fb, nb,
-      ldb, d, alpha, ptr, idx, val, capacity, nnz, mem);
+      dot_names, [=] { return check_sim_metric(metric); }, dot_count<T>(d, metric, alpha, weighted, k), Fa, na, lda, Fb,
+      nb, ldb, d, alpha, ptr, idx, val, capacity, nnz, mem, k);
+}
+template <class T>
+static int dot_kth_impl(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d, int metric,
+                        int k, T* tau, int mem) {
+  return features_kth_impl<T>(
+      dot_names, [=] { return check_sim_metric(metric); },
+      [=](const T* da, int64_t na_, int64_t la, const T* db, int64_t nb_, int64_t lb, T* dtau) {
+        return dot_kth<T>(da, na_, la, db, nb_, lb, d, metric, nullptr, nullptr, k, dtau);
+      },
+      Fa, na, lda, Fb, nb, ldb, d, k, tau, mem);
 }
 template <class T>
 static int graph_create_vectors_impl(int64_t nq, int64_t ns, int64_t nt, int64_t d, int metric, const T* Fq,
                                      int64_t ldq, const T* Fs, int64_t lds_, const int64_t* y_ptr, const int32_t* y_idx,
-                                     const T* y_val, int index_base, T alpha, int weighted, int mem, ss_graph** out) {
+                                     const T* y_val, int index_base, T alpha, int weighted, int mem, ss_graph** out,
+                                     int k = 0) {
   return features_graph_impl<T, DotCsr<T>>(
-      dot_names, [=] { return check_sim_metric(metric); }, dot_count<T>(d, metric, alpha, weighted), nq, ns, nt, d, Fq,
-      ldq, Fs, lds_, y_ptr, y_idx, y_val, index_base, alpha, mem, out);
+      dot_names, [=] { return check_sim_metric(metric); }, dot_count<T>(d, metric, alpha, weighted, k), nq, ns, nt, d, Fq,
+      ldq, Fs, lds_, y_ptr, y_idx, y_val, index_base, alpha, mem, out, k);
 }
 
 // ------------------------------------------------------------------ cutoff sweeps: featurize on resident CSR
@@ -2625,7 +2696,7 @@ static int queries_create_fingerprint_impl(const ss_graph* gh, int64_t nq, int64
 template <class T, class Prod, class Check, class Count>
 static int features_queries_impl(const FeatureNames& nm, Check check, Count count, const ss_graph* gh, int64_t nq,
                                  int64_t ns, int64_t d, const T* Fq, int64_t ldq, const T* Fs, int64_t lds_, T alpha,
-                                 int mem, ss_queries** out) {
+                                 int mem, ss_queries** out, int k = 0) {
   Graph<T>* g = nullptr;
   SS_TRY(queries_begin<T>(gh, nq, mem, out, &g));
   SS_TRY(queries_check_sources(*g, ns));
@@ -2638,7 +2709,7 @@ static int features_queries_impl(const FeatureNames& nm, Check check, Count coun
   SS_TRY(stage_features(Fs, ns, lds_, d, mem, bs, &ds, &ls));
   SS_TRY(stage_features(Fq, nq, ldq, d, mem, bq, &dq, &lq));
   return queries_from_producer<T, Prod>(
-      gh, nq, ns, [&](Prod& p) { return count(p, dq, nq, lq, ds, ns, ls); }, nm.tag_cross, out);
+      gh, nq, ns, [&](Prod& p) { return count(p, dq, nq, lq, ds, ns, ls); }, nm.tag(false, k), out);
 }
 
 template <class T>
@@ -3450,6 +3521,143 @@ int ss_queries_create_vectors_f64(const ss_graph* g, int64_t nq, int64_t ns, int
   return features_queries_impl<double, DotCsr<double>>(
       dot_names, [=] { return check_sim_metric(metric); }, dot_count<double>(d, metric, alpha, weighted), g, nq, ns, d,
       Fq, ldq, Fs, lds, alpha, mem, out);
+}
+
+// ---- include/simspread_hip_neighbours_real.h: the neighbour floor of the weighted-Jaccard and inner-product producers
+int ss_similarity_jaccard_kth_f32(const float* Fa, int64_t na, int64_t lda, const float* Fb, int64_t nb, int64_t ldb,
+                                  int64_t d, int k, float* tau, int mem) {
+  SS_API_LOCK();
+  return jaccard_kth_impl<float>(Fa, na, lda, Fb, nb, ldb, d, k, tau, mem);
+}
+int ss_similarity_jaccard_floor_csr_f32(const float* Fa, int64_t na, int64_t lda, const float* Fb, int64_t nb, int64_t ldb,
+                                        int64_t d, float alpha, int k, int weighted, int64_t* ptr, int32_t* idx, float* val,
+                                        int64_t capacity, int64_t* nnz, int mem) {
+  SS_API_LOCK();
+  SS_TRY(check_floor<float>(k, alpha));
+  return jaccard_csr_impl<float>(Fa, na, lda, Fb, nb, ldb, d, alpha, weighted, ptr, idx, val, capacity, nnz, mem, k);
+}
+int ss_similarity_dot_kth_f32(const float* Fa, int64_t na, int64_t lda, const float* Fb, int64_t nb, int64_t ldb, int64_t d,
+                              int metric, int k, float* tau, int mem) {
+  SS_API_LOCK();
+  return dot_kth_impl<float>(Fa, na, lda, Fb, nb, ldb, d, metric, k, tau, mem);
+}
+int ss_similarity_dot_floor_csr_f32(const float* Fa, int64_t na, int64_t lda, const float* Fb, int64_t nb, int64_t ldb,
+                                    int64_t d, int metric, float alpha, int k, int weighted, int64_t* ptr, int32_t* idx,
+                                    float* val, int64_t capacity, int64_t* nnz, int mem) {
+  SS_API_LOCK();
+  SS_TRY(check_floor<float>(k, alpha));
+  return dot_csr_impl<float>(Fa, na, lda, Fb, nb, ldb, d, metric, alpha, weighted, ptr, idx, val, capacity, nnz, mem, k);
+}
+int ss_graph_create_features_floor_f32(int64_t nq, int64_t ns, int64_t nt, int64_t d, const float* Fq, int64_t ldq,
+                                       const float* Fs, int64_t lds, const int64_t* y_ptr, const int32_t* y_idx,
+                                       const float* y_val, int index_base, float alpha, int k, int weighted, int mem,
+                                       ss_graph** out) {
+  SS_API_LOCK();
+  if (out) *out = nullptr;
+  SS_TRY(check_floor<float>(k, alpha));
+  return graph_create_features_impl<float>(nq, ns, nt, d, Fq, ldq, Fs, lds, y_ptr, y_idx, y_val, index_base, alpha, weighted,
+                                       mem, out, k);
+}
+int ss_graph_create_vectors_floor_f32(int64_t nq, int64_t ns, int64_t nt, int64_t d, int metric, const float* Fq,
+                                      int64_t ldq, const float* Fs, int64_t lds, const int64_t* y_ptr, const int32_t* y_idx,
+                                      const float* y_val, int index_base, float alpha, int k, int weighted, int mem,
+                                      ss_graph** out) {
+  SS_API_LOCK();
+  if (out) *out = nullptr;
+  SS_TRY(check_floor<float>(k, alpha));
+  return graph_create_vectors_impl<float>(nq, ns, nt, d, metric, Fq, ldq, Fs, lds, y_ptr, y_idx, y_val, index_base, alpha,
+                                      weighted, mem, out, k);
+}
+int ss_queries_create_features_floor_f32(const ss_graph* g, int64_t nq, int64_t ns, int64_t d, const float* Fq,
+                                         int64_t ldq, const float* Fs, int64_t lds, float alpha, int k, int weighted, int mem,
+                                         ss_queries** out) {
+  SS_API_LOCK();
+  if (out) *out = nullptr;
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  SS_TRY(check_floor<float>(k, alpha));
+  return features_queries_impl<float, JaccardCsr<float>>(jaccard_names, no_check, jaccard_count<float>(d, alpha, weighted, k), g,
+                                                   nq, ns, d, Fq, ldq, Fs, lds, alpha, mem, out, k);
+}
+int ss_queries_create_vectors_floor_f32(const ss_graph* g, int64_t nq, int64_t ns, int64_t d, int metric,
+                                        const float* Fq, int64_t ldq, const float* Fs, int64_t lds, float alpha, int k,
+                                        int weighted, int mem, ss_queries** out) {
+  SS_API_LOCK();
+  if (out) *out = nullptr;
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  SS_TRY(check_floor<float>(k, alpha));
+  return features_queries_impl<float, DotCsr<float>>(
+      dot_names, [=] { return check_sim_metric(metric); }, dot_count<float>(d, metric, alpha, weighted, k), g, nq, ns, d, Fq,
+      ldq, Fs, lds, alpha, mem, out, k);
+}
+// ---- include/simspread_hip_neighbours_real.h: the neighbour floor of the weighted-Jaccard and inner-product producers
+int ss_similarity_jaccard_kth_f64(const double* Fa, int64_t na, int64_t lda, const double* Fb, int64_t nb, int64_t ldb,
+                                  int64_t d, int k, double* tau, int mem) {
+  SS_API_LOCK();
+  return jaccard_kth_impl<double>(Fa, na, lda, Fb, nb, ldb, d, k, tau, mem);
+}
+int ss_similarity_jaccard_floor_csr_f64(const double* Fa, int64_t na, int64_t lda, const double* Fb, int64_t nb, int64_t ldb,
+                                        int64_t d, double alpha, int k, int weighted, int64_t* ptr, int32_t* idx, double* val,
+                                        int64_t capacity, int64_t* nnz, int mem) {
+  SS_API_LOCK();
+  SS_TRY(check_floor<double>(k, alpha));
+  return jaccard_csr_impl<double>(Fa, na, lda, Fb, nb, ldb, d, alpha, weighted, ptr, idx, val, capacity, nnz, mem, k);
+}
+int ss_similarity_dot_kth_f64(const double* Fa, int64_t na, int64_t lda, const double* Fb, int64_t nb, int64_t ldb, int64_t d,
+                              int metric, int k, double* tau, int mem) {
+  SS_API_LOCK();
+  return dot_kth_impl<double>(Fa, na, lda, Fb, nb, ldb, d, metric, k, tau, mem);
+}
+int ss_similarity_dot_floor_csr_f64(const double* Fa, int64_t na, int64_t lda, const double* Fb, int64_t nb, int64_t ldb,
+                                    int64_t d, int metric, double alpha, int k, int weighted, int64_t* ptr, int32_t* idx,
+                                    double* val, int64_t capacity, int64_t* nnz, int mem) {
+  SS_API_LOCK();
+  SS_TRY(check_floor<double>(k, alpha));
+  return dot_csr_impl<double>(Fa, na, lda, Fb, nb, ldb, d, metric, alpha, weighted, ptr, idx, val, capacity, nnz, mem, k);
+}
+int ss_graph_create_features_floor_f64(int64_t nq, int64_t ns, int64_t nt, int64_t d, const double* Fq, int64_t ldq,
+                                       const double* Fs, int64_t lds, const int64_t* y_ptr, const int32_t* y_idx,
+                                       const double* y_val, int index_base, double alpha, int k, int weighted, int mem,
+                                       ss_graph** out) {
+  SS_API_LOCK();
+  if (out) *out = nullptr;
+  SS_TRY(check_floor<double>(k, alpha));
+  return graph_create_features_impl<double>(nq, ns, nt, d, Fq, ldq, Fs, lds, y_ptr, y_idx, y_val, index_base, alpha, weighted,
+                                       mem, out, k);
+}
+int ss_graph_create_vectors_floor_f64(int64_t nq, int64_t ns, int64_t nt, int64_t d, int metric, const double* Fq,
+                                      int64_t ldq, const double* Fs, int64_t lds, const int64_t* y_ptr, const int32_t* y_idx,
+                                      const double* y_val, int index_base, double alpha, int k, int weighted, int mem,
+                                      ss_graph** out) {
+  SS_API_LOCK();
+  if (out) *out = nullptr;
+  SS_TRY(check_floor<double>(k, alpha));
+  return graph_create_vectors_impl<double>(nq, ns, nt, d, metric, Fq, ldq, Fs, lds, y_ptr, y_idx, y_val, index_base, alpha,
+                                      weighted, mem, out, k);
+}
+int ss_queries_create_features_floor_f64(const ss_graph* g, int64_t nq, int64_t ns, int64_t d, const double* Fq,
+                                         int64_t ldq, const double* Fs, int64_t lds, double alpha, int k, int weighted, int mem,
+                                         ss_queries** out) {
+  SS_API_LOCK();
+  if (out) *out = nullptr;
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  SS_TRY(check_floor<double>(k, alpha));
+  return features_queries_impl<double, JaccardCsr<double>>(jaccard_names, no_check, jaccard_count<double>(d, alpha, weighted, k), g,
+                                                   nq, ns, d, Fq, ldq, Fs, lds, alpha, mem, out, k);
+}
+int ss_queries_create_vectors_floor_f64(const ss_graph* g, int64_t nq, int64_t ns, int64_t d, int metric,
+                                        const double* Fq, int64_t ldq, const double* Fs, int64_t lds, double alpha, int k,
+                                        int weighted, int mem, ss_queries** out) {
+  SS_API_LOCK();
+  if (out) *out = nullptr;
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  SS_TRY(check_floor<double>(k, alpha));
+  return features_queries_impl<double, DotCsr<double>>(
+      dot_names, [=] { return check_sim_metric(metric); }, dot_count<double>(d, metric, alpha, weighted, k), g, nq, ns, d, Fq,
+      ldq, Fs, lds, alpha, mem, out, k);
 }
 
 int ss_queries_destroy(ss_queries* q) {

@@ -29,9 +29,17 @@
 // accumulators into s in place; the kept pairs of a tile become bit rows in LDS (one wave ballot per accumulator
 // register, no atomics), and counts and in-row offsets are popcounts of those.  In symmetric mode only the tiles on and
 // above the diagonal run; an off-diagonal tile emits its pairs for its rows and, mirrored, for its columns.
+//
+// This file holds what is the producer's own: the keep rule, the bit-row epilogue and the host side.  The staging, the
+// MFMA sequence, the norms and the expression of s are dot_tile.hpp, shared with the selection pass of the neighbour
+// floor (real_floor.hip): with k > 0, count() first asks it for tau[na], the k-th largest positive similarity of every
+// row, and the tile kernel keeps (i, j) iff v != 0 and (s >= alpha or (s > 0 and s >= tau[i])).  That rule is not
+// symmetric, so the floor case runs the full (ntj, nti) grid with Fb = Fa instead of the triangle; its diagonal is
+// still exactly 1, and every other pair is what the cross producer computes for (i, j).
 #include <algorithm>
 #include <hip/hip_runtime.h>
 
+#include "dot_tile.hpp"
 #include "graph.hpp"
 #include "pair_tile.hpp"
 
@@ -39,71 +47,11 @@ namespace ss {
 
 namespace {
 
-constexpr int TILE = 128;  // rows and columns per workgroup tile
-constexpr int BK = 16;     // feature columns staged per step
-constexpr int NT = 256;    // 4 waves as 2 x 2, a wave owns 64 x 64 pairs
-constexpr int WT = 64;     // rows and columns per wave
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f64x4 = __attribute__((ext_vector_type(4))) double;
-
-// The matrix instruction of T: MT x MT results per instruction from KS feature columns, NR results per lane.
-// Operands: lane l holds A[l % MT][l / MT] and B[l / MT][l % MT].  Result register r of lane l is the pair
-// (row(r, l), l % MT) of the MFMA tile.
-template <class T>
-struct Mma;
-template <>
-struct Mma<float> {
-  static constexpr int MT = 32, KS = 2, NR = 16;
-  static constexpr int PAD = 0;  // ds_read_b32 serves 32 lanes per cycle: 32 consecutive floats never conflict
-  using acc_t = f32x16;
-  static __device__ __forceinline__ acc_t mma(float a, float b, acc_t c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
-};
-template <>
-struct Mma<double> {
-  static constexpr int MT = 16, KS = 4, NR = 4;
-  static constexpr int PAD = 16;  // ds_read_b64 serves 32 lanes = two k rows per cycle: the rows go to opposite bank halves
-  using acc_t = f64x4;
-  static __device__ __forceinline__ acc_t mma(double a, double b, acc_t c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int r, int lane) { return (lane >> 4) + 4 * r; }
-};
-
-// the rule after the three sums; ra, rb: sqrt(A), sqrt(B) for the cosine, A, B otherwise
-template <class T>
-__device__ __forceinline__ T dot_sim(T g, T ra, T rb, int metric) {
-#pragma clang fp contract(off)
-  T num = g, den;
-  if (metric == SS_SIM_COSINE) {
-    den = ra * rb;
-  } else if (metric == SS_SIM_TANIMOTO) {
-    den = (ra + rb) - g;
-  } else {
-    den = ra + rb;
-    num = g + g;
-  }
-  if (den == T(0)) return (ra == T(0) && rb == T(0)) ? T(1) : T(0);  // sqrt(A) == 0 iff A == 0
-  T s = num / den;
-  if (metric == SS_SIM_COSINE) s = s < T(-1) ? T(-1) : (s > T(1) ? T(1) : s);  // a NaN stays a NaN
-  return s;
-}
-
-// N[i] = sum_k F[i, k]^2 in T, one thread per row (consecutive threads read consecutive rows of a column)
-template <class T>
-__global__ void row_norm_kernel(const T* __restrict__ F, int64_t n, int64_t ld, int64_t d, T* __restrict__ N) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  T s = T(0);
-  for (int64_t k = 0; k < d; ++k) {
-    const T x = F[i + k * ld];
-    s += x * x;
-  }
-  N[i] = s;
-}
+using dottile::Mma;
+using dottile::NT;
+using dottile::row_norm_kernel;
+using dottile::TILE;
+using dottile::WT;
 
 // MT bits of a 128-bit row of the tile's bit matrices: piece p = bits MT * p .. MT * p + MT - 1
 template <int MT>
@@ -120,20 +68,21 @@ __device__ __forceinline__ int bits_before(const uint32_t (*m)[4], int r, int c)
 
 // FILL == false: write the per-(tile, row) counts and the tile flag.  FILL == true: write the entries of the tiles that
 // kept something (counts then hold in-row offsets).
-template <class T, bool SYM, bool FILL>
+// FLOOR: the per-row cut tau[na] next to alpha; a pair is then decided by its row alone, so there is no mirror (!SYM);
+// self: Fb is Fa, so the pairs (i, i) have s = 1 as in the symmetric mode.
+template <class T, bool SYM, bool FILL, bool FLOOR>
 __global__ void __launch_bounds__(NT) dot_tile_kernel(
     const T* __restrict__ Fa, int64_t na, int64_t lda, const T* __restrict__ Fb, int64_t nb, int64_t ldb, int64_t d,
-    const T* __restrict__ norm_a, const T* __restrict__ norm_b, int metric, T alpha, int weighted, int64_t nti,
-    int* __restrict__ counts, int* __restrict__ tile_nz, const int64_t* __restrict__ ptr, int* __restrict__ oidx,
-    T* __restrict__ oval, int* __restrict__ not_binary) {
+    const T* __restrict__ norm_a, const T* __restrict__ norm_b, int metric, T alpha, const T* __restrict__ tau, int self,
+    int weighted, int64_t nti, int* __restrict__ counts, int* __restrict__ tile_nz, const int64_t* __restrict__ ptr,
+    int* __restrict__ oidx, T* __restrict__ oval, int* __restrict__ not_binary) {
+  static_assert(!(SYM && FLOOR), "a per-row cut decides (i, j) and (j, i) separately");
   using M = Mma<T>;
-  constexpr int MT = M::MT, KS = M::KS, NR = M::NR;
-  constexpr int NM = WT / MT;          // MFMA tiles per wave edge
-  constexpr int LDT = TILE + M::PAD;
+  constexpr int MT = M::MT, NR = M::NR;
+  constexpr int NM = dottile::NM<T>;   // MFMA tiles per wave edge
   static_assert(NM * NM * NR == 64, "one kept bit per accumulator register in a 64-bit mask");
-  __shared__ __attribute__((aligned(16))) T As[BK][LDT];
-  __shared__ __attribute__((aligned(16))) T Bs[BK][LDT];
   __shared__ T na_s[TILE], nb_s[TILE];  // sqrt(A), sqrt(B) (cosine) or A, B of the tile's rows and columns
+  __shared__ T tau_s[FLOOR ? TILE : 1];  // FLOOR: the cut of the tile's rows
   __shared__ uint32_t rowbits[TILE][4];  // [row]: bit c = pair (row, c) is kept
   __shared__ uint32_t colbits[TILE][4];  // [column]: bit r = pair (r, column) is kept (SYM, off-diagonal tiles)
 
@@ -143,63 +92,16 @@ __global__ void __launch_bounds__(NT) dot_tile_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const bool mirror = t.mirror;
+  const bool diag1 = SYM || (FLOOR && self != 0);  // the block is a set against itself: s(i, i) = 1
 
   typename M::acc_t acc[NM][NM];
-#pragma unroll
-  for (int i = 0; i < NM; ++i)
-#pragma unroll
-    for (int j = 0; j < NM; ++j)
-#pragma unroll
-      for (int r = 0; r < NR; ++r) acc[i][j][r] = T(0);
-
-  // staging: BK feature columns of the tile's 128 rows of each side; consecutive threads read consecutive rows of one
-  // column (coalesced).  Past d or past the last row the value is 0: a padded k adds a zero product, and padded rows /
-  // columns are masked below.
-  constexpr int PER = BK * TILE / NT;
-  T ra[PER], rb[PER];
-  auto load = [&](int64_t k0) {
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int e = tid + q * NT;
-      const int kk = e / TILE, r = e % TILE;
-      const int64_t k = k0 + kk;
-      ra[q] = (k < d && i0 + r < na) ? Fa[i0 + r + k * lda] : T(0);
-      rb[q] = (k < d && j0 + r < nb) ? Fb[j0 + r + k * ldb] : T(0);
-    }
-  };
-  if (d > 0) load(0);
-  for (int64_t k0 = 0; k0 < d; k0 += BK) {
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int e = tid + q * NT;
-      As[e / TILE][e % TILE] = ra[q];
-      Bs[e / TILE][e % TILE] = rb[q];
-    }
-    __syncthreads();
-    if (k0 + BK < d) load(k0 + BK);  // the next step's loads are in flight during this step's matrix work
-#pragma unroll
-    for (int kk = 0; kk < BK; kk += KS) {
-      const int kr = kk + lane / MT, c = lane % MT;
-      T av[NM], bv[NM];
-#pragma unroll
-      for (int i = 0; i < NM; ++i) av[i] = As[kr][wm * WT + i * MT + c];
-#pragma unroll
-      for (int j = 0; j < NM; ++j) bv[j] = Bs[kr][wn * WT + j * MT + c];
-#pragma unroll
-      for (int i = 0; i < NM; ++i)
-#pragma unroll
-        for (int j = 0; j < NM; ++j) acc[i][j] = M::mma(av[i], bv[j], acc[i][j]);
-    }
-    __syncthreads();
-  }
+  dottile::dot_tile_gram<T>(Fa, na, lda, Fb, nb, ldb, d, i0, j0, acc);
 
   if (tid < TILE) {
-    const T x = i0 + tid < na ? norm_a[i0 + tid] : T(0);
-    na_s[tid] = metric == SS_SIM_COSINE ? sqrt(x) : x;
+    dottile::stage_norm<T>(na_s, tid, norm_a, i0, na, metric);
+    if constexpr (FLOOR) tau_s[tid] = i0 + tid < na ? tau[i0 + tid] : T(0);
   } else {
-    const int r = tid - TILE;
-    const T x = j0 + r < nb ? norm_b[j0 + r] : T(0);
-    nb_s[r] = metric == SS_SIM_COSINE ? sqrt(x) : x;
+    dottile::stage_norm<T>(nb_s, tid - TILE, norm_b, j0, nb, metric);
   }
   __syncthreads();
 
@@ -217,10 +119,11 @@ __global__ void __launch_bounds__(NT) dot_tile_kernel(
 #pragma unroll
       for (int r = 0; r < NR; ++r) {
         const int row = wm * WT + i * MT + M::row(r, lane);
-        T s = dot_sim<T>(acc[i][j][r], na_s[row], cb, metric);
-        if (SYM && i0 + row == j0 + col) s = T(1);
+        const T s = dottile::dot_pair_sim<T>(acc[i][j][r], na_s[row], cb, metric, diag1 && i0 + row == j0 + col);
         const T v = wgt ? s : T(1);
-        const bool k = i0 + row < na && j0 + col < nb && s >= alpha && v != T(0);
+        bool k = i0 + row < na && j0 + col < nb && v != T(0);
+        if constexpr (FLOOR) k = k && (s >= alpha || (s > T(0) && s >= tau_s[row]));
+        else k = k && s >= alpha;
         acc[i][j][r] = v;
         kept |= (uint64_t)(k ? 1 : 0) << ((i * NM + j) * NR + r);
         cm |= (k ? 1u : 0u) << M::row(r, lane);
@@ -280,48 +183,63 @@ __global__ void __launch_bounds__(NT) dot_tile_kernel(
 }  // namespace
 
 template <class T>
+int dot_row_norms(const T* F, int64_t n, int64_t ld, int64_t d, T* norm) {
+  hipLaunchKernelGGL(row_norm_kernel<T>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx().stream, F, n, ld, d, norm);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+template <class T>
 int DotCsr<T>::count(const T* Fa_, int64_t na_, int64_t lda_, const T* Fb_, int64_t nb_, int64_t ldb_, int64_t d_,
-                     int metric_, T alpha_, bool weighted_) {
-  hipStream_t st = ctx().stream;
+                     int metric_, T alpha_, bool weighted_, int k) {
   what = "dot_csr";
-  sym = (Fb_ == nullptr);
+  self = (Fb_ == nullptr);
+  sym = self;
   Fa = Fa_;
-  Fb = sym ? Fa_ : Fb_;
+  Fb = self ? Fa_ : Fb_;
   lda = lda_;
-  ldb = sym ? lda_ : ldb_;
+  ldb = self ? lda_ : ldb_;
   d = d_;
   metric = metric_;
   alpha = alpha_;
   weighted = weighted_;
+  tau = nullptr;
   if (metric != SS_SIM_COSINE && metric != SS_SIM_TANIMOTO && metric != SS_SIM_DICE)
     return fail(SS_EINVAL, "dot_csr: unknown metric %d", metric);
   if (alpha != alpha) return fail(SS_EINVAL, "dot_csr: alpha is NaN");
   SS_TRY(this->refuse_nan_features(Fa, na_, lda, Fb, nb_, ldb, d));
-  SS_TRY(this->begin_tiles(na_, sym ? na_ : nb_, TILE, true));
+  sym = self && k == 0;  // a per-row cut has no mirror: the full grid
+  SS_TRY(this->begin_tiles(na_, self ? na_ : nb_, TILE, true));
   if (na == 0 || nb == 0) return SS_OK;
   SS_TRY(norm_a.alloc((size_t)na));
-  hipLaunchKernelGGL(row_norm_kernel<T>, dim3((unsigned)ceil_div(na, 256)), dim3(256), 0, st, Fa, na, lda, d, norm_a.p);
-  SS_LAUNCH_CHECK();
-  if (!sym) {
+  SS_TRY(dot_row_norms<T>(Fa, na, lda, d, norm_a.p));
+  if (!self) {
     SS_TRY(norm_b.alloc((size_t)nb));
-    hipLaunchKernelGGL(row_norm_kernel<T>, dim3((unsigned)ceil_div(nb, 256)), dim3(256), 0, st, Fb, nb, ldb, d,
-                       norm_b.p);
-    SS_LAUNCH_CHECK();
+    SS_TRY(dot_row_norms<T>(Fb, nb, ldb, d, norm_b.p));
+  }
+  if (k > 0) {
+    SS_TRY(tau_buf.alloc(na));
+    SS_TRY(dot_kth<T>(Fa, na, lda, self ? nullptr : Fb, nb, ldb, d, metric, norm_a.p, self ? norm_a.p : norm_b.p, k,
+                      tau_buf.p));
+    tau = tau_buf.p;
   }
   return this->count_pass();
 }
 
 template <class T>
 int DotCsr<T>::launch(bool fill, int* idx, T* val, int* flag) {
-  auto* kernel = sym ? (fill ? dot_tile_kernel<T, true, true> : dot_tile_kernel<T, true, false>)
-                     : (fill ? dot_tile_kernel<T, false, true> : dot_tile_kernel<T, false, false>);
+  auto* kernel = tau   ? (fill ? dot_tile_kernel<T, false, true, true> : dot_tile_kernel<T, false, false, true>)
+                 : sym ? (fill ? dot_tile_kernel<T, true, true, false> : dot_tile_kernel<T, true, false, false>)
+                       : (fill ? dot_tile_kernel<T, false, true, false> : dot_tile_kernel<T, false, false, false>);
   hipLaunchKernelGGL(kernel, this->tile_grid(), dim3(NT), 0, ctx().stream, Fa, na, lda, Fb, nb, ldb, d, norm_a.p,
-                     sym ? norm_a.p : norm_b.p, metric, alpha, weighted ? 1 : 0, nti, counts.p, tile_nz.p, ptr.p, idx,
-                     val, flag);
+                     self ? norm_a.p : norm_b.p, metric, alpha, tau, self ? 1 : 0, weighted ? 1 : 0, nti, counts.p,
+                     tile_nz.p, ptr.p, idx, val, flag);
   SS_LAUNCH_CHECK();
   return SS_OK;
 }
 
+template int dot_row_norms<float>(const float*, int64_t, int64_t, int64_t, float*);
+template int dot_row_norms<double>(const double*, int64_t, int64_t, int64_t, double*);
 template struct DotCsr<float>;
 template struct DotCsr<double>;
 

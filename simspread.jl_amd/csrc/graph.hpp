@@ -438,6 +438,11 @@ struct PairCsr {
   // may be null, and *flag = 1 when a value is not 1), over tile_grid() when it is tiled
   virtual int launch(bool fill, int* idx, T* val, int* flag) = 0;
 };
+// SS_EINVAL when Fa (na x d, column-major, lda >= na; padding rows are not read) or Fb (nullptr: no second side) holds
+// a NaN (synchronises)
+template <class T>
+int refuse_nan_rows(const char* what, const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb,
+                    int64_t d);
 // the members a producer names unqualified
 #define SS_PAIR_CSR_MEMBERS(T)                                                                                       \
   using PairCsr<T>::what, PairCsr<T>::na, PairCsr<T>::nb, PairCsr<T>::nti, PairCsr<T>::ntj, PairCsr<T>::nnz,          \
@@ -483,8 +488,12 @@ struct JaccardCsr : PairCsr<T> {
   const T* Fa = nullptr;
   const T* Fb = nullptr;
   int64_t lda = 0, ldb = 0, d = 0;
+  bool self = false;       // Fb == Fa (sym says whether the triangle grid runs: not with a per-row cut)
+  const T* tau = nullptr;  // per-row cut of the neighbour floor: entry (i, j) is also kept when 0 < s and s >= tau[i]
+  DevBuf<T> tau_buf;
+  // k > 0: the neighbour floor -- tau = jaccard_kth(k) first, then the count pass over the full (ntj, nti) grid
   int count(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d, T alpha,
-            bool weighted);
+            bool weighted, int k = 0);
 
  protected:
   int launch(bool fill, int* idx, T* val, int* flag) override;
@@ -500,13 +509,32 @@ struct DotCsr : PairCsr<T> {
   const T* Fb = nullptr;
   int64_t lda = 0, ldb = 0, d = 0;
   int metric = 0;
-  DevBuf<T> norm_a, norm_b;  // squared row norms of each side (norm_b unused in symmetric mode)
+  DevBuf<T> norm_a, norm_b;  // squared row norms of each side (norm_b unused when Fb == Fa)
+  bool self = false;         // Fb == Fa (sym says whether the triangle grid runs: not with a per-row cut)
+  const T* tau = nullptr;    // per-row cut of the neighbour floor, as JaccardCsr::tau
+  DevBuf<T> tau_buf;
+  // k > 0: the neighbour floor -- tau = dot_kth(k) first, then the count pass over the full (ntj, nti) grid
   int count(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d, int metric, T alpha,
-            bool weighted);
+            bool weighted, int k = 0);
 
  protected:
   int launch(bool fill, int* idx, T* val, int* flag) override;
 };
+// norm[i] = sum_k F[i, k]^2 in T (enqueued on the stream): the squared row norms the producer and dot_kth share
+template <class T>
+int dot_row_norms(const T* F, int64_t n, int64_t ld, int64_t d, T* norm);
+
+// ---- real_floor.hip: the neighbour floor of the two producers above.  tau[i] = the k-th largest of the positive
+// similarities s(i, j) of row i of Fa against the rows of Fb (multiplicity counted), +0 when there are fewer than k;
+// 1 <= k <= NEIGHBOUR_K_MAX; s is bit for bit the producer's (jaccard_tile.hpp, dot_tile.hpp).  Device pointers, layout
+// as for the producers, Fb == nullptr: Fb = Fa (dot: s(i, i) = 1).  norm_a / norm_b: the squared row norms (norm_a ==
+// nullptr: computed here).  Enqueued on the stream; the scratch is freed after a synchronisation.  Bitwise repeatable.
+// NaN features are the caller's to refuse.
+template <class T>
+int jaccard_kth(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d, int k, T* tau);
+template <class T>
+int dot_kth(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d, int metric,
+            const T* norm_a, const T* norm_b, int k, T* tau);
 
 // ---- recut.hip: featurize on a device CSR matrix (entry kept iff v >= alpha, alpha > 0; as v when weighted, else 1),
 // two streaming passes over `in`, which must outlive the producer.  graph_recut: g = p with Xq, Xs, XsT cut, the labels

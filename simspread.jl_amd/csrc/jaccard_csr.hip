@@ -16,150 +16,119 @@
 // pair_tile.hpp, the host side PairCsr (pair_csr.hip):
 //   count  per (column tile, row): the number of kept entries -> counts[jt * rows + i]; per tile: any kept -> tile_nz
 //   fill   the tiles that kept something, again, each slot written at ptr[i] + its offset in column order.
-// Register blocks: fp32 8 x 8 pairs per thread (256 threads, 128 accumulator VGPRs), fp64 4 x 8 (512 threads, the
-// same 128 VGPRs).  This file holds what is the producer's own: the staging, the two sums and the keep rule.
+// This file holds what is the producer's own: the keep rule and the host side.  The staging, the two sums and the
+// expression of s are jaccard_tile.hpp, shared with the selection pass of the neighbour floor (real_floor.hip): with
+// k > 0, count() first asks it for tau[na], the k-th largest positive similarity of every row, and the tile kernel keeps
+// (i, j) iff v != 0 and (s >= alpha or (s > 0 and s >= tau[i])).  That rule is not symmetric, so the floor case runs the
+// full (ntj, nti) grid with Fb = Fa instead of the triangle.
 #include <hip/hip_runtime.h>
 
 #include "graph.hpp"
+#include "jaccard_tile.hpp"
 #include "pair_tile.hpp"
 
 namespace ss {
 
 namespace {
 
-constexpr int TILE = 128;  // rows and columns per workgroup tile
-constexpr int BK = 16;     // feature columns staged per step
-constexpr int RC = 8;      // columns per thread
-constexpr int NTX = TILE / RC;  // 16 thread columns
-
-template <class T>
-struct Block;
-template <>
-struct Block<float> {
-  static constexpr int RA = 8;  // rows per thread
-};
-template <>
-struct Block<double> {
-  static constexpr int RA = 4;
-};
-
-__device__ __forceinline__ float vmin(float a, float b) { return __builtin_fminf(a, b); }
-__device__ __forceinline__ float vmax(float a, float b) { return __builtin_fmaxf(a, b); }
-__device__ __forceinline__ double vmin(double a, double b) { return __builtin_fmin(a, b); }
-__device__ __forceinline__ double vmax(double a, double b) { return __builtin_fmax(a, b); }
+using jctile::BK;
+using jctile::Block;
+using jctile::NTX;
+using jctile::RC;
+using jctile::threads;
+using jctile::TILE;
 
 template <class T>
 __device__ __forceinline__ bool jaccard_keep(T smin, T smax, T alpha, bool weighted, T& v) {
-  const T s = smax == T(0) ? T(1) : smin / smax;
+  const T s = jctile::jaccard_similarity<T>(smin, smax);
   v = weighted ? s : T(1);
   return s >= alpha && v != T(0);
 }
 
+// the neighbour floor (real_floor.hip): row i also keeps its positive similarities >= tau = tau[i], the k-th largest of
+// them (+0 when it has fewer than k: all of them stay)
+template <class T>
+__device__ __forceinline__ bool jaccard_keep_floor(T smin, T smax, T alpha, T tau, bool weighted, T& v) {
+  const T s = jctile::jaccard_similarity<T>(smin, smax);
+  v = weighted ? s : T(1);
+  return v != T(0) && (s >= alpha || (s > T(0) && s >= tau));
+}
+
 // FILL == false: write the per-(tile, row) counts and the tile flag.  FILL == true: write the entries of the tiles that
 // kept something (counts then hold in-row offsets).
-template <class T, bool SYM, bool FILL>
-__global__ void __launch_bounds__(NTX * (TILE / Block<T>::RA)) jaccard_tile_kernel(
+// FLOOR: the per-row cut tau[na] next to alpha; a pair is then decided by its row alone, so there is no mirror (!SYM).
+template <class T, bool SYM, bool FILL, bool FLOOR>
+__global__ void __launch_bounds__(threads<T>()) jaccard_tile_kernel(
     const T* __restrict__ Fa, int64_t na, int64_t lda, const T* __restrict__ Fb, int64_t nb, int64_t ldb, int64_t d,
-    T alpha, int weighted, int64_t nti, int* __restrict__ counts, int* __restrict__ tile_nz,
-    const int64_t* __restrict__ ptr, int* __restrict__ oidx, T* __restrict__ oval, int* __restrict__ not_binary) {
+    T alpha, const T* __restrict__ tau, int weighted, int64_t nti, int* __restrict__ counts,
+    int* __restrict__ tile_nz, const int64_t* __restrict__ ptr, int* __restrict__ oidx, T* __restrict__ oval,
+    int* __restrict__ not_binary) {
+  static_assert(!(SYM && FLOOR), "a per-row cut decides (i, j) and (j, i) separately");
   constexpr int RA = Block<T>::RA;
-  constexpr int NTY = TILE / RA;       // thread rows
-  constexpr int NT = NTX * NTY;        // threads
-  __shared__ __attribute__((aligned(16))) T As[BK][TILE];
-  __shared__ __attribute__((aligned(16))) T Bs[BK][TILE];
 
   if (FILL && tile_nz[pair_tile_index<SYM>()] == 0) return;  // uniform over the block
   const PairTile t = pair_tile<SYM, TILE>(nti);
-  const int64_t i0 = t.i0, j0 = t.j0;
-  const int tid = threadIdx.x, tx = tid % NTX, ty = tid / NTX;
 
-  // acc[a][b] = (smin, smax) of one pair: the two sums sit in adjacent registers, so that fp32 adds them with one
-  // v_pk_add_f32 (lane-wise, each lane one correctly rounded add -- the same two adds)
-  typedef T T2 __attribute__((ext_vector_type(2)));
-  T2 acc[RA][RC];
-#pragma unroll
-  for (int a = 0; a < RA; ++a)
-#pragma unroll
-    for (int b = 0; b < RC; ++b) acc[a][b] = T2{T(0), T(0)};
-
-  // staging: BK feature columns of the tile's 128 rows of each side; consecutive threads read consecutive rows of one
-  // column (coalesced).  Past d or past the last row the value is 0: a padded k adds +0 to both sums, which changes
-  // nothing, and padded rows / columns are masked below.
-  constexpr int PER = BK * TILE / NT;
-  T ra[PER], rb[PER];
-  auto load = [&](int64_t k0) {
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int e = tid + q * NT;
-      const int kk = e / TILE, r = e % TILE;
-      const int64_t k = k0 + kk;
-      ra[q] = (k < d && i0 + r < na) ? Fa[i0 + r + k * lda] : T(0);
-      rb[q] = (k < d && j0 + r < nb) ? Fb[j0 + r + k * ldb] : T(0);
-    }
-  };
-  if (d > 0) load(0);
-  for (int64_t k0 = 0; k0 < d; k0 += BK) {
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int e = tid + q * NT;
-      As[e / TILE][e % TILE] = ra[q];
-      Bs[e / TILE][e % TILE] = rb[q];
-    }
-    __syncthreads();
-    if (k0 + BK < d) load(k0 + BK);  // the next step's loads are in flight during this step's arithmetic
-#pragma unroll
-    for (int kk = 0; kk < BK; ++kk) {
-      T av[RA], bv[RC];
-#pragma unroll
-      for (int a = 0; a < RA; ++a) av[a] = As[kk][RA * ty + a];
-#pragma unroll
-      for (int b = 0; b < RC; ++b) bv[b] = Bs[kk][RC * tx + b];
-#pragma unroll
-      for (int a = 0; a < RA; ++a)
-#pragma unroll
-        for (int b = 0; b < RC; ++b) acc[a][b] += T2{vmin(av[a], bv[b]), vmax(av[a], bv[b])};
-    }
-    __syncthreads();
-  }
+  jctile::Sums<T> acc[RA][RC];
+  jctile::jaccard_tile_sums<T>(Fa, na, lda, Fb, nb, ldb, d, t.i0, t.j0, acc);
 
   const bool wgt = weighted != 0;
-  pair_tile_emit<T, TILE, RA, RC, SYM, FILL, true>(
-      t, na, nb, [&](int a, int b, T& v) { return jaccard_keep<T>(acc[a][b].x, acc[a][b].y, alpha, wgt, v); }, counts,
-      tile_nz, ptr, oidx, oval, not_binary);
-}
-
-template <class T>
-constexpr int threads() {
-  return NTX * (TILE / Block<T>::RA);
+  if constexpr (FLOOR) {
+    const int ty = threadIdx.x / NTX;
+    T ta[RA];
+#pragma unroll
+    for (int a = 0; a < RA; ++a) {
+      const int64_t i = t.i0 + RA * ty + a;
+      ta[a] = i < na ? tau[i] : T(0);
+    }
+    pair_tile_emit<T, TILE, RA, RC, false, FILL, true>(
+        t, na, nb,
+        [&](int a, int b, T& v) { return jaccard_keep_floor<T>(acc[a][b].x, acc[a][b].y, alpha, ta[a], wgt, v); },
+        counts, tile_nz, ptr, oidx, oval, not_binary);
+  } else {
+    pair_tile_emit<T, TILE, RA, RC, SYM, FILL, true>(
+        t, na, nb, [&](int a, int b, T& v) { return jaccard_keep<T>(acc[a][b].x, acc[a][b].y, alpha, wgt, v); }, counts,
+        tile_nz, ptr, oidx, oval, not_binary);
+  }
 }
 
 }  // namespace
 
 template <class T>
 int JaccardCsr<T>::count(const T* Fa_, int64_t na_, int64_t lda_, const T* Fb_, int64_t nb_, int64_t ldb_, int64_t d_,
-                         T alpha_, bool weighted_) {
+                         T alpha_, bool weighted_, int k) {
   what = "jaccard";
-  sym = (Fb_ == nullptr);
+  self = (Fb_ == nullptr);
+  sym = self;
   Fa = Fa_;
-  Fb = sym ? Fa_ : Fb_;
+  Fb = self ? Fa_ : Fb_;
   lda = lda_;
-  ldb = sym ? lda_ : ldb_;
+  ldb = self ? lda_ : ldb_;
   d = d_;
   alpha = alpha_;
   weighted = weighted_;
+  tau = nullptr;
   if (alpha != alpha) return fail(SS_EINVAL, "jaccard: alpha is NaN");
   SS_TRY(this->refuse_nan_features(Fa, na_, lda, Fb, nb_, ldb, d));
-  SS_TRY(this->begin_tiles(na_, sym ? na_ : nb_, TILE, true));
+  sym = self && k == 0;  // a per-row cut has no mirror: the full grid
+  SS_TRY(this->begin_tiles(na_, self ? na_ : nb_, TILE, true));
   if (na == 0 || nb == 0) return SS_OK;
+  if (k > 0) {
+    SS_TRY(tau_buf.alloc(na));
+    SS_TRY(jaccard_kth<T>(Fa, na, lda, self ? nullptr : Fb, nb, ldb, d, k, tau_buf.p));
+    tau = tau_buf.p;
+  }
   return this->count_pass();
 }
 
 template <class T>
 int JaccardCsr<T>::launch(bool fill, int* idx, T* val, int* flag) {
-  auto* kernel = sym ? (fill ? jaccard_tile_kernel<T, true, true> : jaccard_tile_kernel<T, true, false>)
-                     : (fill ? jaccard_tile_kernel<T, false, true> : jaccard_tile_kernel<T, false, false>);
+  auto* kernel =
+      tau   ? (fill ? jaccard_tile_kernel<T, false, true, true> : jaccard_tile_kernel<T, false, false, true>)
+      : sym ? (fill ? jaccard_tile_kernel<T, true, true, false> : jaccard_tile_kernel<T, true, false, false>)
+            : (fill ? jaccard_tile_kernel<T, false, true, false> : jaccard_tile_kernel<T, false, false, false>);
   hipLaunchKernelGGL(kernel, this->tile_grid(), dim3(threads<T>()), 0, ctx().stream, Fa, na, lda, Fb, nb, ldb, d, alpha,
-                     weighted ? 1 : 0, nti, counts.p, tile_nz.p, ptr.p, idx, val, flag);
+                     tau, weighted ? 1 : 0, nti, counts.p, tile_nz.p, ptr.p, idx, val, flag);
   SS_LAUNCH_CHECK();
   return SS_OK;
 }

@@ -15,9 +15,8 @@
 //            leaves the k largest positive values of every row among those columns in part[g][row][0..k), +0 padded.
 //            Column groups are the second level of parallelism: few rows against many columns (query batches) would
 //            otherwise be a handful of blocks.
-//   merge    one wave per row: the k-th largest of the row's groups * k partial values by rank counting (value v is
-//            the answer iff fewer than k values are greater and at least k are greater or equal), which does not
-//            depend on the order of the values.
+//   merge    kth_merge.hpp, shared with the selections of the real-valued producers (real_floor.hip), as is the sizing
+//            of the column groups.
 // Scratch: na * k * groups values.  Every device loop is bounded by k, the tile width, the tiles of a group or
 // groups * k <= 4096 (host-checked); there are no spin-waits and no flags between workgroups.
 //
@@ -29,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include "graph.hpp"
+#include "kth_merge.hpp"
 #include "row_select.hpp"
 #include "tanimoto_tile.hpp"
 
@@ -39,12 +39,6 @@ namespace {
 using fptile::BK;
 using fptile::RB;
 using fptile::TILE;
-
-constexpr int MAX_GROUPS = 64;                         // column groups: groups * k values per row fit the merge's LDS
-constexpr int MERGE_VALUES = MAX_GROUPS * NEIGHBOUR_K_MAX;
-constexpr int MIN_GROUP_TILES = 4;                     // a group's first tile fills the lists: not worth less
-constexpr int64_t TARGET_BLOCKS = 4096;                // 256 CUs x 3 resident blocks, a few rounds of them
-constexpr int64_t MAX_SCRATCH_BYTES = 512LL << 20;
 
 // the pair similarity of the selection: THE expression of the emit pass
 template <class T>
@@ -61,7 +55,7 @@ __global__ void __launch_bounds__(256) tanimoto_kth_partial_kernel(
     T* __restrict__ part, Sim sim) {
   __shared__ __attribute__((aligned(16))) uint32_t As[BK][TILE];
   __shared__ __attribute__((aligned(16))) uint32_t Bs[BK][TILE];
-  __shared__ RowSelect<T, TILE, RB, ROWS> sel;
+  __shared__ RowSelect<T, TILE, ROWS> sel;
 
   constexpr int NH = TILE / ROWS;  // blocks per row strip
   const int64_t it = blockIdx.x / NH;
@@ -104,39 +98,6 @@ __global__ void __launch_bounds__(256) tanimoto_kth_partial_kernel(
   sel.store(i0 + sel0, na, k, cnt, part + g * na * k);
 }
 
-// tau[i] = the k-th largest of part[g][i][0..k), g < groups, when at least k of them are positive, else +0
-template <class T>
-__global__ void __launch_bounds__(64) kth_merge_kernel(const T* __restrict__ part, int64_t na, int k, int groups,
-                                                       T* __restrict__ tau) {
-  __shared__ T buf[MERGE_VALUES];
-  const int64_t i = blockIdx.x;
-  const int lane = threadIdx.x;
-  const int n = groups * k;  // <= MERGE_VALUES (host-checked)
-  for (int e = lane; e < n; e += 64) {
-    const int g = e / k, j = e - g * k;
-    buf[e] = part[((int64_t)g * na + i) * k + j];
-  }
-  __syncthreads();
-  T found = T(0);
-  for (int e = lane; e < n; e += 64) {
-    const T v = buf[e];
-    if (!(v > T(0))) continue;
-    int gt = 0, ge = 0;
-    for (int x = 0; x < n; ++x) {
-      const T w = buf[x];
-      gt += w > v ? 1 : 0;
-      ge += w >= v ? 1 : 0;
-    }
-    if (gt < k && ge >= k) found = v;  // every lane that finds one finds the same value
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const T o = __shfl_xor(found, off);
-    found = o > found ? o : found;
-  }
-  if (lane == 0) tau[i] = found;
-}
-
 }  // namespace
 
 template <class T>
@@ -177,17 +138,8 @@ int tanimoto_kth(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb,
     return fail(SS_EUNSUPPORTED, "tanimoto kth: the lists of %d rows x k = %d do not fit in LDS", rows, k);
   const int64_t ntj = ceil_div(nb, TILE);
   const int64_t row_blocks = ceil_div(na, TILE) * (TILE / rows);
-  if (row_blocks >= (1LL << 31))
-    return fail(SS_EUNSUPPORTED, "tanimoto kth: %lld rows need more blocks than one launch holds", (long long)na);
-  int64_t groups = ceil_div(TARGET_BLOCKS, row_blocks);
-  groups = std::min<int64_t>(groups, ceil_div(ntj, MIN_GROUP_TILES));
-  groups = std::min<int64_t>(groups, MAX_GROUPS);
-  groups = std::min<int64_t>(groups, MAX_SCRATCH_BYTES / (na * k * (int64_t)sizeof(T)));
-  groups = std::max<int64_t>(groups, 1);
-  const int64_t tiles_per_group = ceil_div(ntj, groups);
-  groups = ceil_div(ntj, tiles_per_group);  // no empty group
-  if (groups * k > MERGE_VALUES)
-    return fail(SS_EUNSUPPORTED, "tanimoto kth: %lld column groups x k = %d exceed the merge buffer", (long long)groups, k);
+  int64_t groups = 0, tiles_per_group = 0;
+  SS_TRY(kth::plan_groups<T>("tanimoto kth", na, ntj, row_blocks, k, groups, tiles_per_group));
 
   DevBuf<T> part;
   SS_TRY(part.alloc((size_t)groups * (size_t)na * (size_t)k));
@@ -196,8 +148,7 @@ int tanimoto_kth(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb,
   hipLaunchKernelGGL(partial, dim3((unsigned)row_blocks, (unsigned)groups), dim3(256), 0, st, Fa, na, Fb, nb, nwords,
                      pop_a, pop_b, k, ntj, tiles_per_group, part.p, TanimotoSim<T>());
   SS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(kth_merge_kernel<T>, dim3((unsigned)na), dim3(64), 0, st, (const T*)part.p, na, k, (int)groups, tau);
-  SS_LAUNCH_CHECK();
+  SS_TRY(kth::launch_merge<T>(part.p, na, k, groups, tau, st));
   SS_HIP(hipStreamSynchronize(st));  // part and the popcounts are freed on return
   return SS_OK;
 }

@@ -96,19 +96,25 @@ dim3 PairCsr<T>::tile_grid() const {
 }
 
 template <class T>
-int PairCsr<T>::refuse_nan_features(const T* Fa, int64_t na_, int64_t lda, const T* Fb, int64_t nb_, int64_t ldb,
-                                    int64_t d) {
+int refuse_nan_rows(const char* what, const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb,
+                    int64_t d) {
   hipStream_t st = ctx().stream;
   DevBuf<int> flag;
   SS_TRY(flag.alloc(1));
   SS_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-  SS_TRY(launch_feature_nan_scan<T>(Fa, na_, lda, d, flag.p));
-  if (!sym) SS_TRY(launch_feature_nan_scan<T>(Fb, nb_, ldb, d, flag.p));
+  SS_TRY(launch_feature_nan_scan<T>(Fa, na, lda, d, flag.p));
+  if (Fb) SS_TRY(launch_feature_nan_scan<T>(Fb, nb, ldb, d, flag.p));
   int bad = 0;
   SS_HIP(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
   SS_HIP(hipStreamSynchronize(st));
   if (bad) return fail(SS_EINVAL, "%s: the features hold a NaN", what);
   return SS_OK;
+}
+
+template <class T>
+int PairCsr<T>::refuse_nan_features(const T* Fa, int64_t na_, int64_t lda, const T* Fb, int64_t nb_, int64_t ldb,
+                                    int64_t d) {
+  return refuse_nan_rows<T>(what, Fa, na_, lda, sym ? nullptr : Fb, nb_, ldb, d);
 }
 
 template <class T>
@@ -166,6 +172,9 @@ int PairCsr<T>::to_dev_csr(DevCsr<T>& out) {
   return SS_OK;
 }
 
+template int refuse_nan_rows<float>(const char*, const float*, int64_t, int64_t, const float*, int64_t, int64_t, int64_t);
+template int refuse_nan_rows<double>(const char*, const double*, int64_t, int64_t, const double*, int64_t, int64_t,
+                                     int64_t);
 template struct PairCsr<float>;
 template struct PairCsr<double>;
 

@@ -269,14 +269,17 @@ class DeviceGraph:
         return cls(h, dt)
 
     @classmethod
-    def from_features(cls, Fq, Fs, Y, alpha: float, weighted: bool = True, dtype=np.float32, index_base: int = 0):
+    def from_features(cls, Fq, Fs, Y, alpha: float, weighted: bool = True, dtype=np.float32, index_base: int = 0,
+                      min_neighbours: int = 0):
         """``construct(y, X)`` with ``X = featurize(1 .- pairwise(Jaccard(), F, dims=1), alpha, weighted)`` for
         real-valued feature rows (the reference's tutorial, docs/src/tutorial/fishers-flowers.jl:66,95-96): Xq =
         cut(J(Fq, Fs)), Xs = cut(J(Fs, Fs)) with J the weighted Jaccard similarity of ``jaccard_csr``, features named
         after the sources, produced as CSR on the device (the dense similarity never exists).  Fq may be None (3-layer
         graph: predict_loo / predict_kfold / evaluate_loo).  Fq, Fs: (n, d) numpy arrays with Y a scipy matrix (ns x
         nt), or float CUDA tensors of the graph's dtype with Y = (ptr, idx, val, nt) device CSR.  index_base as for
-        ``from_fingerprints``."""
+        ``from_fingerprints``.  min_neighbours = k > 0 (at most 64) adds the neighbour floor of ``jaccard_csr``: every
+        source and every query also keeps its k nearest sources (ties included), whatever alpha says; everything said of
+        it at ``from_fingerprints`` holds here."""
         dt = _feature_dtype(dtype)
         dev = _is_torch(Fs)
         keep = []
@@ -288,9 +291,14 @@ class DeviceGraph:
         lib = L.lib()
         h = C.c_void_p()
         ctype = C.c_float if dt == np.float32 else C.c_double
-        fn = getattr(lib, f"ss_graph_create_features_{_suffix(dt)}")
-        L.check(fn(nq, ns, nt, d, fq, ldq, fs, lds, yptr, yidx, yval, index_base, ctype(alpha), 1 if weighted else 0, mem,
-                   C.byref(h)))
+        if min_neighbours:
+            fn = getattr(lib, f"ss_graph_create_features_floor_{_suffix(dt)}")
+            L.check(fn(nq, ns, nt, d, fq, ldq, fs, lds, yptr, yidx, yval, index_base, ctype(alpha), int(min_neighbours),
+                       1 if weighted else 0, mem, C.byref(h)))
+        else:
+            fn = getattr(lib, f"ss_graph_create_features_{_suffix(dt)}")
+            L.check(fn(nq, ns, nt, d, fq, ldq, fs, lds, yptr, yidx, yval, index_base, ctype(alpha), 1 if weighted else 0,
+                       mem, C.byref(h)))
         if dev:
             L.check(lib.ss_synchronize())
         del keep
@@ -298,12 +306,13 @@ class DeviceGraph:
 
     @classmethod
     def from_vectors(cls, Fq, Fs, Y, alpha: float, metric="cosine", weighted: bool = True, dtype=np.float32,
-                     index_base: int = 0):
+                     index_base: int = 0, min_neighbours: int = 0):
         """``construct(y, X)`` with ``X = featurize(S(F), alpha, weighted)``, S the inner-product similarity ``metric``
         ("cosine", "tanimoto", "dice") of ``dot_csr`` between real-valued rows (embeddings, continuous descriptors): Xq =
         cut(S(Fq, Fs)), Xs = cut(S(Fs, Fs)), features named after the sources, produced as CSR on the device (the dense
         similarity never exists).  Fq may be None (3-layer graph: predict_loo / predict_kfold / evaluate_loo).  Inputs
-        as ``from_features``."""
+        as ``from_features``, min_neighbours included: the k nearest are the k largest positive similarities, so negative
+        ones (signed embeddings) never count among them."""
         dt = _feature_dtype(dtype)
         m = _sim_metric(metric)
         dev = _is_torch(Fs)
@@ -316,10 +325,15 @@ class DeviceGraph:
         lib = L.lib()
         h = C.c_void_p()
         ctype = C.c_float if dt == np.float32 else C.c_double
-        fn = getattr(lib, f"ss_graph_create_vectors_{_suffix(dt)}")
-        L.check(fn(nq, ns, nt, d, m, fq, ldq, fs, lds, yptr, yidx, yval, index_base, ctype(alpha), 1 if weighted else 0,
-                   mem,
-                   C.byref(h)))
+        if min_neighbours:
+            fn = getattr(lib, f"ss_graph_create_vectors_floor_{_suffix(dt)}")
+            L.check(fn(nq, ns, nt, d, m, fq, ldq, fs, lds, yptr, yidx, yval, index_base, ctype(alpha), int(min_neighbours),
+                       1 if weighted else 0, mem, C.byref(h)))
+        else:
+            fn = getattr(lib, f"ss_graph_create_vectors_{_suffix(dt)}")
+            L.check(fn(nq, ns, nt, d, m, fq, ldq, fs, lds, yptr, yidx, yval, index_base, ctype(alpha),
+                       1 if weighted else 0, mem,
+                       C.byref(h)))
         if dev:
             L.check(lib.ss_synchronize())
         del keep
@@ -674,7 +688,7 @@ class DeviceQueries:
         return cls(h, graph)
 
     @classmethod
-    def _from_rows(cls, name, graph, Fq, Fs, mid, alpha, weighted):
+    def _from_rows(cls, name, graph, Fq, Fs, mid, alpha, weighted, min_neighbours=0):
         lib = L.lib()
         dt = graph.dtype.type
         dev = _is_torch(Fs)
@@ -684,8 +698,9 @@ class DeviceQueries:
         if Fq is not None and dq != d:
             raise ValueError("Fq and Fs have different numbers of features")
         h = C.c_void_p()
-        fn = getattr(lib, f"ss_queries_create_{name}_{_suffix(dt)}")
-        L.check(fn(graph._h, nq, ns, d, *mid, fq, ldq, fs, lds, graph._ctype()(alpha), 1 if weighted else 0,
+        floor = (int(min_neighbours),) if min_neighbours else ()       # the floor entry points take k after alpha
+        fn = getattr(lib, f"ss_queries_create_{name}{'_floor' if floor else ''}_{_suffix(dt)}")
+        L.check(fn(graph._h, nq, ns, d, *mid, fq, ldq, fs, lds, graph._ctype()(alpha), *floor, 1 if weighted else 0,
                    L.SS_MEM_DEVICE if dev else L.SS_MEM_HOST, C.byref(h)))
         if dev:
             L.check(lib.ss_synchronize())
@@ -693,14 +708,17 @@ class DeviceQueries:
         return cls(h, graph)
 
     @classmethod
-    def from_features(cls, graph: DeviceGraph, Fq, Fs, alpha: float, weighted: bool = True):
-        """Xq = cut(J(Fq, Fs)), the weighted Jaccard block of ``DeviceGraph.from_features``; inputs as there."""
-        return cls._from_rows("features", graph, Fq, Fs, (), alpha, weighted)
+    def from_features(cls, graph: DeviceGraph, Fq, Fs, alpha: float, weighted: bool = True, min_neighbours: int = 0):
+        """Xq = cut(J(Fq, Fs)), the weighted Jaccard block of ``DeviceGraph.from_features``; inputs as there.
+        min_neighbours = k > 0: every query also keeps its k nearest sources, as ``from_fingerprints``."""
+        return cls._from_rows("features", graph, Fq, Fs, (), alpha, weighted, min_neighbours)
 
     @classmethod
-    def from_vectors(cls, graph: DeviceGraph, Fq, Fs, alpha: float, metric="cosine", weighted: bool = True):
-        """Xq = cut(S(Fq, Fs)), the inner-product block of ``DeviceGraph.from_vectors``; inputs as there."""
-        return cls._from_rows("vectors", graph, Fq, Fs, (_sim_metric(metric),), alpha, weighted)
+    def from_vectors(cls, graph: DeviceGraph, Fq, Fs, alpha: float, metric="cosine", weighted: bool = True,
+                     min_neighbours: int = 0):
+        """Xq = cut(S(Fq, Fs)), the inner-product block of ``DeviceGraph.from_vectors``; inputs as there.
+        min_neighbours = k > 0: every query also keeps its k nearest sources, as ``from_fingerprints``."""
+        return cls._from_rows("vectors", graph, Fq, Fs, (_sim_metric(metric),), alpha, weighted, min_neighbours)
 
     def degrees(self) -> np.ndarray:
         """Stored entries of every query row: 0 = no source is similar enough (outside the applicability domain)."""
@@ -1599,9 +1617,9 @@ def _sim_metric(metric):
     return SIM_METRICS[metric]
 
 
-def _feature_pair_csr(name, Fa, Fb, mid, alpha, weighted, dtype):
-    """The size protocol shared by the feature-row producers ss_similarity_<name>_csr_*: `mid` are the arguments between
-    d and alpha."""
+def _feature_pair_csr(name, Fa, Fb, mid, alpha, weighted, dtype, min_neighbours=0):
+    """The size protocol shared by the feature-row producers ss_similarity_<name>_csr_* and, with min_neighbours = k > 0,
+    ss_similarity_<name>_floor_csr_* (k after alpha): `mid` are the arguments between d and alpha."""
     dt = _feature_dtype(dtype)
     dev = _is_torch(Fa)
     keep = []
@@ -1611,10 +1629,11 @@ def _feature_pair_csr(name, Fa, Fb, mid, alpha, weighted, dtype):
         nb, db, ldb = na, d, lda
     if db != d:
         raise ValueError("Fa and Fb have different numbers of features")
-    fn = getattr(L_.lib(), f"ss_similarity_{name}_csr_{_suffix(dt)}")
+    floor = (int(min_neighbours),) if min_neighbours else ()
+    fn = getattr(L_.lib(), f"ss_similarity_{name}{'_floor' if floor else ''}_csr_{_suffix(dt)}")
     ctype = C.c_float if dt == np.float32 else C.c_double
     nnz = C.c_int64(0)
-    head = (pa, na, lda, pb, nb, ldb, d) + tuple(mid) + (ctype(alpha), 1 if weighted else 0)
+    head = (pa, na, lda, pb, nb, ldb, d) + tuple(mid) + (ctype(alpha),) + floor + (1 if weighted else 0,)
     if dev:
         import torch
         ptr = torch.empty(na + 1, dtype=torch.int64, device=Fa.device)
@@ -1634,27 +1653,75 @@ def _feature_pair_csr(name, Fa, Fb, mid, alpha, weighted, dtype):
     return sp.csr_matrix((val[:nnz.value], idx[:nnz.value], ptr), shape=(na, nb))
 
 
-def jaccard_csr(Fa, Fb=None, alpha=None, weighted: bool = True, dtype=np.float32):
+def _feature_kth(name, Fa, Fb, mid, k, dtype):
+    """tau of ss_similarity_<name>_kth_*: `mid` are the arguments between d and k."""
+    if k is None:
+        raise TypeError(f"{name}_kth needs k")
+    dt = _feature_dtype(dtype)
+    dev = _is_torch(Fa)
+    keep = []
+    pa, na, d, lda = _features(Fa, dt, dev, keep)
+    pb, nb, db, ldb = _features(Fb, dt, dev, keep)
+    if Fb is None:
+        nb, db, ldb = na, d, lda
+    if db != d:
+        raise ValueError("Fa and Fb have different numbers of features")
+    fn = getattr(L_.lib(), f"ss_similarity_{name}_kth_{_suffix(dt)}")
+    head = (pa, na, lda, pb, nb, ldb, d) + tuple(mid) + (int(k),)
+    if dev:
+        import torch
+        tau = torch.empty(na, dtype=torch.float32 if dt == np.float32 else torch.float64, device=Fa.device)
+        L_.check(fn(*head, tau.data_ptr(), L_.SS_MEM_DEVICE))
+        del keep
+        return tau
+    tau = np.empty(na, dt)
+    L_.check(fn(*head, tau.ctypes.data, L_.SS_MEM_HOST))
+    del keep
+    return tau
+
+
+def jaccard_kth(Fa, Fb=None, k=None, dtype=np.float32):
+    """tau[i] = the k-th largest of the positive weighted-Jaccard similarities of row Fa[i] against the rows of Fb
+    (multiplicity counted; Fb None: Fb = Fa, the diagonal included), +0 where a row has fewer than k: the per-row cut of
+    ``jaccard_csr(..., min_neighbours=k)``, computed on the device without the dense similarity.  1 <= k <= 64.  Inputs
+    as ``jaccard_csr``; host input returns a numpy vector, device input a CUDA tensor."""
+    return _feature_kth("jaccard", Fa, Fb, (), k, dtype)
+
+
+def dot_kth(Fa, Fb=None, metric="cosine", k=None, dtype=np.float32):
+    """tau[i] of ``dot_csr(..., metric=metric, min_neighbours=k)``: the k-th largest of the positive similarities of row
+    Fa[i] against the rows of Fb (Fb None: Fb = Fa, the diagonal, exactly 1, included), +0 where a row has fewer than k.
+    Negative similarities never count.  1 <= k <= 64.  Inputs and outputs as ``jaccard_kth``."""
+    return _feature_kth("dot", Fa, Fb, (_sim_metric(metric),), k, dtype)
+
+
+def jaccard_csr(Fa, Fb=None, alpha=None, weighted: bool = True, dtype=np.float32, min_neighbours: int = 0):
     """``featurize(1 .- pairwise(Jaccard(), X, dims=1), alpha, weighted)`` for real-valued feature rows, produced as CSR
     on the device without the dense similarity: entry (i, j) = J(Fa[i], Fb[j]) = sum(min) / sum(max) (1 when both rows
     are all zero) when it is >= alpha (1 when not weighted), bitwise what ``jaccard_similarity`` followed by the cutoff
     gives.  Fb None: Fb = Fa.  Host input ((n, d) numpy) returns a scipy.sparse.csr_matrix; device input ((n, d) CUDA
-    tensors of dtype) returns (ptr int64, idx int32, val) tensors.  A NaN feature or alpha raises SimSpreadError."""
+    tensors of dtype) returns (ptr int64, idx int32, val) tensors.  A NaN feature or alpha raises SimSpreadError.
+    min_neighbours = k > 0 (at most 64) adds the neighbour floor, as ``tanimoto_csr``: row i also keeps every positive
+    similarity >= tau_i (``jaccard_kth``), i.e. at least its k nearest columns whatever alpha says (alpha = inf: exactly
+    those); ties at tau_i are all kept, a row with fewer than k positive similarities keeps all of them, and the result
+    is in general not symmetric."""
     if alpha is None:
         raise TypeError("jaccard_csr needs alpha")
-    return _feature_pair_csr("jaccard", Fa, Fb, (), alpha, weighted, dtype)
+    return _feature_pair_csr("jaccard", Fa, Fb, (), alpha, weighted, dtype, min_neighbours)
 
 
-def dot_csr(Fa, Fb=None, metric="cosine", alpha=None, weighted: bool = True, dtype=np.float32):
+def dot_csr(Fa, Fb=None, metric="cosine", alpha=None, weighted: bool = True, dtype=np.float32, min_neighbours: int = 0):
     """``featurize(S, alpha, weighted)`` with S an inner-product similarity of real-valued rows (embeddings, continuous
     descriptors), produced as CSR on the device without the dense similarity; the Gram blocks run on the matrix cores in
     full ``dtype`` precision.  metric: "cosine" g / (|a| |b|), "tanimoto" g / (|a|^2 + |b|^2 - g), "dice" 2g / (|a|^2 +
     |b|^2), g = a.b; two all-zero rows have s = 1, a zero row against a non-zero one s = 0.  Entry (i, j) = s when it
     is >= alpha (1 when not weighted).  Fb None: Fb = Fa (the diagonal is exactly 1 and the matrix bitwise symmetric).
-    Inputs and outputs as ``jaccard_csr``.  A NaN feature or alpha raises SimSpreadError."""
+    Inputs and outputs as ``jaccard_csr``.  A NaN feature or alpha raises SimSpreadError.  min_neighbours = k > 0 (at
+    most 64) adds the neighbour floor as there (``dot_kth``): negative similarities never count among the k, the
+    diagonal of Fb = Fa stays exactly 1 and counts, and the floor matrix is not symmetric."""
     if alpha is None:
         raise TypeError("dot_csr needs alpha")
-    return _feature_pair_csr("dot", Fa, Fb, (_sim_metric(metric),), alpha, weighted, dtype)
+    return _feature_pair_csr("dot", Fa, Fb, (_sim_metric(metric),), alpha, weighted, dtype, min_neighbours)
 
 
 def cutoff_csr(X, alpha: float, weighted: bool = False, dtype=np.float32, shape=None):
