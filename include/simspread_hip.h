@@ -51,7 +51,8 @@ enum {
   SS_ENOMEM = -2,       /* device or host allocation failed */
   SS_EHIP = -3,         /* a HIP runtime call failed (message has the HIP error string) */
   SS_ENODEV = -4,       /* no usable gfx950 device / ss_init not called */
-  SS_EUNSUPPORTED = -5  /* valid request this build cannot serve (e.g. nnz >= 2^31) */
+  SS_EUNSUPPORTED = -5, /* valid request this build cannot serve (e.g. nnz >= 2^31) */
+  SS_EINTERNAL = -6     /* a bound the library sets for itself was exceeded: a defect, reported instead of looping on */
 };
 
 enum { SS_MEM_HOST = 0, SS_MEM_DEVICE = 1 };
@@ -705,5 +706,6 @@ int ss_spmat_cost(const ss_spmat* w, int64_t B, double* bytes, double* flops);
 #include "simspread_hip_screening.h"
 #include "simspread_hip_neighbours.h"
 #include "simspread_hip_neighbours_real.h"
+#include "simspread_hip_clusters.h"
 
 #endif /* SIMSPREAD_HIP_H */

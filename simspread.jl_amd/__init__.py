@@ -7,12 +7,13 @@ kernels in ``libsimspread_hip.so`` (C ABI: include/simspread_hip.h).  No CPU fal
 from . import _lib
 from ._lib import SimSpreadError, init, path_last, timing_hold, timing_last, use_torch_stream
 from .core import (NamedMatrix, Network, clean, clean_, construct, cutoff, featurize, k, names, precisionatL, predict,
-                   read_namedmatrix, recallatL, save, save_loo, split, spread, writedlm)
+                   read_namedmatrix, recallatL, save, save_loo, split, split_clusters, spread, writedlm)
 from .dist import (comm_destroy, comm_init, comm_unique_id, gather_scores, gather_topl, lib_gather_scores, pooled_metrics,
                    shard_range, target_topl)
 from .engine import (BINARY_ROWS_FIELDS, POOLED_FIELDS, RANK_ROWS_FIELDS, TARGET_TOPL_FIELDS, DeviceGraph, DeviceQueries, DeviceSpMat,
                      Pool,
-                     TargetTopL, binary_metrics_rows, cutoff_csr,
+                     TargetTopL, ButinaClusters, binary_metrics_rows, butina_clusters, cluster_folds, cross_fold_edges,
+                     cutoff_csr,
                      dot_csr, dot_kth, jaccard_csr, jaccard_kth,
                      jaccard_similarity, pack_fingerprints, rank_metrics, rank_metrics_rows, tanimoto_csr, tanimoto_kth, topl)
 from .metrics import (AuPRC, AuROC, BEDROC, ROCNums, accuracy, balancedaccuracy, f1score, maxperformance, mcc,
@@ -22,4 +23,4 @@ __all__ = ["NamedMatrix", "Network", "DeviceGraph", "DeviceQueries", "DeviceSpMa
            "shard_range", "pooled_metrics", "Pool", "POOLED_FIELDS", "target_topl", "TargetTopL", "TARGET_TOPL_FIELDS", "gather_scores", "gather_topl", "comm_unique_id", "comm_init", "comm_destroy", "lib_gather_scores", "k", "cutoff", "featurize", "construct", "spread", "predict", "clean", "clean_", "names", "split", "save", "save_loo", "topl", "recallatL", "precisionatL",
            "read_namedmatrix", "writedlm", "rank_metrics", "rank_metrics_rows", "RANK_ROWS_FIELDS", "binary_metrics_rows", "BINARY_ROWS_FIELDS", "jaccard_similarity", "jaccard_csr", "dot_csr", "cutoff_csr", "pack_fingerprints", "tanimoto_csr", "tanimoto_kth", "jaccard_kth", "dot_kth", "AuROC", "AuPRC", "BEDROC", "validity_ratio", "roc", "ROCNums",
            "f1score", "mcc", "accuracy", "balancedaccuracy", "recall", "precision", "maxperformance", "meanperformance",
-           "meanstdperformance"]
+           "meanstdperformance", "ButinaClusters", "butina_clusters", "cluster_folds", "cross_fold_edges", "split_clusters"]

@@ -16,13 +16,14 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip.h")
 SCREENING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_screening.h")   # included by it
 NEIGHBOURS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_neighbours.h")  # included by it
 REAL_NEIGHBOURS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_neighbours_real.h")  # too
+CLUSTERS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_clusters.h")                # too
 
 SS_OK = 0
 SS_MEM_HOST, SS_MEM_DEVICE = 0, 1
 SS_ROWS_QUERY, SS_ROWS_SOURCE, SS_ROWS_LOO = 0, 1, 2
 SS_LAYOUT_ROWMAJOR, SS_LAYOUT_COLMAJOR = 0, 1
 
-_ERR_NAMES = {-1: "SS_EINVAL", -2: "SS_ENOMEM", -3: "SS_EHIP", -4: "SS_ENODEV", -5: "SS_EUNSUPPORTED"}
+_ERR_NAMES = {-1: "SS_EINVAL", -2: "SS_ENOMEM", -3: "SS_EHIP", -4: "SS_ENODEV", -5: "SS_EUNSUPPORTED", -6: "SS_EINTERNAL"}
 
 
 class SimSpreadError(RuntimeError):
@@ -193,6 +194,24 @@ def _real_neighbour_sigs():
 REAL_NEIGHBOUR_SIGNATURES = _real_neighbour_sigs()
 
 
+def _cluster_sigs():
+    """include/simspread_hip_clusters.h: Butina clusters of a neighbour pattern, cluster folds, cross-fold edges"""
+    out = [_vp, _vp, _vp, _vp, _vp, _int]                               # centre, label, size, nclusters, rounds, mem
+    s = {
+        "ss_cluster_butina_csr": ([_i64, _vp, _vp, _int] + out, _int),
+        "ss_cluster_folds": ([_vp, _i64, _i64, _int, _vp, _int], _int),
+        "ss_cluster_cross_edges": ([_i64, _vp, _vp, _int, _vp, _int, _vp, _int], _int),
+    }
+    for suf, ft in (("f32", C.c_float), ("f64", C.c_double)):
+        s[f"ss_cluster_butina_fingerprint_{suf}"] = ([_vp, _i64, _i64, ft] + out, _int)
+        s[f"ss_cluster_butina_features_{suf}"] = ([_vp, _i64, _i64, _i64, ft] + out, _int)
+        s[f"ss_cluster_butina_vectors_{suf}"] = ([_int, _vp, _i64, _i64, _i64, ft] + out, _int)
+    return s
+
+
+CLUSTER_SIGNATURES = _cluster_sigs()
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function the C header declares (used by the symbol-export test)."""
     with open(path) as f:
@@ -216,6 +235,11 @@ def real_neighbours_header_symbols():
     return header_symbols(REAL_NEIGHBOURS_HEADER_PATH)
 
 
+def clusters_header_symbols():
+    """Every function include/simspread_hip_clusters.h declares."""
+    return header_symbols(CLUSTERS_HEADER_PATH)
+
+
 def load():
     """dlopen the library (no GPU needed for this step)."""
     global _lib
@@ -227,7 +251,8 @@ def load():
             "(make -C simspread.jl_amd/csrc).  There is no CPU fallback for the HIP path.")
     lib = C.CDLL(LIB_PATH)
     for name, (args, res) in (list(SIGNATURES.items()) + list(SCREENING_SIGNATURES.items())
-                              + list(NEIGHBOUR_SIGNATURES.items()) + list(REAL_NEIGHBOUR_SIGNATURES.items())):
+                              + list(NEIGHBOUR_SIGNATURES.items()) + list(REAL_NEIGHBOUR_SIGNATURES.items())
+                              + list(CLUSTER_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res

@@ -360,6 +360,23 @@ def split(y: NamedMatrix, k: int, seed: int = 1) -> List[List[str]]:
     return groups
 
 
+def split_clusters(y: NamedMatrix, label, k: int) -> List[List[str]]:
+    """Leave-cluster-out grouping of the source names, in the shape ``split`` returns: ``label[i]`` is the cluster of
+    source ``y.names(1)[i]`` (``butina_clusters(...).label``), every cluster stays whole, and the clusters are dealt to
+    the k groups by ``cluster_folds`` (largest first, to the group with the fewest sources so far).  Within a group the
+    names keep their order in y.  Deterministic: no seed."""
+    from .engine import cluster_folds
+    sources = list(y.names(1))
+    lab = np.asarray(label.cpu() if type(label).__module__.startswith("torch") else label)
+    if lab.shape != (len(sources),):
+        raise ValueError("label needs one entry per source of y")
+    fold = cluster_folds(lab, k)
+    groups: List[List[str]] = [[] for _ in range(k)]
+    for s, f in zip(sources, fold):
+        groups[int(f)].append(s)
+    return groups
+
+
 def _julia_number(x) -> str:
     """How Julia's join/print shows a matrix element: Ints bare, floats shortest round-trip with a trailing .0"""
     if isinstance(x, (int, np.integer)):

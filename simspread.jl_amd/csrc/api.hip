@@ -789,6 +789,235 @@ static int graph_create_vectors_impl(int64_t nq, int64_t ns, int64_t nt, int64_t
       ldq, Fs, lds_, y_ptr, y_idx, y_val, index_base, alpha, mem, out, k);
 }
 
+// ------------------------------------------------------------------ Butina clusters, cluster folds, cross-fold edges
+// (include/simspread_hip_clusters.h; the device path is cluster.hip)
+struct ClusterOut {
+  int32_t *centre, *label, *size;
+  int64_t *nclusters, *rounds;
+};
+// the common head of the clustering entry points: nothing is written before these pass
+static int cluster_begin(int64_t n, const ClusterOut& o, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  path_note().clear();
+  timing_begin_call();
+  if (n < 0) return fail(SS_EINVAL, "butina: negative source count");
+  if (n >= (1LL << 31) - 64) return fail(SS_EUNSUPPORTED, "butina: %lld sources (>= 2^31)", (long long)n);
+  if (!o.nclusters) return fail(SS_EINVAL, "butina: nclusters must not be NULL");
+  if (n > 0 && (!o.centre || !o.label)) return fail(SS_EINVAL, "butina: centre and label must not be NULL");
+  return SS_OK;
+}
+// cluster the device pattern (dptr, didx) and deliver centre, label and size in `mem`
+static int cluster_deliver(int64_t n, const int64_t* dptr, const int32_t* didx, int base, int64_t nnz_in, bool validate,
+                           const ClusterOut& o, int mem) {
+  hipStream_t st = ctx().stream;
+  DevBuf<int> bc, bl, bs;
+  int *dc = o.centre, *dl = o.label, *dsz = o.size;
+  if (mem == SS_MEM_HOST || validate) {
+    // a pattern that is still to be checked must not cost the caller's buffers their contents
+    SS_TRY(bc.alloc(n));
+    SS_TRY(bl.alloc(n));
+    dc = bc.p;
+    dl = bl.p;
+    if (o.size) {
+      SS_TRY(bs.alloc(n));
+      dsz = bs.p;
+    }
+  }
+  int64_t nc = 0, rounds = 0;
+  StageTimer total(ST_TOTAL);
+  SS_TRY(butina_csr(n, dptr, didx, base, nnz_in, validate, dc, dl, dsz, &nc, &rounds));
+  total.stop();
+  if (dc != o.centre) {
+    const hipMemcpyKind back = mem == SS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    SS_HIP(hipMemcpyAsync(o.centre, dc, (size_t)n * sizeof(int), back, st));
+    SS_HIP(hipMemcpyAsync(o.label, dl, (size_t)n * sizeof(int), back, st));
+    if (o.size) SS_HIP(hipMemcpyAsync(o.size, dsz, (size_t)nc * sizeof(int), back, st));
+    SS_HIP(hipStreamSynchronize(st));
+  }
+  *o.nclusters = nc;
+  if (o.rounds) *o.rounds = rounds;
+  return SS_OK;
+}
+
+// a caller's n x n pattern on the device: ptr[0] == index_base and the entry count, read before anything is staged
+struct UserPattern {
+  DevBuf<int64_t> bptr;
+  DevBuf<int32_t> bidx;
+  const int64_t* ptr = nullptr;
+  const int32_t* idx = nullptr;
+  int64_t nnz_in = 0;
+};
+static int stage_pattern(const char* what, int64_t n, const int64_t* ptr, const int32_t* idx, int index_base, int mem,
+                         UserPattern& u) {
+  hipStream_t st = ctx().stream;
+  if (index_base != 0 && index_base != 1) return fail(SS_EINVAL, "%s: index_base must be 0 or 1", what);
+  if (!ptr) return fail(SS_EINVAL, "%s: row pointer array is NULL", what);
+  int64_t first = 0, last = 0;
+  if (mem == SS_MEM_HOST) {
+    first = ptr[0];
+    last = ptr[n];
+  } else {
+    SS_HIP(hipMemcpyAsync(&last, ptr + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    SS_HIP(hipMemcpyAsync(&first, ptr, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    SS_HIP(hipStreamSynchronize(st));
+  }
+  if (first != index_base) return fail(SS_EINVAL, "%s: row pointer does not start at index_base", what);
+  u.nnz_in = last - index_base;
+  if (u.nnz_in < 0) return fail(SS_EINVAL, "%s: negative entry count in row pointers", what);
+  if (u.nnz_in >= (1LL << 31) - 64) return fail(SS_EUNSUPPORTED, "%s: %lld stored entries (>= 2^31)", what,
+                                                (long long)u.nnz_in);
+  if (u.nnz_in > 0 && !idx) return fail(SS_EINVAL, "%s: column index array is NULL", what);
+  u.ptr = ptr;
+  u.idx = idx;
+  if (mem == SS_MEM_HOST) {
+    SS_TRY(u.bptr.alloc(n + 1));
+    SS_TRY(upload(u.bptr.p, ptr, n + 1, mem));
+    SS_TRY(u.bidx.alloc(u.nnz_in));
+    SS_TRY(upload(u.bidx.p, idx, u.nnz_in, mem));
+    u.ptr = u.bptr.p;
+    u.idx = u.bidx.p;
+  }
+  return SS_OK;
+}
+
+static int cluster_butina_csr_impl(int64_t n, const int64_t* ptr, const int32_t* idx, int index_base,
+                                   const ClusterOut& o, int mem) {
+  SS_TRY(cluster_begin(n, o, mem));
+  path_add("butina_csr");
+  if (n == 0) {
+    *o.nclusters = 0;
+    if (o.rounds) *o.rounds = 0;
+    return SS_OK;
+  }
+  UserPattern u;
+  SS_TRY(stage_pattern("butina", n, ptr, idx, index_base, mem, u));
+  if (u.nnz_in >= (1LL << 30))
+    return fail(SS_EUNSUPPORTED, "butina: %lld stored entries (>= 2^30)", (long long)u.nnz_in);
+  return cluster_deliver(n, u.ptr, u.idx, index_base, u.nnz_in, true, o, mem);
+}
+
+// the plain self-similarity pattern of producer p (counted already): its indices, then the clustering, on the device
+template <class T>
+static int cluster_from_producer(PairCsr<T>& p, int64_t n, const ClusterOut& o, int mem) {
+  if (p.nnz >= (1LL << 30))
+    return fail(SS_EUNSUPPORTED, "butina: the %s pattern has %lld entries (>= 2^30): raise the cutoff", p.what,
+                (long long)p.nnz);
+  DevBuf<int> idx;
+  SS_TRY(idx.alloc(p.nnz));
+  if (p.nnz > 0) SS_TRY(p.fill(idx.p, nullptr, nullptr));
+  return cluster_deliver(n, p.ptr.p, idx.p, 0, p.nnz, false, o, mem);
+}
+static int cluster_empty(const ClusterOut& o) {
+  *o.nclusters = 0;
+  if (o.rounds) *o.rounds = 0;
+  return SS_OK;
+}
+
+template <class T>
+static int cluster_butina_fingerprint_impl(const uint64_t* F, int64_t n, int64_t nwords, T cutoff, const ClusterOut& o,
+                                           int mem) {
+  SS_TRY(cluster_begin(n, o, mem));
+  SS_TRY(check_nwords(nwords));
+  SS_TRY(check_fingerprints("F", F, n, nwords));
+  if (cutoff != cutoff) return fail(SS_EINVAL, "butina: cutoff is NaN");
+  path_add("butina_csr");
+  path_add(tanimoto_tag(true, 0));
+  if (n == 0) return cluster_empty(o);
+  DevBuf<uint64_t> bf;
+  const uint64_t* df = nullptr;
+  SS_TRY(stage_fingerprints(F, n, nwords, mem, bf, &df));
+  TanimotoCsr<T> tc;
+  SS_TRY(tc.count(df, n, nullptr, n, nwords, cutoff, false, 0));
+  return cluster_from_producer<T>(tc, n, o, mem);
+}
+
+template <class T, class Prod, class Check, class Count>
+static int cluster_butina_rows_impl(const FeatureNames& nm, Check check, Count count, const T* F, int64_t n, int64_t d,
+                                    int64_t ld, T cutoff, const ClusterOut& o, int mem) {
+  SS_TRY(cluster_begin(n, o, mem));
+  SS_TRY(check_feature_args(nm, check, d, cutoff));
+  SS_TRY(check_features("F", F, n, ld, d));
+  path_add("butina_csr");
+  path_add(nm.tag(true, 0));
+  if (n == 0) return cluster_empty(o);
+  DevBuf<T> bf;
+  const T* df = nullptr;
+  int64_t lf = 0;
+  SS_TRY(stage_features(F, n, ld, d, mem, bf, &df, &lf));
+  Prod p;
+  SS_TRY(count(p, df, n, lf, nullptr, n, lf));
+  return cluster_from_producer<T>(p, n, o, mem);
+}
+template <class T>
+static int cluster_butina_features_impl(const T* F, int64_t n, int64_t d, int64_t ld, T cutoff, const ClusterOut& o,
+                                        int mem) {
+  return cluster_butina_rows_impl<T, JaccardCsr<T>>(jaccard_names, no_check, jaccard_count<T>(d, cutoff, 0), F, n, d, ld,
+                                                    cutoff, o, mem);
+}
+template <class T>
+static int cluster_butina_vectors_impl(int metric, const T* F, int64_t n, int64_t d, int64_t ld, T cutoff,
+                                       const ClusterOut& o, int mem) {
+  return cluster_butina_rows_impl<T, DotCsr<T>>(
+      dot_names, [=] { return check_sim_metric(metric); }, dot_count<T>(d, metric, cutoff, 0), F, n, d, ld, cutoff, o,
+      mem);
+}
+
+static int cluster_folds_impl(const int32_t* label, int64_t n, int64_t nclusters, int nfolds, int32_t* fold, int mem) {
+  SS_TRY(check_mem(mem));
+  if (mem == SS_MEM_DEVICE) SS_TRY(require_init());
+  if (n < 0 || nclusters < 0) return fail(SS_EINVAL, "cluster folds: negative count");
+  if (nfolds < 1) return fail(SS_EINVAL, "cluster folds: nfolds = %d < 1", nfolds);
+  if (n == 0) return SS_OK;
+  if (!label || !fold) return fail(SS_EINVAL, "cluster folds: NULL argument");
+  if (mem == SS_MEM_HOST) {
+    std::vector<int32_t> out((size_t)n);
+    SS_TRY(cluster_folds(label, n, nclusters, nfolds, out.data()));
+    std::copy(out.begin(), out.end(), fold);
+    return SS_OK;
+  }
+  hipStream_t st = ctx().stream;
+  std::vector<int32_t> in((size_t)n), out((size_t)n);
+  SS_HIP(hipMemcpyAsync(in.data(), label, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  SS_TRY(cluster_folds(in.data(), n, nclusters, nfolds, out.data()));
+  SS_HIP(hipMemcpyAsync(fold, out.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
+}
+
+static int cluster_cross_edges_impl(int64_t n, const int64_t* ptr, const int32_t* idx, int index_base,
+                                    const int32_t* fold, int nfolds, int64_t* count, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  path_note().clear();
+  if (n < 0) return fail(SS_EINVAL, "cross edges: negative source count");
+  if (n >= (1LL << 31) - 64) return fail(SS_EUNSUPPORTED, "cross edges: %lld sources (>= 2^31)", (long long)n);
+  if (nfolds < 1) return fail(SS_EINVAL, "cross edges: nfolds = %d < 1", nfolds);
+  if (!count || (n > 0 && !fold)) return fail(SS_EINVAL, "cross edges: NULL argument");
+  path_add("cross_edges");
+  hipStream_t st = ctx().stream;
+  UserPattern u;
+  DevBuf<int32_t> bfold;
+  DevBuf<int64_t> bcount;
+  const int32_t* dfold = fold;
+  if (n > 0) {
+    SS_TRY(stage_pattern("cross edges", n, ptr, idx, index_base, mem, u));
+    if (mem == SS_MEM_HOST) {
+      SS_TRY(bfold.alloc(n));
+      SS_TRY(upload(bfold.p, fold, n, mem));
+      dfold = bfold.p;
+    }
+  }
+  // counted aside: a pattern or a fold vector that fails its check leaves `count` as it was
+  SS_TRY(bcount.alloc(nfolds));
+  SS_TRY(cross_edges(n, u.ptr, u.idx, index_base, u.nnz_in, dfold, nfolds, bcount.p));
+  SS_HIP(hipMemcpyAsync(count, bcount.p, (size_t)nfolds * sizeof(int64_t),
+                        mem == SS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
+}
+
 // ------------------------------------------------------------------ cutoff sweeps: featurize on resident CSR
 // an unstored zero passes an unweighted cutoff at alpha <= 0, which CSR cannot hold
 template <class T>
@@ -4240,6 +4469,60 @@ int ss_target_topl_metrics(ss_target_topl* h, int64_t* hits, int64_t* npos, doub
   SS_HANDLE_LOCK(h);
   return dt == 4 ? tl_metrics_impl(*reinterpret_cast<TlBox<float>*>(h), hits, npos, out, mem)
                  : tl_metrics_impl(*reinterpret_cast<TlBox<double>*>(h), hits, npos, out, mem);
+}
+
+/* ---- include/simspread_hip_clusters.h */
+int ss_cluster_butina_csr(int64_t n, const int64_t* ptr, const int32_t* idx, int index_base, int32_t* centre,
+                          int32_t* label, int32_t* size, int64_t* nclusters, int64_t* rounds, int mem) {
+  SS_API_LOCK();
+  return cluster_butina_csr_impl(n, ptr, idx, index_base, ClusterOut{centre, label, size, nclusters, rounds}, mem);
+}
+int ss_cluster_butina_fingerprint_f32(const uint64_t* F, int64_t n, int64_t nwords, float cutoff, int32_t* centre,
+                                      int32_t* label, int32_t* size, int64_t* nclusters, int64_t* rounds, int mem) {
+  SS_API_LOCK();
+  return cluster_butina_fingerprint_impl<float>(F, n, nwords, cutoff, ClusterOut{centre, label, size, nclusters, rounds},
+                                                mem);
+}
+int ss_cluster_butina_fingerprint_f64(const uint64_t* F, int64_t n, int64_t nwords, double cutoff, int32_t* centre,
+                                      int32_t* label, int32_t* size, int64_t* nclusters, int64_t* rounds, int mem) {
+  SS_API_LOCK();
+  return cluster_butina_fingerprint_impl<double>(F, n, nwords, cutoff,
+                                                 ClusterOut{centre, label, size, nclusters, rounds}, mem);
+}
+int ss_cluster_butina_features_f32(const float* F, int64_t n, int64_t d, int64_t ld, float cutoff, int32_t* centre,
+                                   int32_t* label, int32_t* size, int64_t* nclusters, int64_t* rounds, int mem) {
+  SS_API_LOCK();
+  return cluster_butina_features_impl<float>(F, n, d, ld, cutoff, ClusterOut{centre, label, size, nclusters, rounds},
+                                             mem);
+}
+int ss_cluster_butina_features_f64(const double* F, int64_t n, int64_t d, int64_t ld, double cutoff, int32_t* centre,
+                                   int32_t* label, int32_t* size, int64_t* nclusters, int64_t* rounds, int mem) {
+  SS_API_LOCK();
+  return cluster_butina_features_impl<double>(F, n, d, ld, cutoff, ClusterOut{centre, label, size, nclusters, rounds},
+                                              mem);
+}
+int ss_cluster_butina_vectors_f32(int metric, const float* F, int64_t n, int64_t d, int64_t ld, float cutoff,
+                                  int32_t* centre, int32_t* label, int32_t* size, int64_t* nclusters, int64_t* rounds,
+                                  int mem) {
+  SS_API_LOCK();
+  return cluster_butina_vectors_impl<float>(metric, F, n, d, ld, cutoff,
+                                            ClusterOut{centre, label, size, nclusters, rounds}, mem);
+}
+int ss_cluster_butina_vectors_f64(int metric, const double* F, int64_t n, int64_t d, int64_t ld, double cutoff,
+                                  int32_t* centre, int32_t* label, int32_t* size, int64_t* nclusters, int64_t* rounds,
+                                  int mem) {
+  SS_API_LOCK();
+  return cluster_butina_vectors_impl<double>(metric, F, n, d, ld, cutoff,
+                                             ClusterOut{centre, label, size, nclusters, rounds}, mem);
+}
+int ss_cluster_folds(const int32_t* label, int64_t n, int64_t nclusters, int nfolds, int32_t* fold_of_source, int mem) {
+  SS_API_LOCK();
+  return cluster_folds_impl(label, n, nclusters, nfolds, fold_of_source, mem);
+}
+int ss_cluster_cross_edges(int64_t n, const int64_t* ptr, const int32_t* idx, int index_base,
+                           const int32_t* fold_of_source, int nfolds, int64_t* count, int mem) {
+  SS_API_LOCK();
+  return cluster_cross_edges_impl(n, ptr, idx, index_base, fold_of_source, nfolds, count, mem);
 }
 
 }  // extern "C"

@@ -552,6 +552,24 @@ struct CutCsr : PairCsr<T> {
 template <class T>
 int graph_recut(const Graph<T>& p, T alpha, bool weighted, Graph<T>& g);
 
+// ---- cluster.hip: Taylor-Butina clustering of an n x n neighbour pattern (include/simspread_hip_clusters.h).  ptr
+// (n + 1 row pointers, the first == base), idx and the outputs are device arrays; row i holds idx[ptr[i] - base ..
+// ptr[i + 1] - base), each entry shifted by base; nnz_in = ptr[n] - base, read by the caller.  validate: check the pointers and the indices on the device first
+// (SS_EINVAL, nothing written); a pattern a producer of this library made needs no check.  centre[n], label[n], size
+// (nullable, capacity n, the first *nclusters written); *nclusters and *rounds on the host.  Synchronises.  The stages
+// are timed as ST_TRANSFER (symmetrise), ST_SPMM (rounds) and ST_EPILOGUE (assign and label).
+int butina_csr(int64_t n, const int64_t* ptr, const int32_t* idx, int base, int64_t nnz_in, bool validate, int* centre,
+               int* label, int* size, int64_t* nclusters, int64_t* rounds);
+// SS_EINVAL unless the pointers are monotone within [0, nnz_in], every index is in 0..n-1 and (fold != nullptr) every
+// fold id in 0..nfolds-1 (synchronises)
+int pattern_check(int64_t n, const int64_t* ptr, const int32_t* idx, int base, int64_t nnz_in, const int32_t* fold,
+                  int nfolds);
+// count[f] (device, nfolds entries) = stored off-diagonal entries (i, j) with fold[i] == f != fold[j]; checks first
+int cross_edges(int64_t n, const int64_t* ptr, const int32_t* idx, int base, int64_t nnz_in, const int32_t* fold,
+                int nfolds, int64_t* count);
+// host arrays: the largest-first fold assignment that keeps clusters whole
+int cluster_folds(const int32_t* label, int64_t n, int64_t nclusters, int nfolds, int32_t* fold);
+
 // ---- comm.hip: in-library score gather over RCCL (dlopen'ed), one process per GPU
 int comm_unique_id(char* id128);
 int comm_init(const char* id128, int rank, int nranks);

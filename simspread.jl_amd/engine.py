@@ -1765,3 +1765,164 @@ def cutoff_csr(X, alpha: float, weighted: bool = False, dtype=np.float32, shape=
     L_.check(fn(rows, cols, _ptr(ip), _ptr(ii), _ptr(iv), 0, ctype(alpha), w, ptr.ctypes.data, idx.ctypes.data,
                 val.ctypes.data, nnz.value, C.byref(nnz), L_.SS_MEM_HOST))
     return sp.csr_matrix((val[:nnz.value], idx[:nnz.value], ptr), shape=(rows, cols))
+
+
+# ------------------------------------------------------------------ Butina clusters, cluster folds, cross-fold edges
+class ButinaClusters:
+    """Result of ``butina_clusters``: ``centre[i]`` the index of source i's centre (``centre[c] == c`` for a centre),
+    ``label[i]`` its cluster, clusters numbered 0..nclusters-1 in priority order of their centres, ``size[l]`` the number
+    of sources with label l, and ``rounds`` the number of rounds the device loop took.  Arrays are numpy for host input
+    and CUDA tensors for device input, always 0-based."""
+
+    __slots__ = ("centre", "label", "size", "rounds")
+
+    def __init__(self, centre, label, size, rounds):
+        self.centre, self.label, self.size, self.rounds = centre, label, size, int(rounds)
+
+    @property
+    def nclusters(self) -> int:
+        return int(self.size.shape[0])
+
+    def __repr__(self):
+        return f"ButinaClusters(n={int(self.label.shape[0])}, nclusters={self.nclusters}, rounds={self.rounds})"
+
+
+def _pattern(X, index_base=0):
+    """(dev, n, ptr pointer, idx pointer, index_base, keep) of an n x n neighbour pattern: a scipy.sparse matrix (or
+    anything csr_matrix accepts), or CSR parts (ptr int64, idx int32[, val]) as numpy arrays or torch CUDA tensors, read
+    with ``index_base`` and as they are -- unsorted rows, duplicates and diagonal entries included."""
+    if index_base not in (0, 1):
+        raise ValueError("index_base must be 0 or 1")
+    if isinstance(X, (tuple, list)):
+        if len(X) not in (2, 3):
+            raise TypeError("CSR parts are (ptr, idx) or (ptr, idx, val)")
+        if _is_torch(X[0]):
+            import torch
+            ptr, idx = X[0].to(torch.int64).contiguous(), X[1].to(torch.int32).contiguous()
+            if not (ptr.is_cuda and idx.is_cuda):
+                raise TypeError("CSR parts must all live on the host (numpy) or all on the device (CUDA tensors)")
+            if ptr.numel() < 1:
+                raise ValueError("ptr must have n + 1 entries")
+            return True, ptr.numel() - 1, ptr.data_ptr(), idx.data_ptr(), index_base, [ptr, idx]
+        ptr = np.ascontiguousarray(X[0], dtype=np.int64)
+        idx = np.ascontiguousarray(X[1], dtype=np.int32)
+        if ptr.ndim != 1 or ptr.size < 1:
+            raise ValueError("ptr must have n + 1 entries")
+        if idx.size < ptr[-1] - index_base:
+            raise ValueError("idx is shorter than the row pointers say")
+        return False, ptr.size - 1, ptr.ctypes.data, idx.ctypes.data, index_base, [ptr, idx]
+    import scipy.sparse as sp
+    if index_base != 0:
+        raise ValueError("a scipy.sparse matrix is 0-based: index_base applies to CSR parts only")
+    m = sp.csr_matrix(X)
+    if m.shape[0] != m.shape[1]:
+        raise ValueError(f"a neighbour pattern is square, got {m.shape}")
+    ptr = np.ascontiguousarray(m.indptr, dtype=np.int64)
+    idx = np.ascontiguousarray(m.indices, dtype=np.int32)
+    return False, m.shape[0], ptr.ctypes.data, idx.ctypes.data, 0, [ptr, idx]
+
+
+def butina_clusters(X=None, *, fingerprints=None, features=None, vectors=None, metric="cosine", cutoff=None,
+                    dtype=np.float32, index_base=0) -> ButinaClusters:
+    """Taylor-Butina clusters (without re-counting) of the sources, on the device.  Exactly one input:
+
+    - ``X``: an n x n neighbour pattern (values are not read) -- scipy.sparse, or CSR parts ``(ptr, idx[, val])`` as
+      numpy arrays or torch CUDA tensors with ``index_base`` 0 or 1; it is symmetrised by union, diagonal and duplicate
+      entries are ignored;
+    - ``fingerprints`` (packed, see ``pack_fingerprints``), ``features`` ((n, d) rows, weighted Jaccard) or ``vectors``
+      ((n, d) rows, ``metric`` "cosine", "tanimoto" or "dice") with ``cutoff``: the pattern ``s >= cutoff`` of
+      ``tanimoto_csr`` / ``jaccard_csr`` / ``dot_csr`` on the rows themselves, made and consumed on the device.
+
+    The rule: neighbours N(i) = {j != i : (i,j) or (j,i) stored}, degree d_i = |N(i)|; i precedes j iff d_i > d_j, or
+    d_i == d_j and i < j; in that order every still-unassigned source becomes a centre and takes its still-unassigned
+    neighbours.  Ties between equal degrees go to the lower index, which is not RDKit's tie order.  The result is
+    unique and bitwise repeatable."""
+    given = [a is not None for a in (X, fingerprints, features, vectors)]
+    if sum(given) != 1:
+        raise TypeError("butina_clusters needs exactly one of X, fingerprints=, features=, vectors=")
+    lib = L_.lib()
+    keep = []
+    if X is not None:
+        if cutoff is not None:
+            raise TypeError("cutoff applies to fingerprints=, features= and vectors=; cut a pattern with cutoff_csr")
+        dev, n, pp, pi, base, keep = _pattern(X, index_base)
+        fn, head = lib.ss_cluster_butina_csr, (n, pp, pi, base)
+    else:
+        if cutoff is None:
+            raise TypeError("butina_clusters needs cutoff")
+        dt = _feature_dtype(dtype)
+        ctype = C.c_float if dt == np.float32 else C.c_double
+        if fingerprints is not None:
+            dev = _is_torch(fingerprints)
+            pf, n, nw = _fingerprints(fingerprints, dev, keep)
+            fn, head = getattr(lib, f"ss_cluster_butina_fingerprint_{_suffix(dt)}"), (pf, n, nw, ctype(cutoff))
+        elif features is not None:
+            dev = _is_torch(features)
+            pf, n, d, ld = _features(features, dt, dev, keep)
+            fn, head = getattr(lib, f"ss_cluster_butina_features_{_suffix(dt)}"), (pf, n, d, ld, ctype(cutoff))
+        else:
+            dev = _is_torch(vectors)
+            pf, n, d, ld = _features(vectors, dt, dev, keep)
+            fn = getattr(lib, f"ss_cluster_butina_vectors_{_suffix(dt)}")
+            head = (_sim_metric(metric), pf, n, d, ld, ctype(cutoff))
+    nc, rounds = C.c_int64(0), C.c_int64(0)
+    if dev:
+        import torch
+        centre, label, size = (torch.empty(max(n, 1), dtype=torch.int32, device="cuda") for _ in range(3))
+        L_.check(fn(*head, centre.data_ptr(), label.data_ptr(), size.data_ptr(), C.byref(nc), C.byref(rounds),
+                    L_.SS_MEM_DEVICE))
+    else:
+        centre, label, size = (np.empty(max(n, 1), np.int32) for _ in range(3))
+        L_.check(fn(*head, centre.ctypes.data, label.ctypes.data, size.ctypes.data, C.byref(nc), C.byref(rounds),
+                    L_.SS_MEM_HOST))
+    del keep
+    return ButinaClusters(centre[:n], label[:n], size[:nc.value], rounds.value)
+
+
+def cluster_folds(label, nfolds: int):
+    """``fold_of_source`` (int32, ids in [0, nfolds)) that keeps every cluster of ``label`` (``butina_clusters(...).label``)
+    in one fold: clusters by size descending (ties: label ascending), each to the fold with the fewest sources so far
+    (ties: the lowest fold id).  Deterministic; the folds differ in size by at most the largest cluster.  The vector goes
+    straight into ``predict_kfold`` / ``evaluate_kfold``.  numpy in, numpy out; CUDA tensor in, CUDA tensor out."""
+    lib = L_.lib()
+    if _is_torch(label):
+        import torch
+        lab = label.to(torch.int32).contiguous()
+        n = lab.numel()
+        nc = int(lab.max().item()) + 1 if n else 0
+        fold = torch.empty(max(n, 1), dtype=torch.int32, device=lab.device)
+        L_.check(lib.ss_cluster_folds(lab.data_ptr(), n, nc, int(nfolds), fold.data_ptr(), L_.SS_MEM_DEVICE))
+        return fold[:n]
+    lab = np.ascontiguousarray(label, dtype=np.int32)
+    if lab.ndim != 1:
+        raise ValueError("label must be a vector")
+    n = lab.size
+    nc = int(lab.max()) + 1 if n else 0
+    fold = np.empty(max(n, 1), np.int32)
+    L_.check(lib.ss_cluster_folds(lab.ctypes.data, n, nc, int(nfolds), fold.ctypes.data, L_.SS_MEM_HOST))
+    return fold[:n]
+
+
+def cross_fold_edges(X, fold_of_source, nfolds: int, index_base=0):
+    """How much a split leaks: ``count[f]`` (int64) = the number of stored off-diagonal entries (i, j) of the neighbour
+    pattern ``X`` (as for ``butina_clusters``; read as given, not symmetrised) with ``fold_of_source[i] == f !=
+    fold_of_source[j]``.  Host input returns numpy, device input (CSR parts and folds as CUDA tensors) a CUDA tensor."""
+    lib = L_.lib()
+    dev, n, pp, pi, base, keep = _pattern(X, index_base)
+    nfolds = int(nfolds)
+    if dev:
+        import torch
+        fold = torch.as_tensor(fold_of_source, device="cuda").to(torch.int32).contiguous()
+        if fold.numel() != n:
+            raise ValueError("fold_of_source needs one entry per source")
+        count = torch.zeros(max(nfolds, 1), dtype=torch.int64, device="cuda")
+        L_.check(lib.ss_cluster_cross_edges(n, pp, pi, base, fold.data_ptr(), nfolds, count.data_ptr(),
+                                            L_.SS_MEM_DEVICE))
+        return count[:max(nfolds, 0)]
+    fold = np.ascontiguousarray(fold_of_source, dtype=np.int32)
+    if fold.shape != (n,):
+        raise ValueError("fold_of_source needs one entry per source")
+    count = np.zeros(max(nfolds, 1), np.int64)
+    L_.check(lib.ss_cluster_cross_edges(n, pp, pi, base, fold.ctypes.data, nfolds, count.ctypes.data, L_.SS_MEM_HOST))
+    del keep
+    return count[:max(nfolds, 0)]
