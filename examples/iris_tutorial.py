@@ -38,6 +38,10 @@ def main(alpha: float = 0.9):
         print(f"alpha={alpha} weighted={weighted}: AuROC={m['AuROC']:.4f} AuPRC={m['AuPRC']:.4f} "
               f"BEDROC={m['BEDROC']:.4f} validity={m['validity_ratio']:.3f} "
               f"top-1 accuracy on the {out[weighted]['predicted']} flowers with a prediction: {hit.mean():.3f}")
+        # which species is predicted well: the same sweep judged per target, without the scores leaving the device
+        per_class = g.evaluate_loo_targets(clean=True)
+        for name, row in zip(classes, per_class):
+            print(f"    {name}: AuROC={row[0]:.4f} AuPRC={row[1]:.4f} BEDROC={row[2]:.4f}")
     return out
 
 

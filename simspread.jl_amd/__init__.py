@@ -9,10 +9,10 @@ from ._lib import SimSpreadError, init, path_last, timing_hold, timing_last, use
 from .core import (NamedMatrix, Network, clean, clean_, construct, cutoff, featurize, k, names, precisionatL, predict,
                    read_namedmatrix, recallatL, save, save_loo, split, split_clusters, spread, writedlm)
 from .dist import (comm_destroy, comm_init, comm_unique_id, gather_scores, gather_topl, lib_gather_scores, pooled_metrics,
-                   shard_range, target_topl)
-from .engine import (BINARY_ROWS_FIELDS, POOLED_FIELDS, RANK_ROWS_FIELDS, TARGET_TOPL_FIELDS, DeviceGraph, DeviceQueries, DeviceSpMat,
+                   shard_range, target_rank, target_rank_positives, target_topl)
+from .engine import (BINARY_ROWS_FIELDS, POOLED_FIELDS, RANK_ROWS_FIELDS, TARGET_RANK_FIELDS, TARGET_TOPL_FIELDS, DeviceGraph, DeviceQueries, DeviceSpMat,
                      Pool,
-                     TargetTopL, ButinaClusters, binary_metrics_rows, butina_clusters, cluster_folds, cross_fold_edges,
+                     TargetRank, TargetTopL, ButinaClusters, binary_metrics_rows, butina_clusters, cluster_folds, cross_fold_edges,
                      cutoff_csr,
                      dot_csr, dot_kth, jaccard_csr, jaccard_kth,
                      jaccard_similarity, pack_fingerprints, rank_metrics, rank_metrics_rows, tanimoto_csr, tanimoto_kth, topl)
@@ -23,4 +23,5 @@ __all__ = ["NamedMatrix", "Network", "DeviceGraph", "DeviceQueries", "DeviceSpMa
            "shard_range", "pooled_metrics", "Pool", "POOLED_FIELDS", "target_topl", "TargetTopL", "TARGET_TOPL_FIELDS", "gather_scores", "gather_topl", "comm_unique_id", "comm_init", "comm_destroy", "lib_gather_scores", "k", "cutoff", "featurize", "construct", "spread", "predict", "clean", "clean_", "names", "split", "save", "save_loo", "topl", "recallatL", "precisionatL",
            "read_namedmatrix", "writedlm", "rank_metrics", "rank_metrics_rows", "RANK_ROWS_FIELDS", "binary_metrics_rows", "BINARY_ROWS_FIELDS", "jaccard_similarity", "jaccard_csr", "dot_csr", "cutoff_csr", "pack_fingerprints", "tanimoto_csr", "tanimoto_kth", "jaccard_kth", "dot_kth", "AuROC", "AuPRC", "BEDROC", "validity_ratio", "roc", "ROCNums",
            "f1score", "mcc", "accuracy", "balancedaccuracy", "recall", "precision", "maxperformance", "meanperformance",
-           "meanstdperformance", "ButinaClusters", "butina_clusters", "cluster_folds", "cross_fold_edges", "split_clusters"]
+           "meanstdperformance", "ButinaClusters", "butina_clusters", "cluster_folds", "cross_fold_edges", "split_clusters", "TargetRank", "TARGET_RANK_FIELDS",
+           "target_rank", "target_rank_positives"]

@@ -17,6 +17,7 @@ SCREENING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspre
 NEIGHBOURS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_neighbours.h")  # included by it
 REAL_NEIGHBOURS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_neighbours_real.h")  # too
 CLUSTERS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_clusters.h")                # too
+TARGET_RANK_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_target_rank.h")          # too
 
 SS_OK = 0
 SS_MEM_HOST, SS_MEM_DEVICE = 0, 1
@@ -212,6 +213,31 @@ def _cluster_sigs():
 CLUSTER_SIGNATURES = _cluster_sigs()
 
 
+def _target_rank_sigs():
+    """include/simspread_hip_target_rank.h: per-target ranking metrics of whole sweeps"""
+    s = {
+        "ss_target_rank_destroy": ([_vp], _int),
+        "ss_target_rank_reset": ([_vp], _int),
+        "ss_target_rank_info": ([_vp, _vp], _int),
+        "ss_target_rank_seal": ([_vp], _int),
+        "ss_target_rank_merge": ([_vp, _vp], _int),
+        "ss_target_rank_export_counts": ([_vp, _vp, _vp, _int], _int),
+        "ss_target_rank_import_counts": ([_vp, _vp, _i64, _i64, _int], _int),
+        "ss_target_rank_metrics": ([_vp, C.c_double, _int, _vp, _int], _int),
+    }
+    for suf in ("f32", "f64"):
+        s[f"ss_target_rank_create_{suf}"] = ([_i64, _vp], _int)
+        s[f"ss_target_rank_add_rows_{suf}"] = ([_vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _i64, _int], _int)
+        s[f"ss_target_rank_add_loo_{suf}"] = ([_vp, _vp, _i64, _i64, _int, _i64], _int)
+        s[f"ss_target_rank_add_kfold_{suf}"] = ([_vp, _vp, _vp, _int, _i64, _i64, _int, _i64, _int], _int)
+        s[f"ss_target_rank_export_positives_{suf}"] = ([_vp, _vp, _vp, _vp, _vp, _int], _int)
+        s[f"ss_target_rank_import_positives_{suf}"] = ([_vp, _vp, _vp, _vp, _i64, _i64, _int], _int)
+    return s
+
+
+TARGET_RANK_SIGNATURES = _target_rank_sigs()
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function the C header declares (used by the symbol-export test)."""
     with open(path) as f:
@@ -240,6 +266,11 @@ def clusters_header_symbols():
     return header_symbols(CLUSTERS_HEADER_PATH)
 
 
+def target_rank_header_symbols():
+    """Every function include/simspread_hip_target_rank.h declares."""
+    return header_symbols(TARGET_RANK_HEADER_PATH)
+
+
 def load():
     """dlopen the library (no GPU needed for this step)."""
     global _lib
@@ -252,7 +283,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (args, res) in (list(SIGNATURES.items()) + list(SCREENING_SIGNATURES.items())
                               + list(NEIGHBOUR_SIGNATURES.items()) + list(REAL_NEIGHBOUR_SIGNATURES.items())
-                              + list(CLUSTER_SIGNATURES.items())):
+                              + list(CLUSTER_SIGNATURES.items()) + list(TARGET_RANK_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res

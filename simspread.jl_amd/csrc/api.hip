@@ -2604,6 +2604,343 @@ static int tl_metrics_impl(TlBox<T>& b, int64_t* hits, int64_t* npos, double* ou
   return SS_OK;
 }
 
+// ------------------------------------------------------------------ per-target ranking metrics (target_rank.hip)
+// A handle is a TrState.  Collect phase: an add appends behind the npos committed triples and only its commit moves
+// npos and rows.  Count phase: an add accumulates into the state's delta and only its commit adds that to the counts.
+// Either way the add's verdict (NaN, a positive that is not the sealed one) comes first, so a failed add leaves the
+// handle as it was.
+constexpr uint32_t SS_TRANK_MAGIC = 0x4b4e5254u;
+template <class T>
+struct TrBox : HandleHead {
+  uint32_t magic = SS_TRANK_MAGIC;
+  TrState<T> s;
+};
+
+static int tr_dtype(const void* h, int* dtype) {
+  if (!h) return fail(SS_EINVAL, "target rank handle is NULL");
+  const TrBox<float>* b = reinterpret_cast<const TrBox<float>*>(h);  // the head and the tag lie alike in both
+  if (b->magic != SS_TRANK_MAGIC || (b->dtype != 4 && b->dtype != 8)) return fail(SS_EINVAL, "not a target rank handle");
+  *dtype = b->dtype;
+  return SS_OK;
+}
+
+template <class T>
+static int tr_check(const void* h, TrBox<T>** out) {
+  int dt = 0;
+  SS_TRY(tr_dtype(h, &dt));
+  if (dt != (int)sizeof(T)) return fail(SS_EINVAL, "target rank handle was created with the other precision");
+  *out = const_cast<TrBox<T>*>(reinterpret_cast<const TrBox<T>*>(h));
+  return SS_OK;
+}
+
+template <class T>
+static int tr_create_impl(int64_t nt, ss_target_rank** out) {
+  SS_TRY(require_init());
+  if (!out) return fail(SS_EINVAL, "out handle pointer is NULL");
+  *out = nullptr;
+  if (nt < 1 || nt >= (1LL << 31)) return fail(SS_EINVAL, "target rank: nt = %lld outside [1, 2^31)", (long long)nt);
+  TrBox<T>* box = new (std::nothrow) TrBox<T>();
+  if (!box) return fail(SS_ENOMEM, "host allocation failed");
+  box->dtype = (int)sizeof(T);
+  box->s.nt = nt;
+  *out = reinterpret_cast<ss_target_rank*>(box);
+  return SS_OK;
+}
+
+// One add (a block of rows, or a whole sweep) into a handle: start before the first block, commit after the last.
+template <class T>
+struct TrAdd {
+  TrState<T>& s;
+  int64_t nrows = 0, npos = 0;
+  explicit TrAdd(TrState<T>& st) : s(st) {}
+  int start() {
+    StageTimer t3(ST_EPILOGUE);
+    return tr_begin(s);
+  }
+  template <class P>
+  int rows(const P* ptr, int64_t shift, const int* idx, int base, int64_t nlab, const T* scores, int64_t nb, int64_t ld,
+           int64_t row0, const int* ids) {
+    if (s.phase == 0) {
+      if (s.npos + npos + nlab >= (1LL << 31))
+        return fail(SS_EUNSUPPORTED, "target rank: 2^31 or more positives in one handle");
+      SS_TRY((tr_collect_block<T, P>(s, s.npos + npos, ptr, shift, idx, base, nlab, scores, nb, ld, row0, ids)));
+    } else {
+      SS_TRY((tr_count_block<T, P>(s, ptr, shift, idx, base, nlab, scores, nb, ld, row0, ids)));
+    }
+    nrows += nb;
+    npos += nlab;
+    return SS_OK;
+  }
+  template <class P>
+  int block(const SweepBlock<T, P>& k) {
+    return rows<P>(k.ptr, k.shift, k.idx, 0, k.nlab, k.scores, k.nb, k.nt, k.row0, k.ids);
+  }
+  int commit() {
+    SS_TRY(tr_finish(s));
+    if (s.phase == 0) {
+      s.rows += nrows;
+      s.npos += npos;
+    } else {
+      SS_TRY(tr_count_commit(s));
+      s.rows_counted += nrows;
+    }
+    return SS_OK;
+  }
+};
+
+template <class T>
+static int tr_add_rows_impl(ss_target_rank* h, const int64_t* yptr, const int32_t* yidx, int base, const T* yhat,
+                            int64_t nrows, int64_t ncols, int64_t ld, int64_t row_begin, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  TrBox<T>* bp = nullptr;
+  SS_TRY(tr_check<T>(h, &bp));
+  TrState<T>& s = bp->s;
+  if (base != 0 && base != 1) return fail(SS_EINVAL, "index_base must be 0 or 1");
+  if (nrows < 0 || nrows >= (1LL << 31))
+    return fail(SS_EINVAL, "target rank add rows: nrows = %lld outside [0, 2^31)", (long long)nrows);
+  if (ncols != s.nt)
+    return fail(SS_EINVAL, "target rank add rows: ncols = %lld, the handle has nt = %lld", (long long)ncols,
+                (long long)s.nt);
+  if (ld < ncols)
+    return fail(SS_EINVAL, "target rank add rows: leading dimension %lld < %lld", (long long)ld, (long long)ncols);
+  if (row_begin < 0 || row_begin + nrows > (1LL << 31))
+    return fail(SS_EINVAL, "target rank add rows: rows %lld.. outside [0, 2^31)", (long long)row_begin);
+  if (nrows == 0) return SS_OK;
+  if (!yptr || !yhat) return fail(SS_EINVAL, "target rank add rows: NULL buffer");
+  StagedRows<T> st;
+  SS_TRY(stage_label_rows("target rank add rows", yptr, yidx, base, yhat, nrows, ncols, ld, mem, st));
+  hipEvent_t e_begin, e_end;
+  SS_TRY(timing_mark(&e_begin));
+  TrAdd<T> add(s);
+  SS_TRY(tr_begin(s));
+  SS_TRY((add.template rows<int64_t>(st.dptr, st.shift, st.didx, base, st.nnz, st.dyhat, nrows, st.dld, row_begin,
+                                     nullptr)));
+  SS_TRY(timing_mark(&e_end));
+  timing_span(ST_TOTAL, e_begin, e_end);
+  timing_span(ST_EPILOGUE, e_begin, e_end);
+  return add.commit();
+}
+
+template <class T>
+static int tr_add_loo_impl(ss_target_rank* th, ss_graph* h, int64_t i_begin, int64_t i_end, int clean,
+                           int64_t block_rows) {
+  SS_TRY(require_init());
+  TrBox<T>* bp = nullptr;
+  SS_TRY(tr_check<T>(th, &bp));
+  Graph<T>* gp = nullptr;
+  SS_TRY(graph_check<T>(h, &gp));
+  Graph<T>& g = *gp;
+  SS_TRY(loo_graph_check(g));
+  SS_TRY(range_check(i_begin, i_end, g.ns));
+  SS_TRY(check_block_rows("target rank add loo", block_rows));
+  if (g.nt != bp->s.nt)
+    return fail(SS_EINVAL, "target rank add loo: the graph has %lld targets, the handle %lld", (long long)g.nt,
+                (long long)bp->s.nt);
+  const int64_t nrows = i_end - i_begin, nt = g.nt;
+  if (nrows == 0) return SS_OK;
+  TrAdd<T> add(bp->s);
+  SS_TRY(loo_blocks<T>(g, i_begin, i_end, clean, sweep_block_rows<T>(block_rows, nrows, nt),
+                       [&] { return add.start(); }, [&](const SweepBlock<T, int>& k) { return add.block(k); }, no_step));
+  return add.commit();
+}
+
+template <class T>
+static int tr_add_kfold_impl(ss_target_rank* th, ss_graph* h, const int32_t* fold_of_source, int nfolds, int64_t i_begin,
+                             int64_t i_end, int clean, int64_t block_rows, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  TrBox<T>* bp = nullptr;
+  SS_TRY(tr_check<T>(th, &bp));
+  Graph<T>* gp = nullptr;
+  SS_TRY(graph_check<T>(h, &gp));
+  Graph<T>& g = *gp;
+  SS_TRY(kfold_graph_check(g));
+  SS_TRY(range_check(i_begin, i_end, g.ns));
+  SS_TRY(check_block_rows("target rank add kfold", block_rows));
+  if (g.nt != bp->s.nt)
+    return fail(SS_EINVAL, "target rank add kfold: the graph has %lld targets, the handle %lld", (long long)g.nt,
+                (long long)bp->s.nt);
+  KfoldPlan plan;
+  SS_TRY(kfold_plan(fold_of_source, nfolds, g.ns, mem, plan));
+  const int64_t nrows = i_end - i_begin, nt = g.nt;
+  if (nrows == 0) return SS_OK;
+  TrAdd<T> add(bp->s);
+  SS_TRY(kfold_blocks<T>(g, plan, i_begin, i_end, clean, sweep_block_rows<T>(block_rows, nrows, nt),
+                         [&] { return add.start(); }, [&](const SweepBlock<T, int64_t>& k) { return add.block(k); },
+                         no_step));
+  return add.commit();
+}
+
+template <class T>
+static int tr_seal_impl(TrBox<T>& b) {
+  SS_TRY(require_init());
+  if (b.s.phase != 0) return fail(SS_EINVAL, "target rank seal: the handle is sealed already");
+  timing_begin_call();
+  return tr_seal(b.s);
+}
+
+template <class T>
+static int tr_merge_impl(ss_target_rank* dh, const ss_target_rank* sh) {
+  SS_TRY(require_init());
+  TrBox<T>* d = nullptr;
+  TrBox<T>* c = nullptr;
+  SS_TRY(tr_check<T>(dh, &d));
+  SS_TRY(tr_check<T>(sh, &c));
+  TrState<T>& a = d->s;
+  const TrState<T>& b = c->s;
+  if (d == c) return fail(SS_EINVAL, "target rank merge: a handle cannot be merged into itself (its row ids would repeat)");
+  if (a.nt != b.nt) return fail(SS_EINVAL, "target rank merge: nt differs (%lld vs %lld)", (long long)a.nt, (long long)b.nt);
+  if (a.phase != b.phase) return fail(SS_EINVAL, "target rank merge: one handle collects, the other counts");
+  timing_begin_call();
+  if (a.phase == 0) {
+    if (a.npos + b.npos >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "target rank: 2^31 or more positives in one handle");
+    const int64_t n = b.npos, rows = b.rows;
+    SS_TRY(tr_append(a, b.ct.p, b.cr.p, b.cv.p, n, false));
+    a.npos += n;
+    a.rows += rows;
+    return SS_OK;
+  }
+  bool same = false;
+  SS_TRY(tr_same_table(a, b, &same));
+  if (!same || a.rows != b.rows)
+    return fail(SS_EINVAL, "target rank merge: the handles do not hold the same sealed positives");
+  SS_TRY(tr_add_counts(a, b.counts.p, false));
+  a.rows_counted += b.rows_counted;
+  return SS_OK;
+}
+
+template <class T>
+static int tr_export_positives_impl(ss_target_rank* h, int32_t* targets, int64_t* rows, T* scores, int64_t* rows_added,
+                                    int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  TrBox<T>* bp = nullptr;
+  SS_TRY(tr_check<T>(h, &bp));
+  const TrState<T>& s = bp->s;
+  if (rows_added) *rows_added = s.rows;
+  hipStream_t st = ctx().stream;
+  const hipMemcpyKind kind = mem == SS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  const size_t n = (size_t)s.npos;
+  if (n) {
+    if (targets) SS_HIP(hipMemcpyAsync(targets, s.phase ? s.st.p : s.ct.p, n * sizeof(int), kind, st));
+    if (rows) SS_HIP(hipMemcpyAsync(rows, s.phase ? s.sr.p : s.cr.p, n * sizeof(int64_t), kind, st));
+    if (scores) SS_HIP(hipMemcpyAsync(scores, s.phase ? s.sv.p : s.cv.p, n * sizeof(T), kind, st));
+  }
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
+}
+
+template <class T>
+static int tr_import_positives_impl(ss_target_rank* h, const int32_t* targets, const int64_t* rows, const T* scores,
+                                    int64_t npos, int64_t rows_added, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  TrBox<T>* bp = nullptr;
+  SS_TRY(tr_check<T>(h, &bp));
+  TrState<T>& s = bp->s;
+  if (s.phase != 0) return fail(SS_EINVAL, "target rank import positives: the handle is sealed");
+  if (npos < 0 || rows_added < 0) return fail(SS_EINVAL, "target rank import positives: negative size");
+  if (s.npos + npos >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "target rank: 2^31 or more positives in one handle");
+  if (s.rows + rows_added > (1LL << 31)) return fail(SS_EINVAL, "target rank import positives: more than 2^31 rows");
+  if (npos > 0 && (!targets || !rows || !scores)) return fail(SS_EINVAL, "target rank import positives: NULL buffer");
+  timing_begin_call();
+  const int* dt = targets;
+  const int64_t* dr = rows;
+  const T* dv = scores;
+  DevBuf<int> bt;
+  DevBuf<int64_t> br;
+  DevBuf<T> bv;
+  if (mem == SS_MEM_HOST && npos > 0) {
+    SS_TRY(bt.alloc((size_t)npos));
+    SS_TRY(br.alloc((size_t)npos));
+    SS_TRY(bv.alloc((size_t)npos));
+    SS_TRY(upload<int>(bt.p, targets, (size_t)npos, SS_MEM_HOST));
+    SS_TRY(upload<int64_t>(br.p, rows, (size_t)npos, SS_MEM_HOST));
+    SS_TRY(upload<T>(bv.p, scores, (size_t)npos, SS_MEM_HOST));
+    dt = bt.p;
+    dr = br.p;
+    dv = bv.p;
+  }
+  SS_TRY(tr_append(s, dt, dr, dv, npos, true));
+  SS_HIP(hipStreamSynchronize(ctx().stream));
+  s.npos += npos;
+  s.rows += rows_added;
+  return SS_OK;
+}
+
+template <class T>
+static int tr_export_counts_impl(TrBox<T>& b, int64_t* counts, int64_t* rows_counted, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  const TrState<T>& s = b.s;
+  if (s.phase != 1) return fail(SS_EINVAL, "target rank export counts: the handle is not sealed");
+  if (rows_counted) *rows_counted = s.rows_counted;
+  hipStream_t st = ctx().stream;
+  if (counts)
+    SS_HIP(hipMemcpyAsync(counts, s.counts.p, (size_t)s.counts_len() * sizeof(int64_t),
+                          mem == SS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
+}
+
+template <class T>
+static int tr_import_counts_impl(TrBox<T>& b, const int64_t* counts, int64_t ncounts, int64_t rows_counted, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  TrState<T>& s = b.s;
+  if (s.phase != 1) return fail(SS_EINVAL, "target rank import counts: the handle is not sealed");
+  if (ncounts != s.counts_len())
+    return fail(SS_EINVAL, "target rank import counts: %lld counts, the handle's table has %lld", (long long)ncounts,
+                (long long)s.counts_len());
+  if (rows_counted < 0 || rows_counted > (1LL << 31) - s.rows_counted)
+    return fail(SS_EINVAL, "target rank import counts: rows_counted = %lld out of range", (long long)rows_counted);
+  if (!counts) return fail(SS_EINVAL, "target rank import counts: NULL buffer");
+  timing_begin_call();
+  const int64_t* dc = counts;
+  DevBuf<int64_t> bc;
+  if (mem == SS_MEM_HOST) {
+    SS_TRY(bc.alloc((size_t)ncounts));
+    SS_TRY(upload<int64_t>(bc.p, counts, (size_t)ncounts, SS_MEM_HOST));
+    dc = bc.p;
+  }
+  SS_TRY(tr_add_counts(s, dc, true));
+  s.rows_counted += rows_counted;
+  return SS_OK;
+}
+
+template <class T>
+static int tr_metrics_impl(TrBox<T>& b, double alpha, int L, double* out, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  const TrState<T>& s = b.s;
+  if (s.phase != 1) return fail(SS_EINVAL, "target rank metrics: the handle is not sealed (collect, seal, then count)");
+  if (s.rows_counted != s.rows)
+    return fail(SS_EINVAL, "target rank metrics: %lld rows counted, %lld collected", (long long)s.rows_counted,
+                (long long)s.rows);
+  if (L < 1) return fail(SS_EINVAL, "Please use a list length greater than 0 (L > 0)");
+  if ((int64_t)L >= s.rows) return fail(SS_EINVAL, "Number of labels is less than length (L > y)");
+  if (!(alpha > 0.0)) return fail(SS_EINVAL, "target rank metrics: alpha must be positive");
+  if (!out) return fail(SS_EINVAL, "output buffer is NULL");
+  timing_begin_call();
+  hipStream_t st = ctx().stream;
+  hipEvent_t e_begin, e_end;
+  SS_TRY(timing_mark(&e_begin));
+  double* dout = out;
+  DevBuf<double> bout;
+  if (mem == SS_MEM_HOST) {
+    SS_TRY(bout.alloc((size_t)s.nt * 6));
+    dout = bout.p;
+  }
+  SS_TRY(tr_metrics(s, alpha, L, dout));
+  SS_TRY(timing_mark(&e_end));
+  timing_span(ST_TOTAL, e_begin, e_end);
+  if (mem == SS_MEM_HOST)
+    SS_HIP(hipMemcpyAsync(out, bout.p, (size_t)s.nt * 6 * sizeof(double), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
+}
+
 // ------------------------------------------------------------------ raw SpMM
 template <class T>
 static int spmat_check(const void* h, SpMat<T>** out) {
@@ -3176,6 +3513,8 @@ int ss_init(int device) {
   // binary_rows.hip's LDS-path row limit, lowered only (tests drive both paths over the same rows with it)
   c.binary_lds_cols = -1;
   if (env_set("SS_BINARY_LDS_COLS")) c.binary_lds_cols = (int)std::max<int64_t>(0, env_int("SS_BINARY_LDS_COLS", 0));
+  c.target_rank_lds = -1;
+  if (env_set("SS_TARGET_RANK_LDS")) c.target_rank_lds = (int)std::max<int64_t>(0, env_int("SS_TARGET_RANK_LDS", 0));
   SS_HIP(hipStreamCreateWithFlags(&c.own_stream, hipStreamNonBlocking));
   c.stream = c.own_stream;
   c.device = device;
@@ -4469,6 +4808,186 @@ int ss_target_topl_metrics(ss_target_topl* h, int64_t* hits, int64_t* npos, doub
   SS_HANDLE_LOCK(h);
   return dt == 4 ? tl_metrics_impl(*reinterpret_cast<TlBox<float>*>(h), hits, npos, out, mem)
                  : tl_metrics_impl(*reinterpret_cast<TlBox<double>*>(h), hits, npos, out, mem);
+}
+
+/* ---- include/simspread_hip_target_rank.h */
+int ss_target_rank_create_f32(int64_t nt, ss_target_rank** out) {
+  SS_API_LOCK();
+  return tr_create_impl<float>(nt, out);
+}
+int ss_target_rank_create_f64(int64_t nt, ss_target_rank** out) {
+  SS_API_LOCK();
+  return tr_create_impl<double>(nt, out);
+}
+int ss_target_rank_destroy(ss_target_rank* h) {
+  SS_API_LOCK();
+  if (!h) return SS_OK;
+  int dt = 0;
+  SS_TRY(tr_dtype(h, &dt));
+  {  // wait for a call that still works on the handle, then for the device
+    SS_HANDLE_LOCK(h);
+    if (ctx().inited) (void)hipStreamSynchronize(ctx().stream);
+  }
+  if (dt == 4) delete reinterpret_cast<TrBox<float>*>(h);
+  else delete reinterpret_cast<TrBox<double>*>(h);
+  return SS_OK;
+}
+int ss_target_rank_reset(ss_target_rank* h) {
+  SS_API_LOCK();
+  int dt = 0;
+  SS_TRY(tr_dtype(h, &dt));
+  SS_HANDLE_LOCK(h);
+  SS_TRY(require_init());
+  auto clear = [](auto* b) -> int {
+    SS_HIP(hipStreamSynchronize(ctx().stream));
+    b->s.phase = 0;
+    b->s.rows = b->s.npos = b->s.rows_counted = 0;
+    b->s.tiles_lds = b->s.tiles_large = 0;
+    return SS_OK;
+  };
+  return dt == 4 ? clear(reinterpret_cast<TrBox<float>*>(h)) : clear(reinterpret_cast<TrBox<double>*>(h));
+}
+int ss_target_rank_info(const ss_target_rank* h, int64_t info[6]) {
+  SS_API_LOCK();
+  int dt = 0;
+  SS_TRY(tr_dtype(h, &dt));
+  if (!info) return fail(SS_EINVAL, "NULL argument");
+  SS_HANDLE_LOCK(h);
+  auto fill = [&](const auto* b) {
+    info[0] = b->s.nt;
+    info[1] = b->s.phase;
+    info[2] = b->s.rows;
+    info[3] = b->s.npos;
+    info[4] = b->s.rows_counted;
+    info[5] = 0;
+  };
+  if (dt == 4) fill(reinterpret_cast<const TrBox<float>*>(h));
+  else fill(reinterpret_cast<const TrBox<double>*>(h));
+  return SS_OK;
+}
+int ss_target_rank_add_rows_f32(ss_target_rank* h, const int64_t* yptr, const int32_t* yidx, int index_base,
+                                const float* yhat, int64_t nrows, int64_t ncols, int64_t ld, int64_t row_begin,
+                                int mem) {
+  SS_API_LOCK();
+  if (!h) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  return tr_add_rows_impl<float>(h, yptr, yidx, index_base, yhat, nrows, ncols, ld, row_begin, mem);
+}
+int ss_target_rank_add_rows_f64(ss_target_rank* h, const int64_t* yptr, const int32_t* yidx, int index_base,
+                                const double* yhat, int64_t nrows, int64_t ncols, int64_t ld, int64_t row_begin,
+                                int mem) {
+  SS_API_LOCK();
+  if (!h) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  return tr_add_rows_impl<double>(h, yptr, yidx, index_base, yhat, nrows, ncols, ld, row_begin, mem);
+}
+// a handle and a graph: the handle's lock first, always
+int ss_target_rank_add_loo_f32(ss_target_rank* h, ss_graph* g, int64_t i_begin, int64_t i_end, int clean,
+                               int64_t block_rows) {
+  SS_API_LOCK();
+  if (!h || !g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  std::unique_lock<std::mutex> _graph_guard(reinterpret_cast<HandleHead*>(g)->mu);
+  return tr_add_loo_impl<float>(h, g, i_begin, i_end, clean, block_rows);
+}
+int ss_target_rank_add_loo_f64(ss_target_rank* h, ss_graph* g, int64_t i_begin, int64_t i_end, int clean,
+                               int64_t block_rows) {
+  SS_API_LOCK();
+  if (!h || !g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  std::unique_lock<std::mutex> _graph_guard(reinterpret_cast<HandleHead*>(g)->mu);
+  return tr_add_loo_impl<double>(h, g, i_begin, i_end, clean, block_rows);
+}
+int ss_target_rank_add_kfold_f32(ss_target_rank* h, ss_graph* g, const int32_t* fold_of_source, int nfolds,
+                                 int64_t i_begin, int64_t i_end, int clean, int64_t block_rows, int mem) {
+  SS_API_LOCK();
+  if (!h || !g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  std::unique_lock<std::mutex> _graph_guard(reinterpret_cast<HandleHead*>(g)->mu);
+  return tr_add_kfold_impl<float>(h, g, fold_of_source, nfolds, i_begin, i_end, clean, block_rows, mem);
+}
+int ss_target_rank_add_kfold_f64(ss_target_rank* h, ss_graph* g, const int32_t* fold_of_source, int nfolds,
+                                 int64_t i_begin, int64_t i_end, int clean, int64_t block_rows, int mem) {
+  SS_API_LOCK();
+  if (!h || !g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  std::unique_lock<std::mutex> _graph_guard(reinterpret_cast<HandleHead*>(g)->mu);
+  return tr_add_kfold_impl<double>(h, g, fold_of_source, nfolds, i_begin, i_end, clean, block_rows, mem);
+}
+int ss_target_rank_seal(ss_target_rank* h) {
+  SS_API_LOCK();
+  int dt = 0;
+  SS_TRY(tr_dtype(h, &dt));
+  SS_HANDLE_LOCK(h);
+  return dt == 4 ? tr_seal_impl(*reinterpret_cast<TrBox<float>*>(h)) : tr_seal_impl(*reinterpret_cast<TrBox<double>*>(h));
+}
+int ss_target_rank_merge(ss_target_rank* dst, const ss_target_rank* src) {
+  SS_API_LOCK();
+  int dd = 0, ds = 0;
+  SS_TRY(tr_dtype(dst, &dd));
+  SS_TRY(tr_dtype(src, &ds));
+  if (dd != ds) return fail(SS_EINVAL, "target rank merge: the handles have different precisions");
+  // two different handles: their locks in address order, so that merge(a, b) and merge(b, a) cannot deadlock
+  HandleHead* a = reinterpret_cast<HandleHead*>(dst);
+  HandleHead* b = reinterpret_cast<HandleHead*>(const_cast<ss_target_rank*>(src));
+  if (b < a) std::swap(a, b);
+  std::unique_lock<std::mutex> la(a->mu);
+  std::unique_lock<std::mutex> lb;
+  if (b != a) lb = std::unique_lock<std::mutex>(b->mu);
+  return dd == 4 ? tr_merge_impl<float>(dst, src) : tr_merge_impl<double>(dst, src);
+}
+int ss_target_rank_export_positives_f32(ss_target_rank* h, int32_t* targets, int64_t* rows, float* scores,
+                                        int64_t* rows_added, int mem) {
+  SS_API_LOCK();
+  if (!h) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  return tr_export_positives_impl<float>(h, targets, rows, scores, rows_added, mem);
+}
+int ss_target_rank_export_positives_f64(ss_target_rank* h, int32_t* targets, int64_t* rows, double* scores,
+                                        int64_t* rows_added, int mem) {
+  SS_API_LOCK();
+  if (!h) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  return tr_export_positives_impl<double>(h, targets, rows, scores, rows_added, mem);
+}
+int ss_target_rank_import_positives_f32(ss_target_rank* h, const int32_t* targets, const int64_t* rows,
+                                        const float* scores, int64_t npos, int64_t rows_added, int mem) {
+  SS_API_LOCK();
+  if (!h) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  return tr_import_positives_impl<float>(h, targets, rows, scores, npos, rows_added, mem);
+}
+int ss_target_rank_import_positives_f64(ss_target_rank* h, const int32_t* targets, const int64_t* rows,
+                                        const double* scores, int64_t npos, int64_t rows_added, int mem) {
+  SS_API_LOCK();
+  if (!h) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(h);
+  return tr_import_positives_impl<double>(h, targets, rows, scores, npos, rows_added, mem);
+}
+int ss_target_rank_export_counts(ss_target_rank* h, int64_t* counts, int64_t* rows_counted, int mem) {
+  SS_API_LOCK();
+  int dt = 0;
+  SS_TRY(tr_dtype(h, &dt));
+  SS_HANDLE_LOCK(h);
+  return dt == 4 ? tr_export_counts_impl(*reinterpret_cast<TrBox<float>*>(h), counts, rows_counted, mem)
+                 : tr_export_counts_impl(*reinterpret_cast<TrBox<double>*>(h), counts, rows_counted, mem);
+}
+int ss_target_rank_import_counts(ss_target_rank* h, const int64_t* counts, int64_t ncounts, int64_t rows_counted,
+                                 int mem) {
+  SS_API_LOCK();
+  int dt = 0;
+  SS_TRY(tr_dtype(h, &dt));
+  SS_HANDLE_LOCK(h);
+  return dt == 4 ? tr_import_counts_impl(*reinterpret_cast<TrBox<float>*>(h), counts, ncounts, rows_counted, mem)
+                 : tr_import_counts_impl(*reinterpret_cast<TrBox<double>*>(h), counts, ncounts, rows_counted, mem);
+}
+int ss_target_rank_metrics(ss_target_rank* h, double alpha, int L, double* out, int mem) {
+  SS_API_LOCK();
+  int dt = 0;
+  SS_TRY(tr_dtype(h, &dt));
+  SS_HANDLE_LOCK(h);
+  return dt == 4 ? tr_metrics_impl(*reinterpret_cast<TrBox<float>*>(h), alpha, L, out, mem)
+                 : tr_metrics_impl(*reinterpret_cast<TrBox<double>*>(h), alpha, L, out, mem);
 }
 
 /* ---- include/simspread_hip_clusters.h */

@@ -69,6 +69,7 @@ struct Ctx {
   int num_cu = 256;
   size_t lds_per_block = 160 * 1024;
   int binary_lds_cols = -1;          // SS_BINARY_LDS_COLS at ss_init: lowers binary_rows.hip's LDS-path row limit
+  int target_rank_lds = -1;          // SS_TARGET_RANK_LDS at ss_init: caps the positives of a target on target_rank.hip's LDS route
   unsigned generation = 0;           // bumped by ss_shutdown: events created before belong to a dead context
 };
 Ctx& ctx();

@@ -359,6 +359,57 @@ int tl_export_table(const TlTable<pool_key_t<T>>& t, int64_t nt, int L, int64_t 
 // hits[t] = positives among target t's entries (device)
 template <class K>
 int tl_hits(const TlTable<K>& t, int64_t nt, int L, int64_t fill, int64_t* hits);
+// ---- target_rank.hip: per-target ranking metrics from the positives and integer counts of negatives
+// (include/simspread_hip_target_rank.h holds the contract and the count layout).  Collect phase: ct / cr / cv hold npos
+// appended triples.  Count phase: st / sr / sv the same triples sorted by (target, score desc, row asc), off[nt + 1] the
+// per-target offsets, counts the 3 npos + 6 nt int64 of the export format.  An add in the count phase accumulates into
+// delta (hist | nz, 32-bit) and dmm (min keys | max keys) and only tr_count_commit adds them to counts.
+template <class T>
+struct TrState {
+  int64_t nt = 0, rows = 0, npos = 0, rows_counted = 0;
+  int phase = 0;
+  DevBuf<int> ct, st, off;
+  DevBuf<int64_t> cr, sr, counts;
+  DevBuf<T> cv, sv;
+  DevBuf<unsigned char> route;  // per tile of 64 targets: 1 = sealed positives and histograms in LDS
+  int64_t tiles_lds = 0, tiles_large = 0;
+  DevBuf<unsigned> delta;
+  DevBuf<unsigned long long> dmm, flag;  // flag[0]: a NaN score; flag[1]: smallest (row << 32 | target) of a mismatch
+  int64_t hist_len() const { return 3 * (npos + nt); }
+  int64_t counts_len() const { return 3 * npos + 6 * nt; }
+};
+// clears the add's flags (and, in the count phase, its delta)
+template <class T>
+int tr_begin(TrState<T>& s);
+// one row-major score block (nb x nt, ld), enqueued only; rows are row_begin + r (rowmap == NULL) or rowmap[r]; labels
+// as for launch_rank_rows (checked beforehand).  collect: its positives are appended at entry `at` (capacity grows,
+// contents kept); count: into delta
+template <class T, class PtrT>
+int tr_collect_block(TrState<T>& s, int64_t at, const PtrT* yptr, int64_t shift, const int* yidx, int base, int64_t nnz,
+                     const T* yhat, int64_t nb, int64_t ld, int64_t row_begin, const int* rowmap);
+template <class T, class PtrT>
+int tr_count_block(TrState<T>& s, const PtrT* yptr, int64_t shift, const int* yidx, int base, int64_t nnz, const T* yhat,
+                   int64_t nb, int64_t ld, int64_t row_begin, const int* rowmap);
+// the add's verdict (syncs): SS_EINVAL for a NaN score or a positive that is not the sealed one
+template <class T>
+int tr_finish(TrState<T>& s);
+// counts += delta (after tr_finish passed)
+template <class T>
+int tr_count_commit(TrState<T>& s);
+template <class T>
+int tr_seal(TrState<T>& s);
+// device triples checked (targets in range, 0 <= rows < 2^31, no NaN) and appended at entry s.npos (npos unchanged)
+template <class T>
+int tr_append(TrState<T>& s, const int* targets, const int64_t* rows, const T* scores, int64_t n, bool check);
+// do both hold the same sealed table, bit for bit (syncs)
+template <class T>
+int tr_same_table(const TrState<T>& a, const TrState<T>& b, bool* same);
+// s.counts += a device table of the export layout; check: hist and nz entries must be >= 0 (SS_EINVAL, nothing added)
+template <class T>
+int tr_add_counts(TrState<T>& s, const int64_t* counts, bool check);
+// out: nt x 6 doubles on the device
+template <class T>
+int tr_metrics(const TrState<T>& s, double alpha, int L, double* out);
 // ---- support.hip: support lists.  Pair p reads transfer row slot[p] of Trows (row-major, leading dimension ldt) and row
 // tgt[p] of Ys' and writes entry pos[p] of src / contrib (M slots each) and nsupp: the sources s with
 // Trows[slot][s] * Ys'[t][s] != 0 under (product descending by isless, s ascending), the first M of them and their count.

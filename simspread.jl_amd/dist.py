@@ -187,3 +187,38 @@ def target_topl(handle, group=None, root: int = 0):
     for vals, rows, labels, npos, rows_added in tables:
         total.import_(vals, rows, labels, npos, rows_added)
     return total
+
+
+def target_rank_positives(handle, group=None):
+    """Between the two passes of a sharded per-target evaluation: every rank has collected its own rows
+    (TargetRank.add_loo / add_kfold over its shard_range); here the positives are all-gathered and every rank imports
+    the other ranks', in rank order, so that every rank seals the same table.  Returns the handle, still collecting.
+    The triples travel through torch.distributed (all_gather_object)."""
+    import torch.distributed as dist
+    rank = dist.get_rank(group)
+    tables = [None] * dist.get_world_size(group)
+    dist.all_gather_object(tables, handle.export_positives(), group=group)
+    for r, (targets, rows, scores, rows_added) in enumerate(tables):
+        if r != rank:
+            handle.import_positives(targets, rows, scores, rows_added)
+    return handle
+
+
+def target_rank(handle, group=None, root: int = 0):
+    """The per-target ranking metrics of a sharded sweep: every rank has sealed the same positives
+    (target_rank_positives) and counted its own rows; here the exported counts are summed at the root in a fresh handle
+    over the same sealed table.  Returns that TargetRank on the root (its metrics() are the sweep's), None elsewhere;
+    the caller's handle is not changed."""
+    import torch.distributed as dist
+    from .engine import TargetRank
+    table = handle.export_counts()
+    rank = dist.get_rank(group)
+    tables = [None] * dist.get_world_size(group) if rank == root else None
+    dist.gather_object(table, tables, dst=_global_rank(root, group), group=group)
+    if rank != root:
+        return None
+    total = TargetRank(handle.info()["nt"], handle.dtype)
+    total.import_positives(*handle.export_positives()).seal()
+    for counts, rows_counted in tables:
+        total.import_counts(counts, rows_counted)
+    return total

@@ -530,6 +530,30 @@ class DeviceGraph:
         finally:
             p.close()
 
+    def evaluate_loo_targets(self, i_begin: int = 0, i_end: Optional[int] = None, clean: bool = False,
+                             alpha: float = 20.0, L: int = 20, block_rows: int = 0) -> np.ndarray:
+        """The leave-one-out folds [i_begin, i_end) judged per target: row t = rank_metrics_rows of column t of
+        predict_loo against column t of the labels, ties by fold index.  Two sweeps (TargetRank: collect, seal, count);
+        no score leaves the device.  Returns (nt, 6) float64 numpy, columns TARGET_RANK_FIELDS."""
+        h = TargetRank(self.nt, self.dtype)
+        try:
+            h.add_loo(self, i_begin, i_end, clean=clean, block_rows=block_rows).seal()
+            return h.add_loo(self, i_begin, i_end, clean=clean, block_rows=block_rows).metrics(alpha, L)
+        finally:
+            h.close()
+
+    def evaluate_kfold_targets(self, fold_of_source, nfolds: Optional[int] = None, i_begin: int = 0,
+                               i_end: Optional[int] = None, clean: bool = False, alpha: float = 20.0, L: int = 20,
+                               block_rows: int = 0) -> np.ndarray:
+        """The k-fold rows [i_begin, i_end) judged per target, as evaluate_loo_targets judges the leave-one-out folds."""
+        h = TargetRank(self.nt, self.dtype)
+        try:
+            h.add_kfold(self, fold_of_source, nfolds, i_begin, i_end, clean=clean, block_rows=block_rows).seal()
+            return h.add_kfold(self, fold_of_source, nfolds, i_begin, i_end, clean=clean,
+                               block_rows=block_rows).metrics(alpha, L)
+        finally:
+            h.close()
+
     def support(self, rows, targets, M: int = 16, queries: Optional["DeviceQueries"] = None, loo: bool = False):
         """Which sources carry the scores of the (row, target) pairs ``zip(rows, targets)`` (ss_support_*): returns
         ``(src, contrib, nsupp)`` with src, contrib of shape (npairs, M) -- the sources s with the largest contributions
@@ -1425,6 +1449,166 @@ class TargetTopL:
     def close(self):
         if self._h is not None and self._h.value:
             L_.load().ss_target_topl_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+TARGET_RANK_FIELDS = RANK_ROWS_FIELDS
+
+
+class TargetRank:
+    """Per target the six ranking metrics of a whole sweep -- AuROC, AuPRC, BEDROC, validity ratio, recall@L,
+    precision@L of (Y[:, t], S[:, t]) as rank_metrics_rows gives them for a vector, ties by ascending row id -- on the
+    device and without the score matrix (ss_target_rank_*).  It costs two sweeps: every row is added once to collect
+    the positives' scores, then, after seal(), once more to count the negatives against them; the second pass is
+    checked to repeat the first.  Row ids are >= 0, < 2^31 and distinct; adds are all or nothing; positives, counts
+    and metrics are one and the same whatever the blocks, their order, merges or export -> import."""
+
+    def __init__(self, nt: int, dtype=np.float32):
+        self.dtype = np.dtype(dtype)
+        self._suf = _suffix(dtype)
+        h = C.c_void_p()
+        L_.check(getattr(L_.lib(), f"ss_target_rank_create_{self._suf}")(int(nt), C.byref(h)))
+        self._h = h
+
+    def info(self) -> dict:
+        """nt, phase ("collect" or "count"), rows and positives collected, rows counted"""
+        buf = (C.c_int64 * 6)()
+        L_.check(L_.lib().ss_target_rank_info(self._h, buf))
+        return dict(nt=int(buf[0]), phase="count" if buf[1] else "collect", rows=int(buf[2]), npos=int(buf[3]),
+                    rows_counted=int(buf[4]))
+
+    def reset(self):
+        L_.check(L_.lib().ss_target_rank_reset(self._h))
+        return self
+
+    def add_rows(self, y, yhat, row_begin: int = 0):
+        """Add the rows of a score block (nrows, nt), row r under the id row_begin + r: collected before seal(),
+        counted after it.  `y` and `yhat` as TargetTopL.add_rows takes them."""
+        torch_in = _is_torch(yhat)
+        if torch_in:
+            import torch
+            if yhat.dim() == 1:
+                yhat = yhat.reshape(1, -1)
+            if yhat.dim() != 2 or not yhat.is_contiguous() or not yhat.is_cuda:
+                raise ValueError("yhat must be a contiguous 1-D or 2-D CUDA tensor")
+            if {torch.float32: "f32", torch.float64: "f64"}.get(yhat.dtype) != self._suf:
+                raise TypeError("yhat dtype does not match the handle's precision")
+            nrows, ncols = (int(v) for v in yhat.shape)
+        else:
+            a = np.asarray(yhat)
+            if a.ndim == 1:
+                a = a.reshape(1, -1)
+            if a.ndim != 2:
+                raise ValueError("yhat must be 1-D or 2-D")
+            if a.dtype != self.dtype:
+                raise TypeError("yhat dtype does not match the handle's precision")
+            a = np.ascontiguousarray(a)
+            nrows, ncols = a.shape
+        if not isinstance(y, tuple) and not hasattr(y, "tocsr"):
+            y = np.asarray(y).reshape(nrows, ncols)
+        dev_labels = isinstance(y, tuple) and _is_torch(y[0])
+        fn = getattr(L_.lib(), f"ss_target_rank_add_rows_{self._suf}")
+        if dev_labels:
+            if not torch_in:
+                raise TypeError("device labels need device scores (a CUDA tensor yhat)")
+            ptr_d, idx_d = y[0].contiguous(), y[1].contiguous()
+        else:
+            hp, hi = _label_csr(y, nrows, ncols)
+            _check_label_order(hp, hi, ncols)
+        if torch_in:
+            import torch
+            if not dev_labels:
+                ptr_d = torch.from_numpy(hp).to(yhat.device)
+                idx_d = torch.from_numpy(hi if hi.size else np.zeros(1, np.int32)).to(yhat.device)
+            L_.check(fn(self._h, ptr_d.data_ptr(), idx_d.data_ptr(), 0, yhat.data_ptr(), nrows, ncols, ncols,
+                        int(row_begin), L_.SS_MEM_DEVICE))
+        else:
+            L_.check(fn(self._h, hp.ctypes.data, hi.ctypes.data, 0, a.ctypes.data, nrows, ncols, ncols, int(row_begin),
+                        L_.SS_MEM_HOST))
+        return self
+
+    def add_loo(self, g: "DeviceGraph", i_begin: int = 0, i_end: Optional[int] = None, clean: bool = False,
+                block_rows: int = 0):
+        """Add the leave-one-out folds [i_begin, i_end) of `g` against its own labels, fold i as row i
+        (ss_target_rank_add_loo_*)."""
+        i_end = g.ns if i_end is None else i_end
+        fn = getattr(L_.lib(), f"ss_target_rank_add_loo_{self._suf}")
+        L_.check(fn(self._h, g._h, int(i_begin), int(i_end), 1 if clean else 0, int(block_rows)))
+        return self
+
+    def add_kfold(self, g: "DeviceGraph", fold_of_source, nfolds: Optional[int] = None, i_begin: int = 0,
+                  i_end: Optional[int] = None, clean: bool = False, block_rows: int = 0):
+        """Add the k-fold rows [i_begin, i_end) of `g` against its own labels, source i as row i
+        (ss_target_rank_add_kfold_*)."""
+        fold, nfolds = g._folds(fold_of_source, nfolds)
+        i_end = g.ns if i_end is None else i_end
+        fn = getattr(L_.lib(), f"ss_target_rank_add_kfold_{self._suf}")
+        L_.check(fn(self._h, g._h, fold.ctypes.data, nfolds, int(i_begin), int(i_end), 1 if clean else 0,
+                    int(block_rows), L_.SS_MEM_HOST))
+        return self
+
+    def seal(self):
+        """End the collect phase: sort the positives; from now on adds count."""
+        L_.check(L_.lib().ss_target_rank_seal(self._h))
+        return self
+
+    def merge(self, other: "TargetRank"):
+        """Collect phase: add `other`'s positives and rows.  Count phase: add its counts (the same sealed positives)."""
+        L_.check(L_.lib().ss_target_rank_merge(self._h, other._h))
+        return self
+
+    def export_positives(self):
+        """(targets int32, rows int64, scores) of the positives and the rows collected: in collection order before
+        seal(), sorted by (target, score descending, row ascending) after it."""
+        n = self.info()["npos"]
+        t, r, v = np.empty(n, np.int32), np.empty(n, np.int64), np.empty(n, self.dtype)
+        rows = C.c_int64()
+        fn = getattr(L_.lib(), f"ss_target_rank_export_positives_{self._suf}")
+        L_.check(fn(self._h, t.ctypes.data, r.ctypes.data, v.ctypes.data, C.byref(rows), L_.SS_MEM_HOST))
+        return t, r, v, int(rows.value)
+
+    def import_positives(self, targets, rows, scores, rows_added: int):
+        """Collect phase: add positives such as export_positives() returns (another rank's)."""
+        t = np.ascontiguousarray(targets, dtype=np.int32)
+        r = np.ascontiguousarray(rows, dtype=np.int64)
+        v = np.ascontiguousarray(scores, dtype=self.dtype)
+        if not (t.ndim == 1 and t.shape == r.shape == v.shape):
+            raise ValueError("targets, rows and scores must be 1-D arrays of one length")
+        fn = getattr(L_.lib(), f"ss_target_rank_import_positives_{self._suf}")
+        L_.check(fn(self._h, t.ctypes.data, r.ctypes.data, v.ctypes.data, t.size, int(rows_added), L_.SS_MEM_HOST))
+        return self
+
+    def export_counts(self):
+        """Count phase: the int64 count table (3 npos + 6 nt entries, layout in include/simspread_hip_target_rank.h)
+        and the rows counted."""
+        i = self.info()
+        c = np.empty(3 * i["npos"] + 6 * i["nt"], np.int64)
+        rows = C.c_int64()
+        L_.check(L_.lib().ss_target_rank_export_counts(self._h, c.ctypes.data, C.byref(rows), L_.SS_MEM_HOST))
+        return c, int(rows.value)
+
+    def import_counts(self, counts, rows_counted: int):
+        """Count phase: add a count table such as export_counts() returns, taken against the same sealed positives."""
+        c = np.ascontiguousarray(counts, dtype=np.int64)
+        L_.check(L_.lib().ss_target_rank_import_counts(self._h, c.ctypes.data, c.size, int(rows_counted),
+                                                       L_.SS_MEM_HOST))
+        return self
+
+    def metrics(self, alpha: float = 20.0, L: int = 20) -> np.ndarray:
+        """(nt, 6) float64, columns TARGET_RANK_FIELDS; every collected row must have been counted and L < rows."""
+        out = np.empty((self.info()["nt"], len(TARGET_RANK_FIELDS)), np.float64)
+        L_.check(L_.lib().ss_target_rank_metrics(self._h, float(alpha), int(L), out.ctypes.data, L_.SS_MEM_HOST))
+        return out
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            L_.load().ss_target_rank_destroy(self._h)
             self._h = None
 
     def __del__(self):
