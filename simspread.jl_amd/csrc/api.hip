@@ -245,6 +245,7 @@ template <class T>
 struct QueriesBox : HandleHead {
   uint64_t graph_id = 0;
   DevCsr<T> Xq;
+  CoefTable<T> coef;   // Xq * inv_kf of its graph, from the first prediction on
 };
 template <class T>
 struct SpMatBox : HandleHead {
@@ -262,12 +263,13 @@ static int graph_check(const void* h, Graph<T>** out) {
 
 // a query set used with the graph handle h (already checked): its precision, and that it was created for that graph
 template <class T>
-static int queries_check(const void* qh, const void* h, const DevCsr<T>** out) {
-  const QueriesBox<T>* q = reinterpret_cast<const QueriesBox<T>*>(qh);
+static int queries_check(const void* qh, const void* h, const DevCsr<T>** out, CoefTable<T>** tab = nullptr) {
+  QueriesBox<T>* q = const_cast<QueriesBox<T>*>(reinterpret_cast<const QueriesBox<T>*>(qh));
   if (q->dtype != (int)sizeof(T)) return fail(SS_EINVAL, "query set was created with the other precision");
   if (q->graph_id != reinterpret_cast<const GraphBox<T>*>(h)->id)
     return fail(SS_EINVAL, "query set was created for another graph");
   *out = &q->Xq;
+  if (tab) *tab = &q->coef;   // (the caller holds the query set's lock)
   return SS_OK;
 }
 
@@ -1208,15 +1210,47 @@ static int stage2_rows(Graph<T>& g, int64_t rb, int64_t nb, const int* kt_clean,
   return sell_rows<T>(g.W, g.Tws.p, g.ns, g.nt, g.Sws, rb, nb, kt_clean, d);
 }
 
+// The coefficient table of left operand L of graph g, kept in tb (a member of g, or of a query set bound to g): built at
+// the first prediction that wants it and again after g's degrees changed.  *out stays NULL -- the kernels gather -- with
+// SS_TRANSFER_COEF=0 and for a table above SS_TRANSFER_COEF_BYTES (default 1 GiB).
+template <class T>
+static int coef_table(const Graph<T>& g, CoefTable<T>& tb, const DevCsr<T>& L, const T* inv1, const int* kf_loo,
+                      const T** out) {
+  *out = nullptr;
+  if (env_off("SS_TRANSFER_COEF")) return SS_OK;
+  const int64_t cap = env_int("SS_TRANSFER_COEF_BYTES", 1LL << 30);
+  if (L.nnz * (int64_t)sizeof(T) > cap) return SS_OK;
+  if (tb.epoch != g.coef_epoch) {
+    tb.drop();
+    SS_TRY(tb.c.alloc((size_t)L.nnz));
+    SS_TRY(transfer_coef_build<T>(L, inv1, kf_loo, tb.c.p));
+    tb.epoch = g.coef_epoch;
+  }
+  *out = tb.c.p;
+  return SS_OK;
+}
+
 // run stage 1 + stage 2 over [row_begin, row_end) into dev_out (row-major nrows x nt, ld = ldo); Xq: the query block
-// SS_ROWS_QUERY rows of a sparse graph are taken from (the graph's own, or a query set's)
+// SS_ROWS_QUERY rows of a sparse graph are taken from (the graph's own, or a query set's, then with its table qtab)
 template <class T>
 static int predict_rows_device(Graph<T>& g, const DevCsr<T>& Xq, int kind, int64_t row_begin, int64_t row_end, int clean,
-                               T* dev_out, int64_t ldo) {
+                               T* dev_out, int64_t ldo, CoefTable<T>* qtab = nullptr) {
   const int64_t nrows = row_end - row_begin;
   const int64_t nj = g.ns;
   SS_TRY(graph_sell(g));
   SS_TRY(graph_chunked(g, kind == SS_ROWS_SOURCE));
+  const T* coef[2] = {nullptr, nullptr};
+  if (!g.dense.on) {
+    if (kind == 2) {
+      SS_TRY(coef_table<T>(g, g.coef_loo, g.Xs, nullptr, g.kf.p, &coef[0]));
+    } else if (kind == SS_ROWS_QUERY) {
+      if (&Xq == &g.Xq) qtab = &g.coef_q;
+      if (qtab) SS_TRY(coef_table<T>(g, *qtab, Xq, g.inv_kf.p, nullptr, &coef[0]));
+    } else {
+      SS_TRY(coef_table<T>(g, g.coef_s, g.Xs, g.inv_kf.p, nullptr, &coef[0]));
+      SS_TRY(coef_table<T>(g, g.coef_y, g.Ys, g.inv_kt.p, nullptr, &coef[1]));
+    }
+  }
   const int64_t rb = transfer_batch_rows(nrows, nj, sizeof(T));
   // the transfer block lives in the handle so that repeated predictions do not re-allocate
   const size_t need = (size_t)rb * (size_t)(nj > 0 ? nj : 1);
@@ -1239,7 +1273,7 @@ static int predict_rows_device(Graph<T>& g, const DevCsr<T>& Xq, int kind, int64
           SS_TRY(launch_transfer<T>(1, L, inv1, M, g.inv_ks.p, row_begin + r0, nb, nj, Tbuf.p, nj, nullptr, true));
         }
       } else if (kind == 2) {
-        SS_TRY(launch_transfer_loo<T>(g.Xs, g.XsTc, g.kf.p, g.ks.p, row_begin + r0, nb, Tbuf.p, nj));
+        SS_TRY(launch_transfer_loo<T>(g.Xs, g.XsTc, g.kf.p, g.ks.p, row_begin + r0, nb, Tbuf.p, nj, coef[0]));
       } else if (kind == SS_ROWS_QUERY) {
         // query rows: SS_TRANSFER_V=2 selects the query-block kernels (measured variants of round 3)
         // when the chunk's sub-row offsets fit in LDS next to >= 8 waves of accumulators; default: the single-wave kernel
@@ -1257,14 +1291,14 @@ static int predict_rows_device(Graph<T>& g, const DevCsr<T>& Xq, int kind, int64
           const DevCsr<T>* L[2] = {&Xq, nullptr};
           const DevChunked<T>* M[2] = {&g.XsTc, nullptr};
           const T* inv1[2] = {g.inv_kf.p, nullptr};
-          SS_TRY(launch_transfer<T>(1, L, inv1, M, g.inv_ks.p, row_begin + r0, nb, nj, Tbuf.p, nj));
+          SS_TRY(launch_transfer<T>(1, L, inv1, M, g.inv_ks.p, row_begin + r0, nb, nj, Tbuf.p, nj, nullptr, false, coef));
         }
       } else {
         // source rows: feature path + target path
         const DevCsr<T>* L[2] = {&g.Xs, &g.Ys};
         const DevChunked<T>* M[2] = {&g.XsTc, &g.YsTc};
         const T* inv1[2] = {g.inv_kf.p, g.inv_kt.p};
-        SS_TRY(launch_transfer<T>(2, L, inv1, M, g.inv_ks.p, row_begin + r0, nb, nj, Tbuf.p, nj));
+        SS_TRY(launch_transfer<T>(2, L, inv1, M, g.inv_ks.p, row_begin + r0, nb, nj, Tbuf.p, nj, nullptr, false, coef));
       }
       timing_count(ST_NTRANSFER, 1);
     }
@@ -1355,7 +1389,8 @@ static int predict_impl(ss_graph* h, int kind, int64_t row_begin, int64_t row_en
   SS_TRY(graph_check<T>(h, &gp));
   Graph<T>& g = *gp;
   const DevCsr<T>* xq = &g.Xq;
-  if (qh) SS_TRY(queries_check<T>(qh, h, &xq));
+  CoefTable<T>* qtab = nullptr;
+  if (qh) SS_TRY(queries_check<T>(qh, h, &xq, &qtab));
   const int64_t limit = (kind == SS_ROWS_QUERY) ? (qh ? xq->rows : g.nq) : g.ns;
   if (g.general && kind != SS_ROWS_QUERY)
     return fail(SS_EINVAL, "a general graph serves SS_ROWS_QUERY only");
@@ -1375,7 +1410,7 @@ static int predict_impl(ss_graph* h, int kind, int64_t row_begin, int64_t row_en
   if (ld < need_ld) return fail(SS_EINVAL, "leading dimension %lld < %lld", (long long)ld, (long long)need_ld);
   ScoreOut<T> so;
   SS_TRY(so.begin(out, ld, layout, mem, nrows, nt));
-  SS_TRY(predict_rows_device<T>(g, *xq, kind, row_begin, row_end, clean, so.dev_rm, so.ld_rm));
+  SS_TRY(predict_rows_device<T>(g, *xq, kind, row_begin, row_end, clean, so.dev_rm, so.ld_rm, qtab));
   SS_TRY(so.deliver());
   // Staging buffers are released on return and host results must be complete: wait for the stream.  With the
   // scores written straight into the caller's device buffer there is nothing to release (the transfer block

@@ -1365,6 +1365,7 @@ int graph_finalize(Graph<T>& g) {
 template <class T>
 int graph_degrees(Graph<T>& g) {
   hipStream_t st = ctx().stream;
+  g.coef_drop();
   SS_TRY(g.kf.alloc(g.nf));
   SS_TRY(g.ks.alloc(g.ns));
   SS_TRY(g.kt.alloc(g.nt));
@@ -1395,6 +1396,7 @@ template <class T>
 int graph_finalize_general(Graph<T>& g) {
   hipStream_t st = ctx().stream;
   const int64_t n = g.ns;
+  g.coef_drop();
   SS_TRY(g.kf.alloc(n));
   SS_TRY(g.inv_kf.alloc(n));
   SS_TRY(g.ks.alloc(n));
@@ -1421,6 +1423,7 @@ int graph_finalize_general(Graph<T>& g) {
 template <class T>
 int graph_finalize_general_targets(Graph<T>& g) {
   hipStream_t st = ctx().stream;
+  g.coef_drop();
   SS_TRY(g.kt.alloc(g.nt));
   SS_TRY(g.inv_kt.alloc(g.nt));
   if (g.nt > 0) {

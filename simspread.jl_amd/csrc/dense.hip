@@ -333,6 +333,7 @@ int dense_degrees(Graph<T>& g) {
   DenseSim<T>& d = g.dense;
   DevBuf<int> kx;
   SS_TRY(kx.alloc(d.ns));
+  g.coef_drop();
   SS_TRY(g.kf.alloc(d.nf));
   SS_TRY(g.inv_kf.alloc(d.nf));
   SS_TRY(d.inv_kf_m1.alloc(d.nf));

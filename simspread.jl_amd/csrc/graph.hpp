@@ -118,6 +118,17 @@ struct DenseSim {
   int64_t Bpl_Np = 0, Bpl_Kp = 0;
 };
 
+// Stage-1 coefficients of a left operand L, entry by entry: c[q] = L.val[q] * inv1[L.idx[q]] (query and source rows), or
+// the leave-one-out coefficient of entry q of Xs.  They depend only on L and the degrees of the graph L is used with, so
+// the handle that owns L keeps them from its first prediction on; `epoch` is the Graph::coef_epoch they were built at
+// (0: not built).  The single-wave kernel then reads c[q] next to L.idx[q] instead of gathering inv1[a] (transfer.hip).
+template <class T>
+struct CoefTable {
+  DevBuf<T> c;
+  uint64_t epoch = 0;
+  void drop() { c.release(); epoch = 0; }
+};
+
 template <class T>
 struct Graph {
   int64_t nq = 0, ns = 0, nf = 0, nt = 0;
@@ -136,6 +147,15 @@ struct Graph {
   DevChunked<T> XsTc, YsTc;  // stage-1 operands (YsTc only for source rows), built lazily
   DevChunked<T> XsTb;        // stage-1 operand of the query-block kernel (sub-rows padded to L2 sectors), built lazily
   DevBuf<T> Cq;              // workspace of that kernel: Xq[r,a] * inv_kf[a], entry by entry
+  // coefficient tables of the graph's own left operands: Xq * inv_kf, Xs * inv_kf, Ys * inv_kt, Xs * 1/(kf-1) (LOO).
+  // Whatever writes kf / kt or their reciprocals, or replaces Xq / Xs / Ys, calls coef_drop(): the tables go and every
+  // table a query set holds for this graph is out of date (its epoch no longer matches).
+  CoefTable<T> coef_q, coef_s, coef_y, coef_loo;
+  uint64_t coef_epoch = 1;
+  void coef_drop() {
+    coef_q.drop(); coef_s.drop(); coef_y.drop(); coef_loo.drop();
+    ++coef_epoch;
+  }
   DevBuf<T> Tws;  // workspace: rows of the transfer block T between stage 1 and stage 2
   DevBuf<T> Sws;  // workspace: sorted-order scores of a skew-sorted stage-2 operand
 };
@@ -194,11 +214,16 @@ template <class T>
 int launch_spread_dense(const T* G, int64_t rows, int64_t cols, int64_t ld, const int* deg, T* W, int64_t ldw);
 
 // stage 1: T[r][j] = inv2[j] * sum_terms sum_a L[r,a] * inv1[a] * Mt[a][j]   (rows row_begin..+nrows)
-// all Mt operands must share SC / nchunks
+// all Mt operands must share SC / nchunks.  coef: per term the coefficient table of L (transfer_coef_build) or NULL;
+// with a table for every term the default kernels read it instead of gathering inv1 (SS_TRANSFER_COEF=0: never).
 template <class T>
 int launch_transfer(int nterms, const DevCsr<T>* L[2], const T* inv1[2], const DevChunked<T>* Mt[2],
                     const T* inv2, int64_t row_begin, int64_t nrows, int64_t nj, T* out, int64_t ld,
-                    const int* row_ids = nullptr, bool accumulate = false);
+                    const int* row_ids = nullptr, bool accumulate = false, const T* const* coef = nullptr);
+// coef[q] of every entry q of L, by the expression the kernel uses when it gathers: L.val[q] * inv1[L.idx[q]], or with
+// kf_loo the leave-one-out coefficient (row != feature and kf - 1 > 0) ? L.val[q] * (1 / (kf - 1)) : 0
+template <class T>
+int transfer_coef_build(const DevCsr<T>& L, const T* inv1, const int* kf_loo, T* coef);
 // stage 1 for plain query rows, query-block workgroups: sub-row offsets in LDS, coefficients precomputed into `coef`
 // (L.nnz values of workspace).  transfer_block_fits: whether offsets + >= 8 waves of accumulators fit in LDS.
 template <class T>
@@ -216,7 +241,7 @@ int launch_fold_inverse(const int* kf, const int* ks, const int* fold, int phi, 
 // leave-one-out flavour: row i of X against X' with the rank-1 degree corrections
 template <class T>
 int launch_transfer_loo(const DevCsr<T>& X, const DevChunked<T>& XT, const int* kf, const int* ks,
-                        int64_t i_begin, int64_t nrows, T* out, int64_t ld);
+                        int64_t i_begin, int64_t nrows, T* out, int64_t ld, const T* coef = nullptr);
 
 // stage 2, wide: F[b][m] = sum_k W[m][k] * R[b][k]   (R, F "column-major": one row of length K / M per b)
 template <class T>

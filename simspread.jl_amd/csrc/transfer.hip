@@ -1,6 +1,7 @@
 // Stage 1 of the SimSpread resource-spreading pass: rows of the transfer block T = (L D1^-1) Mt D2^-1 (the sparse x
 // sparse -> dense product hidden in the reference's W*W, src/core.jl:413).  transfer_kernel is the default (one
-// single-wave workgroup per row and column chunk; also leave-one-out, k-fold, two-term and accumulating rows); the
+// single-wave workgroup per row and column chunk; also leave-one-out, k-fold, two-term and accumulating rows; COEF: the
+// coefficients of a neighbour group from a table the handle keeps, transfer_coef_rows_kernel, not gathered); the
 // block family (transfer_block / _qflat / _wide / _wide2_kernel: NW rows of L per workgroup on one chunk, opt-in with
 // SS_TRANSFER_V=2) is the measured record behind DESIGN.md 4.1.  Shared: BlockLayout, quad_fetch, quad_fold (all that
 // have them), block_prologue (block, qflat), block_row (qflat), fixed_scale (block, wide, wide2), fixed_store (block, qflat,
@@ -31,6 +32,7 @@ struct TransferArgs {
   int nterms;
   CsrView<T> L[2];
   const T* inv1[2];
+  const T* coef[2];  // COEF kernels: the coefficient of entry q of L[t], ready made (transfer_coef_build)
   ChunkedView<T> M[2];
   const T* inv2;
   const int* kf;  // LOO: integer degrees
@@ -341,9 +343,13 @@ __device__ __forceinline__ FixedScale fixed_scale(int lb, int le, int lane, floa
 }
 
 // ---------------------------------------------------------------- the single-wave kernel
-template <class T, bool LOO, int U, bool BINM, bool DUAL, bool FIX = false, bool BUF = false>
+// COEF (default family only: no DUAL / FIX / BUF): a group's coefficients come from p.coef[t][q], one coalesced load
+// issued together with L.idx[q], instead of L.val[q] and the 64-lane gather inv1[a] (LOO: kf[a]); the gather of the
+// sub-row bounds no longer waits for the coefficient: it is unconditional and a zero coefficient zeroes the length.
+template <class T, bool LOO, int U, bool BINM, bool DUAL, bool FIX = false, bool BUF = false, bool COEF = false>
 __global__ void __launch_bounds__(TRANSFER_THREADS) transfer_kernel(TransferArgs<T> p) {
   static_assert(64 % (2 * U) == 0, "U must divide 32");
+  static_assert(!COEF || (!DUAL && !FIX && !BUF), "coefficient tables serve the default family only");
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* acc = reinterpret_cast<T*>(smem_raw);                        // [SC] sums + [64] per-lane dummies (x2 when DUAL)
   const int astride = p.SC + 64;
@@ -401,7 +407,15 @@ __global__ void __launch_bounds__(TRANSFER_THREADS) transfer_kernel(TransferArgs
       const int q = g0 + lane;
       int b_l = 0, n_l = 0;
       T cf_l = T(0);
-      if (q < le) {
+      if constexpr (COEF) {
+        if (q < le) {
+          const int a = L.idx[q];
+          cf_l = p.coef[t][q];
+          const int o0 = off[a], o1 = off[a + 1];
+          b_l = o0;
+          n_l = cf_l != T(0) ? o1 - o0 : 0;
+        }
+      } else if (q < le) {
         const int a = L.idx[q];
         const T lv = L.val[q];
         if (LOO) {
@@ -1219,8 +1233,52 @@ int launch_transfer_block(const DevCsr<T>& L, const T* inv1, const DevChunked<T>
   });
 }
 
+// ---------------------------------------------------------------- coefficient tables of the single-wave kernel
+// One workgroup per row of L (the leave-one-out coefficient needs the row of an entry), entries 256 at a time: every
+// load but the degree gather is coalesced.  The expressions are transfer_kernel's own, so the bits are too.
+template <class T, bool LOO>
+__global__ void __launch_bounds__(256) transfer_coef_rows_kernel(CsrView<T> L, const T* __restrict__ inv1,
+                                                                 const int* __restrict__ kf, int64_t nrows,
+                                                                 T* __restrict__ coef) {
+  for (int64_t r = blockIdx.x; r < nrows; r += gridDim.x) {
+    const int lb = L.ptr[r], le = L.ptr[r + 1];
+    for (int q = lb + (int)threadIdx.x; q < le; q += 256) {
+      const int a = L.idx[q];
+      const T lv = L.val[q];
+      if (LOO) {
+        const int d = kf[a] - 1;
+        coef[q] = (a != (int)r && d > 0) ? lv * (T(1) / T(d)) : T(0);
+      } else {
+        coef[q] = lv * inv1[a];
+      }
+    }
+  }
+}
+
+template <class T>
+int transfer_coef_build(const DevCsr<T>& L, const T* inv1, const int* kf_loo, T* coef) {
+  if (L.rows <= 0 || L.nnz <= 0) return SS_OK;
+  const unsigned grid = (unsigned)(L.rows < 65536 ? L.rows : 65536);
+  if (kf_loo)
+    hipLaunchKernelGGL((transfer_coef_rows_kernel<T, true>), dim3(grid), dim3(256), 0, ctx().stream, view(L), inv1, kf_loo,
+                       L.rows, coef);
+  else
+    hipLaunchKernelGGL((transfer_coef_rows_kernel<T, false>), dim3(grid), dim3(256), 0, ctx().stream, view(L), inv1, kf_loo,
+                       L.rows, coef);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+// SS_TRANSFER_COEF: 0 = gather the coefficients (the kernels before the tables), unset / 1 = tables, 2 = tables and the
+// tag coef_table in the path note
+static int transfer_coef_mode() {
+  const int m = (int)env_int("SS_TRANSFER_COEF", 1);
+  return m == 0 ? 0 : (m == 2 ? 2 : 1);
+}
+
 // The single-wave kernel, by (U, BINM, DUAL); fp32 query / source rows with one accumulator copy also by FIX
-// (SS_TRANSFER_FIX1=1: a single term that does not accumulate) and BUF (SS_TRANSFER_LD=1), where U is 4 or 8.
+// (SS_TRANSFER_FIX1=1: a single term that does not accumulate) and BUF (SS_TRANSFER_LD=1), where U is 4 or 8.  The
+// default family (U 4 or 8, none of DUAL / FIX / BUF) reads coefficient tables when the caller passed one per term.
 template <class T, bool LOO>
 static int launch_transfer_variant(const TransferArgs<T>& p, unsigned grid, size_t lds, bool binm, bool dual) {
   auto launch = [&](auto kernel) {
@@ -1229,6 +1287,19 @@ static int launch_transfer_variant(const TransferArgs<T>& p, unsigned grid, size
     return (int)SS_OK;
   };
   const int u = transfer_u();
+  // the default family with a table for every term; else the gather kernels below
+  bool coef = !dual && (u == 4 || u == 8) && transfer_coef_mode() != 0 && p.row_ids == nullptr;   // (row_ids: k-fold)
+  if constexpr (std::is_same<T, float>::value && !LOO)
+    coef = coef && env_int("SS_TRANSFER_LD", 0) != 1 && env_int("SS_TRANSFER_FIX1", 0) != 1;
+  for (int t = 0; t < p.nterms; ++t) coef = coef && p.coef[t] != nullptr;
+  if (coef) {
+    if (transfer_coef_mode() == 2) path_add("coef_table");
+    return dispatch_int<4, 8>(u, [&](auto U) {
+      return dispatch_bool(binm, [&](auto B) {
+        return launch(transfer_kernel<T, LOO, decltype(U)::value, decltype(B)::value, false, false, false, true>);
+      });
+    });
+  }
   if constexpr (std::is_same<T, float>::value && !LOO) {
     const bool buf = !dual && env_int("SS_TRANSFER_LD", 0) == 1;
     const bool fix = !dual && env_int("SS_TRANSFER_FIX1", 0) == 1 && p.nterms == 1 && !p.accumulate;
@@ -1258,7 +1329,7 @@ static int launch_transfer_variant(const TransferArgs<T>& p, unsigned grid, size
 template <class T>
 int launch_transfer(int nterms, const DevCsr<T>* L[2], const T* inv1[2], const DevChunked<T>* Mt[2],
                     const T* inv2, int64_t row_begin, int64_t nrows, int64_t nj, T* out, int64_t ld,
-                    const int* row_ids, bool accumulate) {
+                    const int* row_ids, bool accumulate, const T* const* coef) {
   if (nrows <= 0 || nj <= 0) return SS_OK;
   TransferArgs<T> p{};
   p.nterms = nterms;
@@ -1266,6 +1337,7 @@ int launch_transfer(int nterms, const DevCsr<T>* L[2], const T* inv1[2], const D
     p.L[t] = view(*L[t]);
     p.M[t] = view(*Mt[t]);
     p.inv1[t] = inv1[t];
+    p.coef[t] = coef ? coef[t] : nullptr;
     if (Mt[t]->SC != Mt[0]->SC || Mt[t]->nchunks != Mt[0]->nchunks)
       return fail(SS_EINVAL, "transfer operands were cut with different chunk sizes");
   }
@@ -1292,7 +1364,7 @@ int launch_transfer(int nterms, const DevCsr<T>* L[2], const T* inv1[2], const D
 
 template <class T>
 int launch_transfer_loo(const DevCsr<T>& X, const DevChunked<T>& XT, const int* kf, const int* ks,
-                        int64_t i_begin, int64_t nrows, T* out, int64_t ld) {
+                        int64_t i_begin, int64_t nrows, T* out, int64_t ld, const T* coef) {
   if (nrows <= 0) return SS_OK;
   TransferArgs<T> p{};
   p.nterms = 1;
@@ -1300,6 +1372,7 @@ int launch_transfer_loo(const DevCsr<T>& X, const DevChunked<T>& XT, const int* 
   p.M[0] = view(XT);
   p.kf = kf;
   p.ks = ks;
+  p.coef[0] = coef;
   p.row_begin = i_begin;
   p.nj = X.rows;
   p.SC = XT.SC;
@@ -1317,12 +1390,13 @@ int launch_transfer_loo(const DevCsr<T>& X, const DevChunked<T>& XT, const int* 
 
 #define SS_INSTANTIATE(T)                                                                                   \
   template int launch_transfer<T>(int, const DevCsr<T>*[2], const T*[2], const DevChunked<T>*[2], const T*, \
-                                  int64_t, int64_t, int64_t, T*, int64_t, const int*, bool);                      \
+                                  int64_t, int64_t, int64_t, T*, int64_t, const int*, bool, const T* const*);     \
+  template int transfer_coef_build<T>(const DevCsr<T>&, const T*, const int*, T*);                          \
   template int launch_transfer_block<T>(const DevCsr<T>&, const T*, const DevChunked<T>&, const T*, int64_t, int64_t, \
                                         int64_t, T*, int64_t, T*, float, bool);                               \
   template bool transfer_block_fits<T>(int64_t, int);                                                        \
   template int launch_transfer_loo<T>(const DevCsr<T>&, const DevChunked<T>&, const int*, const int*,       \
-                                      int64_t, int64_t, T*, int64_t);
+                                      int64_t, int64_t, T*, int64_t, const T*);
 SS_INSTANTIATE(float)
 SS_INSTANTIATE(double)
 
