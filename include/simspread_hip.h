@@ -708,5 +708,6 @@ int ss_spmat_cost(const ss_spmat* w, int64_t B, double* bytes, double* flops);
 #include "simspread_hip_neighbours_real.h"
 #include "simspread_hip_clusters.h"
 #include "simspread_hip_target_rank.h"
+#include "simspread_hip_half.h"
 
 #endif /* SIMSPREAD_HIP_H */

@@ -15,7 +15,8 @@ from .engine import (BINARY_ROWS_FIELDS, POOLED_FIELDS, RANK_ROWS_FIELDS, TARGET
                      TargetRank, TargetTopL, ButinaClusters, binary_metrics_rows, butina_clusters, cluster_folds, cross_fold_edges,
                      cutoff_csr,
                      dot_csr, dot_kth, jaccard_csr, jaccard_kth,
-                     jaccard_similarity, pack_fingerprints, rank_metrics, rank_metrics_rows, tanimoto_csr, tanimoto_kth, topl)
+                     jaccard_similarity, pack_fingerprints, rank_metrics, rank_metrics_rows, tanimoto_csr, tanimoto_kth,
+                     to_bf16_bits, topl)
 from .metrics import (AuPRC, AuROC, BEDROC, ROCNums, accuracy, balancedaccuracy, f1score, maxperformance, mcc,
                       meanperformance, meanstdperformance, precision, recall, roc, validity_ratio)
 
@@ -24,4 +25,4 @@ __all__ = ["NamedMatrix", "Network", "DeviceGraph", "DeviceQueries", "DeviceSpMa
            "read_namedmatrix", "writedlm", "rank_metrics", "rank_metrics_rows", "RANK_ROWS_FIELDS", "binary_metrics_rows", "BINARY_ROWS_FIELDS", "jaccard_similarity", "jaccard_csr", "dot_csr", "cutoff_csr", "pack_fingerprints", "tanimoto_csr", "tanimoto_kth", "jaccard_kth", "dot_kth", "AuROC", "AuPRC", "BEDROC", "validity_ratio", "roc", "ROCNums",
            "f1score", "mcc", "accuracy", "balancedaccuracy", "recall", "precision", "maxperformance", "meanperformance",
            "meanstdperformance", "ButinaClusters", "butina_clusters", "cluster_folds", "cross_fold_edges", "split_clusters", "TargetRank", "TARGET_RANK_FIELDS",
-           "target_rank", "target_rank_positives"]
+           "target_rank", "target_rank_positives", "to_bf16_bits"]

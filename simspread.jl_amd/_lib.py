@@ -18,11 +18,13 @@ NEIGHBOURS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspr
 REAL_NEIGHBOURS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_neighbours_real.h")  # too
 CLUSTERS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_clusters.h")                # too
 TARGET_RANK_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_target_rank.h")          # too
+HALF_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_half.h")                        # too
 
 SS_OK = 0
 SS_MEM_HOST, SS_MEM_DEVICE = 0, 1
 SS_ROWS_QUERY, SS_ROWS_SOURCE, SS_ROWS_LOO = 0, 1, 2
 SS_LAYOUT_ROWMAJOR, SS_LAYOUT_COLMAJOR = 0, 1
+SS_H16_BF16, SS_H16_F16 = 0, 1
 
 _ERR_NAMES = {-1: "SS_EINVAL", -2: "SS_ENOMEM", -3: "SS_EHIP", -4: "SS_ENODEV", -5: "SS_EUNSUPPORTED", -6: "SS_EINTERNAL"}
 
@@ -238,6 +240,22 @@ def _target_rank_sigs():
 TARGET_RANK_SIGNATURES = _target_rank_sigs()
 
 
+def _half_sigs():
+    """include/simspread_hip_half.h: the inner-product producer on 16-bit (bf16 / fp16) row-major rows"""
+    f32 = C.c_float
+    return {
+        "ss_similarity_dot_csr_h16": ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _int, f32, _int, _vp, _vp, _vp, _i64,
+                                       _vp, _int], _int),
+        "ss_graph_create_vectors_h16": ([_i64] * 4 + [_int, _int, _vp, _i64, _vp, _i64] + [_vp] * 3
+                                        + [_int, f32, _int, _int, _vp], _int),
+        "ss_queries_create_vectors_h16": ([_vp, _i64, _i64, _i64, _int, _int, _vp, _i64, _vp, _i64, f32, _int, _int, _vp],
+                                          _int),
+    }
+
+
+HALF_SIGNATURES = _half_sigs()
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function the C header declares (used by the symbol-export test)."""
     with open(path) as f:
@@ -271,6 +289,11 @@ def target_rank_header_symbols():
     return header_symbols(TARGET_RANK_HEADER_PATH)
 
 
+def half_header_symbols():
+    """Every function include/simspread_hip_half.h declares."""
+    return header_symbols(HALF_HEADER_PATH)
+
+
 def load():
     """dlopen the library (no GPU needed for this step)."""
     global _lib
@@ -283,7 +306,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (args, res) in (list(SIGNATURES.items()) + list(SCREENING_SIGNATURES.items())
                               + list(NEIGHBOUR_SIGNATURES.items()) + list(REAL_NEIGHBOUR_SIGNATURES.items())
-                              + list(CLUSTER_SIGNATURES.items()) + list(TARGET_RANK_SIGNATURES.items())):
+                              + list(CLUSTER_SIGNATURES.items()) + list(TARGET_RANK_SIGNATURES.items())
+                              + list(HALF_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res

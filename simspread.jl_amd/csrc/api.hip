@@ -791,6 +791,89 @@ static int graph_create_vectors_impl(int64_t nq, int64_t ns, int64_t nt, int64_t
       ldq, Fs, lds_, y_ptr, y_idx, y_val, index_base, alpha, mem, out, k);
 }
 
+// ------------------- 16-bit rows (include/simspread_hip_half.h): ROW-MAJOR bf16 / fp16 patterns -> DotCsrH16, fp32 CSR
+static const char* h16_tag(bool sym) { return sym ? "dot_h16_sym" : "dot_h16_cross"; }
+// what the 16-bit entry points refuse before anything is staged or written
+static int check_h16_args(int storage, int metric, int64_t d, float alpha) {
+  if (storage != SS_H16_BF16 && storage != SS_H16_F16)
+    return fail(SS_EINVAL, "dot_h16: storage %d is not SS_H16_BF16 or SS_H16_F16", storage);
+  if (metric != SS_SIM_COSINE && metric != SS_SIM_TANIMOTO && metric != SS_SIM_DICE)
+    return fail(SS_EINVAL, "dot_h16: metric %d is not SS_SIM_COSINE, SS_SIM_TANIMOTO or SS_SIM_DICE", metric);
+  if (d < 0) return fail(SS_EINVAL, "dot_h16: negative feature count");
+  if (alpha != alpha) return fail(SS_EINVAL, "dot_h16: alpha is NaN");
+  return SS_OK;
+}
+static int check_rows_h16(const char* what, const uint16_t* F, int64_t n, int64_t ld, int64_t d) {
+  if (n < 0) return fail(SS_EINVAL, "%s: negative row count", what);
+  if (n >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "%s: %lld rows (>= 2^31)", what, (long long)n);
+  if (ld < d) return fail(SS_EINVAL, "%s: leading dimension %lld < %lld features (16-bit rows are row-major)", what,
+                          (long long)ld, (long long)d);
+  if (n > 0 && d > 0 && !F) return fail(SS_EINVAL, "%s is NULL", what);
+  return SS_OK;
+}
+// rows on the device: the caller's buffer (SS_MEM_DEVICE) or a staged copy with ld = d; of a host row only its d
+// elements are read
+static int stage_rows_h16(const uint16_t* F, int64_t n, int64_t ld, int64_t d, int mem, DevBuf<uint16_t>& buf,
+                          const uint16_t** dev, int64_t* dev_ld) {
+  if (mem == SS_MEM_DEVICE || n == 0 || d == 0) {
+    *dev = F;
+    *dev_ld = ld;
+    return SS_OK;
+  }
+  SS_TRY(buf.alloc((size_t)n * (size_t)d));
+  SS_HIP(hipMemcpy2DAsync(buf.p, d * sizeof(uint16_t), F, ld * sizeof(uint16_t), d * sizeof(uint16_t), n,
+                          hipMemcpyHostToDevice, ctx().stream));
+  *dev = buf.p;
+  *dev_ld = d;
+  return SS_OK;
+}
+
+static int dot_csr_h16_impl(const uint16_t* Fa, int64_t na, int64_t lda, const uint16_t* Fb, int64_t nb, int64_t ldb,
+                            int64_t d, int storage, int metric, float alpha, int weighted, int64_t* ptr, int32_t* idx,
+                            float* val, int64_t capacity, int64_t* nnz, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  path_note().clear();
+  const bool sym = (Fb == nullptr);
+  if (sym) {
+    nb = na;
+    ldb = lda;
+  }
+  SS_TRY(check_h16_args(storage, metric, d, alpha));
+  SS_TRY(check_rows_h16("Fa", Fa, na, lda, d));
+  if (!sym) SS_TRY(check_rows_h16("Fb", Fb, nb, ldb, d));
+  if (!ptr || !nnz) return fail(SS_EINVAL, "dot_h16: ptr and nnz must not be NULL");
+  DevBuf<uint16_t> ba, bb;
+  const uint16_t *da = nullptr, *db = nullptr;
+  int64_t la = 0, lb = 0;
+  SS_TRY(stage_rows_h16(Fa, na, lda, d, mem, ba, &da, &la));
+  if (!sym) SS_TRY(stage_rows_h16(Fb, nb, ldb, d, mem, bb, &db, &lb));
+  DotCsrH16 p;
+  SS_TRY(p.count(da, na, la, sym ? nullptr : db, nb, lb, d, storage, metric, alpha, weighted != 0));
+  path_add(h16_tag(sym));
+  return emit_pair_csr<float>(p, na, ptr, idx, val, capacity, nnz, mem);
+}
+
+static int graph_create_vectors_h16_impl(int64_t nq, int64_t ns, int64_t nt, int64_t d, int storage, int metric,
+                                         const uint16_t* Fq, int64_t ldq, const uint16_t* Fs, int64_t lds_,
+                                         const int64_t* y_ptr, const int32_t* y_idx, const float* y_val, int index_base,
+                                         float alpha, int weighted, int mem, ss_graph** out) {
+  SS_TRY(graph_create_begin(mem, nt, out));
+  SS_TRY(check_h16_args(storage, metric, d, alpha));
+  SS_TRY(check_rows_h16("Fq", Fq, nq, ldq, d));
+  SS_TRY(check_rows_h16("Fs", Fs, ns, lds_, d));
+  DevBuf<uint16_t> bq, bs;
+  const uint16_t *dq = nullptr, *ds = nullptr;
+  int64_t lq = 0, ls = 0;
+  SS_TRY(stage_rows_h16(Fs, ns, lds_, d, mem, bs, &ds, &ls));
+  SS_TRY(stage_rows_h16(Fq, nq, ldq, d, mem, bq, &dq, &lq));
+  const bool wgt = weighted != 0;
+  return graph_from_producers<float, DotCsrH16>(
+      nq, ns, nt, [&](DotCsrH16& p) { return p.count(ds, ns, ls, nullptr, ns, ls, d, storage, metric, alpha, wgt); },
+      [&](DotCsrH16& p) { return p.count(dq, nq, lq, ds, ns, ls, d, storage, metric, alpha, wgt); }, h16_tag(true),
+      h16_tag(false), y_ptr, y_idx, y_val, index_base, mem, out);
+}
+
 // ------------------------------------------------------------------ Butina clusters, cluster folds, cross-fold edges
 // (include/simspread_hip_clusters.h; the device path is cluster.hip)
 struct ClusterOut {
@@ -5077,6 +5160,45 @@ int ss_cluster_cross_edges(int64_t n, const int64_t* ptr, const int32_t* idx, in
                            const int32_t* fold_of_source, int nfolds, int64_t* count, int mem) {
   SS_API_LOCK();
   return cluster_cross_edges_impl(n, ptr, idx, index_base, fold_of_source, nfolds, count, mem);
+}
+
+// ---- include/simspread_hip_half.h: the inner-product producer on 16-bit rows
+int ss_similarity_dot_csr_h16(const uint16_t* Fa, int64_t na, int64_t lda, const uint16_t* Fb, int64_t nb, int64_t ldb,
+                              int64_t d, int storage, int metric, float alpha, int weighted, int64_t* ptr, int32_t* idx,
+                              float* val, int64_t capacity, int64_t* nnz, int mem) {
+  SS_API_LOCK();
+  return dot_csr_h16_impl(Fa, na, lda, Fb, nb, ldb, d, storage, metric, alpha, weighted, ptr, idx, val, capacity, nnz,
+                          mem);
+}
+int ss_graph_create_vectors_h16(int64_t nq, int64_t ns, int64_t nt, int64_t d, int storage, int metric,
+                                const uint16_t* Fq, int64_t ldq, const uint16_t* Fs, int64_t lds, const int64_t* y_ptr,
+                                const int32_t* y_idx, const float* y_val, int index_base, float alpha, int weighted,
+                                int mem, ss_graph** out) {
+  SS_API_LOCK();
+  return graph_create_vectors_h16_impl(nq, ns, nt, d, storage, metric, Fq, ldq, Fs, lds, y_ptr, y_idx, y_val, index_base,
+                                       alpha, weighted, mem, out);
+}
+int ss_queries_create_vectors_h16(const ss_graph* g, int64_t nq, int64_t ns, int64_t d, int storage, int metric,
+                                  const uint16_t* Fq, int64_t ldq, const uint16_t* Fs, int64_t lds, float alpha,
+                                  int weighted, int mem, ss_queries** out) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  Graph<float>* gp = nullptr;
+  SS_TRY(queries_begin<float>(g, nq, mem, out, &gp));
+  SS_TRY(queries_check_sources(*gp, ns));
+  SS_TRY(check_h16_args(storage, metric, d, alpha));
+  SS_TRY(check_rows_h16("Fq", Fq, nq, ldq, d));
+  SS_TRY(check_rows_h16("Fs", Fs, ns, lds, d));
+  DevBuf<uint16_t> bq, bs;
+  const uint16_t *dq = nullptr, *ds = nullptr;
+  int64_t lq = 0, ls = 0;
+  SS_TRY(stage_rows_h16(Fs, ns, lds, d, mem, bs, &ds, &ls));
+  SS_TRY(stage_rows_h16(Fq, nq, ldq, d, mem, bq, &dq, &lq));
+  return queries_from_producer<float, DotCsrH16>(
+      g, nq, ns,
+      [&](DotCsrH16& p) { return p.count(dq, nq, lq, ds, ns, ls, d, storage, metric, alpha, weighted != 0); },
+      h16_tag(false), out);
 }
 
 }  // extern "C"

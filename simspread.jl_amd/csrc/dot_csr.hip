@@ -36,10 +36,16 @@
 // row, and the tile kernel keeps (i, j) iff v != 0 and (s >= alpha or (s > 0 and s >= tau[i])).  That rule is not
 // symmetric, so the floor case runs the full (ntj, nti) grid with Fb = Fa instead of the triangle; its diagonal is
 // still exactly 1, and every other pair is what the cross producer computes for (i, j).
+//
+// 16-bit rows (DotCsrH16, include/simspread_hip_half.h): the same kernel with the operand type as a template parameter.
+// The rows are raw bf16 / fp16 patterns, ROW-MAJOR; the Gram block is dot_tile_gram_h16 (dot_tile_h16.hpp) on
+// v_mfma_f32_32x32x16_{bf16,f16}, whose products are exact in fp32 and whose results lie in the accumulator registers
+// exactly as the fp32 instruction's do, so everything from the norms on is the text below with T = float.
 #include <algorithm>
 #include <hip/hip_runtime.h>
 
 #include "dot_tile.hpp"
+#include "dot_tile_h16.hpp"
 #include "graph.hpp"
 #include "pair_tile.hpp"
 
@@ -69,14 +75,28 @@ __device__ __forceinline__ int bits_before(const uint32_t (*m)[4], int r, int c)
 // FILL == false: write the per-(tile, row) counts and the tile flag.  FILL == true: write the entries of the tiles that
 // kept something (counts then hold in-row offsets).
 // FLOOR: the per-row cut tau[na] next to alpha; a pair is then decided by its row alone, so there is no mirror (!SYM);
-// self: Fb is Fa, so the pairs (i, i) have s = 1 as in the symmetric mode.
-template <class T, bool SYM, bool FILL, bool FLOOR>
+// flags & TILE_SELF: Fb is Fa, so the pairs (i, i) have s = 1 as in the symmetric mode.
+// Op: the operands.  Op == T: column-major rows of T, dot_tile_gram.  dottile::Bf16 / dottile::F16 (T == float): row-major
+// 16-bit patterns, dot_tile_gram_h16, with flags & TILE_FAST_A / TILE_FAST_B allowing a side its 16-byte loads.  The
+// accumulators come out in the same registers either way, so everything after the Gram block is one text.
+enum { TILE_SELF = 1, TILE_FAST_A = 2, TILE_FAST_B = 4 };
+template <class Op>
+struct OperandElem { using type = typename Op::elem; };
+template <>
+struct OperandElem<float> { using type = float; };
+template <>
+struct OperandElem<double> { using type = double; };
+
+template <class T, bool SYM, bool FILL, bool FLOOR, class Op = T>
 __global__ void __launch_bounds__(NT) dot_tile_kernel(
-    const T* __restrict__ Fa, int64_t na, int64_t lda, const T* __restrict__ Fb, int64_t nb, int64_t ldb, int64_t d,
-    const T* __restrict__ norm_a, const T* __restrict__ norm_b, int metric, T alpha, const T* __restrict__ tau, int self,
+    const typename OperandElem<Op>::type* __restrict__ Fa, int64_t na, int64_t lda,
+    const typename OperandElem<Op>::type* __restrict__ Fb, int64_t nb, int64_t ldb, int64_t d,
+    const T* __restrict__ norm_a, const T* __restrict__ norm_b, int metric, T alpha, const T* __restrict__ tau, int flags,
     int weighted, int64_t nti, int* __restrict__ counts, int* __restrict__ tile_nz, const int64_t* __restrict__ ptr,
     int* __restrict__ oidx, T* __restrict__ oval, int* __restrict__ not_binary) {
   static_assert(!(SYM && FLOOR), "a per-row cut decides (i, j) and (j, i) separately");
+  static_assert(std::is_same<Op, T>::value || (std::is_same<T, float>::value && !FLOOR),
+                "16-bit operands: fp32 graphs, no per-row cut");
   using M = Mma<T>;
   constexpr int MT = M::MT, NR = M::NR;
   constexpr int NM = dottile::NM<T>;   // MFMA tiles per wave edge
@@ -92,10 +112,14 @@ __global__ void __launch_bounds__(NT) dot_tile_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const bool mirror = t.mirror;
-  const bool diag1 = SYM || (FLOOR && self != 0);  // the block is a set against itself: s(i, i) = 1
+  const bool diag1 = SYM || (FLOOR && (flags & TILE_SELF) != 0);  // the block is a set against itself: s(i, i) = 1
 
   typename M::acc_t acc[NM][NM];
-  dottile::dot_tile_gram<T>(Fa, na, lda, Fb, nb, ldb, d, i0, j0, acc);
+  if constexpr (std::is_same<Op, T>::value)
+    dottile::dot_tile_gram<T>(Fa, na, lda, Fb, nb, ldb, d, i0, j0, acc);
+  else
+    dottile::dot_tile_gram_h16<Op>(Fa, na, lda, Fb, nb, ldb, d, i0, j0, (flags & TILE_FAST_A) != 0,
+                                   (flags & TILE_FAST_B) != 0, acc);
 
   if (tid < TILE) {
     dottile::stage_norm<T>(na_s, tid, norm_a, i0, na, metric);
@@ -232,8 +256,93 @@ int DotCsr<T>::launch(bool fill, int* idx, T* val, int* flag) {
                  : sym ? (fill ? dot_tile_kernel<T, true, true, false> : dot_tile_kernel<T, true, false, false>)
                        : (fill ? dot_tile_kernel<T, false, true, false> : dot_tile_kernel<T, false, false, false>);
   hipLaunchKernelGGL(kernel, this->tile_grid(), dim3(NT), 0, ctx().stream, Fa, na, lda, Fb, nb, ldb, d, norm_a.p,
-                     self ? norm_a.p : norm_b.p, metric, alpha, tau, self ? 1 : 0, weighted ? 1 : 0, nti, counts.p,
-                     tile_nz.p, ptr.p, idx, val, flag);
+                     self ? norm_a.p : norm_b.p, metric, alpha, tau, self ? (int)TILE_SELF : 0, weighted ? 1 : 0, nti,
+                     counts.p, tile_nz.p, ptr.p, idx, val, flag);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+// ---- 16-bit rows (include/simspread_hip_half.h)
+namespace {
+// a side may use 16-byte loads: every chunk address base + 2 (i ld + k), k % 8 == 0, is then 16-byte aligned
+bool h16_fast(const uint16_t* F, int64_t ld) { return (reinterpret_cast<uintptr_t>(F) & 15) == 0 && ld % 8 == 0; }
+
+template <class Op>
+int h16_norms(const uint16_t* F, int64_t n, int64_t ld, int64_t d, float* norm) {
+  hipLaunchKernelGGL(dottile::row_norm_h16_kernel<Op>, dim3((unsigned)ceil_div(n * 16, 256)), dim3(256), 0, ctx().stream,
+                     F, n, ld, d, norm);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+template <class Op>
+int h16_nan_scan(const uint16_t* F, int64_t n, int64_t ld, int64_t d, int* flag) {
+  if (n == 0 || d == 0) return SS_OK;
+  const int64_t blocks = std::min<int64_t>(ceil_div(n * 16, 256), 4096);  // 16 lanes per row
+  hipLaunchKernelGGL(dottile::nan_scan_h16_kernel<Op>, dim3((unsigned)blocks), dim3(256), 0, ctx().stream, F, n, ld, d,
+                     flag);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+// SS_EINVAL when an element k < d of Fa or (not NULL) Fb is a NaN pattern (synchronises)
+template <class Op>
+int h16_refuse_nan(const uint16_t* Fa, int64_t na, int64_t lda, const uint16_t* Fb, int64_t nb, int64_t ldb, int64_t d) {
+  hipStream_t st = ctx().stream;
+  DevBuf<int> flag;
+  SS_TRY(flag.alloc(1));
+  SS_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
+  SS_TRY(h16_nan_scan<Op>(Fa, na, lda, d, flag.p));
+  if (Fb) SS_TRY(h16_nan_scan<Op>(Fb, nb, ldb, d, flag.p));
+  int bad = 0;
+  SS_HIP(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  if (bad) return fail(SS_EINVAL, "dot_h16: the features hold a NaN");
+  return SS_OK;
+}
+template <class Op>
+void h16_launch(const DotCsrH16& p, dim3 grid, bool fill, int* idx, float* val, int* flag) {
+  auto* kernel = p.sym ? (fill ? dot_tile_kernel<float, true, true, false, Op> : dot_tile_kernel<float, true, false, false, Op>)
+                       : (fill ? dot_tile_kernel<float, false, true, false, Op>
+                               : dot_tile_kernel<float, false, false, false, Op>);
+  const int flags = (p.sym ? (int)TILE_SELF : 0) | (h16_fast(p.Fa, p.lda) ? (int)TILE_FAST_A : 0) |
+                    (h16_fast(p.Fb, p.ldb) ? (int)TILE_FAST_B : 0);
+  hipLaunchKernelGGL(kernel, grid, dim3(NT), 0, ctx().stream, p.Fa, p.na, p.lda, p.Fb, p.nb, p.ldb, p.d, p.norm_a.p,
+                     p.sym ? p.norm_a.p : p.norm_b.p, p.metric, p.alpha, (const float*)nullptr, flags, p.weighted ? 1 : 0,
+                     p.nti, p.counts.p, p.tile_nz.p, p.ptr.p, idx, val, flag);
+}
+}  // namespace
+
+int DotCsrH16::count(const uint16_t* Fa_, int64_t na_, int64_t lda_, const uint16_t* Fb_, int64_t nb_, int64_t ldb_,
+                     int64_t d_, int storage_, int metric_, float alpha_, bool weighted_) {
+  what = "dot_h16";
+  sym = (Fb_ == nullptr);
+  Fa = Fa_;
+  Fb = sym ? Fa_ : Fb_;
+  lda = lda_;
+  ldb = sym ? lda_ : ldb_;
+  d = d_;
+  storage = storage_;
+  metric = metric_;
+  alpha = alpha_;
+  weighted = weighted_;
+  // storage, metric and alpha are the caller's to check (check_h16_args of api.hip, before anything is staged)
+  const bool bf = storage == SS_H16_BF16;
+  const uint16_t* scan_b = sym ? nullptr : Fb;
+  SS_TRY(bf ? h16_refuse_nan<dottile::Bf16>(Fa, na_, lda, scan_b, nb_, ldb, d)
+            : h16_refuse_nan<dottile::F16>(Fa, na_, lda, scan_b, nb_, ldb, d));
+  SS_TRY(this->begin_tiles(na_, sym ? na_ : nb_, TILE, true));
+  if (na == 0 || nb == 0) return SS_OK;
+  SS_TRY(norm_a.alloc((size_t)na));
+  SS_TRY(bf ? h16_norms<dottile::Bf16>(Fa, na, lda, d, norm_a.p) : h16_norms<dottile::F16>(Fa, na, lda, d, norm_a.p));
+  if (!sym) {
+    SS_TRY(norm_b.alloc((size_t)nb));
+    SS_TRY(bf ? h16_norms<dottile::Bf16>(Fb, nb, ldb, d, norm_b.p) : h16_norms<dottile::F16>(Fb, nb, ldb, d, norm_b.p));
+  }
+  return this->count_pass();
+}
+
+int DotCsrH16::launch(bool fill, int* idx, float* val, int* flag) {
+  if (storage == SS_H16_BF16) h16_launch<dottile::Bf16>(*this, this->tile_grid(), fill, idx, val, flag);
+  else h16_launch<dottile::F16>(*this, this->tile_grid(), fill, idx, val, flag);
   SS_LAUNCH_CHECK();
   return SS_OK;
 }

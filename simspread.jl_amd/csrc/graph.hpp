@@ -600,6 +600,24 @@ struct DotCsr : PairCsr<T> {
 template <class T>
 int dot_row_norms(const T* F, int64_t n, int64_t ld, int64_t d, T* norm);
 
+// ---- dot_csr.hip, 16-bit operands (include/simspread_hip_half.h): DotCsr<float> on rows stored as raw bf16 / fp16 bit
+// patterns (storage: SS_H16_BF16 / SS_H16_F16), ROW-MAJOR -- element (i, k) at F[i * ld + k], ld >= d -- on the 16-bit
+// matrix instructions with fp32 accumulation; the same tile kernel and epilogue.  Device pointers; Fb == nullptr: Fb = Fa
+// (symmetric).  count() refuses a NaN pattern, an unknown storage or metric and a NaN alpha before anything is written.
+// No neighbour floor: its selection pass (dot_kth) would have to run the same 16-bit Gram tile.
+struct DotCsrH16 : PairCsr<float> {
+  const uint16_t* Fa = nullptr;
+  const uint16_t* Fb = nullptr;
+  int64_t lda = 0, ldb = 0, d = 0;
+  int storage = 0, metric = 0;
+  DevBuf<float> norm_a, norm_b;  // squared row norms of each side (norm_b unused when Fb == Fa)
+  int count(const uint16_t* Fa, int64_t na, int64_t lda, const uint16_t* Fb, int64_t nb, int64_t ldb, int64_t d,
+            int storage, int metric, float alpha, bool weighted);
+
+ protected:
+  int launch(bool fill, int* idx, float* val, int* flag) override;
+};
+
 // ---- real_floor.hip: the neighbour floor of the two producers above.  tau[i] = the k-th largest of the positive
 // similarities s(i, j) of row i of Fa against the rows of Fb (multiplicity counted), +0 when there are fewer than k;
 // 1 <= k <= NEIGHBOUR_K_MAX; s is bit for bit the producer's (jaccard_tile.hpp, dot_tile.hpp).  Device pointers, layout

@@ -306,13 +306,38 @@ class DeviceGraph:
 
     @classmethod
     def from_vectors(cls, Fq, Fs, Y, alpha: float, metric="cosine", weighted: bool = True, dtype=np.float32,
-                     index_base: int = 0, min_neighbours: int = 0):
+                     index_base: int = 0, min_neighbours: int = 0, storage=None):
         """``construct(y, X)`` with ``X = featurize(S(F), alpha, weighted)``, S the inner-product similarity ``metric``
         ("cosine", "tanimoto", "dice") of ``dot_csr`` between real-valued rows (embeddings, continuous descriptors): Xq =
         cut(S(Fq, Fs)), Xs = cut(S(Fs, Fs)), features named after the sources, produced as CSR on the device (the dense
         similarity never exists).  Fq may be None (3-layer graph: predict_loo / predict_kfold / evaluate_loo).  Inputs
         as ``from_features``, min_neighbours included: the k nearest are the k largest positive similarities, so negative
-        ones (signed embeddings) never count among them."""
+        ones (signed embeddings) never count among them.
+
+        storage "bf16" / "f16": the 16-bit route of ``dot_csr`` (inputs as there: torch.bfloat16 / torch.float16 CUDA
+        tensors read in place, numpy float16, raw uint16 patterns, or real arrays rounded on the host).  The graph is an
+        ordinary float32 graph afterwards.  Here 16-bit CUDA tensors must name their storage: without it they are
+        refused as tensors of the wrong dtype, as before; numpy float16 arrays select "f16" as in ``dot_csr``."""
+        code = _h16_storage(storage, (Fs, Fq), dtype, min_neighbours, auto_tensor=False)
+        if code is not None:
+            m = _sim_metric(metric)
+            dev = _is_torch(Fs)
+            keep = []
+            fq, nq, dq, ldq = _features_h16(Fq, code, dev, keep)
+            fs, ns, d, lds = _features_h16(Fs, code, dev, keep)
+            if Fq is None:
+                ldq = max(d, 1)
+            elif dq != d:
+                raise ValueError("Fq and Fs have different numbers of features")
+            yptr, yidx, yval, nt, mem = _source_labels(Y, ns, np.float32, dev, keep, index_base)
+            lib = L.lib()
+            h = C.c_void_p()
+            L.check(lib.ss_graph_create_vectors_h16(nq, ns, nt, d, code, m, fq, ldq, fs, lds, yptr, yidx, yval, index_base,
+                                                    C.c_float(alpha), 1 if weighted else 0, mem, C.byref(h)))
+            if dev:
+                L.check(lib.ss_synchronize())
+            del keep
+            return cls(h, np.float32)
         dt = _feature_dtype(dtype)
         m = _sim_metric(metric)
         dev = _is_torch(Fs)
@@ -739,9 +764,31 @@ class DeviceQueries:
 
     @classmethod
     def from_vectors(cls, graph: DeviceGraph, Fq, Fs, alpha: float, metric="cosine", weighted: bool = True,
-                     min_neighbours: int = 0):
+                     min_neighbours: int = 0, storage=None):
         """Xq = cut(S(Fq, Fs)), the inner-product block of ``DeviceGraph.from_vectors``; inputs as there.
-        min_neighbours = k > 0: every query also keeps its k nearest sources, as ``from_fingerprints``."""
+        min_neighbours = k > 0: every query also keeps its k nearest sources, as ``from_fingerprints``.
+        storage "bf16" / "f16" (or 16-bit CUDA tensors, by their dtype; numpy float16 as in ``dot_csr``): the 16-bit route of ``dot_csr``,
+        on a float32 graph built by any constructor."""
+        code = _h16_storage(storage, (Fs, Fq), graph.dtype, min_neighbours)
+        if code is not None:
+            m = _sim_metric(metric)
+            dev = _is_torch(Fs)
+            keep = []
+            fq, nq, dq, ldq = _features_h16(Fq, code, dev, keep)
+            fs, ns, d, lds = _features_h16(Fs, code, dev, keep)
+            if Fq is None:
+                ldq = max(d, 1)
+            elif dq != d:
+                raise ValueError("Fq and Fs have different numbers of features")
+            lib = L.lib()
+            h = C.c_void_p()
+            L.check(lib.ss_queries_create_vectors_h16(graph._h, nq, ns, d, code, m, fq, ldq, fs, lds, C.c_float(alpha),
+                                                      1 if weighted else 0, L.SS_MEM_DEVICE if dev else L.SS_MEM_HOST,
+                                                      C.byref(h)))
+            if dev:
+                L.check(lib.ss_synchronize())
+            del keep
+            return cls(h, graph)
         return cls._from_rows("vectors", graph, Fq, Fs, (_sim_metric(metric),), alpha, weighted, min_neighbours)
 
     def degrees(self) -> np.ndarray:
@@ -1801,6 +1848,137 @@ def _sim_metric(metric):
     return SIM_METRICS[metric]
 
 
+H16_STORAGES = {"bf16": L.SS_H16_BF16, "f16": L.SS_H16_F16}     # SS_H16_* of include/simspread_hip_half.h
+
+
+def to_bf16_bits(x) -> np.ndarray:
+    """The bfloat16 bit patterns (uint16, same shape) of real numbers, rounded to nearest, ties to even; a NaN stays a
+    NaN (quiet bit set), what lies above the largest bfloat16 becomes inf, +-0 and subnormals are kept.  fp32 input gives what
+    ``torch.Tensor.to(torch.bfloat16)`` gives; fp64 input is rounded once, not through fp32."""
+    a = np.asarray(x)
+    if a.dtype.kind not in "fiu":
+        raise TypeError(f"to_bf16_bits needs real numbers, got {a.dtype}")
+    if a.dtype == np.float64:
+        # fp64 -> fp32 rounded to odd (truncate, the last bit set when inexact), so that the second rounding is the only one
+        with np.errstate(over="ignore", invalid="ignore"):
+            f = a.astype(np.float32)
+        u = f.view(np.uint32).astype(np.uint64)
+        fin = np.isfinite(f) & np.isfinite(a)
+        back = f.astype(np.float64)
+        inexact = fin & (back != a)
+        away = inexact & (np.abs(back) > np.abs(a))          # fp32 rounded away from zero: step back to the truncation
+        u = np.where(away, u - 1, u)
+        u = np.where(inexact, u | 1, u)
+    else:
+        u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    nan = (u & 0x7FFFFFFF) > 0x7F800000
+    r = (u + 0x7FFF + ((u >> 16) & 1)) >> 16
+    return np.where(nan, (u >> 16) | 0x0040, r).astype(np.uint16).reshape(a.shape)     # quiet, sign and payload kept
+
+
+def _module_is_torch(x) -> bool:
+    return type(x).__module__.startswith("torch")
+
+
+def _h16_storage(storage, inputs, dtype, min_neighbours=0, auto_tensor=True):
+    """The storage code (SS_H16_*) of the 16-bit route, or None for the fp32 / fp64 route.  Needs no device.  storage
+    None: chosen by the inputs.  A 16-bit torch tensor (auto_tensor) selects its dtype's storage.  numpy float16 arrays
+    select "f16" only where that changes no call that worked without it: every given input is float16, the graph
+    precision is float32 and there is no neighbour floor; otherwise they are widened exactly, as they always were."""
+    if storage is not None and storage not in H16_STORAGES:
+        raise ValueError(f"storage must be None or one of {sorted(H16_STORAGES)}, got {storage!r}")
+    given = [F for F in inputs if F is not None]
+    if storage is None:
+        half = {"torch.bfloat16": "bf16", "torch.float16": "f16"}
+        tensors = [half[str(F.dtype)] for F in given if _module_is_torch(F) and str(F.dtype) in half]
+        if tensors and auto_tensor:
+            storage = tensors[0]            # a tensor of another dtype next to it is refused by _features_h16
+        elif (given and not min_neighbours and np.dtype(dtype) == np.float32
+              and all(getattr(F, "dtype", None) == np.float16 and not _module_is_torch(F) for F in given)):
+            storage = "f16"
+    if storage is None:
+        return None
+    if np.dtype(dtype) != np.float32:
+        raise TypeError("16-bit storage builds float32 graphs: dtype must be float32")
+    if min_neighbours:
+        raise NotImplementedError("the neighbour floor (min_neighbours > 0) has no 16-bit route: widen the features")
+    if len({_module_is_torch(F) for F in given}) > 1:
+        raise TypeError("features must all live on the host (numpy) or all on the device (CUDA tensors)")
+    return H16_STORAGES[storage]
+
+
+def _features_h16(F, code, dev, keep):
+    """(pointer, rows, d, ld) of 16-bit feature rows in the row-major layout of include/simspread_hip_half.h.  Device: an
+    (n, d) CUDA tensor of the storage's dtype, used in place when its rows are contiguous (ld = stride(0)).  Host: numpy
+    float16 for "f16" or uint16 (raw bit patterns) as they are, any other real array rounded to the storage."""
+    if F is None:
+        return None, 0, 0, 1
+    if dev:
+        import torch
+        want = torch.bfloat16 if code == L.SS_H16_BF16 else torch.float16
+        if not (_module_is_torch(F) and F.is_cuda and F.ndim == 2):
+            raise TypeError("device features must be (n, d) CUDA tensors")
+        if F.dtype != want:
+            raise TypeError(f"device features of this storage must be {want}, got {F.dtype}")
+        n, d = F.shape
+        rows_ok = d <= 1 or F.stride(1) == 1                  # the d elements of a row are consecutive
+        ld_ok = n <= 1 or F.stride(0) >= d                    # rows do not overlap
+        if not (rows_ok and ld_ok):
+            F = F.contiguous()
+        keep.append(F)
+        ld = F.stride(0) if n > 1 else d
+        return F.data_ptr(), n, d, max(ld, d, 1)
+    if _module_is_torch(F):
+        raise TypeError("features must all live on the host (numpy) or all on the device (CUDA tensors)")
+    a = np.asarray(F)
+    if a.ndim != 2:
+        raise ValueError("features must be an (n, d) matrix")
+    if a.dtype.kind not in "fiu":
+        raise TypeError(f"features must be real numbers, got {a.dtype}")
+    if a.dtype == np.uint16:
+        bits = a                                                      # raw patterns
+    elif code == L.SS_H16_F16:
+        with np.errstate(over="ignore"):
+            bits = a.astype(np.float16, copy=False).view(np.uint16)   # numpy rounds to nearest even, straight from fp64
+    else:
+        bits = to_bf16_bits(a)
+    bits = np.ascontiguousarray(bits)
+    keep.append(bits)
+    return bits.ctypes.data, a.shape[0], a.shape[1], max(a.shape[1], 1)
+
+
+def _pair_csr_h16(Fa, Fb, code, m, alpha, weighted):
+    """ss_similarity_dot_csr_h16 under the size protocol of ``_feature_pair_csr``."""
+    dev = _is_torch(Fa)
+    keep = []
+    pa, na, d, lda = _features_h16(Fa, code, dev, keep)
+    pb, nb, db, ldb = _features_h16(Fb, code, dev, keep)
+    if Fb is None:
+        nb, db, ldb = na, d, lda
+    if db != d:
+        raise ValueError("Fa and Fb have different numbers of features")
+    fn = L_.lib().ss_similarity_dot_csr_h16
+    nnz = C.c_int64(0)
+    head = (pa, na, lda, pb, nb, ldb, d, code, m, C.c_float(alpha), 1 if weighted else 0)
+    if dev:
+        import torch
+        ptr = torch.empty(na + 1, dtype=torch.int64, device=Fa.device)
+        L_.check(fn(*head, ptr.data_ptr(), None, None, 0, C.byref(nnz), L_.SS_MEM_DEVICE))
+        idx = torch.empty(max(nnz.value, 1), dtype=torch.int32, device=Fa.device)
+        val = torch.empty(max(nnz.value, 1), dtype=torch.float32, device=Fa.device)
+        L_.check(fn(*head, ptr.data_ptr(), idx.data_ptr(), val.data_ptr(), nnz.value, C.byref(nnz), L_.SS_MEM_DEVICE))
+        del keep
+        return ptr, idx[:nnz.value], val[:nnz.value]
+    import scipy.sparse as sp
+    ptr = np.zeros(na + 1, np.int64)
+    L_.check(fn(*head, ptr.ctypes.data, None, None, 0, C.byref(nnz), L_.SS_MEM_HOST))
+    idx = np.empty(max(nnz.value, 1), np.int32)
+    val = np.empty(max(nnz.value, 1), np.float32)
+    L_.check(fn(*head, ptr.ctypes.data, idx.ctypes.data, val.ctypes.data, nnz.value, C.byref(nnz), L_.SS_MEM_HOST))
+    del keep
+    return sp.csr_matrix((val[:nnz.value], idx[:nnz.value], ptr), shape=(na, nb))
+
+
 def _feature_pair_csr(name, Fa, Fb, mid, alpha, weighted, dtype, min_neighbours=0):
     """The size protocol shared by the feature-row producers ss_similarity_<name>_csr_* and, with min_neighbours = k > 0,
     ss_similarity_<name>_floor_csr_* (k after alpha): `mid` are the arguments between d and alpha."""
@@ -1894,7 +2072,8 @@ def jaccard_csr(Fa, Fb=None, alpha=None, weighted: bool = True, dtype=np.float32
     return _feature_pair_csr("jaccard", Fa, Fb, (), alpha, weighted, dtype, min_neighbours)
 
 
-def dot_csr(Fa, Fb=None, metric="cosine", alpha=None, weighted: bool = True, dtype=np.float32, min_neighbours: int = 0):
+def dot_csr(Fa, Fb=None, metric="cosine", alpha=None, weighted: bool = True, dtype=np.float32, min_neighbours: int = 0,
+            storage=None):
     """``featurize(S, alpha, weighted)`` with S an inner-product similarity of real-valued rows (embeddings, continuous
     descriptors), produced as CSR on the device without the dense similarity; the Gram blocks run on the matrix cores in
     full ``dtype`` precision.  metric: "cosine" g / (|a| |b|), "tanimoto" g / (|a|^2 + |b|^2 - g), "dice" 2g / (|a|^2 +
@@ -1902,9 +2081,21 @@ def dot_csr(Fa, Fb=None, metric="cosine", alpha=None, weighted: bool = True, dty
     is >= alpha (1 when not weighted).  Fb None: Fb = Fa (the diagonal is exactly 1 and the matrix bitwise symmetric).
     Inputs and outputs as ``jaccard_csr``.  A NaN feature or alpha raises SimSpreadError.  min_neighbours = k > 0 (at
     most 64) adds the neighbour floor as there (``dot_kth``): negative similarities never count among the k, the
-    diagonal of Fb = Fa stays exactly 1 and counts, and the floor matrix is not symmetric."""
+    diagonal of Fb = Fa stays exactly 1 and counts, and the floor matrix is not symmetric.
+
+    storage "bf16" / "f16" takes the 16-bit route (include/simspread_hip_half.h): the rows are bfloat16 / half values,
+    the Gram blocks run on the 16-bit matrix instructions with fp32 accumulation -- every product is exact, so the result
+    is a valid output of the fp32 rule on the widened inputs up to the order of the sums, and bitwise the fp32 result
+    when all partial sums are exact.  CUDA tensors of torch.bfloat16 / torch.float16 select it by their dtype and are
+    read in place, row-major, when ``stride(1) == 1`` (no copy, no widening); numpy float16 arrays select "f16" when
+    every input is float16, dtype is float32 and min_neighbours is 0 (otherwise they are widened exactly, as before); with
+    an explicit storage numpy uint16 arrays are raw bit patterns and other real arrays are rounded on the host (nearest
+    even; ``to_bf16_bits``).  dtype must be float32; min_neighbours > 0 raises NotImplementedError."""
     if alpha is None:
         raise TypeError("dot_csr needs alpha")
+    code = _h16_storage(storage, (Fa, Fb), dtype, min_neighbours)
+    if code is not None:
+        return _pair_csr_h16(Fa, Fb, code, _sim_metric(metric), alpha, weighted)
     return _feature_pair_csr("dot", Fa, Fb, (_sim_metric(metric),), alpha, weighted, dtype, min_neighbours)
 
 
@@ -2024,6 +2215,9 @@ def butina_clusters(X=None, *, fingerprints=None, features=None, vectors=None, m
     given = [a is not None for a in (X, fingerprints, features, vectors)]
     if sum(given) != 1:
         raise TypeError("butina_clusters needs exactly one of X, fingerprints=, features=, vectors=")
+    if vectors is not None and _module_is_torch(vectors) and str(vectors.dtype) in ("torch.bfloat16", "torch.float16"):
+        raise NotImplementedError("butina_clusters has no 16-bit route (its selection would have to run the 16-bit Gram "
+                                  "tile): cluster the pattern of dot_csr(vectors, weighted=False) or widen the vectors")
     lib = L_.lib()
     keep = []
     if X is not None:
