@@ -11,11 +11,11 @@ from .core import (NamedMatrix, Network, clean, clean_, construct, cutoff, featu
 from .dist import (comm_destroy, comm_init, comm_unique_id, gather_scores, gather_topl, lib_gather_scores, pooled_metrics,
                    shard_range, target_rank, target_rank_positives, target_topl)
 from .engine import (BINARY_ROWS_FIELDS, POOLED_FIELDS, RANK_ROWS_FIELDS, TARGET_RANK_FIELDS, TARGET_TOPL_FIELDS, DeviceGraph, DeviceQueries, DeviceSpMat,
-                     Pool,
+                     CutoffProfile, Pool,
                      TargetRank, TargetTopL, ButinaClusters, binary_metrics_rows, butina_clusters, cluster_folds, cross_fold_edges,
                      cutoff_csr,
-                     dot_csr, dot_kth, jaccard_csr, jaccard_kth,
-                     jaccard_similarity, pack_fingerprints, rank_metrics, rank_metrics_rows, tanimoto_csr, tanimoto_kth,
+                     dot_csr, dot_kth, dot_profile, jaccard_csr, jaccard_kth, jaccard_profile,
+                     jaccard_similarity, pack_fingerprints, rank_metrics, rank_metrics_rows, tanimoto_csr, tanimoto_kth, tanimoto_profile,
                      to_bf16_bits, topl)
 from .metrics import (AuPRC, AuROC, BEDROC, ROCNums, accuracy, balancedaccuracy, f1score, maxperformance, mcc,
                       meanperformance, meanstdperformance, precision, recall, roc, validity_ratio)
@@ -25,4 +25,5 @@ __all__ = ["NamedMatrix", "Network", "DeviceGraph", "DeviceQueries", "DeviceSpMa
            "read_namedmatrix", "writedlm", "rank_metrics", "rank_metrics_rows", "RANK_ROWS_FIELDS", "binary_metrics_rows", "BINARY_ROWS_FIELDS", "jaccard_similarity", "jaccard_csr", "dot_csr", "cutoff_csr", "pack_fingerprints", "tanimoto_csr", "tanimoto_kth", "jaccard_kth", "dot_kth", "AuROC", "AuPRC", "BEDROC", "validity_ratio", "roc", "ROCNums",
            "f1score", "mcc", "accuracy", "balancedaccuracy", "recall", "precision", "maxperformance", "meanperformance",
            "meanstdperformance", "ButinaClusters", "butina_clusters", "cluster_folds", "cross_fold_edges", "split_clusters", "TargetRank", "TARGET_RANK_FIELDS",
-           "target_rank", "target_rank_positives", "to_bf16_bits"]
+           "target_rank", "target_rank_positives", "to_bf16_bits", "CutoffProfile", "tanimoto_profile", "jaccard_profile",
+           "dot_profile"]

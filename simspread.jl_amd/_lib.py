@@ -19,6 +19,7 @@ REAL_NEIGHBOURS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "s
 CLUSTERS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_clusters.h")                # too
 TARGET_RANK_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_target_rank.h")          # too
 HALF_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_half.h")                        # too
+PROFILE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_profile.h")                  # too
 
 SS_OK = 0
 SS_MEM_HOST, SS_MEM_DEVICE = 0, 1
@@ -256,6 +257,22 @@ def _half_sigs():
 HALF_SIGNATURES = _half_sigs()
 
 
+def _profile_sigs():
+    """include/simspread_hip_profile.h: cutoff profiles of the fused producers (cuts, ncuts, weighted, total, rows, mem
+    after the producer's operands)"""
+    tail = [_vp, _int, _int, _vp, _vp, _int]
+    s = {}
+    for suf in ("f32", "f64"):
+        s[f"ss_similarity_tanimoto_profile_{suf}"] = ([_vp, _i64, _vp, _i64, _i64] + tail, _int)
+        s[f"ss_similarity_jaccard_profile_{suf}"] = ([_vp, _i64, _i64, _vp, _i64, _i64, _i64] + tail, _int)
+        s[f"ss_similarity_dot_profile_{suf}"] = ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, _int] + tail, _int)
+    s["ss_similarity_dot_profile_h16"] = ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _int] + tail, _int)
+    return s
+
+
+PROFILE_SIGNATURES = _profile_sigs()
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function the C header declares (used by the symbol-export test)."""
     with open(path) as f:
@@ -294,6 +311,11 @@ def half_header_symbols():
     return header_symbols(HALF_HEADER_PATH)
 
 
+def profile_header_symbols():
+    """Every function include/simspread_hip_profile.h declares."""
+    return header_symbols(PROFILE_HEADER_PATH)
+
+
 def load():
     """dlopen the library (no GPU needed for this step)."""
     global _lib
@@ -307,7 +329,7 @@ def load():
     for name, (args, res) in (list(SIGNATURES.items()) + list(SCREENING_SIGNATURES.items())
                               + list(NEIGHBOUR_SIGNATURES.items()) + list(REAL_NEIGHBOUR_SIGNATURES.items())
                               + list(CLUSTER_SIGNATURES.items()) + list(TARGET_RANK_SIGNATURES.items())
-                              + list(HALF_SIGNATURES.items())):
+                              + list(HALF_SIGNATURES.items()) + list(PROFILE_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "graph.hpp"
+#include "pair_tile.hpp"  // PROFILE_CUTS_MAX
 
 namespace ss {
 
@@ -872,6 +873,141 @@ static int graph_create_vectors_h16_impl(int64_t nq, int64_t ns, int64_t nt, int
       nq, ns, nt, [&](DotCsrH16& p) { return p.count(ds, ns, ls, nullptr, ns, ls, d, storage, metric, alpha, wgt); },
       [&](DotCsrH16& p) { return p.count(dq, nq, lq, ds, ns, ls, d, storage, metric, alpha, wgt); }, h16_tag(true),
       h16_tag(false), y_ptr, y_idx, y_val, index_base, mem, out);
+}
+
+// ------------------- cutoff profiles (include/simspread_hip_profile.h; the device path is cut_profile.hip).  The operand
+// checks and the staging are the matching producer's; what is the profile's own is the check of the cuts and the
+// delivery of total / rows.
+template <class T>
+static int check_cuts(const char* what, const T* cuts, int ncuts) {
+  if (ncuts < 1 || ncuts > PROFILE_CUTS_MAX)
+    return fail(SS_EINVAL, "%s: %d cuts outside 1..%d", what, ncuts, PROFILE_CUTS_MAX);
+  if (!cuts) return fail(SS_EINVAL, "%s: cuts is NULL", what);
+  for (int b = 0; b < ncuts; ++b) {
+    if (cuts[b] != cuts[b]) return fail(SS_EINVAL, "%s: cut %d is NaN", what, b);
+    if (b > 0 && cuts[b] < cuts[b - 1]) return fail(SS_EINVAL, "%s: the cuts decrease at %d", what, b);
+  }
+  return SS_OK;
+}
+// run(total, rows) fills device arrays; they are the caller's (SS_MEM_DEVICE) or copied to the caller afterwards, so a
+// refusal of run leaves the caller's arrays as they were
+template <class Run>
+static int profile_deliver(const char* what, const char* tag, int64_t na, int ncuts, int64_t* total, int32_t* rows,
+                           int mem, Run run) {
+  if (!total) return fail(SS_EINVAL, "%s: total must not be NULL", what);
+  DevBuf<int64_t> dt;
+  DevBuf<int> dr;
+  int64_t* t = total;
+  int* r = rows;
+  if (mem == SS_MEM_HOST) {
+    SS_TRY(dt.alloc((size_t)ncuts));
+    t = dt.p;
+    if (rows) {
+      SS_TRY(dr.alloc((size_t)na * (size_t)ncuts));
+      r = dr.p;
+    }
+  }
+  SS_TRY(run(t, r));
+  path_add(tag);
+  if (mem == SS_MEM_HOST) {
+    hipStream_t st = ctx().stream;
+    SS_HIP(hipMemcpyAsync(total, t, (size_t)ncuts * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (rows && na > 0)
+      SS_HIP(hipMemcpyAsync(rows, r, (size_t)na * (size_t)ncuts * sizeof(int), hipMemcpyDeviceToHost, st));
+    SS_HIP(hipStreamSynchronize(st));
+  }
+  return SS_OK;
+}
+
+template <class T>
+static int tanimoto_profile_impl(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords,
+                                 const T* cuts, int ncuts, int weighted, int64_t* total, int32_t* rows, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  path_note().clear();
+  const bool sym = (Fb == nullptr);
+  if (sym) nb = na;
+  SS_TRY(check_cuts("tanimoto profile", cuts, ncuts));
+  SS_TRY(check_nwords(nwords));
+  SS_TRY(check_fingerprints("Fa", Fa, na, nwords));
+  if (!sym) SS_TRY(check_fingerprints("Fb", Fb, nb, nwords));
+  DevBuf<uint64_t> ba, bb;
+  const uint64_t *da = nullptr, *db = nullptr;
+  SS_TRY(stage_fingerprints(Fa, na, nwords, mem, ba, &da));
+  if (!sym) SS_TRY(stage_fingerprints(Fb, nb, nwords, mem, bb, &db));
+  return profile_deliver("tanimoto profile", "tanimoto_profile", na, ncuts, total, rows, mem, [&](int64_t* t, int* r) {
+    return tanimoto_profile<T>(da, na, sym ? nullptr : db, nb, nwords, cuts, ncuts, weighted != 0, t, r);
+  });
+}
+
+// the profile of a producer of column-major feature rows: run(da, na, la, db, nb, lb, total, rows) on device rows
+template <class T, class Check, class Run>
+static int features_profile_impl(const FeatureNames& nm, const char* tag, Check check, Run run, const T* Fa, int64_t na,
+                                 int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d, const T* cuts, int ncuts,
+                                 int64_t* total, int32_t* rows, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  path_note().clear();
+  const bool sym = (Fb == nullptr);
+  if (sym) {
+    nb = na;
+    ldb = lda;
+  }
+  SS_TRY(check_cuts(tag, cuts, ncuts));
+  SS_TRY(check_feature_args(nm, check, d, cuts[0]));
+  SS_TRY(check_features("Fa", Fa, na, lda, d));
+  if (!sym) SS_TRY(check_features("Fb", Fb, nb, ldb, d));
+  DevBuf<T> ba, bb;
+  const T *da = nullptr, *db = nullptr;
+  int64_t la = 0, lb = 0;
+  SS_TRY(stage_features(Fa, na, lda, d, mem, ba, &da, &la));
+  if (!sym) SS_TRY(stage_features(Fb, nb, ldb, d, mem, bb, &db, &lb));
+  return profile_deliver(tag, tag, na, ncuts, total, rows, mem,
+                         [&](int64_t* t, int* r) { return run(da, na, la, sym ? nullptr : db, nb, lb, t, r); });
+}
+template <class T>
+static int jaccard_profile_impl(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d,
+                                const T* cuts, int ncuts, int weighted, int64_t* total, int32_t* rows, int mem) {
+  return features_profile_impl<T>(
+      jaccard_names, "jaccard_profile", no_check,
+      [=](const T* da, int64_t na_, int64_t la, const T* db, int64_t nb_, int64_t lb, int64_t* t, int* r) {
+        return jaccard_profile<T>(da, na_, la, db, nb_, lb, d, cuts, ncuts, weighted != 0, t, r);
+      },
+      Fa, na, lda, Fb, nb, ldb, d, cuts, ncuts, total, rows, mem);
+}
+template <class T>
+static int dot_profile_impl(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d,
+                            int metric, const T* cuts, int ncuts, int weighted, int64_t* total, int32_t* rows, int mem) {
+  return features_profile_impl<T>(
+      dot_names, "dot_profile", [=] { return check_sim_metric(metric); },
+      [=](const T* da, int64_t na_, int64_t la, const T* db, int64_t nb_, int64_t lb, int64_t* t, int* r) {
+        return dot_profile<T>(da, na_, la, db, nb_, lb, d, metric, cuts, ncuts, weighted != 0, t, r);
+      },
+      Fa, na, lda, Fb, nb, ldb, d, cuts, ncuts, total, rows, mem);
+}
+static int dot_profile_h16_impl(const uint16_t* Fa, int64_t na, int64_t lda, const uint16_t* Fb, int64_t nb, int64_t ldb,
+                                int64_t d, int storage, int metric, const float* cuts, int ncuts, int weighted,
+                                int64_t* total, int32_t* rows, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  path_note().clear();
+  const bool sym = (Fb == nullptr);
+  if (sym) {
+    nb = na;
+    ldb = lda;
+  }
+  SS_TRY(check_cuts("dot_h16_profile", cuts, ncuts));
+  SS_TRY(check_h16_args(storage, metric, d, cuts[0]));
+  SS_TRY(check_rows_h16("Fa", Fa, na, lda, d));
+  if (!sym) SS_TRY(check_rows_h16("Fb", Fb, nb, ldb, d));
+  DevBuf<uint16_t> ba, bb;
+  const uint16_t *da = nullptr, *db = nullptr;
+  int64_t la = 0, lb = 0;
+  SS_TRY(stage_rows_h16(Fa, na, lda, d, mem, ba, &da, &la));
+  if (!sym) SS_TRY(stage_rows_h16(Fb, nb, ldb, d, mem, bb, &db, &lb));
+  return profile_deliver("dot_h16_profile", "dot_h16_profile", na, ncuts, total, rows, mem, [&](int64_t* t, int* r) {
+    return dot_profile_h16(da, na, la, sym ? nullptr : db, nb, lb, d, storage, metric, cuts, ncuts, weighted != 0, t, r);
+  });
 }
 
 // ------------------------------------------------------------------ Butina clusters, cluster folds, cross-fold edges
@@ -5199,6 +5335,50 @@ int ss_queries_create_vectors_h16(const ss_graph* g, int64_t nq, int64_t ns, int
       g, nq, ns,
       [&](DotCsrH16& p) { return p.count(dq, nq, lq, ds, ns, ls, d, storage, metric, alpha, weighted != 0); },
       h16_tag(false), out);
+}
+
+// ---- include/simspread_hip_profile.h: cutoff profiles of the fused producers
+int ss_similarity_tanimoto_profile_f32(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords,
+                                       const float* cuts, int ncuts, int weighted, int64_t* total, int32_t* rows,
+                                       int mem) {
+  SS_API_LOCK();
+  return tanimoto_profile_impl<float>(Fa, na, Fb, nb, nwords, cuts, ncuts, weighted, total, rows, mem);
+}
+int ss_similarity_tanimoto_profile_f64(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords,
+                                       const double* cuts, int ncuts, int weighted, int64_t* total, int32_t* rows,
+                                       int mem) {
+  SS_API_LOCK();
+  return tanimoto_profile_impl<double>(Fa, na, Fb, nb, nwords, cuts, ncuts, weighted, total, rows, mem);
+}
+int ss_similarity_jaccard_profile_f32(const float* Fa, int64_t na, int64_t lda, const float* Fb, int64_t nb, int64_t ldb,
+                                      int64_t d, const float* cuts, int ncuts, int weighted, int64_t* total,
+                                      int32_t* rows, int mem) {
+  SS_API_LOCK();
+  return jaccard_profile_impl<float>(Fa, na, lda, Fb, nb, ldb, d, cuts, ncuts, weighted, total, rows, mem);
+}
+int ss_similarity_jaccard_profile_f64(const double* Fa, int64_t na, int64_t lda, const double* Fb, int64_t nb,
+                                      int64_t ldb, int64_t d, const double* cuts, int ncuts, int weighted,
+                                      int64_t* total, int32_t* rows, int mem) {
+  SS_API_LOCK();
+  return jaccard_profile_impl<double>(Fa, na, lda, Fb, nb, ldb, d, cuts, ncuts, weighted, total, rows, mem);
+}
+int ss_similarity_dot_profile_f32(const float* Fa, int64_t na, int64_t lda, const float* Fb, int64_t nb, int64_t ldb,
+                                  int64_t d, int metric, const float* cuts, int ncuts, int weighted, int64_t* total,
+                                  int32_t* rows, int mem) {
+  SS_API_LOCK();
+  return dot_profile_impl<float>(Fa, na, lda, Fb, nb, ldb, d, metric, cuts, ncuts, weighted, total, rows, mem);
+}
+int ss_similarity_dot_profile_f64(const double* Fa, int64_t na, int64_t lda, const double* Fb, int64_t nb, int64_t ldb,
+                                  int64_t d, int metric, const double* cuts, int ncuts, int weighted, int64_t* total,
+                                  int32_t* rows, int mem) {
+  SS_API_LOCK();
+  return dot_profile_impl<double>(Fa, na, lda, Fb, nb, ldb, d, metric, cuts, ncuts, weighted, total, rows, mem);
+}
+int ss_similarity_dot_profile_h16(const uint16_t* Fa, int64_t na, int64_t lda, const uint16_t* Fb, int64_t nb,
+                                  int64_t ldb, int64_t d, int storage, int metric, const float* cuts, int ncuts,
+                                  int weighted, int64_t* total, int32_t* rows, int mem) {
+  SS_API_LOCK();
+  return dot_profile_h16_impl(Fa, na, lda, Fb, nb, ldb, d, storage, metric, cuts, ncuts, weighted, total, rows, mem);
 }
 
 }  // extern "C"

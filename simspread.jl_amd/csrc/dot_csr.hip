@@ -263,10 +263,10 @@ int DotCsr<T>::launch(bool fill, int* idx, T* val, int* flag) {
 }
 
 // ---- 16-bit rows (include/simspread_hip_half.h)
-namespace {
 // a side may use 16-byte loads: every chunk address base + 2 (i ld + k), k % 8 == 0, is then 16-byte aligned
 bool h16_fast(const uint16_t* F, int64_t ld) { return (reinterpret_cast<uintptr_t>(F) & 15) == 0 && ld % 8 == 0; }
 
+namespace {
 template <class Op>
 int h16_norms(const uint16_t* F, int64_t n, int64_t ld, int64_t d, float* norm) {
   hipLaunchKernelGGL(dottile::row_norm_h16_kernel<Op>, dim3((unsigned)ceil_div(n * 16, 256)), dim3(256), 0, ctx().stream,
@@ -311,6 +311,15 @@ void h16_launch(const DotCsrH16& p, dim3 grid, bool fill, int* idx, float* val, 
 }
 }  // namespace
 
+int h16_row_norms(int storage, const uint16_t* F, int64_t n, int64_t ld, int64_t d, float* norm) {
+  return storage == SS_H16_BF16 ? h16_norms<dottile::Bf16>(F, n, ld, d, norm) : h16_norms<dottile::F16>(F, n, ld, d, norm);
+}
+int h16_refuse_nan_rows(int storage, const uint16_t* Fa, int64_t na, int64_t lda, const uint16_t* Fb, int64_t nb,
+                        int64_t ldb, int64_t d) {
+  return storage == SS_H16_BF16 ? h16_refuse_nan<dottile::Bf16>(Fa, na, lda, Fb, nb, ldb, d)
+                                : h16_refuse_nan<dottile::F16>(Fa, na, lda, Fb, nb, ldb, d);
+}
+
 int DotCsrH16::count(const uint16_t* Fa_, int64_t na_, int64_t lda_, const uint16_t* Fb_, int64_t nb_, int64_t ldb_,
                      int64_t d_, int storage_, int metric_, float alpha_, bool weighted_) {
   what = "dot_h16";
@@ -325,17 +334,14 @@ int DotCsrH16::count(const uint16_t* Fa_, int64_t na_, int64_t lda_, const uint1
   alpha = alpha_;
   weighted = weighted_;
   // storage, metric and alpha are the caller's to check (check_h16_args of api.hip, before anything is staged)
-  const bool bf = storage == SS_H16_BF16;
-  const uint16_t* scan_b = sym ? nullptr : Fb;
-  SS_TRY(bf ? h16_refuse_nan<dottile::Bf16>(Fa, na_, lda, scan_b, nb_, ldb, d)
-            : h16_refuse_nan<dottile::F16>(Fa, na_, lda, scan_b, nb_, ldb, d));
+  SS_TRY(h16_refuse_nan_rows(storage, Fa, na_, lda, sym ? nullptr : Fb, nb_, ldb, d));
   SS_TRY(this->begin_tiles(na_, sym ? na_ : nb_, TILE, true));
   if (na == 0 || nb == 0) return SS_OK;
   SS_TRY(norm_a.alloc((size_t)na));
-  SS_TRY(bf ? h16_norms<dottile::Bf16>(Fa, na, lda, d, norm_a.p) : h16_norms<dottile::F16>(Fa, na, lda, d, norm_a.p));
+  SS_TRY(h16_row_norms(storage, Fa, na, lda, d, norm_a.p));
   if (!sym) {
     SS_TRY(norm_b.alloc((size_t)nb));
-    SS_TRY(bf ? h16_norms<dottile::Bf16>(Fb, nb, ldb, d, norm_b.p) : h16_norms<dottile::F16>(Fb, nb, ldb, d, norm_b.p));
+    SS_TRY(h16_row_norms(storage, Fb, nb, ldb, d, norm_b.p));
   }
   return this->count_pass();
 }

@@ -519,6 +519,11 @@ struct PairCsr {
 template <class T>
 int refuse_nan_rows(const char* what, const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb,
                     int64_t d);
+// the tile grid of na x nb pairs in tile x tile blocks: nti, ntj, and the blocks of one launch (sym: the upper triangle
+// of nti x nti tiles); SS_EUNSUPPORTED when one launch does not hold them.  pair_tile_grid: that launch's grid.
+int pair_tile_blocks(const char* what, int64_t na, int64_t nb, int64_t tile, bool sym, int64_t& nti, int64_t& ntj,
+                     int64_t& nblocks);
+dim3 pair_tile_grid(bool sym, int64_t nti, int64_t ntj);
 // the members a producer names unqualified
 #define SS_PAIR_CSR_MEMBERS(T)                                                                                       \
   using PairCsr<T>::what, PairCsr<T>::na, PairCsr<T>::nb, PairCsr<T>::nti, PairCsr<T>::ntj, PairCsr<T>::nnz,          \
@@ -617,6 +622,32 @@ struct DotCsrH16 : PairCsr<float> {
  protected:
   int launch(bool fill, int* idx, float* val, int* flag) override;
 };
+
+// what DotCsrH16::count does before its tile pass, for the other passes over 16-bit rows (cut_profile.hip):
+// a side may use 16-byte loads; norm[i] = sum_k w(F[i, k])^2 in fp32 (enqueued); SS_EINVAL when an element k < d of Fa
+// or (not nullptr) Fb is a NaN pattern (synchronises)
+bool h16_fast(const uint16_t* F, int64_t ld);
+int h16_row_norms(int storage, const uint16_t* F, int64_t n, int64_t ld, int64_t d, float* norm);
+int h16_refuse_nan_rows(int storage, const uint16_t* Fa, int64_t na, int64_t lda, const uint16_t* Fb, int64_t nb,
+                        int64_t ldb, int64_t d);
+
+// ---- cut_profile.hip: cutoff profiles (include/simspread_hip_profile.h holds the rule).  For each of the ncuts
+// nondecreasing, NaN-free cuts (host array, 1 <= ncuts <= 32: checked by the caller) total[b] = the nnz and
+// rows[i * ncuts + b] (rows may be nullptr) = the row degrees of the CSR the plain producer builds at alpha = cuts[b],
+// from ONE run of the producer's own tile pass over the producer's own grid.  Operands, total and rows on the device,
+// operands as for the producers (Fb == nullptr: symmetric).  NaN features are refused (SS_EINVAL) before total or rows
+// are written; both are complete on return (synchronises).  Bitwise repeatable.
+template <class T>
+int tanimoto_profile(const uint64_t* Fa, int64_t na, const uint64_t* Fb, int64_t nb, int64_t nwords, const T* cuts,
+                     int ncuts, bool weighted, int64_t* total, int* rows);
+template <class T>
+int jaccard_profile(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d,
+                    const T* cuts, int ncuts, bool weighted, int64_t* total, int* rows);
+template <class T>
+int dot_profile(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64_t ldb, int64_t d, int metric,
+                const T* cuts, int ncuts, bool weighted, int64_t* total, int* rows);
+int dot_profile_h16(const uint16_t* Fa, int64_t na, int64_t lda, const uint16_t* Fb, int64_t nb, int64_t ldb, int64_t d,
+                    int storage, int metric, const float* cuts, int ncuts, bool weighted, int64_t* total, int* rows);
 
 // ---- real_floor.hip: the neighbour floor of the two producers above.  tau[i] = the k-th largest of the positive
 // similarities s(i, j) of row i of Fa against the rows of Fb (multiplicity counted), +0 when there are fewer than k;

@@ -76,15 +76,27 @@ int PairCsr<T>::begin(int64_t na_, int64_t nb_, int64_t tile) {
   return SS_OK;
 }
 
+int pair_tile_blocks(const char* what, int64_t na, int64_t nb, int64_t tile, bool sym, int64_t& nti, int64_t& ntj,
+                     int64_t& nblocks) {
+  nti = ceil_div(na, tile);
+  ntj = ceil_div(nb, tile);
+  nblocks = sym ? nti * (nti + 1) / 2 : nti * ntj;
+  if (sym ? nblocks >= (1LL << 31) : (ntj >= (1LL << 31) || nti > 65535))
+    return fail(SS_EUNSUPPORTED, "%s: %lld x %lld pairs need more tiles than one launch holds", what, (long long)na,
+                (long long)nb);
+  return SS_OK;
+}
+
+dim3 pair_tile_grid(bool sym, int64_t nti, int64_t ntj) {
+  return sym ? dim3((unsigned)(nti * (nti + 1) / 2)) : dim3((unsigned)ntj, (unsigned)nti);
+}
+
 template <class T>
 int PairCsr<T>::begin_tiles(int64_t na_, int64_t nb_, int64_t tile, bool with_tile_nz) {
   SS_TRY(begin(na_, nb_, tile));
   if (na == 0 || nb == 0) return SS_OK;
-  nti = ceil_div(na, tile);
-  const int64_t nblocks = sym ? nti * (nti + 1) / 2 : nti * ntj;
-  if (sym ? nblocks >= (1LL << 31) : (ntj >= (1LL << 31) || nti > 65535))
-    return fail(SS_EUNSUPPORTED, "%s: %lld x %lld pairs need more tiles than one launch holds", what, (long long)na,
-                (long long)nb);
+  int64_t nblocks = 0;
+  SS_TRY(pair_tile_blocks(what, na, nb, tile, sym, nti, ntj, nblocks));
   SS_TRY(counts.alloc((size_t)ntj * (size_t)na));
   if (with_tile_nz) SS_TRY(tile_nz.alloc((size_t)nblocks));
   return SS_OK;
@@ -92,7 +104,7 @@ int PairCsr<T>::begin_tiles(int64_t na_, int64_t nb_, int64_t tile, bool with_ti
 
 template <class T>
 dim3 PairCsr<T>::tile_grid() const {
-  return sym ? dim3((unsigned)(nti * (nti + 1) / 2)) : dim3((unsigned)ntj, (unsigned)nti);
+  return pair_tile_grid(sym, nti, ntj);
 }
 
 template <class T>

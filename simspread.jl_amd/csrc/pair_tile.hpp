@@ -8,6 +8,8 @@
 // In symmetric mode (Fb = Fa) only the tiles on and above the diagonal run, as a 1-D grid over the triangle; an
 // off-diagonal tile emits its pairs for its rows and, mirrored, for its columns (na == nb there).  Positions come from
 // scans, never from atomics, so the output is bitwise repeatable.
+// A third epilogue next to count and fill, pair_tile_profile at the end of this file, counts the kept pairs of every row
+// at up to 32 cuts at once (cut_profile.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -174,6 +176,106 @@ __device__ __forceinline__ void pair_tile_emit(const PairTile& t, int64_t na, in
       }
     }
     if (nb_flag) *not_binary = 1;
+  }
+}
+
+// ---- The count epilogue (cut_profile.hip): a cutoff profile.  Next to "emit" (which pairs stay at one alpha, and
+// where) it answers "how many pairs of every row stay at each of up to 32 ascending cuts", without positions.
+constexpr int PROFILE_CUTS_MAX = 32;
+template <class T>
+struct ProfileCuts {  // a kernel argument: the cuts, nondecreasing, no NaN (host-checked)
+  T c[PROFILE_CUTS_MAX];
+  int n;  // 1 .. PROFILE_CUTS_MAX
+};
+
+// m = #{b : s >= cuts[b]}: binary search over the nondecreasing cuts with the producers' own >=; a NaN s gives 0
+template <class T>
+__device__ __forceinline__ int profile_bin(const T* cuts, int ncuts, T s) {
+  if (!(s >= cuts[0])) return 0;  // most pairs of a sparse graph
+  int lo = 1, hi = ncuts;         // s >= cuts[b] for b < lo, not for b >= hi
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (s >= cuts[mid]) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// The count epilogue of a kernel whose NT threads each hold NP pairs of the tile.  pair(e, row, col) gives the tile-local
+// row and column and returns the similarity s of the calling thread's pair e (e is a constant after unrolling, so the
+// caller's register block is indexed statically).  Pairs past the last row or column are dropped here.
+//   v = weighted ? s : 1; pair (i, j) counts for cut b iff s >= cuts[b] and v != 0; a NaN s counts for none
+//   every held pair finds its bin m = #{b : s >= cuts[b]} (0 when v == 0) and adds 1 to the tile's LDS histogram
+//   hist[row][m]; after the tile the non-zero bins are added to ghist[(i0 + row) * (ncuts + 1) + m].  A mirrored tile
+//   (SYM, off the diagonal) then clears the histogram and runs the same bins through it by column, for rows j0 + col.
+//   Bin 0 (the pair counts for no cut) is never read by the finish, so nothing is added to it.
+// Only integers are added (LDS and global integer atomics), so ghist does not depend on the order: bitwise repeatable.
+// A bin of the tile's histogram holds at most TILE = 128 pairs (one row or one column of the tile), so it is one byte,
+// four to a 32-bit word, and an add is an integer LDS add of 1 << 8 * (byte of the word), which never carries into the
+// next bin: TILE x 33 bytes = 4.1 KB instead of 16.5 KB of ints.  That keeps the 16-bit profile kernel (36 KB of
+// staging) at three workgroups per CU, like its producer.  There is still one histogram, used twice by a mirrored tile:
+// the bins of a thread's pairs wait in NP / 4 registers meanwhile.
+template <class T, int TILE, int NT, int NP, bool SYM, class Pair>
+__device__ __forceinline__ void pair_tile_profile(const PairTile& t, int64_t na, int64_t nb, const ProfileCuts<T>& cuts,
+                                                  bool weighted, int* __restrict__ ghist, Pair pair) {
+  static_assert(NP % 4 == 0, "four 8-bit bins per register");
+  static_assert(TILE <= 255, "a bin of the tile's histogram is one byte");
+  constexpr int HS = PROFILE_CUTS_MAX + 1;  // bins (bytes) per row of the histogram
+  constexpr int HW = (TILE * HS + 3) / 4;   // its words
+  __shared__ T cuts_s[PROFILE_CUTS_MAX];
+  __shared__ uint32_t hist[HW];
+  const int tid = threadIdx.x;
+  const int ncuts = cuts.n, nbin = ncuts + 1;
+  auto clear = [&] {
+    for (int e = tid; e < HW; e += NT) hist[e] = 0;
+  };
+  auto add = [&](int r, int m) {
+    const int at = r * HS + m;
+    atomicAdd(&hist[at >> 2], 1u << (8 * (at & 3)));
+  };
+  // the non-zero bins of the histogram's rows into the table rows r0 + r (a non-zero bin: that row exists)
+  auto merge = [&](int64_t r0) {
+    for (int e = tid; e < TILE * ncuts; e += NT) {
+      const int r = e / ncuts, m = 1 + e % ncuts;
+      const int at = r * HS + m;
+      const int c = (int)((hist[at >> 2] >> (8 * (at & 3))) & 0xffu);
+      if (c) atomicAdd(&ghist[(r0 + r) * nbin + m], c);
+    }
+  };
+  if (tid < ncuts) cuts_s[tid] = cuts.c[tid];
+  clear();
+  __syncthreads();
+
+  uint32_t bins[NP / 4];
+#pragma unroll
+  for (int q = 0; q < NP / 4; ++q) bins[q] = 0;
+#pragma unroll
+  for (int e = 0; e < NP; ++e) {
+    int row, col;
+    const T s = pair(e, row, col);
+    const bool live = t.i0 + row < na && t.j0 + col < nb && (!weighted || s != T(0));
+    const int m = live ? profile_bin<T>(cuts_s, ncuts, s) : 0;
+    bins[e / 4] |= (uint32_t)m << (8 * (e % 4));
+    if (m) add(row, m);
+  }
+  __syncthreads();
+  merge(t.i0);
+  if constexpr (SYM) {
+    if (!t.mirror) return;  // uniform over the block
+    __syncthreads();
+    clear();
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < NP; ++e) {
+      const int m = (bins[e / 4] >> (8 * (e % 4))) & 0xff;
+      if (m) {
+        int row, col;
+        (void)pair(e, row, col);
+        add(col, m);
+      }
+    }
+    __syncthreads();
+    merge(t.j0);  // SYM: na == nb
   }
 }
 

@@ -2099,6 +2099,177 @@ def dot_csr(Fa, Fb=None, metric="cosine", alpha=None, weighted: bool = True, dty
     return _feature_pair_csr("dot", Fa, Fb, (_sim_metric(metric),), alpha, weighted, dtype, min_neighbours)
 
 
+PROFILE_CUTS_MAX = 32
+
+
+def _profile_cuts(cuts, dt) -> np.ndarray:
+    """The cuts of a profile as a contiguous vector of dt: 1..32 of them, nondecreasing, no NaN (ValueError otherwise).
+    Needs no device.  They are compared after the conversion to dt, as the library compares them."""
+    if cuts is None or cuts is Ellipsis:
+        raise TypeError("a cutoff profile needs cuts")
+    c = np.atleast_1d(np.asarray(cuts, dtype=np.float64))
+    if c.ndim != 1:
+        raise ValueError("cuts must be a vector")
+    if not 1 <= c.size <= PROFILE_CUTS_MAX:
+        raise ValueError(f"a profile takes 1..{PROFILE_CUTS_MAX} cuts, got {c.size}")
+    if np.isnan(c).any():
+        raise ValueError("a cut is NaN")
+    with np.errstate(over="ignore"):
+        c = np.ascontiguousarray(c.astype(dt))
+    if (c[1:] < c[:-1]).any():
+        raise ValueError("cuts must be sorted (nondecreasing)")
+    return c
+
+
+class CutoffProfile:
+    """What ``tanimoto_profile`` / ``jaccard_profile`` / ``dot_profile`` return: for every cut b, the size and the row
+    degrees of the graph the matching ``*_csr`` producer builds at ``alpha = cuts[b]``, from one pass over the pairs.
+
+    cuts      (ncuts,) the cuts, in the graph's dtype, ascending
+    nnz       (ncuts,) int64: the producer's nnz at each cut (exact also at and above 2^31, where the producer refuses)
+    degrees   (na, ncuts) int32: row i's entries at each cut, ``ptr[i + 1] - ptr[i]`` of the producer; numpy for host
+              input, a CUDA tensor for device input
+    shape     (na, nb)
+    symmetric Fb was None: the graph is Fa against itself and holds its diagonal, whose similarity is 1
+
+    The members below work on the host in numpy (device degrees are copied once per call)."""
+
+    def __init__(self, cuts, nnz, degrees, shape, symmetric=False):
+        self.cuts = np.asarray(cuts)
+        self.nnz = np.asarray(nnz, dtype=np.int64)
+        self.degrees = degrees
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.symmetric = bool(symmetric)
+
+    def __repr__(self):
+        return f"CutoffProfile(shape={self.shape}, cuts={self.cuts.tolist()}, nnz={self.nnz.tolist()})"
+
+    def _host_degrees(self) -> np.ndarray:
+        d = self.degrees
+        if _module_is_torch(d):
+            d = d.cpu().numpy()
+        return np.asarray(d).reshape(self.shape[0], self.cuts.size)
+
+    def fill(self) -> np.ndarray:
+        """nnz / (na * nb) per cut: the share of the pairs that are entries (0 for an empty shape)."""
+        pairs = self.shape[0] * self.shape[1]
+        if pairs == 0:
+            return np.zeros(self.cuts.size)
+        return self.nnz / float(pairs)
+
+    def coverage(self, min_degree: int = 1, exclude_self: bool = False) -> np.ndarray:
+        """Per cut, the share of rows with at least min_degree entries (0 when there are no rows): with the defaults the
+        rows that still have a neighbour, the quantity that trades against accuracy when alpha rises.  exclude_self
+        (symmetric profiles only) does not count a row's own diagonal entry: its similarity is 1, so it is an entry of
+        the graph exactly at the cuts <= 1, and there 1 is subtracted from every non-zero degree first."""
+        if exclude_self and not self.symmetric:
+            raise ValueError("exclude_self needs a symmetric profile (Fb=None)")
+        deg = self._host_degrees().astype(np.int64)
+        if deg.shape[0] == 0:
+            return np.zeros(self.cuts.size)
+        if exclude_self:
+            deg = np.maximum(deg - (self.cuts <= 1).astype(np.int64)[None, :], 0)
+        return (deg >= int(min_degree)).mean(axis=0)
+
+    def alpha_for_nnz(self, budget):
+        """The smallest cut whose nnz <= budget (the lowest alpha whose graph fits), None when none does."""
+        ok = np.flatnonzero(self.nnz <= budget)
+        return self.cuts[ok[0]].item() if ok.size else None
+
+    def alpha_for_mean_degree(self, k):
+        """The smallest cut whose mean row degree nnz / na <= k, None when none has."""
+        ok = np.flatnonzero(self.nnz <= k * self.shape[0])
+        return self.cuts[ok[0]].item() if ok.size else None
+
+
+def _profile_call(fn, head, na, nb, cuts, weighted, dev, device, symmetric):
+    """One ss_similarity_*_profile_* call: `head` are the operands up to the cuts."""
+    nc = cuts.size
+    tail = (cuts.ctypes.data, nc, 1 if weighted else 0)
+    if dev:
+        import torch
+        total = torch.zeros(nc, dtype=torch.int64, device=device)
+        deg = torch.zeros((na, nc), dtype=torch.int32, device=device)
+        L_.check(fn(*head, *tail, total.data_ptr(), deg.data_ptr(), L_.SS_MEM_DEVICE))
+        return CutoffProfile(cuts, total.cpu().numpy(), deg, (na, nb), symmetric)
+    total = np.zeros(nc, np.int64)
+    deg = np.zeros((na, nc), np.int32)
+    L_.check(fn(*head, *tail, total.ctypes.data, deg.ctypes.data, L_.SS_MEM_HOST))
+    return CutoffProfile(cuts, total, deg, (na, nb), symmetric)
+
+
+def tanimoto_profile(Fa, Fb=None, cuts=None, weighted: bool = True, dtype=np.float32):
+    """The cutoff profile of ``tanimoto_csr``: for up to 32 ascending cuts, the nnz and the row degrees of
+    ``tanimoto_csr(Fa, Fb, alpha=cut, weighted=weighted, dtype=dtype)`` at every cut, bit for bit, from ONE pass over
+    the pairs and without building a graph (the similarity of a pair does not depend on alpha).  Inputs as
+    ``tanimoto_csr``; returns a ``CutoffProfile``.  Cuts that are unsorted, NaN, none or more than 32 raise ValueError
+    (checked here, no device needed); equal cuts and +-inf are fine.  There is no 2^31 refusal: the profile answers at
+    cuts where the producer would refuse."""
+    dt = _feature_dtype(dtype)
+    c = _profile_cuts(cuts, dt)
+    fn = getattr(L_.lib(), f"ss_similarity_tanimoto_profile_{_suffix(dt)}")
+    dev = _is_torch(Fa)
+    keep = []
+    pa, na, nw = _fingerprints(Fa, dev, keep)
+    pb, nb, nwb = _fingerprints(Fb, dev, keep)
+    if Fb is None:
+        nb, nwb = na, nw
+    if nwb != nw:
+        raise ValueError("Fa and Fb have different fingerprint widths")
+    out = _profile_call(fn, (pa, na, pb, nb, nw), na, nb, c, weighted, dev, Fa.device if dev else None, Fb is None)
+    del keep
+    return out
+
+
+def _feature_profile(name, Fa, Fb, mid, cuts, weighted, dtype):
+    """ss_similarity_<name>_profile_*: `mid` are the arguments between d and the cuts."""
+    dt = _feature_dtype(dtype)
+    c = _profile_cuts(cuts, dt)
+    dev = _is_torch(Fa)
+    keep = []
+    pa, na, d, lda = _features(Fa, dt, dev, keep)
+    pb, nb, db, ldb = _features(Fb, dt, dev, keep)
+    if Fb is None:
+        nb, db, ldb = na, d, lda
+    if db != d:
+        raise ValueError("Fa and Fb have different numbers of features")
+    fn = getattr(L_.lib(), f"ss_similarity_{name}_profile_{_suffix(dt)}")
+    out = _profile_call(fn, (pa, na, lda, pb, nb, ldb, d) + tuple(mid), na, nb, c, weighted, dev,
+                        Fa.device if dev else None, Fb is None)
+    del keep
+    return out
+
+
+def jaccard_profile(Fa, Fb=None, cuts=None, weighted: bool = True, dtype=np.float32):
+    """The cutoff profile of ``jaccard_csr`` (weighted Jaccard of real-valued rows), as ``tanimoto_profile``.  A NaN
+    feature raises SimSpreadError, as in the producer."""
+    return _feature_profile("jaccard", Fa, Fb, (), cuts, weighted, dtype)
+
+
+def dot_profile(Fa, Fb=None, metric="cosine", cuts=None, weighted: bool = True, dtype=np.float32, storage=None):
+    """The cutoff profile of ``dot_csr`` (cosine / Tanimoto / Dice of real-valued rows on the matrix cores), as
+    ``tanimoto_profile``: inputs, metric, ``storage`` and the choice of the 16-bit route exactly as ``dot_csr`` with
+    ``min_neighbours=0`` (16-bit CUDA tensors and storage "bf16" / "f16" take it; dtype must then be float32).  In
+    symmetric mode the diagonal counts with s = 1 exactly, and the degrees are those of the bitwise symmetric matrix."""
+    m = _sim_metric(metric)
+    code = _h16_storage(storage, (Fa, Fb), dtype)
+    if code is None:
+        return _feature_profile("dot", Fa, Fb, (m,), cuts, weighted, dtype)
+    c = _profile_cuts(cuts, np.float32)
+    dev = _is_torch(Fa)
+    keep = []
+    pa, na, d, lda = _features_h16(Fa, code, dev, keep)
+    pb, nb, db, ldb = _features_h16(Fb, code, dev, keep)
+    if Fb is None:
+        nb, db, ldb = na, d, lda
+    if db != d:
+        raise ValueError("Fa and Fb have different numbers of features")
+    out = _profile_call(L_.lib().ss_similarity_dot_profile_h16, (pa, na, lda, pb, nb, ldb, d, code, m), na, nb, c,
+                        weighted, dev, Fa.device if dev else None, Fb is None)
+    del keep
+    return out
+
+
 def cutoff_csr(X, alpha: float, weighted: bool = False, dtype=np.float32, shape=None):
     """``featurize(X, alpha, weighted)`` on a sparse matrix, on the device: entry (i, j) with stored value v stays iff
     v >= alpha, as v when weighted and 1 otherwise (alpha > 0: the non-zeros of ``cutoff`` on the densified matrix).
