@@ -1159,10 +1159,29 @@ __global__ void abs_range_kernel(const T* __restrict__ v, int64_t n, int* __rest
 }
 
 // ------------------------------------------------------------------ CSR -> column-chunked CSR (stage-1 operand)
+// Class-pure tails (stage-1 operands, align 1 or 32).  Column j of a chunk has class j & 3, sub-row (chunk, row a) has
+// class a & 3.  A sub-row of n > 64 entries keeps in its tail, positions 64 .. 64 + t - 1 with t = min(n - 64, 16), only
+// entries of its own class: the transfer kernels fold the tails of four sub-rows of four different classes in one
+// plain LDS read-add-write, whose columns are then distinct by construction (transfer.hip, "tails").  The other entries
+// fill the head (positions 0 .. 63) and, from position 80 on, the rest.  A sub-row that owns m < t entries of its class
+// (filler case) stores a full tail of 16: its m entries, then 16 - m sentinels (column SC -- the first dummy word of
+// every kernel's sums, the padding column of the align-32 operand -- with value 0); everything else goes to the head
+// and the rest, so the stored length is n + 16 - m > 80.
+struct ChunkTail {
+  int real;     // entries of the sub-row's class in the tail
+  int len;      // positions of the tail region, sentinels included
+  int stored;   // stored length of the sub-row
+};
+__device__ __forceinline__ ChunkTail chunk_tail(int n, int m) {
+  const int t = n - 64 < 16 ? n - 64 : 16;
+  if (m >= t) return ChunkTail{t, t, n};
+  return ChunkTail{m, 16, n + 16 - m};
+}
+
 // one thread per (chunk, row): entries of the row inside the chunk
 __global__ void chunk_count_kernel(const int* __restrict__ ptr, const int* __restrict__ idx, int64_t rows, int SC,
-                                   int nchunks, int align, int* __restrict__ cnt, unsigned short* __restrict__ len16,
-                                   int* __restrict__ toolong) {
+                                   int nchunks, int align, int cls_tails, int* __restrict__ cnt,
+                                   unsigned short* __restrict__ len16, int* __restrict__ toolong) {
   const int64_t total = rows * nchunks;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int c = (int)(i / rows);
@@ -1174,24 +1193,55 @@ __global__ void chunk_count_kernel(const int* __restrict__ ptr, const int* __res
     const int first = a;
     b = hi;
     while (a < b) { const int m = (a + b) >> 1; if (idx[m] < k1) a = m + 1; else b = m; }
-    cnt[i] = (a - first + align - 1) / align;  // in units of `align` entries
-    if (len16) {                               // exact entry count of the sub-row (the units only give the padded length)
-      len16[i] = (unsigned short)(a - first);
-      if (a - first > 65535) *toolong = 1;
+    int n = a - first;
+    if (cls_tails && n > 64) {   // stored length: sentinels of the filler case included
+      const int cls = (int)(r & 3);
+      int m = 0;
+      for (int x = first; x < a; ++x) m += (int)(((idx[x] - k0) & 3) == cls);
+      n = chunk_tail(n, m).stored;
+    }
+    cnt[i] = (n + align - 1) / align;  // in units of `align` entries
+    if (len16) {                       // exact stored length of the sub-row (the units only give the padded length)
+      len16[i] = (unsigned short)n;
+      if (n > 65535) *toolong = 1;
     }
   }
 }
 
+// Bank schedule (stage-1 operand only) of the first n entries, 32 < n <= 64, of a sub-row, one per lane (col < 0: none).
+// The transfer kernel folds them into its LDS accumulators in one read-add-write, which the LDS serves in two groups
+// of 32 lanes, one cycle per group when the 32 addresses fall into different banks (bank = column mod 32) and one more
+// for every extra address on a busy bank.  The columns of a sub-row are distinct, so their order is free: sort the
+// entries by bank and deal them round-robin over the two lane groups -- a bank then meets a group twice only when more
+// than two of the columns share it.  The second group holds the remainder L = n - 32: the first 2 L entries alternate,
+// the rest go to the first group.  Returns the lane's position.
+__device__ __forceinline__ int chunk_sched_pos(int n, int col, int lane) {
+  const int bank = col < 0 ? -1 : (col & 31);
+  int p = 0, base = 0;   // p: entries in a lower bank, or in the same bank and a lower lane
+  for (int b = 0; b < 32; ++b) {
+    const unsigned long long m = __ballot(bank == b);
+    if (bank == b) p = base + __popcll(m & ((1ull << lane) - 1ull));
+    base += __popcll(m);
+  }
+  const int L = n - 32;
+  return p < 2 * L ? (p & 1) * 32 + (p >> 1) : L + (p - 2 * L);
+}
+
 // wave per (chunk, row): copy the sub-row with chunk-local indices, padded to whole units
-constexpr int CHUNK_SCHED_ITERS = 4;  // sub-rows of up to 256 entries are bank-scheduled, longer ones copied in order
 template <class T>
-__global__ void chunk_fill_kernel(const int* __restrict__ ptr, const int* __restrict__ idx, const T* __restrict__ val,
-                                  int64_t rows, int SC, int nchunks, int align, int sched,
-                                  const int* __restrict__ off, unsigned short* __restrict__ oidx, T* __restrict__ oval) {
+__global__ void __launch_bounds__(256) chunk_fill_kernel(const int* __restrict__ ptr, const int* __restrict__ idx,
+                                                         const T* __restrict__ val, int64_t rows, int SC, int nchunks,
+                                                         int align, int sched, int cls_tails,
+                                                         const int* __restrict__ off, unsigned short* __restrict__ oidx,
+                                                         T* __restrict__ oval) {
+  __shared__ int hcol[4][64];   // per wave: the head of a long sub-row, before it is scheduled
+  __shared__ T hval[4][64];
   const int lane = threadIdx.x & 63;
+  const int wv = (threadIdx.x >> 6) & 3;
   const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
   const int64_t total = rows * nchunks;
+  const unsigned long long below = (1ull << lane) - 1ull;
   for (int64_t i = wave0; i < total; i += nwaves) {
     const int c = (int)(i / rows);
     const int64_t r = i - (int64_t)c * rows;
@@ -1206,53 +1256,65 @@ __global__ void chunk_fill_kernel(const int* __restrict__ ptr, const int* __rest
     b = hi;
     while (a < b) { const int m = (a + b) >> 1; if (idx[m] < k1) a = m + 1; else b = m; }
     const int n = a - first;
-    if (sched && n > 32 && n <= 64 * CHUNK_SCHED_ITERS) {
-      // Bank schedule (stage-1 operand only).  The transfer kernel folds a sub-row into its LDS accumulators 64
-      // entries per read-add-write, which the LDS serves in two groups of 32 lanes, one cycle per group when the
-      // 32 addresses fall into different banks (bank = column mod 32) and one more for every extra address on a
-      // busy bank.  The columns of a sub-row are distinct, so their order is free: sort the entries by bank and
-      // deal them round-robin over the G = ceil(n/32) lane groups -- a bank then meets a group twice only when
-      // more than G of the sub-row's columns share it.  The last group holds the remainder L = n - 32(G-1): the
-      // first L*G entries go round all G groups, the rest round the first G-1.
-      const int G = (n + 31) >> 5;
-      const int L = n - 32 * (G - 1);
-      int cnt = 0;  // lane b < 32: entries of the sub-row in bank b
-      int bank[CHUNK_SCHED_ITERS], col[CHUNK_SCHED_ITERS];
-#pragma unroll
-      for (int j = 0; j < CHUNK_SCHED_ITERS; ++j) {
-        const int x = lane + 64 * j;
-        col[j] = x < n ? (int)(idx[first + x] - k0) : -1;
-        bank[j] = x < n ? (col[j] & 31) : -1;
+    if (cls_tails && n > 64) {
+      // tail first (entries of the sub-row's class, in column order), then the head (the first 64 of the others, bank-
+      // scheduled unless SS_CHUNK_SCHED=0), then the rest from position 80 on (in column order)
+      const int cls = (int)(r & 3);
+      int m = 0;
+      for (int x0 = 0; x0 < n; x0 += 64) {
+        const int x = x0 + lane;
+        m += __popcll(__ballot(x < n && ((idx[first + x] - k0) & 3) == cls));
       }
-      for (int b = 0; b < 32; ++b) {
-        int c = 0;
-#pragma unroll
-        for (int j = 0; j < CHUNK_SCHED_ITERS; ++j) c += __popcll(__ballot(bank[j] == b));
-        if (lane == b) cnt = c;
-      }
-      int base = 0;  // exclusive prefix of cnt over the banks
-      for (int b = 0; b < 31; ++b) {
-        const int c = __builtin_amdgcn_readlane(cnt, b);
-        if (lane > b) base += c;
-      }
-      int run = 0;  // lane b: entries of bank b placed so far
-#pragma unroll
-      for (int j = 0; j < CHUNK_SCHED_ITERS; ++j) {
-        int p = -1;
-        for (int b = 0; b < 32; ++b) {
-          const unsigned long long m = __ballot(bank[j] == b);
-          const int bb = __builtin_amdgcn_readlane(base, b) + __builtin_amdgcn_readlane(run, b);
-          if (bank[j] == b) p = bb + __popcll(m & ((1ull << lane) - 1ull));
-          if (lane == b) run += __popcll(m);
+      const ChunkTail tl = chunk_tail(n, m);
+      int seen_c = 0, seen_o = 0;   // entries of the class / other entries in front of this pass (wave-uniform)
+      for (int x0 = 0; x0 < n; x0 += 64) {
+        const int x = x0 + lane;
+        const bool valid = x < n;
+        const int col = valid ? (int)(idx[first + x] - k0) : 0;
+        const T v = valid ? val[first + x] : T(0);
+        const unsigned long long mc = __ballot(valid && (col & 3) == cls);
+        const int rc = seen_c + __popcll(mc & below);
+        const bool in_tail = valid && (col & 3) == cls && rc < tl.real;
+        const unsigned long long mo = __ballot(valid && !in_tail);
+        const int ro = seen_o + __popcll(mo & below);
+        if (in_tail) {
+          oidx[o + 64 + rc] = (unsigned short)col;
+          oval[o + 64 + rc] = v;
+        } else if (valid) {
+          if (ro < 64) {
+            hcol[wv][ro] = col;
+            hval[wv][ro] = v;
+          } else {
+            oidx[o + 16 + ro] = (unsigned short)col;
+            oval[o + 16 + ro] = v;
+          }
         }
-        if (p >= 0) {
-          int grp, slot;
-          if (p < L * G) { grp = p % G; slot = p / G; }
-          else { const int q = p - L * G; grp = q % (G - 1); slot = L + q / (G - 1); }
-          const int pos = grp * 32 + slot;
-          oidx[o + pos] = (unsigned short)col[j];
-          oval[o + pos] = val[first + lane + 64 * j];
-        }
+        seen_c += __popcll(mc);
+        seen_o += __popcll(mo);
+      }
+      for (int x = tl.real + lane; x < tl.len; x += 64) {   // filler case: sentinels
+        oidx[o + 64 + x] = (unsigned short)SC;
+        oval[o + 64 + x] = T(0);
+      }
+      __builtin_amdgcn_wave_barrier();   // (the wave's own LDS operations execute in order)
+      const int hc = hcol[wv][lane];
+      const T hv = hval[wv][lane];
+      __builtin_amdgcn_wave_barrier();
+      const int pos = sched ? chunk_sched_pos(64, hc, lane) : lane;
+      oidx[o + pos] = (unsigned short)hc;
+      oval[o + pos] = hv;
+      for (int x = tl.stored + lane; x < npad; x += 64) {   // padded sub-rows (align 32) end in zero entries
+        oidx[o + x] = (unsigned short)SC;
+        oval[o + x] = T(0);
+      }
+      continue;
+    }
+    if (sched && n > 32 && n <= 64) {
+      const int col = lane < n ? (int)(idx[first + lane] - k0) : -1;
+      const int pos = chunk_sched_pos(n, col, lane);
+      if (lane < n) {
+        oidx[o + pos] = (unsigned short)col;
+        oval[o + pos] = val[first + lane];
       }
       // the scheduled entries occupy positions [0, n); padded sub-rows (align 32) end in zero entries
       for (int x = n + lane; x < npad; x += 64) {
@@ -1292,6 +1354,8 @@ int chunked_build(const DevCsr<T>& in, int SC, int align, DevChunked<T>& out) {
   }
   DevBuf<int> cnt;
   SS_TRY(cnt.alloc(total));
+  // stage-1 operands (align 1 or 32): class-pure tails, which the transfer kernels rely on -- not a switch
+  const int cls_tails = (align == 1 || align == 32) ? 1 : 0;
   DevBuf<int> toolong;
   if (align == 32) {   // the flat-stream transfer kernel walks exact sub-row lengths (starts stay sector-aligned)
     SS_TRY(out.len.alloc(total));
@@ -1299,7 +1363,7 @@ int chunked_build(const DevCsr<T>& in, int SC, int align, DevChunked<T>& out) {
     SS_HIP(hipMemsetAsync(toolong.p, 0, sizeof(int), st));
   }
   hipLaunchKernelGGL(chunk_count_kernel, dim3(grid_for(total, 256)), dim3(256), 0, st, in.ptr.p, in.idx.p, in.rows, SC,
-                     out.nchunks, align, cnt.p, align == 32 ? out.len.p : (unsigned short*)nullptr,
+                     out.nchunks, align, cls_tails, cnt.p, align == 32 ? out.len.p : (unsigned short*)nullptr,
                      align == 32 ? toolong.p : (int*)nullptr);
   SS_LAUNCH_CHECK();
   if (align == 32) {
@@ -1334,10 +1398,10 @@ int chunked_build(const DevCsr<T>& in, int SC, int align, DevChunked<T>& out) {
   SS_TRY(out.val.alloc(out.stored + 256));
   SS_HIP(hipMemsetAsync(out.idx.p + out.stored, 0, 256 * sizeof(unsigned short), st));
   SS_HIP(hipMemsetAsync(out.val.p + out.stored, 0, 256 * sizeof(T), st));
-  // entry order inside a sub-row: bank-scheduled for the stage-1 operands (align 1 or 32) unless SS_CHUNK_SCHED=0
-  const int sched = ((align == 1 || align == 32) && !env_off("SS_CHUNK_SCHED")) ? 1 : 0;
+  // order of a sub-row's first 64 entries: bank-scheduled for the stage-1 operands unless SS_CHUNK_SCHED=0
+  const int sched = (cls_tails && !env_off("SS_CHUNK_SCHED")) ? 1 : 0;
   hipLaunchKernelGGL(chunk_fill_kernel<T>, dim3(grid_for(total * 64, 256)), dim3(256), 0, st, in.ptr.p, in.idx.p,
-                     in.val.p, in.rows, SC, out.nchunks, align, sched, out.off.p, out.idx.p, out.val.p);
+                     in.val.p, in.rows, SC, out.nchunks, align, sched, cls_tails, out.off.p, out.idx.p, out.val.p);
   SS_LAUNCH_CHECK();
   SS_HIP(hipStreamSynchronize(st));
   return SS_OK;

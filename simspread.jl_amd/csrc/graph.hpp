@@ -72,11 +72,13 @@ struct DevChunked {
   bool binary = false;         // every stored value == 1 (unweighted features): kernels may skip the value stream
   int SC = 0, nchunks = 0;
   int align = 1;               // sub-rows padded to whole units of `align` entries; off[] counts units.
-                               // Padding entries carry local index SC (a zero operand row) and value 0.
+                               // Padding entries carry local index SC (a zero operand row) and value 0; so do
+                               // the sentinels in the class-pure tails of the stage-1 operands (align 1, 32:
+                               // a sub-row's stored length can exceed its entry count, see chunk_tail).
   DevBuf<int> off;             // [nchunks*rows + 1]
   DevBuf<unsigned short> idx;  // [stored + 64]
   DevBuf<T> val;               // [stored + 64]
-  DevBuf<unsigned short> len;  // align 32 only: exact entry count of every sub-row [nchunks*rows]
+  DevBuf<unsigned short> len;  // align 32 only: exact stored length of every sub-row [nchunks*rows]
   bool len_ok = false;         //   ... all of them < 65536
   float vmax = 0.f, vmin = 0.f;  // largest / smallest non-zero |value|
 };

@@ -230,25 +230,32 @@ __device__ __forceinline__ void subrows_fold_any(const SubRows<T, U>& s, T* acc,
 
 // ---------------------------------------------------------------- tails: entries 64.. of the long sub-rows of a group
 // With the chunk sized for a mean sub-row of ~60 entries, ~40 % of the sub-rows are longer than one wave, by ~6 entries.
-// Their entries 64..79 are taken once per group of 64 neighbours, after the heads, FOUR sub-rows to a load pair: the
-// group's long sub-rows are compacted to the low lanes (one lane permutation of start, length and coefficient per
-// group: no scalar work per sub-row), round r serves the long sub-rows 4r .. 4r+3, lane group g = lane >> 4 the
-// sub-row 4r + g with its 16 lanes.  A group without a long sub-row (sub-rows of ~40 entries, C3) pays one ballot and
-// one branch.  The four tails of a round are folded one after the other: the columns inside a sub-row are distinct,
-// those of different sub-rows are not, so tails never share a plain read-add-write (the fixed-point fold adds all four
-// in one integer atomic).  Lanes outside the group, past the end of the tail, or of a slot past the last long sub-row
-// (it holds a short one: nothing past position 64) go to their dummy word.  Entries from position 80 on (~1 % of the
-// sub-rows at 62.5 +- 7.7 entries) take the rest loop, bounds re-read by lane index.
-// Order of a group's sums: heads in neighbour order, tails in neighbour order, rests in neighbour order -- a fixed
+// Their entries 64..79 are taken once per group of 64 neighbours, after the heads, FOUR sub-rows to a load pair AND to a
+// read-add-write pair.  What keeps the four apart is the operand (assemble.hip, "class-pure tails"): the tail of the
+// sub-row of operand row a holds only columns j with (j & 3) == (a & 3) -- or sentinels on the first dummy word -- so
+// tails of four different classes a & 3 have pairwise distinct columns.  The group's long sub-rows are compacted by
+// class (four ballots and one lane permutation of start, length and coefficient per group: no scalar work per
+// sub-row): the k-th long sub-row of class c, in neighbour order, goes to slot 4k + c; round r serves slots 4r .. 4r+3,
+// lane group g = lane >> 4 the slot 4r + g, i.e. a sub-row of class g, with its 16 lanes.  Rounds = the largest class
+// count.  A group without a long sub-row (sub-rows of ~40 entries, C3) pays one ballot and one branch.  Lanes past the
+// end of the tail or of a slot that no sub-row took (length forced to 0: the permutation's result in a lane nobody
+// writes is not relied on) go to their dummy word; the fixed-point fold adds the round in one integer atomic.  Entries
+// from position 80 on (~1 % of the sub-rows at 62.5 +- 7.7 entries) take the rest loop, bounds re-read by lane index;
+// so does, from position 64, a long sub-row beyond the 16th of its class in the group (overflow).
+// Order of a column's sums inside a group: heads in neighbour order; tails in neighbour order (a column only meets
+// tails of its own class, one per round); then the rests and the overflowing sub-rows in neighbour order -- a fixed
 // function of the row's neighbour list.
-// AHEAD rounds are fetched together; the first AHEAD of a group fly while its heads are folded.  Measured at C2
-// (profiles/stage1_tails_time.json): 4 with pattern-only operands (one register a round), 2 with values (4 rounds
-// take the U = 8 kernel from 6 to 5 waves per SIMD: 1.39 instead of 1.33 ms).
+// AHEAD rounds are fetched together; the first AHEAD of a group fly while its heads are folded: 4 with pattern-only
+// operands (one register a round), 3 with values (2 in the opt-in DUAL / FIX / BUF and block kernels, as before the classes).  By class a group has ~8.9 rounds where it had 6.6, so with values
+// one more round per flight pays (C2 stage 1: 1.273 ms with 2, 1.265 ms with 3, profiles/stage1_tail_classes_time.json)
+// and fits: the U = 8 kernel holds 78 registers with 3 (6 waves per SIMD) and 81 with 4 (5 waves; before the classes
+// 4 rounds measured 1.39 instead of 1.33 ms, profiles/stage1_tails_time.json).
 template <class T, int AHEAD>
 struct Tails {
   static constexpr int TAIL_AHEAD = AHEAD;
-  int nt;      // long sub-rows of the group (wave-uniform)
-  int cb, cn;  // lane i: start and length of the i-th long sub-row, i < nt; the short ones follow
+  int nr;                  // rounds of the group (wave-uniform); 0: no long sub-row
+  unsigned long long ovf;  // long sub-rows without a slot (wave-uniform)
+  int cb, cn;              // lane s: start and length of the sub-row in slot s; length 0 in an empty slot
   T ccf;
   unsigned short tj[TAIL_AHEAD];
   T tv[TAIL_AHEAD];
@@ -259,23 +266,41 @@ template <class T, int TAIL_AHEAD, class LD>
 __device__ __forceinline__ void tails_fetch(Tails<T, TAIL_AHEAD>& t, int r0, int lane, LD&& ld) {
 #pragma unroll
   for (int i = 0; i < TAIL_AHEAD; ++i) {
-    if (4 * (r0 + i) >= t.nt) break;
+    if (r0 + i >= t.nr) break;
     const unsigned b = (unsigned)__builtin_amdgcn_ds_bpermute((4 * (r0 + i) + (lane >> 4)) * 4, t.cb);
     ld(b + 64u + (unsigned)(lane & 15), t.tj[i], t.tv[i]);   // (any start + 80 is inside the operand and its slack)
     __builtin_amdgcn_sched_barrier(0);
   }
 }
 
-// compaction of the group's long sub-rows, and the loads of the first rounds
+// compaction of the group's long sub-rows by class (a_l: the lane's operand row), and the loads of the first rounds
 template <class T, int TAIL_AHEAD, class LD>
-__device__ __forceinline__ void tails_begin(Tails<T, TAIL_AHEAD>& t, int b_l, int n_l, T cf_l, int lane, LD&& ld) {
-  const unsigned long long longs = __ballot(n_l > 64);
-  t.nt = __builtin_popcountll(longs);
-  if (t.nt == 0) return;
-  const int k = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(longs >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)longs, 0u));
-  const int to4 = (n_l > 64 ? k : t.nt + lane - k) * 4;   // a permutation of the 64 lanes
-  t.cb = __builtin_amdgcn_ds_permute(to4, b_l);
-  t.cn = __builtin_amdgcn_ds_permute(to4, n_l);
+__device__ __forceinline__ void tails_begin(Tails<T, TAIL_AHEAD>& t, int a_l, int b_l, int n_l, T cf_l, int lane, LD&& ld) {
+  const bool lng = n_l > 64;
+  const unsigned long long longs = __ballot(lng);
+  t.nr = 0;
+  if (longs == 0ull) return;
+  const int cls = a_l & 3;
+  int k = 0, rounds = 0, fewest = 16, spare = 0, taken = 0;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const unsigned long long mc = __ballot(lng && cls == c);
+    const int kc = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mc >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mc, 0u));
+    int cc = __builtin_popcountll(mc);
+    cc = cc < 16 ? cc : 16;
+    k = cls == c ? kc : k;
+    rounds = cc > rounds ? cc : rounds;
+    if (cc < fewest) { fewest = cc; spare = 4 * cc + c; }   // a slot nobody takes (none only when all 64 are taken)
+    taken = (lane & 3) == c ? cc : taken;                   // slot s is taken when (s >> 2) < count of class s & 3
+  }
+  const bool placed = lng && k < 16;
+  t.nr = rounds;
+  t.ovf = __ballot(lng && k >= 16);
+  const int to4 = (placed ? 4 * k + cls : spare) * 4;       // every lane without a slot writes the spare one
+  const bool mine = (lane >> 2) < taken;
+  const int pb = __builtin_amdgcn_ds_permute(to4, b_l), pn = __builtin_amdgcn_ds_permute(to4, n_l);
+  t.cb = mine ? pb : 0;
+  t.cn = mine ? pn : 0;
   t.ccf = BitsOf<T>::push(to4, cf_l);
   tails_fetch(t, 0, lane, ld);
 }
@@ -284,12 +309,12 @@ template <class T, bool BINM, bool FIX, int TAIL_AHEAD, class LD>
 __device__ __forceinline__ void tails_finish(Tails<T, TAIL_AHEAD>& t, int b_l, int n_l, T cf_l, T* __restrict__ acc, int dummy,
                                              const unsigned short* __restrict__ midx, const T* __restrict__ mval, int lane,
                                              LD&& ld) {
-  if (t.nt == 0) return;
-  for (int r0 = 0; 4 * r0 < t.nt; r0 += TAIL_AHEAD) {
+  if (t.nr == 0) return;
+  for (int r0 = 0; r0 < t.nr; r0 += TAIL_AHEAD) {
     if (r0 > 0) tails_fetch(t, r0, lane, ld);
 #pragma unroll
     for (int i = 0; i < TAIL_AHEAD; ++i) {
-      if (4 * (r0 + i) >= t.nt) break;
+      if (r0 + i >= t.nr) break;
       const int from4 = (4 * (r0 + i) + (lane >> 4)) * 4;
       const int tn = __builtin_amdgcn_ds_bpermute(from4, t.cn) - 64;   // entries past position 64 (<= 0: none); may exceed 16
       const T tcf = BitsOf<T>::pull(from4, t.ccf);
@@ -298,22 +323,20 @@ __device__ __forceinline__ void tails_finish(Tails<T, TAIL_AHEAD>& t, int b_l, i
         atomicAdd(reinterpret_cast<unsigned*>(acc) + (live ? (int)t.tj[i] : dummy),
                   (unsigned)cvt_rpi(live ? (float)(tcf * t.tv[i]) : 0.f));
       } else {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int j = (live && (lane >> 4) == g) ? (int)t.tj[i] : dummy;
-          acc[j] = fma(tcf, t.tv[i], acc[j]);
-        }
+        const int j = live ? (int)t.tj[i] : dummy;   // the four tails of the round: four classes, distinct columns
+        acc[j] = fma(tcf, t.tv[i], acc[j]);
       }
     }
   }
-  unsigned long long m = __ballot(n_l > 80);
+  // rests from position 80; overflowing sub-rows whole from position 64
+  unsigned long long m = __ballot(n_l > 80) | t.ovf;
   while (m != 0ull) {
     const int src = __builtin_ctzll(m);
     m &= m - 1ull;
     const int n = __builtin_amdgcn_readlane(n_l, src);
     const unsigned b = (unsigned)__builtin_amdgcn_readlane(b_l, src);
     const T cf = BitsOf<T>::bcast(cf_l, src);
-    for (int x = 80 + lane; x < n; x += 64) {
+    for (int x = (((t.ovf >> src) & 1ull) ? 64 : 80) + lane; x < n; x += 64) {
       const int j = midx[b + x];
       const T v = BINM ? T(1) : mval[b + x];
       if constexpr (FIX) atomicAdd(reinterpret_cast<unsigned*>(acc) + j, (unsigned)cvt_rpi((float)(cf * v)));
@@ -405,18 +428,18 @@ __global__ void __launch_bounds__(TRANSFER_THREADS) transfer_kernel(TransferArgs
     for (int g0 = lb; g0 < le; g0 += 64) {
       // ---- the next 64 neighbours a of r, one per lane: coefficient and sub-row bounds
       const int q = g0 + lane;
-      int b_l = 0, n_l = 0;
+      int a_l = 0, b_l = 0, n_l = 0;   // a_l: the neighbour, i.e. the operand row (its class cuts the tails)
       T cf_l = T(0);
       if constexpr (COEF) {
         if (q < le) {
-          const int a = L.idx[q];
+          const int a = a_l = L.idx[q];
           cf_l = p.coef[t][q];
           const int o0 = off[a], o1 = off[a + 1];
           b_l = o0;
           n_l = cf_l != T(0) ? o1 - o0 : 0;
         }
       } else if (q < le) {
-        const int a = L.idx[q];
+        const int a = a_l = L.idx[q];
         const T lv = L.val[q];
         if (LOO) {
           const int d = p.kf[a] - 1;  // the query leaves every feature column it touched
@@ -451,8 +474,8 @@ __global__ void __launch_bounds__(TRANSFER_THREADS) transfer_kernel(TransferArgs
           v = BINM ? T(1) : mval[e];
         }
       };
-      Tails<T, (BINM ? 4 : 2)> tails;
-      tails_begin(tails, b_l, n_l, cf_l, lane, tail_ld);
+      Tails<T, (BINM ? 4 : (DUAL || FIX || BUF) ? 2 : 3)> tails;   // (3 was measured on the default family only)
+      tails_begin(tails, a_l, b_l, n_l, cf_l, lane, tail_ld);
       load(A, 0);
       for (int u0 = 0; u0 < cnt; u0 += 2 * U) {
         if (u0 + U < cnt) load(B, u0 + U);
@@ -471,7 +494,7 @@ __global__ void __launch_bounds__(TRANSFER_THREADS) transfer_kernel(TransferArgs
     const int* off = M.off + (int64_t)c * M.rows;
     for (int x = off[gr] + lane; x < off[gr + 1]; x += 64) {
       const int j = M.idx[x];
-      atomicOr(&bits[j >> 5], 1u << (j & 31));
+      if (j < p.SC) atomicOr(&bits[j >> 5], 1u << (j & 31));   // (not a tail's sentinel)
     }
   }
   __syncthreads();
@@ -498,7 +521,7 @@ constexpr int TRANSFER_U = 8;
 static bool transfer_dual() { return env_int("SS_TRANSFER_DUAL", 0) != 0; }
 
 // sub-rows in flight per wave: 8.  Until the tails left the batch small weighted operands took 4, which
-// reached 30 instead of 20 single-wave workgroups per CU (55 instead of 90 registers); now U = 8 holds 77 registers
+// reached 30 instead of 20 single-wave workgroups per CU (55 instead of 90 registers); now U = 8 holds 78 registers
 // (24 workgroups per CU) and measures faster everywhere: C2 weighted 1.33 vs 1.37 ms, pattern-only 1.15 vs 1.19 ms
 // (profiles/stage1_tails_time.json).  SS_TRANSFER_U overrides.
 static int transfer_u() {
@@ -662,10 +685,10 @@ __global__ void __launch_bounds__(1024) transfer_block_kernel(TransferArgs<T> p,
   }
   for (int g0 = lb; g0 < le; g0 += 64) {
     const int q = g0 + lane;
-    int b_l = 0, n_l = 0;
+    int a_l = 0, b_l = 0, n_l = 0;
     T cf_l = T(0);
     if (q < le) {
-      const int a = L.idx[q];
+      const int a = a_l = L.idx[q];
       cf_l = coef[q];
       if constexpr (FIX) cf_l = (T)((float)cf_l * scale);   // exact: a power of two
       if (cf_l != T(0)) {
@@ -684,7 +707,7 @@ __global__ void __launch_bounds__(1024) transfer_block_kernel(TransferArgs<T> p,
       v = BINM ? T(1) : mval[e];
     };
     Tails<T, (BINM ? 4 : 2)> tails;
-    tails_begin(tails, b_l, n_l, cf_l, lane, tail_ld);
+    tails_begin(tails, a_l, b_l, n_l, cf_l, lane, tail_ld);
     load(A, 0);
     for (int u0 = 0; u0 < cnt; u0 += 2 * U) {
       if (u0 + U < cnt) load(B, u0 + U);
