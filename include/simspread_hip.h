@@ -709,6 +709,7 @@ int ss_spmat_cost(const ss_spmat* w, int64_t B, double* bytes, double* flops);
 #include "simspread_hip_clusters.h"
 #include "simspread_hip_target_rank.h"
 #include "simspread_hip_half.h"
+#include "simspread_hip_int8.h"
 #include "simspread_hip_profile.h"
 
 #endif /* SIMSPREAD_HIP_H */

@@ -14,9 +14,9 @@ from .engine import (BINARY_ROWS_FIELDS, POOLED_FIELDS, RANK_ROWS_FIELDS, TARGET
                      CutoffProfile, Pool,
                      TargetRank, TargetTopL, ButinaClusters, binary_metrics_rows, butina_clusters, cluster_folds, cross_fold_edges,
                      cutoff_csr,
-                     dot_csr, dot_kth, dot_profile, jaccard_csr, jaccard_kth, jaccard_profile,
+                     dot_csr, dot_kth, dot_kth_i8, dot_profile, jaccard_csr, jaccard_kth, jaccard_profile,
                      jaccard_similarity, pack_fingerprints, rank_metrics, rank_metrics_rows, tanimoto_csr, tanimoto_kth, tanimoto_profile,
-                     to_bf16_bits, topl)
+                     quantize_i8, to_bf16_bits, topl)
 from .metrics import (AuPRC, AuROC, BEDROC, ROCNums, accuracy, balancedaccuracy, f1score, maxperformance, mcc,
                       meanperformance, meanstdperformance, precision, recall, roc, validity_ratio)
 
@@ -26,4 +26,4 @@ __all__ = ["NamedMatrix", "Network", "DeviceGraph", "DeviceQueries", "DeviceSpMa
            "f1score", "mcc", "accuracy", "balancedaccuracy", "recall", "precision", "maxperformance", "meanperformance",
            "meanstdperformance", "ButinaClusters", "butina_clusters", "cluster_folds", "cross_fold_edges", "split_clusters", "TargetRank", "TARGET_RANK_FIELDS",
            "target_rank", "target_rank_positives", "to_bf16_bits", "CutoffProfile", "tanimoto_profile", "jaccard_profile",
-           "dot_profile"]
+           "dot_profile", "quantize_i8", "dot_kth_i8"]

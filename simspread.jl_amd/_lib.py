@@ -20,6 +20,7 @@ CLUSTERS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simsprea
 TARGET_RANK_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_target_rank.h")          # too
 HALF_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_half.h")                        # too
 PROFILE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_profile.h")                  # too
+INT8_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simspread_hip_int8.h")                        # too
 
 SS_OK = 0
 SS_MEM_HOST, SS_MEM_DEVICE = 0, 1
@@ -273,6 +274,24 @@ def _profile_sigs():
 PROFILE_SIGNATURES = _profile_sigs()
 
 
+def _int8_sigs():
+    """include/simspread_hip_int8.h: the inner-product producer and its neighbour floor on int8 row-major rows (k after
+    alpha, as in the floor entry points of the real-valued producers)"""
+    f32 = C.c_float
+    return {
+        "ss_similarity_dot_csr_i8": ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, f32, _int, _int, _vp, _vp, _vp, _i64,
+                                      _vp, _int], _int),
+        "ss_similarity_dot_kth_i8": ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _int, _vp, _int], _int),
+        "ss_graph_create_vectors_i8": ([_i64] * 4 + [_int, _vp, _i64, _vp, _i64] + [_vp] * 3
+                                       + [_int, f32, _int, _int, _int, _vp], _int),
+        "ss_queries_create_vectors_i8": ([_vp, _i64, _i64, _i64, _int, _vp, _i64, _vp, _i64, f32, _int, _int, _int, _vp],
+                                         _int),
+    }
+
+
+INT8_SIGNATURES = _int8_sigs()
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function the C header declares (used by the symbol-export test)."""
     with open(path) as f:
@@ -316,6 +335,11 @@ def profile_header_symbols():
     return header_symbols(PROFILE_HEADER_PATH)
 
 
+def int8_header_symbols():
+    """Every function include/simspread_hip_int8.h declares."""
+    return header_symbols(INT8_HEADER_PATH)
+
+
 def load():
     """dlopen the library (no GPU needed for this step)."""
     global _lib
@@ -329,7 +353,8 @@ def load():
     for name, (args, res) in (list(SIGNATURES.items()) + list(SCREENING_SIGNATURES.items())
                               + list(NEIGHBOUR_SIGNATURES.items()) + list(REAL_NEIGHBOUR_SIGNATURES.items())
                               + list(CLUSTER_SIGNATURES.items()) + list(TARGET_RANK_SIGNATURES.items())
-                              + list(HALF_SIGNATURES.items()) + list(PROFILE_SIGNATURES.items())):
+                              + list(HALF_SIGNATURES.items()) + list(PROFILE_SIGNATURES.items())
+                              + list(INT8_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res

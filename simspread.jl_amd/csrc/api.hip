@@ -875,6 +875,128 @@ static int graph_create_vectors_h16_impl(int64_t nq, int64_t ns, int64_t nt, int
       h16_tag(false), y_ptr, y_idx, y_val, index_base, mem, out);
 }
 
+// ------------------- int8 rows (include/simspread_hip_int8.h): ROW-MAJOR signed bytes -> DotCsrI8, fp32 CSR
+static const FeatureNames i8_names = {"dot_i8", "dot_i8_sym", "dot_i8_cross", "dot_i8_floor_sym", "dot_i8_floor_cross",
+                                      "dot_i8_kth"};
+constexpr int64_t I8_D_MAX = 131071;  // d * 2^14 <= 2^31 - 1: the three sums are exact in int32
+// what the int8 entry points refuse before anything is read, staged or written (k_min: 0, or 1 for the selection alone)
+static int check_i8_args(int metric, int64_t d, float alpha, int k, int k_min) {
+  if (metric != SS_SIM_COSINE && metric != SS_SIM_TANIMOTO && metric != SS_SIM_DICE)
+    return fail(SS_EINVAL, "dot_i8: metric %d is not SS_SIM_COSINE, SS_SIM_TANIMOTO or SS_SIM_DICE", metric);
+  if (d < 0) return fail(SS_EINVAL, "dot_i8: negative feature count");
+  if (d > I8_D_MAX)
+    return fail(SS_EINVAL, "dot_i8: %lld features; the sums are exact in int32 up to d = %lld", (long long)d,
+                (long long)I8_D_MAX);
+  if (alpha != alpha) return fail(SS_EINVAL, "dot_i8: alpha is NaN");
+  if (k < k_min || k > NEIGHBOUR_K_MAX)
+    return fail(SS_EINVAL, "dot_i8: k = %d outside %d..%d", k, k_min, NEIGHBOUR_K_MAX);
+  return SS_OK;
+}
+static int check_rows_i8(const char* what, const int8_t* F, int64_t n, int64_t ld, int64_t d) {
+  if (n < 0) return fail(SS_EINVAL, "%s: negative row count", what);
+  if (n >= (1LL << 31)) return fail(SS_EUNSUPPORTED, "%s: %lld rows (>= 2^31)", what, (long long)n);
+  if (ld < d) return fail(SS_EINVAL, "%s: leading dimension %lld < %lld features (int8 rows are row-major)", what,
+                          (long long)ld, (long long)d);
+  if (n > 0 && d > 0 && !F) return fail(SS_EINVAL, "%s is NULL", what);
+  return SS_OK;
+}
+// rows on the device: the caller's buffer (SS_MEM_DEVICE) or a staged copy with ld = d; of a host row only its d bytes
+// are read
+static int stage_rows_i8(const int8_t* F, int64_t n, int64_t ld, int64_t d, int mem, DevBuf<int8_t>& buf,
+                         const int8_t** dev, int64_t* dev_ld) {
+  if (mem == SS_MEM_DEVICE || n == 0 || d == 0) {
+    *dev = F;
+    *dev_ld = ld;
+    return SS_OK;
+  }
+  SS_TRY(buf.alloc((size_t)n * (size_t)d));
+  SS_HIP(hipMemcpy2DAsync(buf.p, d, F, ld, d, n, hipMemcpyHostToDevice, ctx().stream));
+  *dev = buf.p;
+  *dev_ld = d;
+  return SS_OK;
+}
+
+static int dot_csr_i8_impl(const int8_t* Fa, int64_t na, int64_t lda, const int8_t* Fb, int64_t nb, int64_t ldb,
+                           int64_t d, int metric, float alpha, int k, int weighted, int64_t* ptr, int32_t* idx,
+                           float* val, int64_t capacity, int64_t* nnz, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  path_note().clear();
+  const bool sym = (Fb == nullptr);
+  if (sym) {
+    nb = na;
+    ldb = lda;
+  }
+  SS_TRY(check_i8_args(metric, d, alpha, k, 0));
+  SS_TRY(check_rows_i8("Fa", Fa, na, lda, d));
+  if (!sym) SS_TRY(check_rows_i8("Fb", Fb, nb, ldb, d));
+  if (!ptr || !nnz) return fail(SS_EINVAL, "dot_i8: ptr and nnz must not be NULL");
+  DevBuf<int8_t> ba, bb;
+  const int8_t *da = nullptr, *db = nullptr;
+  int64_t la = 0, lb = 0;
+  SS_TRY(stage_rows_i8(Fa, na, lda, d, mem, ba, &da, &la));
+  if (!sym) SS_TRY(stage_rows_i8(Fb, nb, ldb, d, mem, bb, &db, &lb));
+  DotCsrI8 p;
+  SS_TRY(p.count(da, na, la, sym ? nullptr : db, nb, lb, d, metric, alpha, weighted != 0, k));
+  path_add(i8_names.tag(sym, k));
+  return emit_pair_csr<float>(p, na, ptr, idx, val, capacity, nnz, mem);
+}
+
+// the order of the checks and the empty inputs are those of features_kth_impl
+static int dot_kth_i8_impl(const int8_t* Fa, int64_t na, int64_t lda, const int8_t* Fb, int64_t nb, int64_t ldb,
+                           int64_t d, int metric, int k, float* tau, int mem) {
+  SS_TRY(require_init());
+  SS_TRY(check_mem(mem));
+  path_note().clear();
+  const bool sym = (Fb == nullptr);
+  if (sym) {
+    nb = na;
+    ldb = lda;
+  }
+  SS_TRY(check_i8_args(metric, d, 0.0f, k, 1));
+  SS_TRY(check_rows_i8("Fa", Fa, na, lda, d));
+  if (!sym) SS_TRY(check_rows_i8("Fb", Fb, nb, ldb, d));
+  if (na > 0 && !tau) return fail(SS_EINVAL, "dot_i8 kth: tau must not be NULL");
+  path_add(i8_names.tag_kth);
+  if (na == 0) return SS_OK;
+  DevBuf<int8_t> ba, bb;
+  const int8_t *da = nullptr, *db = nullptr;
+  int64_t la = 0, lb = 0;
+  SS_TRY(stage_rows_i8(Fa, na, lda, d, mem, ba, &da, &la));
+  if (!sym) SS_TRY(stage_rows_i8(Fb, nb, ldb, d, mem, bb, &db, &lb));
+  hipStream_t st = ctx().stream;
+  DevBuf<float> dt;
+  float* dtau = tau;
+  if (mem == SS_MEM_HOST) {
+    SS_TRY(dt.alloc(na));
+    dtau = dt.p;
+  }
+  SS_TRY(dot_kth_i8(da, na, la, sym ? nullptr : db, nb, lb, d, metric, nullptr, nullptr, k, dtau));
+  if (mem == SS_MEM_HOST) SS_HIP(hipMemcpyAsync(tau, dtau, (size_t)na * sizeof(float), hipMemcpyDeviceToHost, st));
+  SS_HIP(hipStreamSynchronize(st));
+  return SS_OK;
+}
+
+static int graph_create_vectors_i8_impl(int64_t nq, int64_t ns, int64_t nt, int64_t d, int metric, const int8_t* Fq,
+                                        int64_t ldq, const int8_t* Fs, int64_t lds_, const int64_t* y_ptr,
+                                        const int32_t* y_idx, const float* y_val, int index_base, float alpha, int k,
+                                        int weighted, int mem, ss_graph** out) {
+  SS_TRY(graph_create_begin(mem, nt, out));
+  SS_TRY(check_i8_args(metric, d, alpha, k, 0));
+  SS_TRY(check_rows_i8("Fq", Fq, nq, ldq, d));
+  SS_TRY(check_rows_i8("Fs", Fs, ns, lds_, d));
+  DevBuf<int8_t> bq, bs;
+  const int8_t *dq = nullptr, *ds = nullptr;
+  int64_t lq = 0, ls = 0;
+  SS_TRY(stage_rows_i8(Fs, ns, lds_, d, mem, bs, &ds, &ls));
+  SS_TRY(stage_rows_i8(Fq, nq, ldq, d, mem, bq, &dq, &lq));
+  const bool wgt = weighted != 0;
+  return graph_from_producers<float, DotCsrI8>(
+      nq, ns, nt, [&](DotCsrI8& p) { return p.count(ds, ns, ls, nullptr, ns, ls, d, metric, alpha, wgt, k); },
+      [&](DotCsrI8& p) { return p.count(dq, nq, lq, ds, ns, ls, d, metric, alpha, wgt, k); }, i8_names.tag(true, k),
+      i8_names.tag(false, k), y_ptr, y_idx, y_val, index_base, mem, out);
+}
+
 // ------------------- cutoff profiles (include/simspread_hip_profile.h; the device path is cut_profile.hip).  The operand
 // checks and the staging are the matching producer's; what is the profile's own is the check of the cuts and the
 // delivery of total / rows.
@@ -5335,6 +5457,48 @@ int ss_queries_create_vectors_h16(const ss_graph* g, int64_t nq, int64_t ns, int
       g, nq, ns,
       [&](DotCsrH16& p) { return p.count(dq, nq, lq, ds, ns, ls, d, storage, metric, alpha, weighted != 0); },
       h16_tag(false), out);
+}
+
+// ---- include/simspread_hip_int8.h: the inner-product producer and its neighbour floor on int8 rows
+int ss_similarity_dot_csr_i8(const int8_t* Fa, int64_t na, int64_t lda, const int8_t* Fb, int64_t nb, int64_t ldb,
+                             int64_t d, int metric, float alpha, int k, int weighted, int64_t* ptr, int32_t* idx,
+                             float* val, int64_t capacity, int64_t* nnz, int mem) {
+  SS_API_LOCK();
+  return dot_csr_i8_impl(Fa, na, lda, Fb, nb, ldb, d, metric, alpha, k, weighted, ptr, idx, val, capacity, nnz, mem);
+}
+int ss_similarity_dot_kth_i8(const int8_t* Fa, int64_t na, int64_t lda, const int8_t* Fb, int64_t nb, int64_t ldb,
+                             int64_t d, int metric, int k, float* tau, int mem) {
+  SS_API_LOCK();
+  return dot_kth_i8_impl(Fa, na, lda, Fb, nb, ldb, d, metric, k, tau, mem);
+}
+int ss_graph_create_vectors_i8(int64_t nq, int64_t ns, int64_t nt, int64_t d, int metric, const int8_t* Fq, int64_t ldq,
+                               const int8_t* Fs, int64_t lds, const int64_t* y_ptr, const int32_t* y_idx,
+                               const float* y_val, int index_base, float alpha, int k, int weighted, int mem,
+                               ss_graph** out) {
+  SS_API_LOCK();
+  return graph_create_vectors_i8_impl(nq, ns, nt, d, metric, Fq, ldq, Fs, lds, y_ptr, y_idx, y_val, index_base, alpha, k,
+                                      weighted, mem, out);
+}
+int ss_queries_create_vectors_i8(const ss_graph* g, int64_t nq, int64_t ns, int64_t d, int metric, const int8_t* Fq,
+                                 int64_t ldq, const int8_t* Fs, int64_t lds, float alpha, int k, int weighted, int mem,
+                                 ss_queries** out) {
+  SS_API_LOCK();
+  if (!g) return fail(SS_EINVAL, "handle is NULL");
+  SS_HANDLE_LOCK(g);
+  Graph<float>* gp = nullptr;
+  SS_TRY(queries_begin<float>(g, nq, mem, out, &gp));
+  SS_TRY(queries_check_sources(*gp, ns));
+  SS_TRY(check_i8_args(metric, d, alpha, k, 0));
+  SS_TRY(check_rows_i8("Fq", Fq, nq, ldq, d));
+  SS_TRY(check_rows_i8("Fs", Fs, ns, lds, d));
+  DevBuf<int8_t> bq, bs;
+  const int8_t *dq = nullptr, *ds = nullptr;
+  int64_t lq = 0, ls = 0;
+  SS_TRY(stage_rows_i8(Fs, ns, lds, d, mem, bs, &ds, &ls));
+  SS_TRY(stage_rows_i8(Fq, nq, ldq, d, mem, bq, &dq, &lq));
+  return queries_from_producer<float, DotCsrI8>(
+      g, nq, ns, [&](DotCsrI8& p) { return p.count(dq, nq, lq, ds, ns, ls, d, metric, alpha, weighted != 0, k); },
+      i8_names.tag(false, k), out);
 }
 
 // ---- include/simspread_hip_profile.h: cutoff profiles of the fused producers

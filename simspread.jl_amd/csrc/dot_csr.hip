@@ -41,11 +41,18 @@
 // The rows are raw bf16 / fp16 patterns, ROW-MAJOR; the Gram block is dot_tile_gram_h16 (dot_tile_h16.hpp) on
 // v_mfma_f32_32x32x16_{bf16,f16}, whose products are exact in fp32 and whose results lie in the accumulator registers
 // exactly as the fp32 instruction's do, so everything from the norms on is the text below with T = float.
+//
+// int8 rows (DotCsrI8, include/simspread_hip_int8.h): the operand tag dottile::I8.  The Gram block is dot_tile_gram_i8
+// (dot_tile_i8.hpp) on v_mfma_i32_32x32x32_i8: g is an exact int32, converted to fp32 once, and the norms are (float) of
+// exact integer sums, so s is a pure function of the two rows and the CSR is bitwise defined for every input.  The
+// selection pass of the neighbour floor runs the same Gram tile (dot_kth_i8 of real_floor.hip), so this operand, unlike
+// the 16-bit ones, has the per-row cut.
 #include <algorithm>
 #include <hip/hip_runtime.h>
 
 #include "dot_tile.hpp"
 #include "dot_tile_h16.hpp"
+#include "dot_tile_i8.hpp"
 #include "graph.hpp"
 #include "pair_tile.hpp"
 
@@ -77,7 +84,8 @@ __device__ __forceinline__ int bits_before(const uint32_t (*m)[4], int r, int c)
 // FLOOR: the per-row cut tau[na] next to alpha; a pair is then decided by its row alone, so there is no mirror (!SYM);
 // flags & TILE_SELF: Fb is Fa, so the pairs (i, i) have s = 1 as in the symmetric mode.
 // Op: the operands.  Op == T: column-major rows of T, dot_tile_gram.  dottile::Bf16 / dottile::F16 (T == float): row-major
-// 16-bit patterns, dot_tile_gram_h16, with flags & TILE_FAST_A / TILE_FAST_B allowing a side its 16-byte loads.  The
+// 16-bit patterns, dot_tile_gram_h16, with flags & TILE_FAST_A / TILE_FAST_B allowing a side its 16-byte loads.
+// dottile::I8 (T == float): row-major int8, dot_tile_gram_i8, the same flags; the only tagged operand with FLOOR.  The
 // accumulators come out in the same registers either way, so everything after the Gram block is one text.
 enum { TILE_SELF = 1, TILE_FAST_A = 2, TILE_FAST_B = 4 };
 template <class Op>
@@ -95,8 +103,9 @@ __global__ void __launch_bounds__(NT) dot_tile_kernel(
     int weighted, int64_t nti, int* __restrict__ counts, int* __restrict__ tile_nz, const int64_t* __restrict__ ptr,
     int* __restrict__ oidx, T* __restrict__ oval, int* __restrict__ not_binary) {
   static_assert(!(SYM && FLOOR), "a per-row cut decides (i, j) and (j, i) separately");
-  static_assert(std::is_same<Op, T>::value || (std::is_same<T, float>::value && !FLOOR),
-                "16-bit operands: fp32 graphs, no per-row cut");
+  static_assert(std::is_same<Op, T>::value ||
+                    (std::is_same<T, float>::value && (!FLOOR || std::is_same<Op, dottile::I8>::value)),
+                "16-bit and int8 operands: fp32 graphs; a per-row cut with int8 only");
   using M = Mma<T>;
   constexpr int MT = M::MT, NR = M::NR;
   constexpr int NM = dottile::NM<T>;   // MFMA tiles per wave edge
@@ -117,6 +126,9 @@ __global__ void __launch_bounds__(NT) dot_tile_kernel(
   typename M::acc_t acc[NM][NM];
   if constexpr (std::is_same<Op, T>::value)
     dottile::dot_tile_gram<T>(Fa, na, lda, Fb, nb, ldb, d, i0, j0, acc);
+  else if constexpr (std::is_same<Op, dottile::I8>::value)
+    dottile::dot_tile_gram_i8(Fa, na, lda, Fb, nb, ldb, d, i0, j0, (flags & TILE_FAST_A) != 0, (flags & TILE_FAST_B) != 0,
+                              acc);
   else
     dottile::dot_tile_gram_h16<Op>(Fa, na, lda, Fb, nb, ldb, d, i0, j0, (flags & TILE_FAST_A) != 0,
                                    (flags & TILE_FAST_B) != 0, acc);
@@ -349,6 +361,66 @@ int DotCsrH16::count(const uint16_t* Fa_, int64_t na_, int64_t lda_, const uint1
 int DotCsrH16::launch(bool fill, int* idx, float* val, int* flag) {
   if (storage == SS_H16_BF16) h16_launch<dottile::Bf16>(*this, this->tile_grid(), fill, idx, val, flag);
   else h16_launch<dottile::F16>(*this, this->tile_grid(), fill, idx, val, flag);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+// ---- int8 rows (include/simspread_hip_int8.h)
+// a side may use 16-byte loads: every chunk address base + i ld + k, k % 16 == 0, is then 16-byte aligned
+bool i8_fast(const int8_t* F, int64_t ld) { return (reinterpret_cast<uintptr_t>(F) & 15) == 0 && ld % 16 == 0; }
+
+int i8_row_norms(const int8_t* F, int64_t n, int64_t ld, int64_t d, float* norm) {
+  hipLaunchKernelGGL(dottile::row_norm_i8_kernel, dim3((unsigned)ceil_div(n * 16, 256)), dim3(256), 0, ctx().stream, F, n,
+                     ld, d, norm);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+int DotCsrI8::count(const int8_t* Fa_, int64_t na_, int64_t lda_, const int8_t* Fb_, int64_t nb_, int64_t ldb_,
+                    int64_t d_, int metric_, float alpha_, bool weighted_, int k) {
+  what = "dot_i8";
+  self = (Fb_ == nullptr);
+  Fa = Fa_;
+  Fb = self ? Fa_ : Fb_;
+  lda = lda_;
+  ldb = self ? lda_ : ldb_;
+  d = d_;
+  metric = metric_;
+  alpha = alpha_;
+  weighted = weighted_;
+  tau = nullptr;
+  // d, metric, alpha and k are the caller's to check (check_i8_args of api.hip, before anything is staged); the sums
+  // below are exact only up to I8_D_MAX, so that one is held here too
+  if (d < 0 || d > dottile::I8_D_MAX) return fail(SS_EINVAL, "dot_i8: %lld features outside 0..131071", (long long)d);
+  sym = self && k == 0;  // a per-row cut has no mirror: the full grid
+  SS_TRY(this->begin_tiles(na_, self ? na_ : nb_, TILE, true));
+  if (na == 0 || nb == 0) return SS_OK;
+  SS_TRY(norm_a.alloc((size_t)na));
+  SS_TRY(i8_row_norms(Fa, na, lda, d, norm_a.p));
+  if (!self) {
+    SS_TRY(norm_b.alloc((size_t)nb));
+    SS_TRY(i8_row_norms(Fb, nb, ldb, d, norm_b.p));
+  }
+  if (k > 0) {
+    SS_TRY(tau_buf.alloc(na));
+    SS_TRY(dot_kth_i8(Fa, na, lda, self ? nullptr : Fb, nb, ldb, d, metric, norm_a.p, self ? norm_a.p : norm_b.p, k,
+                      tau_buf.p));
+    tau = tau_buf.p;
+  }
+  return this->count_pass();
+}
+
+int DotCsrI8::launch(bool fill, int* idx, float* val, int* flag) {
+  using Op = dottile::I8;
+  auto* kernel = tau   ? (fill ? dot_tile_kernel<float, false, true, true, Op> : dot_tile_kernel<float, false, false, true, Op>)
+                 : sym ? (fill ? dot_tile_kernel<float, true, true, false, Op> : dot_tile_kernel<float, true, false, false, Op>)
+                       : (fill ? dot_tile_kernel<float, false, true, false, Op>
+                               : dot_tile_kernel<float, false, false, false, Op>);
+  const int flags = (self ? (int)TILE_SELF : 0) | (i8_fast(Fa, lda) ? (int)TILE_FAST_A : 0) |
+                    (i8_fast(Fb, ldb) ? (int)TILE_FAST_B : 0);
+  hipLaunchKernelGGL(kernel, this->tile_grid(), dim3(NT), 0, ctx().stream, Fa, na, lda, Fb, nb, ldb, d, norm_a.p,
+                     self ? norm_a.p : norm_b.p, metric, alpha, tau, flags, weighted ? 1 : 0, nti, counts.p, tile_nz.p,
+                     ptr.p, idx, val, flag);
   SS_LAUNCH_CHECK();
   return SS_OK;
 }

@@ -633,6 +633,33 @@ int h16_row_norms(int storage, const uint16_t* F, int64_t n, int64_t ld, int64_t
 int h16_refuse_nan_rows(int storage, const uint16_t* Fa, int64_t na, int64_t lda, const uint16_t* Fb, int64_t nb,
                         int64_t ldb, int64_t d);
 
+// ---- dot_csr.hip, int8 operands (include/simspread_hip_int8.h): DotCsr<float> on rows of signed 8-bit integers,
+// ROW-MAJOR -- element (i, k) at F[i * ld + k], ld >= d -- on v_mfma_i32_32x32x32_i8 with exact int32 sums; the same tile
+// kernel and epilogue.  Device pointers; Fb == nullptr: Fb = Fa.  d <= 131071, the metric, alpha and k are the caller's
+// to check before anything is staged.  There is no NaN to refuse.
+struct DotCsrI8 : PairCsr<float> {
+  const int8_t* Fa = nullptr;
+  const int8_t* Fb = nullptr;
+  int64_t lda = 0, ldb = 0, d = 0;
+  int metric = 0;
+  DevBuf<float> norm_a, norm_b;  // (float) of the exact squared row norms (norm_b unused when Fb == Fa)
+  bool self = false;             // Fb == Fa (sym says whether the triangle grid runs: not with a per-row cut)
+  const float* tau = nullptr;    // per-row cut of the neighbour floor, as DotCsr::tau
+  DevBuf<float> tau_buf;
+  // k > 0: the neighbour floor -- tau = dot_kth_i8(k) first, then the count pass over the full (ntj, nti) grid
+  int count(const int8_t* Fa, int64_t na, int64_t lda, const int8_t* Fb, int64_t nb, int64_t ldb, int64_t d, int metric,
+            float alpha, bool weighted, int k = 0);
+
+ protected:
+  int launch(bool fill, int* idx, float* val, int* flag) override;
+};
+// a side may use 16-byte loads (16-byte-aligned base, ld % 16 == 0); norm[i] = (float) sum_k F[i, k]^2 (enqueued)
+bool i8_fast(const int8_t* F, int64_t ld);
+int i8_row_norms(const int8_t* F, int64_t n, int64_t ld, int64_t d, float* norm);
+// real_floor.hip: dot_kth on int8 rows, s bit for bit the producer's (dot_tile_i8.hpp); norm_a / norm_b as there
+int dot_kth_i8(const int8_t* Fa, int64_t na, int64_t lda, const int8_t* Fb, int64_t nb, int64_t ldb, int64_t d,
+               int metric, const float* norm_a, const float* norm_b, int k, float* tau);
+
 // ---- cut_profile.hip: cutoff profiles (include/simspread_hip_profile.h holds the rule).  For each of the ncuts
 // nondecreasing, NaN-free cuts (host array, 1 <= ncuts <= 32: checked by the caller) total[b] = the nnz and
 // rows[i * ncuts + b] (rows may be nullptr) = the row degrees of the CSR the plain producer builds at alpha = cuts[b],

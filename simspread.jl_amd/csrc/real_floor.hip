@@ -24,10 +24,13 @@
 //   fp32  staging 16 KiB (+ 1 KiB of norms for dot), lists of 128 rows x 64 values = 32 KiB: the whole strip
 //   fp64  staging 32 KiB (jaccard) / 36 KiB + 2 KiB of norms (dot), lists of 2048 values = 16 KiB: 64 rows for k <= 32,
 //         32 rows above; the 2 or 4 blocks of a strip each compute the strip's full tile and select from their rows
+//   int8  (dot, operand dottile::I8, T = float) staging 36 KiB + 1 KiB of norms, lists of 4096 values = 16 KiB: 128 rows
+//         for k <= 32, 64 rows above.  The Gram tile is dot_tile_gram_i8 (dot_tile_i8.hpp), the emit pass's own.
 // floor_rows() is the host-side check of every configuration; one that does not fit is SS_EUNSUPPORTED, never launched.
 #include <hip/hip_runtime.h>
 
 #include "dot_tile.hpp"
+#include "dot_tile_i8.hpp"
 #include "graph.hpp"
 #include "jaccard_tile.hpp"
 #include "kth_merge.hpp"
@@ -52,8 +55,14 @@ struct Lists<double> {
   static constexpr int LIST = 2048, MAX_ROWS = 64;
 };
 
-template <class T, int ROWS>
-using Select = RowSelect<T, TILE, ROWS, Lists<T>::LIST>;
+template <>
+struct Lists<dottile::I8> {  // fp32 values next to the 36 KiB int8 staging
+  static constexpr int LIST = 4096, MAX_ROWS = 128;
+};
+
+// Op: what the lists are sized for -- T, or the operand tag of a kernel whose staging is not T's
+template <class T, int ROWS, class Op = T>
+using Select = RowSelect<T, TILE, ROWS, Lists<Op>::LIST>;
 
 template <class T, int ROWS>
 __global__ void __launch_bounds__(jctile::threads<T>()) jaccard_kth_partial_kernel(
@@ -99,9 +108,12 @@ __global__ void __launch_bounds__(jctile::threads<T>()) jaccard_kth_partial_kern
   sel.store(i0 + sel0, na, k, cnt, part + g * na * k);
 }
 
-template <class T, int ROWS>
+// Op: the operands, as in dot_tile_kernel.  Op == T: column-major rows of T.  dottile::I8 (T == float): row-major int8
+// rows; `self` then also carries the sides that may use 16-byte loads (bit 0: Fb is Fa, bit 1: Fa, bit 2: Fb).
+template <class T, int ROWS, class Op = T>
 __global__ void __launch_bounds__(dottile::NT) dot_kth_partial_kernel(
-    const T* __restrict__ Fa, int64_t na, int64_t lda, const T* __restrict__ Fb, int64_t nb, int64_t ldb, int64_t d,
+    const typename dottile::operand_elem<Op>::type* __restrict__ Fa, int64_t na, int64_t lda,
+    const typename dottile::operand_elem<Op>::type* __restrict__ Fb, int64_t nb, int64_t ldb, int64_t d,
     const T* __restrict__ norm_a, const T* __restrict__ norm_b, int metric, int self, int k, int64_t ntj,
     int64_t tiles_per_group, T* __restrict__ part) {
   using dottile::WT;
@@ -110,8 +122,11 @@ __global__ void __launch_bounds__(dottile::NT) dot_kth_partial_kernel(
   constexpr int NM = dottile::NM<T>;
   constexpr int NV = NM * NM * NR;  // 64 pairs per lane
   __shared__ T na_s[TILE], nb_s[TILE];  // sqrt(A), sqrt(B) (cosine) or A, B of the strip's rows and the tile's columns
-  __shared__ Select<T, ROWS> sel;
-  static_assert(dottile::gram_lds_bytes(sizeof(T), dottile::LDT<T>) + sizeof(na_s) + sizeof(nb_s) + sizeof(sel) <= 64 * 1024,
+  constexpr bool INT8 = std::is_same<Op, dottile::I8>::value;
+  static_assert(std::is_same<Op, T>::value || (INT8 && std::is_same<T, float>::value), "int8 operands: fp32 values");
+  __shared__ Select<T, ROWS, Op> sel;
+  static_assert((INT8 ? dottile::gram_i8_lds_bytes() : dottile::gram_lds_bytes(sizeof(T), dottile::LDT<T>)) +
+                        sizeof(na_s) + sizeof(nb_s) + sizeof(sel) <= 64 * 1024,
                 "static LDS with the tile staging");
 
   constexpr int NH = TILE / ROWS;  // blocks per row strip
@@ -122,7 +137,7 @@ __global__ void __launch_bounds__(dottile::NT) dot_kth_partial_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int cl = lane % MT;
-  const bool diag1 = self != 0;
+  const bool diag1 = INT8 ? (self & 1) != 0 : self != 0;
 
   if (tid < TILE) dottile::stage_norm<T>(na_s, tid, norm_a, i0, na, metric);
   int cnt;
@@ -135,7 +150,10 @@ __global__ void __launch_bounds__(dottile::NT) dot_kth_partial_kernel(
     int64_t i0t = i0, ldat = lda, ldbt = ldb;  // opaque per tile, as in jaccard_kth_partial_kernel
     asm volatile("" : "+s"(i0t), "+s"(ldat), "+s"(ldbt));
     typename M::acc_t acc[NM][NM];
-    dottile::dot_tile_gram<T>(Fa, na, ldat, Fb, nb, ldbt, d, i0t, j0, acc);
+    if constexpr (INT8)
+      dottile::dot_tile_gram_i8(Fa, na, ldat, Fb, nb, ldbt, d, i0t, j0, (self & 2) != 0, (self & 4) != 0, acc);
+    else
+      dottile::dot_tile_gram<T>(Fa, na, ldat, Fb, nb, ldbt, d, i0t, j0, acc);
     // the last read of the previous tile's nb_s lies before the barriers of its absorb_flat
     if (tid < TILE) dottile::stage_norm<T>(nb_s, tid, norm_b, j0, nb, metric);
     __syncthreads();
@@ -166,18 +184,19 @@ __global__ void __launch_bounds__(dottile::NT) dot_kth_partial_kernel(
 }
 
 // rows a block selects for: the most whose lists of k values fit; SS_EUNSUPPORTED when not even the fewest do
-template <class T>
+// (Op: the key of Lists)
+template <class Op>
 int floor_rows(const char* what, int k, int& rows) {
-  rows = Lists<T>::MAX_ROWS;
-  if ((int64_t)rows * k > Lists<T>::LIST) rows /= 2;
-  if ((int64_t)rows * k > Lists<T>::LIST)
+  rows = Lists<Op>::MAX_ROWS;
+  if ((int64_t)rows * k > Lists<Op>::LIST) rows /= 2;
+  if ((int64_t)rows * k > Lists<Op>::LIST)
     return fail(SS_EUNSUPPORTED, "%s: the lists of %d rows x k = %d do not fit in LDS", what, rows, k);
   return SS_OK;
 }
 
 // What the two selections share on the host: the checks, the empty cases, the column groups, the scratch and the merge.
 // partial(rows, grid, ntj, tiles_per_group, part) enqueues the producer's partial kernel for `rows` rows per block.
-template <class T, class Partial>
+template <class T, class Op = T, class Partial>
 int kth_drive(const char* what, int64_t na, int64_t nb, int k, T* tau, Partial partial) {
   hipStream_t st = ctx().stream;
   if (k < 1 || k > NEIGHBOUR_K_MAX) return fail(SS_EINVAL, "%s: k = %d outside 1..%d", what, k, NEIGHBOUR_K_MAX);
@@ -188,7 +207,7 @@ int kth_drive(const char* what, int64_t na, int64_t nb, int k, T* tau, Partial p
     return SS_OK;
   }
   int rows = 0;
-  SS_TRY(floor_rows<T>(what, k, rows));
+  SS_TRY(floor_rows<Op>(what, k, rows));
   const int64_t ntj = ceil_div(nb, TILE);
   const int64_t row_blocks = ceil_div(na, TILE) * (TILE / rows);
   int64_t groups = 0, tiles_per_group = 0;
@@ -257,6 +276,47 @@ int dot_kth(const T* Fa, int64_t na, int64_t lda, const T* Fb, int64_t nb, int64
     hipLaunchKernelGGL(kernel, grid, dim3(dottile::NT), 0, ctx().stream, Fa, na, lda, Fb, nb, ldb, d, norm_a, norm_b,
                        metric, self ? 1 : 0, k, ntj, tiles_per_group, part);
   });
+}
+
+int dot_kth_i8(const int8_t* Fa, int64_t na, int64_t lda, const int8_t* Fb, int64_t nb, int64_t ldb, int64_t d,
+               int metric, const float* norm_a, const float* norm_b, int k, float* tau) {
+  using Op = dottile::I8;
+  if (metric != SS_SIM_COSINE && metric != SS_SIM_TANIMOTO && metric != SS_SIM_DICE)
+    return fail(SS_EINVAL, "dot_i8 kth: unknown metric %d", metric);
+  if (d < 0 || d > dottile::I8_D_MAX) return fail(SS_EINVAL, "dot_i8 kth: %lld features outside 0..131071", (long long)d);
+  const bool self = !Fb;
+  if (self) {
+    Fb = Fa;
+    nb = na;
+    ldb = lda;
+    norm_b = norm_a;
+  }
+  DevBuf<float> own_a, own_b;
+  if (na > 0 && nb > 0 && k >= 1 && k <= NEIGHBOUR_K_MAX) {
+    if (!norm_a) {
+      SS_TRY(own_a.alloc((size_t)na));
+      SS_TRY(i8_row_norms(Fa, na, lda, d, own_a.p));
+      norm_a = own_a.p;
+      if (self) norm_b = norm_a;
+    }
+    if (!norm_b) {
+      SS_TRY(own_b.alloc((size_t)nb));
+      SS_TRY(i8_row_norms(Fb, nb, ldb, d, own_b.p));
+      norm_b = own_b.p;
+    }
+  }
+  const int flags = (self ? 1 : 0) | (i8_fast(Fa, lda) ? 2 : 0) | (i8_fast(Fb, ldb) ? 4 : 0);
+  // (the norms are freed on return, after the synchronisation of kth_drive)
+  return kth_drive<float, Op>(
+      "dot_i8 kth", na, nb, k, tau, [&](int rows, dim3 grid, int64_t ntj, int64_t tiles_per_group, float* part) {
+        constexpr int R = Lists<Op>::MAX_ROWS;
+        static_assert(R * NEIGHBOUR_K_MAX > Lists<Op>::LIST && (R / 2) * NEIGHBOUR_K_MAX <= Lists<Op>::LIST,
+                      "two kernels: R rows while R k values fit, R / 2 above");
+        auto* kernel = dot_kth_partial_kernel<float, R, Op>;
+        if (rows != R) kernel = dot_kth_partial_kernel<float, R / 2, Op>;
+        hipLaunchKernelGGL(kernel, grid, dim3(dottile::NT), 0, ctx().stream, Fa, na, lda, Fb, nb, ldb, d, norm_a, norm_b,
+                           metric, flags, k, ntj, tiles_per_group, part);
+      });
 }
 
 template int jaccard_kth<float>(const float*, int64_t, int64_t, const float*, int64_t, int64_t, int64_t, int, float*);

@@ -317,7 +317,30 @@ class DeviceGraph:
         storage "bf16" / "f16": the 16-bit route of ``dot_csr`` (inputs as there: torch.bfloat16 / torch.float16 CUDA
         tensors read in place, numpy float16, raw uint16 patterns, or real arrays rounded on the host).  The graph is an
         ordinary float32 graph afterwards.  Here 16-bit CUDA tensors must name their storage: without it they are
-        refused as tensors of the wrong dtype, as before; numpy float16 arrays select "f16" as in ``dot_csr``."""
+        refused as tensors of the wrong dtype, as before; numpy float16 arrays select "f16" as in ``dot_csr``.
+
+        storage "i8": the exact int8 route of ``dot_csr`` (inputs as there), min_neighbours allowed; taken only when
+        named.  The graph is an ordinary float32 graph afterwards."""
+        if _i8_storage(storage, (Fs, Fq), dtype, min_neighbours):
+            m = _sim_metric(metric)
+            dev = _is_torch(Fs)
+            keep = []
+            fq, nq, dq, ldq = _features_i8(Fq, dev, keep)
+            fs, ns, d, lds = _features_i8(Fs, dev, keep)
+            if Fq is None:
+                ldq = max(d, 1)
+            elif dq != d:
+                raise ValueError("Fq and Fs have different numbers of features")
+            yptr, yidx, yval, nt, mem = _source_labels(Y, ns, np.float32, dev, keep, index_base)
+            lib = L.lib()
+            h = C.c_void_p()
+            L.check(lib.ss_graph_create_vectors_i8(nq, ns, nt, d, m, fq, ldq, fs, lds, yptr, yidx, yval, index_base,
+                                                   C.c_float(alpha), int(min_neighbours), 1 if weighted else 0, mem,
+                                                   C.byref(h)))
+            if dev:
+                L.check(lib.ss_synchronize())
+            del keep
+            return cls(h, np.float32)
         code = _h16_storage(storage, (Fs, Fq), dtype, min_neighbours, auto_tensor=False)
         if code is not None:
             m = _sim_metric(metric)
@@ -768,7 +791,26 @@ class DeviceQueries:
         """Xq = cut(S(Fq, Fs)), the inner-product block of ``DeviceGraph.from_vectors``; inputs as there.
         min_neighbours = k > 0: every query also keeps its k nearest sources, as ``from_fingerprints``.
         storage "bf16" / "f16" (or 16-bit CUDA tensors, by their dtype; numpy float16 as in ``dot_csr``): the 16-bit route of ``dot_csr``,
-        on a float32 graph built by any constructor."""
+        on a float32 graph built by any constructor.  storage "i8": the exact int8 route, min_neighbours allowed."""
+        if _i8_storage(storage, (Fs, Fq), graph.dtype, min_neighbours):
+            m = _sim_metric(metric)
+            dev = _is_torch(Fs)
+            keep = []
+            fq, nq, dq, ldq = _features_i8(Fq, dev, keep)
+            fs, ns, d, lds = _features_i8(Fs, dev, keep)
+            if Fq is None:
+                ldq = max(d, 1)
+            elif dq != d:
+                raise ValueError("Fq and Fs have different numbers of features")
+            lib = L.lib()
+            h = C.c_void_p()
+            L.check(lib.ss_queries_create_vectors_i8(graph._h, nq, ns, d, m, fq, ldq, fs, lds, C.c_float(alpha),
+                                                     int(min_neighbours), 1 if weighted else 0,
+                                                     L.SS_MEM_DEVICE if dev else L.SS_MEM_HOST, C.byref(h)))
+            if dev:
+                L.check(lib.ss_synchronize())
+            del keep
+            return cls(h, graph)
         code = _h16_storage(storage, (Fs, Fq), graph.dtype, min_neighbours)
         if code is not None:
             m = _sim_metric(metric)
@@ -1886,7 +1928,8 @@ def _h16_storage(storage, inputs, dtype, min_neighbours=0, auto_tensor=True):
     select "f16" only where that changes no call that worked without it: every given input is float16, the graph
     precision is float32 and there is no neighbour floor; otherwise they are widened exactly, as they always were."""
     if storage is not None and storage not in H16_STORAGES:
-        raise ValueError(f"storage must be None or one of {sorted(H16_STORAGES)}, got {storage!r}")
+        raise ValueError(f"storage must be None or one of {sorted(H16_STORAGES)} (\"i8\": dot_csr and the from_vectors "
+                         f"constructors), got {storage!r}")
     given = [F for F in inputs if F is not None]
     if storage is None:
         half = {"torch.bfloat16": "bf16", "torch.float16": "f16"}
@@ -1979,6 +2022,146 @@ def _pair_csr_h16(Fa, Fb, code, m, alpha, weighted):
     return sp.csr_matrix((val[:nnz.value], idx[:nnz.value], ptr), shape=(na, nb))
 
 
+NEIGHBOUR_K_MAX = 64
+
+
+def quantize_i8(X):
+    """Symmetric per-tensor quantisation of real numbers for ``storage="i8"``: ``(Q, scale)`` with
+    ``Q = round(X * 127 / max|X|)`` (int8, same shape; round to nearest, ties to even) and ``scale = max|X| / 127``, so
+    that ``X ~ Q * scale``.  An all-zero (or empty) X gives zeros and scale 1.  Cosine, Tanimoto and Dice are all
+    invariant under a common scale of both sides, so the similarities of ``Q`` are those of ``Q * scale``: quantise
+    every block that meets another one (sources and queries) with ONE scale, i.e. in one call.  A non-finite value
+    raises ValueError."""
+    a = np.asarray(X)
+    if a.dtype.kind not in "fiub":
+        raise TypeError(f"quantize_i8 needs real numbers, got {a.dtype}")
+    a = a.astype(np.float64)
+    if not np.isfinite(a).all():
+        raise ValueError("quantize_i8: X holds a NaN or an infinity")
+    top = float(np.abs(a).max(initial=0.0))
+    if top == 0.0:
+        return np.zeros(a.shape, np.int8), 1.0
+    q = np.rint(a * (127.0 / top))
+    return np.clip(q, -127, 127).astype(np.int8), top / 127.0
+
+
+def _i8_storage(storage, inputs, dtype, min_neighbours=0, k_min=0) -> bool:
+    """True when the call names the int8 route (storage == "i8"; it is never chosen by the inputs).  Needs no device.
+    Checks what the route asks of the other arguments: a float32 graph, k in range, one memory kind."""
+    if not (isinstance(storage, str) and storage == "i8"):
+        return False
+    if np.dtype(dtype) != np.float32:
+        raise TypeError("int8 storage builds float32 graphs: dtype must be float32")
+    k = int(min_neighbours)
+    if k != min_neighbours or not k_min <= k <= NEIGHBOUR_K_MAX:
+        raise ValueError(f"k / min_neighbours = {min_neighbours!r} outside {k_min}..{NEIGHBOUR_K_MAX}")
+    given = [F for F in inputs if F is not None]
+    if len({_module_is_torch(F) for F in given}) > 1:
+        raise TypeError("features must all live on the host (numpy) or all on the device (CUDA tensors)")
+    return True
+
+
+def _features_i8(F, dev, keep):
+    """(pointer, rows, d, ld) of int8 feature rows in the row-major layout of include/simspread_hip_int8.h.  Device: an
+    (n, d) torch.int8 CUDA tensor, used in place when its rows are contiguous (ld = stride(0)).  Host: numpy int8 as it
+    is.  Anything else must hold integers in -128 .. 127 and is converted exactly; there is no rounding: ValueError."""
+    if F is None:
+        return None, 0, 0, 1
+    if dev:
+        import torch
+        if not (_module_is_torch(F) and F.is_cuda and F.ndim == 2):
+            raise TypeError("device features must be (n, d) CUDA tensors")
+        if F.dtype != torch.int8:
+            if F.dtype == torch.bool or F.is_complex():
+                raise ValueError(f"int8 storage needs integers in -128..127, got {F.dtype}")
+            G = F.to(torch.int8)
+            if F.numel() and not bool(((G.to(F.dtype) == F) & (F >= -128) & (F <= 127)).all()):
+                raise ValueError("int8 storage needs integers in -128..127 (quantize_i8 rounds real numbers)")
+            F = G
+        n, d = F.shape
+        rows_ok = d <= 1 or F.stride(1) == 1                  # the d bytes of a row are consecutive
+        ld_ok = n <= 1 or F.stride(0) >= d                    # rows do not overlap
+        if not (rows_ok and ld_ok):
+            F = F.contiguous()
+        keep.append(F)
+        ld = F.stride(0) if n > 1 else d
+        return F.data_ptr(), n, d, max(ld, d, 1)
+    if _module_is_torch(F):
+        raise TypeError("features must all live on the host (numpy) or all on the device (CUDA tensors)")
+    a = np.asarray(F)
+    if a.ndim != 2:
+        raise ValueError("features must be an (n, d) matrix")
+    if a.dtype != np.int8:
+        if a.dtype.kind not in "fiu":
+            raise ValueError(f"int8 storage needs integers in -128..127, got {a.dtype}")
+        ok = a <= 127                                            # a NaN fails every comparison
+        if a.dtype.kind != "u":
+            ok = ok & (a >= -128)
+        if a.dtype.kind == "f":
+            with np.errstate(invalid="ignore"):
+                ok = ok & (a == np.trunc(a))
+        if not np.all(ok):
+            raise ValueError("int8 storage needs integers in -128..127 (quantize_i8 rounds real numbers)")
+        a = a.astype(np.int8)
+    a = np.ascontiguousarray(a)
+    keep.append(a)
+    return a.ctypes.data, a.shape[0], a.shape[1], max(a.shape[1], 1)
+
+
+def _pair_i8_operands(Fa, Fb):
+    dev = _is_torch(Fa)
+    keep = []
+    pa, na, d, lda = _features_i8(Fa, dev, keep)
+    pb, nb, db, ldb = _features_i8(Fb, dev, keep)
+    if Fb is None:
+        nb, db, ldb = na, d, lda
+    if db != d:
+        raise ValueError("Fa and Fb have different numbers of features")
+    return dev, keep, (pa, na, lda, pb, nb, ldb, d), na, nb
+
+
+def _pair_csr_i8(Fa, Fb, m, alpha, k, weighted):
+    """ss_similarity_dot_csr_i8 under the size protocol of ``_feature_pair_csr``."""
+    dev, keep, ops, na, nb = _pair_i8_operands(Fa, Fb)
+    fn = L_.lib().ss_similarity_dot_csr_i8
+    nnz = C.c_int64(0)
+    head = ops + (m, C.c_float(alpha), int(k), 1 if weighted else 0)
+    if dev:
+        import torch
+        ptr = torch.empty(na + 1, dtype=torch.int64, device=Fa.device)
+        L_.check(fn(*head, ptr.data_ptr(), None, None, 0, C.byref(nnz), L_.SS_MEM_DEVICE))
+        idx = torch.empty(max(nnz.value, 1), dtype=torch.int32, device=Fa.device)
+        val = torch.empty(max(nnz.value, 1), dtype=torch.float32, device=Fa.device)
+        L_.check(fn(*head, ptr.data_ptr(), idx.data_ptr(), val.data_ptr(), nnz.value, C.byref(nnz), L_.SS_MEM_DEVICE))
+        del keep
+        return ptr, idx[:nnz.value], val[:nnz.value]
+    import scipy.sparse as sp
+    ptr = np.zeros(na + 1, np.int64)
+    L_.check(fn(*head, ptr.ctypes.data, None, None, 0, C.byref(nnz), L_.SS_MEM_HOST))
+    idx = np.empty(max(nnz.value, 1), np.int32)
+    val = np.empty(max(nnz.value, 1), np.float32)
+    L_.check(fn(*head, ptr.ctypes.data, idx.ctypes.data, val.ctypes.data, nnz.value, C.byref(nnz), L_.SS_MEM_HOST))
+    del keep
+    return sp.csr_matrix((val[:nnz.value], idx[:nnz.value], ptr), shape=(na, nb))
+
+
+def _kth_i8(Fa, Fb, m, k):
+    """tau of ss_similarity_dot_kth_i8, as ``_feature_kth``."""
+    dev, keep, ops, na, nb = _pair_i8_operands(Fa, Fb)
+    fn = L_.lib().ss_similarity_dot_kth_i8
+    head = ops + (m, int(k))
+    if dev:
+        import torch
+        tau = torch.empty(na, dtype=torch.float32, device=Fa.device)
+        L_.check(fn(*head, tau.data_ptr(), L_.SS_MEM_DEVICE))
+        del keep
+        return tau
+    tau = np.empty(na, np.float32)
+    L_.check(fn(*head, tau.ctypes.data, L_.SS_MEM_HOST))
+    del keep
+    return tau
+
+
 def _feature_pair_csr(name, Fa, Fb, mid, alpha, weighted, dtype, min_neighbours=0):
     """The size protocol shared by the feature-row producers ss_similarity_<name>_csr_* and, with min_neighbours = k > 0,
     ss_similarity_<name>_floor_csr_* (k after alpha): `mid` are the arguments between d and alpha."""
@@ -2053,8 +2236,19 @@ def jaccard_kth(Fa, Fb=None, k=None, dtype=np.float32):
 def dot_kth(Fa, Fb=None, metric="cosine", k=None, dtype=np.float32):
     """tau[i] of ``dot_csr(..., metric=metric, min_neighbours=k)``: the k-th largest of the positive similarities of row
     Fa[i] against the rows of Fb (Fb None: Fb = Fa, the diagonal, exactly 1, included), +0 where a row has fewer than k.
-    Negative similarities never count.  1 <= k <= 64.  Inputs and outputs as ``jaccard_kth``."""
+    Negative similarities never count.  1 <= k <= 64.  Inputs and outputs as ``jaccard_kth``.  The int8 route has its
+    own entry, ``dot_kth_i8``."""
     return _feature_kth("dot", Fa, Fb, (_sim_metric(metric),), k, dtype)
+
+
+def dot_kth_i8(Fa, Fb=None, metric="cosine", k=None):
+    """``dot_kth`` on the exact int8 route: tau[i] of ``dot_csr(..., metric=metric, min_neighbours=k, storage="i8")``,
+    float32, bit for bit the k-th largest positive value of the rule.  1 <= k <= 64.  Inputs as ``dot_csr`` with
+    ``storage="i8"``; host input returns a numpy vector, device input a CUDA tensor."""
+    if k is None:
+        raise TypeError("dot_kth_i8 needs k")
+    _i8_storage("i8", (Fa, Fb), np.float32, k, k_min=1)
+    return _kth_i8(Fa, Fb, _sim_metric(metric), k)
 
 
 def jaccard_csr(Fa, Fb=None, alpha=None, weighted: bool = True, dtype=np.float32, min_neighbours: int = 0):
@@ -2090,9 +2284,18 @@ def dot_csr(Fa, Fb=None, metric="cosine", alpha=None, weighted: bool = True, dty
     read in place, row-major, when ``stride(1) == 1`` (no copy, no widening); numpy float16 arrays select "f16" when
     every input is float16, dtype is float32 and min_neighbours is 0 (otherwise they are widened exactly, as before); with
     an explicit storage numpy uint16 arrays are raw bit patterns and other real arrays are rounded on the host (nearest
-    even; ``to_bf16_bits``).  dtype must be float32; min_neighbours > 0 raises NotImplementedError."""
+    even; ``to_bf16_bits``).  dtype must be float32; min_neighbours > 0 raises NotImplementedError.
+
+    storage "i8" takes the exact int8 route (include/simspread_hip_int8.h), only when named: the rows are signed 8-bit
+    integers, the Gram blocks run on the integer matrix instruction and g, |a|^2, |b|^2 are exact integers (d <=
+    131071), each converted to float32 once, so the CSR is bitwise defined for every input, at a quarter of the bytes
+    of float32 rows.  min_neighbours is allowed.  Inputs: numpy int8 as it is; torch.int8 CUDA tensors, read in place,
+    row-major, when ``stride(1) == 1``; any other array whose values are integers in -128 .. 127, converted exactly --
+    anything else raises ValueError (``quantize_i8`` rounds real numbers).  dtype must be float32."""
     if alpha is None:
         raise TypeError("dot_csr needs alpha")
+    if _i8_storage(storage, (Fa, Fb), dtype, min_neighbours):
+        return _pair_csr_i8(Fa, Fb, _sim_metric(metric), alpha, min_neighbours, weighted)
     code = _h16_storage(storage, (Fa, Fb), dtype, min_neighbours)
     if code is not None:
         return _pair_csr_h16(Fa, Fb, code, _sim_metric(metric), alpha, weighted)
