@@ -258,8 +258,9 @@ int ss_graph_create_dense_f64(int64_t nq, int64_t ns, int64_t nf, int64_t nt,
  * the stage-1 product, which runs on the matrix cores (bf16 MFMA over exact bf16 planes of the fp32 operands;
  * SS_DENSE_BF16=0: fp32-input MFMA); the labels Y stay sparse (CSR, ns x nt).
  * Sq (nq x ns) and Ss (ns x ns) are column-major raw similarities whose columns are the features named
- * after the sources; nq may be 0.  Serves ss_predict_f32 (query and source rows), ss_predict_loo_f32 and
- * ss_predict_kfold_f32.
+ * after the sources; nq may be 0.  Ss need not be symmetric: element (s, f), at Ss[s + f * lds], is source s (row)
+ * against feature f (column), so kf counts a column and ks a row.  Serves ss_predict_f32 (query and source rows),
+ * ss_predict_loo_f32 and ss_predict_kfold_f32.
  * _f32: bf16 matrix cores on exact bf16 planes (the reference's GPU=true precision, src/core.jl:404); _f64: the fp64
  * matrix instruction (the reference's default precision, src/core.jl:402 GPU=false).
  * Input domain, the same in every engine and in ss_graph_set_cutoff_*: the rule is featurize's

@@ -168,7 +168,8 @@ class DeviceGraph:
     def from_similarity(cls, Sq, Ss, Y, alpha: float, weighted: bool = True, dtype=np.float32, index_base: int = 0,
                         ld_pad: int = 0):
         """Dense-similarity regime: raw similarities Sq (nq x ns, may be None) and Ss (ns x ns) stay dense on the
-        device, the cutoff is applied inside the MFMA stage-1 product; Y (ns x nt) is sparse.  dtype float32: bf16
+        device, the cutoff is applied inside the MFMA stage-1 product; Y (ns x nt) is sparse.  Ss need not be
+        symmetric: element (s, f) is source s (row) against feature f (column).  dtype float32: bf16
         matrix cores on exact bf16 planes (the reference's GPU=true precision); float64: the fp64 matrix instruction
         (the reference's default precision).  Inputs: numpy arrays / scipy matrix on the host, or torch CUDA tensors
         for Sq, Ss with Y = (ptr, idx, val, nt) device CSR.  Serves predict (query / source rows), predict_loo and

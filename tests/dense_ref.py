@@ -122,6 +122,67 @@ def plane_scores_source(X, Y, weighted, rows, **defect):
     return plane_scores(X[rows], X, Y, weighted, **defect) + _target_scores(X, Y, rows)[0]
 
 
+# ----------------------------------------------------------------------------- the orientation of Ss and its defects
+# Element (s, f) of the thresholded source similarity X is source s (row) against feature f (column).  Every place of
+# the regime that indexes it is a parameter of transposed_scores: name -> the modes whose device path goes through it
+# (k-fold recounts its degrees per fold and never reads the graph's kf / ks).
+TRANSPOSE_DEFECTS = {
+    "has_transposed": ("loo",),                                    # the LOO divisor ks - has reads X[q, s], not X[s, q]
+    "degrees_swapped": ("query", "source", "loo"),                 # kf from row counts, ks from column counts
+    "fold_recount_transposed": ("kfold",),                         # per-fold kf / ks counted over X[f, m] / X[f, s]
+    "source_operand_transposed": ("query", "source", "loo", "kfold"),   # the product reads X[f, s]
+    "input_transposed": ("query", "source", "loo", "kfold"),       # the whole Ss handed over transposed
+}
+
+
+def transposed_scores(mode, X, Y, Xq=None, fold=None, rows=None, defect=None):
+    """What the device computes in `mode` ("query", "source", "loo", "kfold"), in fp64 and in the device's own form
+    (degrees counted once, leave-one-out by the rank-1 corrections of the degrees, k-fold by a recount per fold), with
+    one index pair of X swapped by `defect` (a key of TRANSPOSE_DEFECTS; None: the correct device).  On a symmetric X
+    every defect performs the very same operations on the very same numbers as the correct form, bit for bit."""
+    assert defect is None or mode in TRANSPOSE_DEFECTS[defect], (mode, defect)
+    X, Y = np.asarray(X, dtype=np.float64), np.asarray(Y, dtype=np.float64)
+    if defect == "input_transposed":
+        X = np.ascontiguousarray(X.T)
+    n = X.shape[0]
+    nz = X != 0
+    ny = np.count_nonzero(Y, axis=1)
+    col, row = nz.sum(axis=0), nz.sum(axis=1)
+    kf, ks = (row, col + ny) if defect == "degrees_swapped" else (col, row + ny)
+    # B[f, s], the source side of the product: X[s, f] (a copy, so that both orientations multiply from the same layout)
+    B = np.ascontiguousarray(X if defect == "source_operand_transposed" else X.T)
+    if mode in ("query", "source"):
+        A = np.asarray(Xq, dtype=np.float64) if mode == "query" else X[rows]
+        out = ((A * _inv(kf)[None, :]) @ B * _inv(ks)[None, :]) @ Y
+        if mode == "source":
+            kt = np.count_nonzero(Y, axis=0)
+            out = out + ((Y[rows] * _inv(kt)[None, :]) @ Y.T * _inv(ks)[None, :]) @ Y
+        return out
+    q = np.arange(n) if rows is None else np.asarray(rows)
+    r = np.arange(len(q))
+    if mode == "loo":
+        U = X[q] * _inv(kf[None, :] - nz[q])
+        U[r, q] = 0.0
+        has = nz[q] if defect == "has_transposed" else nz[:, q].T
+        V = U @ B * _inv(ks[None, :] - has)
+        V[r, q] = 0.0
+        return V @ Y
+    assert mode == "kfold"
+    fold = np.asarray(fold)
+    out = np.zeros((len(q), Y.shape[1]))
+    for phi in np.unique(fold[q]):
+        keep = np.flatnonzero(fold != phi)
+        sel = fold[q] == phi
+        nzk = nz[np.ix_(keep, keep)]
+        if defect == "fold_recount_transposed":
+            fkf, fks = nzk.sum(axis=1), nzk.sum(axis=0) + ny[keep]
+        else:
+            fkf, fks = nzk.sum(axis=0), nzk.sum(axis=1) + ny[keep]
+        A = X[np.ix_(q[sel], keep)]
+        out[sel] = ((A * _inv(fkf)[None, :]) @ B[np.ix_(keep, keep)] * _inv(fks)[None, :]) @ Y[keep]
+    return out
+
+
 # ----------------------------------------------------------------------------- fp64 references (the oracle)
 def _target_scores(X, Y, rows):
     """Target path of the source rows, (Ys D_t^-1) Ys' (D_s^-1 Ys), and its count of non-zero terms per score."""
@@ -253,6 +314,8 @@ FAMILY_LOW = float(np.float32(0.5 + 2.0 ** -10 - 2.0 ** -19))
 BLOCKS_QUERY = (32,) * 3 + (16,) * 4 + (8,) * 5 + (4,) * 6 + (2,) * 8 + (1,) * 15        # ns = 255
 BLOCKS_LOO = (33,) * 2 + (17,) * 2 + (9,) * 3 + (5,) * 3 + (3,) * 4 + (2,) * 5           # ns = 164
 BLOCKS_KFOLD = (36,) * 4                                                                 # ns = 144, 9 folds x 4 members
+# asymmetric values: no leave-one-out block of two (its one product reads only the diagonal of the source operand)
+BLOCKS_LOO_ASYM = (33,) * 2 + (17,) * 2 + (9,) * 3 + (5,) * 5 + (3,) * 4                 # ns = 164
 
 
 def _family(rng, shape):
@@ -272,23 +335,38 @@ def _sym(a):
     return np.triu(a) + np.triu(a, 1).T
 
 
-def exact_inputs(mode, seed=0, nq=130, alpha_edge=False):
+def _family_asym(rng, n):
+    """_family values on an n x n matrix with element (i, j) != element (j, i) for every i != j (the lo plane of the
+    lower triangle is one of the two other values of its mirror)."""
+    up = rng.integers(-1, 2, size=(n, n))
+    low = (up.T + 1 + rng.integers(1, 3, size=(n, n))) % 3 - 1
+    return (0.5 + 2.0 ** -10 + (np.triu(up) + np.tril(low, -1)) * 2.0 ** -19).astype(np.float32)
+
+
+def exact_inputs(mode, seed=0, nq=130, alpha_edge=False, symmetric=True):
     """Exactly summable weighted inputs (tier 1).  mode "query": blocks of 2^j sources with 2^j targets each (kf = 2^j,
     ks = 2^(j+1)); "loo": blocks of 2^j + 1 with 2^j targets (kf - 1 = 2^j, ks - has = 2^(j+1)); "kfold": blocks of 36 =
     9 folds x 4 members with 32 targets per source (per-fold kf = 32, ks = 64).  All pairs inside a block are kept and
     nothing else, members are scattered by a random permutation, every target has exactly one source.  alpha is 0.4,
     or with alpha_edge the lowest value of the family, so that a third of the kept entries sit exactly at alpha (a kept
     entry of value float32(0.4) cannot belong to an exactly summable family: its planes are not stable).
+    symmetric=False: the same block pattern (the exactness argument needs it) with Ss[i, j] != Ss[j, i] for every pair
+    inside a block and an independent filler on either side of the diagonal; leave-one-out blocks have three or more
+    members.  The values stay exactly summable.
     Returns a dict: Sq, Ss (fp32), Y (dense fp32), alpha, fold (kfold) and the block id of every source."""
     rng = np.random.default_rng(seed)
-    sizes = {"query": BLOCKS_QUERY, "loo": BLOCKS_LOO, "kfold": BLOCKS_KFOLD}[mode]
+    sizes = {"query": BLOCKS_QUERY, "loo": BLOCKS_LOO if symmetric else BLOCKS_LOO_ASYM, "kfold": BLOCKS_KFOLD}[mode]
     alpha = FAMILY_LOW if alpha_edge else ALPHA
     ns = int(sum(sizes))
     perm = rng.permutation(ns)
     block = np.empty(ns, dtype=np.int64)
     fold = np.zeros(ns, dtype=np.int32)
-    Ss = _sym(_filler(rng, (ns, ns), alpha))
-    fam = _sym(_family(rng, (ns, ns)))
+    if symmetric:
+        Ss = _sym(_filler(rng, (ns, ns), alpha))
+        fam = _sym(_family(rng, (ns, ns)))
+    else:
+        Ss = _filler(rng, (ns, ns), alpha)
+        fam = _family_asym(rng, ns)
     tcount = np.zeros(ns, dtype=np.int64)
     o = 0
     for b, size in enumerate(sizes):
@@ -307,12 +385,15 @@ def exact_inputs(mode, seed=0, nq=130, alpha_edge=False):
     return dict(Sq=Sq, Ss=Ss, Y=Y, alpha=alpha, fold=fold, block=block, mode=mode)
 
 
-def single_feature_inputs(seed=1, nq=129, ns=260, alpha=0.85):
+def single_feature_inputs(seed=1, nq=129, ns=260, alpha=0.85, symmetric=True):
     """Unweighted, one feature per query row, one source per target (tier 2): the score is the single term
     fl(1/kf) * fl(1/ks).  Degrees are whatever the random symmetric pattern gives (15 % of the pairs kept: around
-    40, odd and even, hardly a power of two)."""
+    40, odd and even, hardly a power of two).  symmetric=False: an iid pattern, kf a column count and ks a row count
+    that differ."""
     rng = np.random.default_rng(seed)
-    Ss = _sym(rng.random((ns, ns)).astype(np.float32))
+    Ss = rng.random((ns, ns)).astype(np.float32)
+    if symmetric:
+        Ss = _sym(Ss)
     np.fill_diagonal(Ss, 1.0)
     Sq = (rng.random((nq, ns)) * np.float32(alpha) * 0.99).astype(np.float32)      # all below alpha ...
     Sq[np.arange(nq), rng.integers(0, ns, nq)] = np.float32(alpha) + rng.random(nq).astype(np.float32) * 0.2  # ... but one
@@ -326,7 +407,21 @@ def single_feature_inputs(seed=1, nq=129, ns=260, alpha=0.85):
 WEIGHTED_BLOCKS = {"query": (1, 2, 4, 8), "loo": (2, 3, 5, 9), "kfold": (3, 6, 12)}
 
 
-def random_inputs(nq, ns, weighted, mode="query", seed=None):
+def _column_pattern(rng, m, per_class, nclass):
+    """m x m boolean pattern, position p in class p % nclass: every column keeps `per_class` positions of each class,
+    its own diagonal among them, the others drawn at random.  Column degrees are per_class * nclass, row degrees are
+    whatever the draw gives, and a kept pair's mirror is kept only by chance."""
+    pat = np.zeros((m, m), dtype=bool)
+    for j in range(m):
+        pat[j, j] = True
+        for c in range(nclass):
+            cand = np.arange(c, m, nclass)
+            own = c == j % nclass
+            pat[rng.choice(cand[cand != j], per_class - own, replace=False), j] = True
+    return pat
+
+
+def random_inputs(nq, ns, weighted, mode="query", seed=None, symmetric=True):
     """General inputs (tiers 2 and 3) with 24-bit random values, one entry exactly at alpha on either side, one source
     per target and 0..2 targets per source, so that a score is one transfer element.
 
@@ -344,7 +439,13 @@ def random_inputs(nq, ns, weighted, mode="query", seed=None):
     "kfold" (per-fold kf = 2^(j+1)).  A weighted term otherwise carries two more roundings, fl(1/kf) and fl(x * fl(1/kf)),
     which the band does not count: with them the fp32-input engine, an exact fma chain, left the band by up to 1.26 on
     iid inputs.  With exact scaling the band is the worst case of that engine: n roundings of the fma chain, fl(1/ks)
-    and the final product.  ks stays arbitrary (block size + 0..2 targets)."""
+    and the final product.  ks stays arbitrary (block size + 0..2 targets).
+
+    symmetric=False.  Unweighted: the iid matrix as drawn, the entry exactly at alpha on one side only; pattern, kf
+    (column counts) and ks (row counts) are all asymmetric.  Weighted: a block of 2 w members for a column degree w
+    from the list above; every column keeps w of the block's rows (its diagonal and a random choice; for "kfold" w / 3
+    of each fold, fold = position % 3), so kf, kf - 1 and the per-fold kf are the same powers of two and the scaling
+    stays exact, while the row degrees, ks and the leave-one-out divisor ks - has vary with the pair."""
     rng = np.random.default_rng((1000 * ns + nq if seed is None else seed) + {"query": 0, "loo": 1, "kfold": 2}[mode] * weighted)
     tcount = rng.integers(0, 3, ns)
     nt = int(tcount.sum())
@@ -352,9 +453,13 @@ def random_inputs(nq, ns, weighted, mode="query", seed=None):
     Y[np.repeat(np.arange(ns), tcount), rng.permutation(nt)] = 1.0
     if not weighted:
         alpha = np.float32(1.0 - np.sqrt(3.0 / ns))
-        Ss = _sym(rng.random((ns, ns)).astype(np.float32))
+        Ss = rng.random((ns, ns)).astype(np.float32)
+        if symmetric:
+            Ss = _sym(Ss)
         np.fill_diagonal(Ss, 1.0)
         Ss[3, 7] = Ss[7, 3] = alpha        # exactly alpha: kept
+        if not symmetric:
+            Ss[7, 3] = alpha * np.float32(0.5)     # ... on one side only
         Sq = rng.random((nq, ns)).astype(np.float32)
         Sq[0, 1] = alpha
         return dict(Sq=Sq, Ss=Ss, Y=Y, alpha=float(alpha), fold=(np.arange(ns) * 7 % 4).astype(np.int32), nfolds=4)
@@ -363,19 +468,31 @@ def random_inputs(nq, ns, weighted, mode="query", seed=None):
     below = lambda shape: (rng.random(shape) * 0.495).astype(np.float32)
     sizes = WEIGHTED_BLOCKS[mode]
     perm = rng.permutation(ns)
-    Ss = _sym(below((ns, ns)))
-    vals = _sym(value((ns, ns)))
+    Ss, vals = below((ns, ns)), value((ns, ns))
+    if symmetric:
+        Ss, vals = _sym(Ss), _sym(vals)
     fold = rng.integers(0, 3, ns).astype(np.int32)
     o, first = 0, None
-    while ns - o >= sizes[-1] + 3:         # the last three or more sources stay without any edge (kf = 0)
+    while ns - o >= (1 if symmetric else 2) * sizes[-1] + 3:    # the last three or more sources stay without any edge (kf = 0)
         size = int(rng.choice(sizes))
+        if not symmetric:
+            # `size` is the column degree w, the block has 2 w members and every column keeps a set of its own
+            pat = _column_pattern(rng, 2 * size, size // 3 if mode == "kfold" else size, 3 if mode == "kfold" else 1)
+            size *= 2
         mem = perm[o:o + size]
         o += size
-        Ss[np.ix_(mem, mem)] = vals[np.ix_(mem, mem)]
+        if symmetric:
+            Ss[np.ix_(mem, mem)] = vals[np.ix_(mem, mem)]
+        else:
+            Ss[np.ix_(mem, mem)] = np.where(pat, vals[np.ix_(mem, mem)], Ss[np.ix_(mem, mem)])
         fold[mem] = np.arange(size) % 3
-        if size > 1 and first is None:
+        if symmetric and size > 1 and first is None:
             first = mem
-    Ss[first[0], first[1]] = Ss[first[1], first[0]] = alpha     # exactly alpha: kept
+        if not symmetric and first is None and (pat & ~pat.T).any():      # a kept pair whose mirror is cut
+            first = mem[np.argwhere(pat & ~pat.T)[0]]
+    Ss[first[0], first[1]] = alpha         # exactly alpha: kept
+    if symmetric:
+        Ss[first[1], first[0]] = alpha
     Sq = np.where(rng.random((nq, ns)) < 0.5, value((nq, ns)), below((nq, ns))).astype(np.float32)
     Sq[0, 1] = alpha
     return dict(Sq=Sq, Ss=Ss, Y=Y, alpha=float(alpha), fold=fold, nfolds=3)

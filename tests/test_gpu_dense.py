@@ -10,6 +10,13 @@ Tier 3: the shapes, row offsets and alignments that choose between vector and sc
         accesses, full and partial tiles, and a last tile group that is one block wide.
 Tier 4: the input domain: NaN similarities, alpha = 0, alpha < 0, zeros and negative weights, against O.cutoff.
 
+Orientation: element (s, f) of Ss is source s (row) against feature f (column), and Ss need not be symmetric.  Every
+tier runs again on dense_ref's symmetric=False inputs: tier 1 with Ss[i, j] != Ss[j, i] inside every block, the bands
+on an asymmetric pattern whose row and column degrees differ, the degrees after set_cutoff, and one graph handed over
+from numpy, from a CUDA tensor and with a padded leading dimension.  tests/test_dense_inputs_cpu.py shows that every
+swap of the two indices (dense_ref.TRANSPOSE_DEFECTS) is invisible on the symmetric inputs and leaves the band on a
+tenth or more of the scores of the asymmetric ones.
+
 Every predict call asserts the engine's tag in ss.path_last().  References are computed once per input and shared by the
 engines; inputs, bands and assertions live in tests/dense_ref.py."""
 import functools
@@ -39,6 +46,7 @@ ENGINES = {
 }
 ALL_TAGS = {t for e in ENGINES.values() for t in e[2:]}
 WORST = {}      # engine -> largest error / band seen so far (printed, recorded in DESIGN.md section 5)
+WORST_ASYM = {}  # the same on the asymmetric inputs
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -80,23 +88,24 @@ def _check_degrees(g, X, Y):
     np.testing.assert_array_equal(kt, okt)
 
 
-def _check_band(eng, got, want, terms, label, weighted, planes=None):
+def _check_band(eng, got, want, terms, label, weighted, planes=None, worst=None):
     """fp32 engines: element-wise band; fp64: the suite's 1e-12 of the block's largest score."""
     if eng["dtype"] == np.float64:
         assert_close(got, want, np.float64)
         return
+    worst = WORST if worst is None else worst
     planes = eng["planes"] if planes is None else planes
     key = eng["name"] if planes == eng["planes"] else eng["name"] + " (k-fold: bf16 planes)"
     ratio = R.assert_band(got, want, R.band_general(*terms, dropped_products=planes and weighted),
                           f"{eng['name']} {label}")
-    WORST[key] = max(WORST.get(key, 0.0), ratio)
-    print(f"[dense] worst so far: {WORST}")
+    worst[key] = max(worst.get(key, 0.0), ratio)
+    print(f"[dense] worst so far{' (asymmetric inputs)' if worst is WORST_ASYM else ''}: {worst}")
 
 
 # ----------------------------------------------------------------------------- tier 1
 @functools.lru_cache(maxsize=None)
-def _exact_case(mode, alpha_edge):
-    inp = R.exact_inputs(mode, alpha_edge=alpha_edge)
+def _exact_case(mode, alpha_edge, symmetric=True):
+    inp = R.exact_inputs(mode, alpha_edge=alpha_edge, symmetric=symmetric)
     X, Xq, Y = R.cut(inp["Ss"], inp["alpha"], True), R.cut(inp["Sq"], inp["alpha"], True), inp["Y"]
     ns = X.shape[0]
     if mode == "query":
@@ -117,7 +126,21 @@ def test_exactly_summable_inputs_bitwise(engine, mode, alpha_edge):
     bit for bit, the fp64 engine equals the oracle bit for bit, the fp32-input engine rounds its 40-bit products and
     gets the general band.  predict("source") is not here: the element of a source's own targets adds the target path's
     0.5 to a feature path below 2^-7 with bits down to 2^-31, which is not representable; it is covered in tier 2."""
-    inp, X, want, terms = _exact_case(mode, alpha_edge)
+    _check_exact(engine, mode, alpha_edge, True)
+
+
+@pytest.mark.parametrize("alpha_edge", [False, True], ids=["alpha=0.4", "alpha=lowest-kept"])
+@pytest.mark.parametrize("mode", ["query", "loo", "kfold"])
+@all_engines
+def test_asymmetric_exactly_summable_inputs_bitwise(engine, mode, alpha_edge):
+    """The same tier with Ss[i, j] != Ss[j, i] for every pair inside a block (exact_inputs(symmetric=False)): an operand
+    read as Ss[f, s], or a column-major Ss taken for row-major, changes a bit in every non-zero score row
+    (tests/test_dense_inputs_cpu.py)."""
+    _check_exact(engine, mode, alpha_edge, False)
+
+
+def _check_exact(engine, mode, alpha_edge, symmetric):
+    inp, X, want, terms = _exact_case(mode, alpha_edge, symmetric)
     g = _graph(inp, True, engine)
     _check_degrees(g, X, inp["Y"])
     if mode == "query":
@@ -132,14 +155,15 @@ def test_exactly_summable_inputs_bitwise(engine, mode, alpha_edge):
     elif engine["planes"] or mode == "kfold":
         R.assert_bitwise(got, want, f"{engine['name']} {mode}")
     else:
-        _check_band(engine, got, want, terms, f"exact inputs, {mode}, weighted", True)
+        _check_band(engine, got, want, terms, f"exact inputs, {mode}, weighted", True,
+                    worst=WORST if symmetric else WORST_ASYM)
     g.close()
 
 
 # ----------------------------------------------------------------------------- tier 2: one term per score
 @functools.lru_cache(maxsize=None)
-def _single_case():
-    inp = R.single_feature_inputs()
+def _single_case(symmetric=True):
+    inp = R.single_feature_inputs(symmetric=symmetric)
     X, Xq = R.cut(inp["Ss"], inp["alpha"], False), R.cut(inp["Sq"], inp["alpha"], False)
     return inp, X, R.oracle_query(Xq, X, inp["Y"])
 
@@ -150,7 +174,17 @@ def test_single_term_scores_within_three_roundings(engine):
     three planes) times fl(1/ks).  Three roundings against the fp64 oracle: 4 * 2^-24 of the score, element-wise.  A
     kernel without the lo plane of the query side misses this on 73 % of the non-zero scores
     (tests/test_dense_inputs_cpu.py)."""
-    inp, X, want = _single_case()
+    _check_single(engine, True)
+
+
+@all_engines
+def test_asymmetric_single_term_scores_within_three_roundings(engine):
+    """The same on an iid pattern: kf is a column count and ks a row count, and they differ for nearly every node."""
+    _check_single(engine, False)
+
+
+def _check_single(engine, symmetric):
+    inp, X, want = _single_case(symmetric)
     g = _graph(inp, False, engine)
     _check_degrees(g, X, inp["Y"])
     got = g.predict("query")
@@ -159,7 +193,7 @@ def test_single_term_scores_within_three_roundings(engine):
         assert_close(got, want, np.float64)
     else:
         ratio = R.assert_band(got, want, R.band_single_term(want), f"{engine['name']} single term")
-        WORST[engine["name"] + " (single term)"] = ratio
+        (WORST if symmetric else WORST_ASYM)[engine["name"] + " (single term)"] = ratio
     g.close()
 
 
@@ -235,6 +269,140 @@ def test_shapes_offsets_and_modes_within_their_bands(engine, shape, weighted):
                 _tag(engine["tag"])
                 _check_band(engine, got, *ref["loo", a, b], f"{shape} leave-one-out rows [{a},{b}), {w}", weighted)
     g.close()
+
+
+# ----------------------------------------------------------------------------- an asymmetric Ss: degrees, bands, layout
+ASYM_SHAPE = (129, 260)         # K padded 260 -> 320 for the planes, M one past a tile, three partial 128-blocks
+
+
+@functools.lru_cache(maxsize=None)
+def _asym_case(weighted):
+    """mode -> (inputs, thresholded Ss, references and terms) on random_inputs(symmetric=False)."""
+    nq, ns = ASYM_SHAPE
+    out = {}
+    for mode in ("query", "loo", "kfold"):
+        inp = R.random_inputs(nq, ns, weighted, mode, symmetric=False)
+        X, Xq, Y = R.cut(inp["Ss"], inp["alpha"], weighted), R.cut(inp["Sq"], inp["alpha"], weighted), inp["Y"]
+        assert ((X != 0) & (X.T == 0)).sum() > ns and (np.count_nonzero(X, axis=0) != np.count_nonzero(X, axis=1)).any()
+        Y64 = Y.astype(np.float64)
+        ref = {}
+        if mode == "query":
+            ref["query"] = (R.oracle_query(Xq, X, Y), R.terms(Xq, X, Y))
+        for a, b in R.row_ranges(ns):
+            rows = np.arange(a, b)
+            if mode == "query":
+                ref["source", a, b] = (R.oracle_source(X, Y, rows), R.terms_source(X, Y, rows))
+            elif mode == "loo":
+                ref["loo", a, b] = (O.predict_loo_factored(X, Y64, queries=rows),
+                                    O.predict_loo_factored(X, Y64, clean_flag=True, queries=rows), R.terms_loo(X, Y, rows))
+        if mode == "kfold":
+            ref["kfold"] = (R.oracle_folds(X, Y, inp["fold"]), R.terms_folds(X, Y, inp["fold"]))
+        out[mode] = (inp, X, ref)
+    return out
+
+
+@pytest.mark.parametrize("weighted", [False, True], ids=["unweighted", "weighted"])
+@all_engines
+def test_asymmetric_degrees_at_every_cutoff(engine, weighted):
+    """kf counts a column of the thresholded Ss and ks a row (plus the labels), at construction and after set_cutoff to
+    a higher and to a lower alpha; on these inputs the two counts differ for most nodes."""
+    inp, X, _ = _asym_case(weighted)["query"]
+    g = _graph(inp, weighted, engine)
+    _check_degrees(g, X, inp["Y"])
+    for alpha in (inp["alpha"] + 0.5 * (1.0 - inp["alpha"]), 0.6 * inp["alpha"], inp["alpha"]):
+        Xa = R.cut(inp["Ss"], alpha, weighted)
+        assert (np.count_nonzero(Xa, axis=0) != np.count_nonzero(Xa, axis=1)).mean() > 0.25
+        _check_degrees(g.set_cutoff(alpha, weighted), Xa, inp["Y"])
+    g.close()
+
+
+@pytest.mark.parametrize("weighted", [False, True], ids=["unweighted", "weighted"])
+@all_engines
+def test_asymmetric_inputs_every_mode_within_its_band(engine, weighted):
+    """Query rows, source rows and leave-one-out rows (with and without clean) over dense_ref.row_ranges, the whole
+    k-fold and a sub-range of its rows, on random_inputs(symmetric=False): an asymmetric pattern, row degrees unlike
+    column degrees, a leave-one-out divisor ks - has that depends on the direction of the pair.  References:
+    oracle_query, oracle_source, O.predict_loo_factored, oracle_folds; the band of the symmetric tier."""
+    nq, ns = ASYM_SHAPE
+    w = "asymmetric, " + ("weighted" if weighted else "unweighted")
+    check = functools.partial(_check_band, engine, weighted=weighted, worst=WORST_ASYM)
+    g = None
+    for mode, (inp, X, ref) in _asym_case(weighted).items():
+        if g is None or weighted:
+            if g is not None:
+                g.close()
+            g = _graph(inp, weighted, engine)
+            _check_degrees(g, X, inp["Y"])
+        if mode == "query":
+            got = g.predict("query")
+            _tag(engine["tag"])
+            check(got, *ref["query"], label=f"query, {w}")
+        if mode == "kfold":
+            fold, k = inp["fold"], inp["nfolds"]
+            got = g.predict_kfold(fold, k)
+            _tag(engine["tag_kfold"])
+            check(got, *ref["kfold"], label=f"k-fold, {w}", planes=engine["dtype"] == np.float32)
+            a, b = R.row_ranges(ns)[1]
+            part = g.predict_kfold_rows(fold, k, a, b)
+            _tag(engine["tag_kfold"])
+            check(part, ref["kfold"][0][a:b], tuple(t[a:b] for t in ref["kfold"][1]), label=f"k-fold rows [{a},{b}), {w}",
+                  planes=engine["dtype"] == np.float32)
+            continue
+        for i, (a, b) in enumerate(R.row_ranges(ns)):
+            layout = "col" if i == 1 else "row"
+            if mode == "query":
+                got = g.predict("source", a, b, layout=layout)
+                _tag(engine["tag"])
+                check(got, *ref["source", a, b], label=f"source rows [{a},{b}), {w}")
+            else:
+                want, want_clean, terms = ref["loo", a, b]
+                got = g.predict_loo(a, b, layout=layout)
+                _tag(engine["tag"])
+                check(got, want, terms, label=f"leave-one-out rows [{a},{b}), {w}")
+                got = g.predict_loo(a, b, clean=True, layout=layout)
+                _tag(engine["tag"])
+                assert np.array_equal(got == -99.0, want_clean == -99.0) and (want_clean == -99.0).any()
+                check(got, want_clean, terms, label=f"leave-one-out rows [{a},{b}) with clean, {w}")
+    g.close()
+
+
+@pytest.mark.parametrize("weighted", [False, True], ids=["unweighted", "weighted"])
+@all_engines
+def test_asymmetric_graph_is_the_same_from_every_layout(engine, weighted):
+    """One asymmetric graph from a numpy array and from a CUDA tensor, each with ld_pad 0 and 3 (NaN under the last
+    row): the query rows and the leave-one-out rows of the four are bitwise equal, and inside their band, so no path
+    hands Ss over transposed."""
+    import torch
+    case = _asym_case(weighted)
+    inp, X, ref = case["query"]
+    a, b = R.row_ranges(ASYM_SHAPE[1])[1]
+    Ycsr = sp.csr_matrix(inp["Y"])
+    tdt = torch.float32 if engine["dtype"] == np.float32 else torch.float64
+    Yd = (torch.from_numpy(Ycsr.indptr.astype(np.int64)).cuda(), torch.from_numpy(Ycsr.indices.astype(np.int32)).cuda(),
+          torch.from_numpy(Ycsr.data).cuda().to(tdt), Ycsr.shape[1])
+    first = None
+    for device in (False, True):
+        for ld_pad in (0, 3):
+            if device:
+                Sq, Ss, Y = torch.from_numpy(inp["Sq"]).cuda(), torch.from_numpy(inp["Ss"]).cuda(), Yd
+            else:
+                Sq, Ss, Y = inp["Sq"], inp["Ss"], Ycsr
+            g = ss.DeviceGraph.from_similarity(Sq, Ss, Y, alpha=inp["alpha"], weighted=weighted, dtype=engine["dtype"],
+                                               ld_pad=ld_pad)
+            _check_degrees(g, X, inp["Y"])
+            q = g.predict("query")
+            _tag(engine["tag"])
+            loo = g.predict_loo(a, b, clean=True)
+            _tag(engine["tag"])
+            g.close()
+            if first is None:
+                first = (q, loo)
+                _check_band(engine, q, *ref["query"], "query, asymmetric, " + ("weighted" if weighted else "unweighted"),
+                            weighted, worst=WORST_ASYM)
+                assert not np.isnan(loo).any() and (loo == -99.0).any()
+            else:
+                assert q.tobytes() == first[0].tobytes(), (device, ld_pad)
+                assert loo.tobytes() == first[1].tobytes(), (device, ld_pad)
 
 
 # ----------------------------------------------------------------------------- tier 4: the input domain

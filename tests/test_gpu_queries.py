@@ -311,7 +311,8 @@ def test_refusals_leave_the_output_untouched(dt):
     dense = ss.DeviceGraph.from_similarity(None, (S + S.T) / 2, Ys, 0.5, dtype=dt)
     B = sp.random(20, 20, density=0.3, format="csr", random_state=rng)
     general = ss.DeviceGraph.general(B[:3], B, B[:, :4].T.tocsr(), dtype=dt)
-    for bad, xq in ((dense, Xq), (general, sp.csr_matrix((3, 20)))):
+    dense_asym = ss.DeviceGraph.from_similarity(None, S, Ys, 0.5, dtype=dt)     # Ss need not be symmetric
+    for bad, xq in ((dense, Xq), (dense_asym, Xq), (general, sp.csr_matrix((3, 20)))):
         with pytest.raises(ss.SimSpreadError) as e:
             ss.DeviceQueries.from_sparse(bad, xq)
         assert e.value.code == EUNSUPPORTED

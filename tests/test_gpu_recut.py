@@ -315,11 +315,12 @@ def test_children_are_independent_of_the_parent(dt):
 
 
 # ----------------------------------------------------------------------------------------------- 4. refusals
-def _similarities(ns, nq, seed):
-    """Raw similarities in (0, 1): Sq (nq x ns) and a symmetric Ss (ns x ns) with unit diagonal."""
+def _similarities(ns, nq, seed, symmetric=True):
+    """Raw similarities in (0, 1): Sq (nq x ns) and a symmetric Ss (ns x ns) with unit diagonal; symmetric=False: the
+    iid matrix itself, element (s, f) source s against feature f."""
     rng = np.random.default_rng(seed)
     U = rng.random((ns, ns))
-    Ss = (U + U.T) / 2
+    Ss = (U + U.T) / 2 if symmetric else U
     np.fill_diagonal(Ss, 1.0)
     return rng.random((nq, ns)), Ss
 
@@ -363,7 +364,6 @@ def test_refusals():
 def test_set_cutoff_gives_the_fresh_dense_similarity_graph(dt):
     ss.init(0)
     ns, nq, nt = 300, 40, 30
-    Sq, Ss = _similarities(ns, nq, 41)
     Y = _labels(ns, nt, 42)
     fold = np.random.default_rng(43).integers(0, 5, ns).astype(np.int32)
 
@@ -376,23 +376,31 @@ def test_set_cutoff_gives_the_fresh_dense_similarity_graph(dt):
             paths[key] = ss.path_last()
         return out, paths
 
-    g = ss.DeviceGraph.from_similarity(Sq, Ss, Y, alpha=0.3, weighted=True, dtype=dt)
-    served(g)                                              # the handle has served (and cached operands) before the change
-    nnz = []
-    for alpha, weighted in ((0.6, True), (0.6, False), (0.9, True), (0.4, False), (0.3, True)):   # up and back down
-        assert g.set_cutoff(alpha, weighted) is g
-        fresh = ss.DeviceGraph.from_similarity(Sq, Ss, Y, alpha=alpha, weighted=weighted, dtype=dt)
-        for a, b, name in zip(g.degrees(), fresh.degrees(), ("kf", "ks", "kt")):
-            assert np.array_equal(a, b), (alpha, weighted, name)
-        nnz.append(int(g.degrees()[0].sum()))
-        got, gpath = served(g)
-        want, wpath = served(fresh)
-        for key in want:
-            assert_same(got[key], want[key], (alpha, weighted, key))
-            assert gpath[key] == wpath[key], (alpha, weighted, key, gpath[key], wpath[key])
-            assert any(t.startswith("transfer_dense") for t in gpath[key]), gpath[key]
-        fresh.close()
-    assert nnz[2] < nnz[0] < nnz[4] and nnz[0] == nnz[1]
+    for symmetric in (True, False):     # an asymmetric Ss: the recount reads columns for kf and rows for ks
+        Sq, Ss = _similarities(ns, nq, 41, symmetric)
+        g = ss.DeviceGraph.from_similarity(Sq, Ss, Y, alpha=0.3, weighted=True, dtype=dt)
+        served(g)                                          # the handle has served (and cached operands) before the change
+        nnz = []
+        for alpha, weighted in ((0.6, True), (0.6, False), (0.9, True), (0.4, False), (0.3, True)):   # up and back down
+            assert g.set_cutoff(alpha, weighted) is g
+            fresh = ss.DeviceGraph.from_similarity(Sq, Ss, Y, alpha=alpha, weighted=weighted, dtype=dt)
+            for a, b, name in zip(g.degrees(), fresh.degrees(), ("kf", "ks", "kt")):
+                assert np.array_equal(a, b), (alpha, weighted, name)
+            if not symmetric:
+                kept = Ss.astype(dt) >= dt(alpha)
+                kf, ks, _ = g.degrees()
+                assert np.array_equal(kf, kept.sum(axis=0)) and not np.array_equal(kf, kept.sum(axis=1))
+                assert np.array_equal(ks, kept.sum(axis=1) + np.diff(sp.csr_matrix(Y).indptr))
+            nnz.append(int(g.degrees()[0].sum()))
+            got, gpath = served(g)
+            want, wpath = served(fresh)
+            for key in want:
+                assert_same(got[key], want[key], (alpha, weighted, key))
+                assert gpath[key] == wpath[key], (alpha, weighted, key, gpath[key], wpath[key])
+                assert any(t.startswith("transfer_dense") for t in gpath[key]), gpath[key]
+            fresh.close()
+        assert nnz[2] < nnz[0] < nnz[4] and nnz[0] == nnz[1]
+        g.close()
 
 
 # ----------------------------------------------------------------------------------------------- 6. a sweep end to end

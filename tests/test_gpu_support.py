@@ -273,6 +273,8 @@ def test_errors_write_nothing(suf, dt):
     S = rng.random((150, 150))
     dense = ss.DeviceGraph.from_similarity(S[:5], (S + S.T) / 2, Ys, 0.5, dtype=dt)
     assert call(dense, None, _lib.SS_ROWS_QUERY, ok_r, ok_t, 5) == EUNSUPPORTED
+    dense_asym = ss.DeviceGraph.from_similarity(S[:5], S, Ys, 0.5, dtype=dt)     # Ss need not be symmetric
+    assert call(dense_asym, None, _lib.SS_ROWS_QUERY, ok_r, ok_t, 5) == EUNSUPPORTED
     for a, b in zip((src, con, cnt), keep):
         assert_same(a, b)
     # no pairs: a no-op after the checks

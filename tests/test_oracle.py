@@ -4,6 +4,7 @@ import os
 
 import numpy as np
 import pytest
+import scipy.sparse as sp
 
 from oracle import simspread_oracle as O
 from oracle.simspread_oracle import Named
@@ -123,23 +124,53 @@ def test_literal_equals_factored(seed, weighted):
     np.testing.assert_allclose(O.predict_single(A3, Ys).array, lit_s, rtol=1e-12, atol=1e-15)
 
 
+def _iid_similarity(rng, n):
+    """An asymmetric source similarity: iid U(0, 1), unit diagonal.  Element (s, f) is source s against feature f."""
+    S = rng.random((n, n))
+    np.fill_diagonal(S, 1.0)
+    return S
+
+
+def _assert_orientation_matters(X, form, want, tol=1e-3):
+    """The cut pattern has one-sided pairs, and `form` on the transposed X is far from the literal result (the clean!
+    markers aside): an input regenerated as symmetric, or a form that reads X[f, s], cannot pass."""
+    X = np.asarray(X)
+    assert ((X != 0) & (X.T == 0)).sum() >= 10
+    other = form(np.ascontiguousarray(X.T))
+    assert np.abs(other - want)[want != -99.0].max() > tol
+
+
+def _literal_loo(X, Y, names, queries=None):
+    """construct(y, X, [name]) -> predict -> clean! for every source (or those of `queries`), one fold at a time."""
+    out = []
+    for i in (range(len(names)) if queries is None else queries):
+        A, B = O.construct_queries(Y, X, [names[i]])
+        yq = Y.sub([names[i]], Y.cols)
+        yhat = O.predict(A, B, yq)
+        O.clean(yhat, A, yq)
+        out.append(yhat.array[0])
+    return np.array(out)
+
+
 @pytest.mark.parametrize("seed,weighted", [(4, True), (5, False)])
 def test_loo_identity(seed, weighted):
     rng = np.random.default_rng(seed)
     n, nt = 24, 6
-    S = rng.random((n, n)); S = (S + S.T) / 2; np.fill_diagonal(S, 1.0)
     names = [f"d{i:02d}" for i in range(n)]
-    X = O.featurize(Named(S, names, names), 0.55, weighted)
-    Y = Named((rng.random((n, nt)) < 0.25).astype(float), names, [f"t{i}" for i in range(nt)])
-    Y.array[:, 2] = 0.0; Y.array[5, 2] = 1.0   # target whose only edge is source 5 -> clean! case
-    fast = O.predict_loo_factored(X.array, Y.array, clean_flag=True)
-    for i, nm in enumerate(names):
-        A, B = O.construct_queries(Y, X, [nm])
-        yq = Y.sub([nm], Y.cols)
-        yhat = O.predict(A, B, yq)
-        O.clean(yhat, A, yq)
-        np.testing.assert_allclose(fast[i], yhat.array[0], rtol=1e-12, atol=1e-15)
-    assert fast[5, 2] == -99.0
+    for symmetric in (True, False):
+        if symmetric:
+            S = rng.random((n, n)); S = (S + S.T) / 2; np.fill_diagonal(S, 1.0)
+        else:
+            S = _iid_similarity(rng, n)
+        X = O.featurize(Named(S, names, names), 0.55, weighted)
+        Y = Named((rng.random((n, nt)) < 0.25).astype(float), names, [f"t{i}" for i in range(nt)])
+        Y.array[:, 2] = 0.0; Y.array[5, 2] = 1.0   # target whose only edge is source 5 -> clean! case
+        fast = O.predict_loo_factored(X.array, Y.array, clean_flag=True)
+        lit = _literal_loo(X, Y, names)
+        np.testing.assert_allclose(fast, lit, rtol=1e-12, atol=1e-15)
+        assert fast[5, 2] == -99.0
+        if not symmetric:
+            _assert_orientation_matters(X.array, lambda Xt: O.predict_loo_factored(Xt, Y.array, clean_flag=True), lit)
 
 
 def test_feature_filter_strips_all_leading_f():
@@ -201,19 +232,30 @@ def test_name_check_needs_equal_counts():
 
 def test_loo_dense_form_equals_factored_form():
     """predict_loo_dense (used to check the dense-similarity regime at sizes where a sparse copy of a 90 % full
-    matrix is impractical) against predict_loo_factored, weighted and unweighted, with an isolated target."""
+    matrix is impractical) against predict_loo_factored, weighted and unweighted, with an isolated target; on an
+    asymmetric similarity both also against the literal fold loop."""
     rng = np.random.default_rng(5)
     n, nt = 60, 17
     S = rng.random((n, n)); S = np.triu(S, 1); S = S + S.T; np.fill_diagonal(S, 1.0)
     Y = (rng.random((n, nt)) < 0.15).astype(np.float64)
     Y[:, 3] = 0.0
     Y[5, 4] = 1.0; Y[:5, 4] = 0.0; Y[6:, 4] = 0.0          # a target whose only edge belongs to one query
-    for alpha, weighted in ((0.1, True), (0.5, False), (0.9, True)):
-        X = O.cutoff(S, alpha, weighted)
-        a = O.predict_loo_dense(X, Y, clean_flag=True)
-        b = O.predict_loo_factored(X, Y, clean_flag=True)
-        assert np.abs(a - b).max() < 1e-13
-        assert ((a == -99) == (b == -99)).all()
+    names = [f"d{i:02d}" for i in range(n)]
+    Yn = Named(Y, names, [f"t{i}" for i in range(nt)])
+    for symmetric in (True, False):
+        if not symmetric:
+            S = _iid_similarity(rng, n)
+        for alpha, weighted in ((0.1, True), (0.5, False), (0.9, True)):
+            X = O.cutoff(S, alpha, weighted)
+            a = O.predict_loo_dense(X, Y, clean_flag=True)
+            b = O.predict_loo_factored(X, Y, clean_flag=True)
+            assert np.abs(a - b).max() < 1e-13
+            assert ((a == -99) == (b == -99)).all()
+            if not symmetric:
+                lit = _literal_loo(Named(X, names, ["f" + c for c in names]), Yn, names)
+                np.testing.assert_allclose(a, lit, rtol=1e-12, atol=1e-15)
+                np.testing.assert_allclose(b, lit, rtol=1e-12, atol=1e-15)
+                _assert_orientation_matters(X, lambda Xt: O.predict_loo_dense(Xt, Y, clean_flag=True), lit)
 
 
 def test_c_oracle_equals_python_oracle():
@@ -276,6 +318,33 @@ def test_c_loo_equals_python_loo(seed):
     assert (got[23] == np.where(got[23] == -99, -99, 0)).all()     # a source linked to nothing else scores 0
     prep.close()
     np.testing.assert_array_equal(c_oracle.predict_loo(X, Y, 10, 30, clean=True), got[10:30])
+    # the pattern above is one-sided almost everywhere, and the orientation matters to both forms
+    for form in (lambda Xt: O.predict_loo_factored(Xt, Y, clean_flag=True),
+                 lambda Xt: c_oracle.predict_loo(sp.csr_matrix(Xt), Y, clean=True)):
+        _assert_orientation_matters(X.toarray(), form, got)
+
+
+@pytest.mark.parametrize("seed,weighted", [(1, True), (2, False)])
+def test_c_loo_equals_the_literal_loop_on_an_asymmetric_similarity(seed, weighted):
+    """oracle_predict_loo_rows against the literal construct -> predict -> clean! loop on an iid similarity with unit
+    diagonal: which of X[s, q] and X[q, s] lowers a source's degree is visible here and nowhere on a symmetric X."""
+    from oracle import c_oracle
+    rng = np.random.default_rng(seed)
+    n, nt = 40, 9
+    names = [f"d{i:02d}" for i in range(n)]
+    Yarr = (rng.random((n, nt)) < 0.2).astype(float)
+    Yarr[:, 2] = 0.0; Yarr[5, 2] = 1.0
+    Yn = Named(Yarr, names, [f"t{i}" for i in range(nt)])
+    for alpha in (0.55, 0.9):
+        X = O.cutoff(_iid_similarity(rng, n), alpha, weighted)
+        lit = _literal_loo(Named(X, names, ["f" + c for c in names]), Yn, names)
+        prep = c_oracle.PreparedLoo(sp.csr_matrix(X), sp.csr_matrix(Yarr))
+        got = prep.predict(clean=True)
+        prep.close()
+        np.testing.assert_allclose(got, lit, rtol=1e-12, atol=1e-15)
+        assert np.array_equal(got == -99, lit == -99) and got[5, 2] == -99.0
+        np.testing.assert_allclose(O.predict_loo_factored(X, Yarr, clean_flag=True), lit, rtol=1e-12, atol=1e-15)
+        _assert_orientation_matters(X, lambda Xt: c_oracle.predict_loo(sp.csr_matrix(Xt), sp.csr_matrix(Yarr), clean=True), lit)
 
 
 def test_c_loo_missing_symbol_is_a_rebuild_error(monkeypatch):
@@ -291,7 +360,8 @@ def test_c_loo_missing_symbol_is_a_rebuild_error(monkeypatch):
 
 def test_blocked_dense_loo_equals_per_fold_dense_loo():
     """predict_loo_dense_blocked (the checker of every C4 fold at 20k) against predict_loo_dense, at block sizes that do
-    and do not divide the fold list, on a 90 % full and a sparse cutoff, weighted and not, with an isolated target."""
+    and do not divide the fold list, on a 90 % full and a sparse cutoff, weighted and not, with an isolated target; on
+    an asymmetric similarity also against the literal fold loop."""
     rng = np.random.default_rng(9)
     n, nt = 150, 31
     S = rng.random((n, n)); S = np.triu(S, 1); S = S + S.T; np.fill_diagonal(S, 1.0)
@@ -300,46 +370,63 @@ def test_blocked_dense_loo_equals_per_fold_dense_loo():
     Y[:, 4] = 0.0; Y[33, 4] = 1.0
     Y[50] = 0.0
     qs = list(range(7, 140))
-    for alpha, weighted in ((0.1, True), (0.1, False), (0.9, True)):
-        X = O.cutoff(S, alpha, weighted)
-        want = O.predict_loo_dense(X, Y, clean_flag=True, queries=qs)
-        for block in (1, 16, 50, 512):
-            got = O.predict_loo_dense_blocked(X, Y, clean_flag=True, queries=qs, block=block)
-            np.testing.assert_allclose(got, want, rtol=1e-13, atol=0)
-            assert np.array_equal(got == -99, want == -99) and np.array_equal(got == 0, want == 0)
-        assert (want[33 - 7, 4] == -99)
-        np.testing.assert_allclose(O.predict_loo_dense_blocked(X, Y, block=64), O.predict_loo_dense(X, Y),
-                                   rtol=1e-13, atol=0)
+    names = [f"d{i:03d}" for i in range(n)]
+    Yn = Named(Y, names, [f"t{i}" for i in range(nt)])
+    lit_rows = [7, 33, 50, 91, 139]
+    for symmetric in (True, False):
+        if not symmetric:
+            S = _iid_similarity(rng, n)
+        for alpha, weighted in ((0.1, True), (0.1, False), (0.9, True)):
+            X = O.cutoff(S, alpha, weighted)
+            want = O.predict_loo_dense(X, Y, clean_flag=True, queries=qs)
+            for block in (1, 16, 50, 512):
+                got = O.predict_loo_dense_blocked(X, Y, clean_flag=True, queries=qs, block=block)
+                np.testing.assert_allclose(got, want, rtol=1e-13, atol=0)
+                assert np.array_equal(got == -99, want == -99) and np.array_equal(got == 0, want == 0)
+            assert (want[33 - 7, 4] == -99)
+            np.testing.assert_allclose(O.predict_loo_dense_blocked(X, Y, block=64), O.predict_loo_dense(X, Y),
+                                       rtol=1e-13, atol=0)
+            if not symmetric:
+                lit = _literal_loo(Named(X, names, ["f" + c for c in names]), Yn, names, queries=lit_rows)
+                blocked = lambda Xt: O.predict_loo_dense_blocked(Xt, Y, clean_flag=True, queries=lit_rows, block=2)
+                np.testing.assert_allclose(blocked(X), lit, rtol=1e-13, atol=1e-14)
+                _assert_orientation_matters(X, blocked, lit)
 
 
 def test_kfold_query_form_equals_the_literal_fold_loop():
     """c_oracle.predict_kfold (the checker of k-fold at 10k sources) against the reference's literal fold loop
     (construct(y, X, members) -> predict -> clean!) on the dense block graph, with a target whose edges all sit in one
-    fold and an empty fold."""
+    fold and an empty fold, on a symmetric and on an asymmetric similarity."""
     from oracle import c_oracle
     rng = np.random.default_rng(13)
     n, nt, k = 70, 19, 6
-    S = rng.random((n, n)); S = (S + S.T) / 2; np.fill_diagonal(S, 1.0)
     names = [f"d{i:02d}" for i in range(n)]; tn = [f"t{i}" for i in range(nt)]
-    Xn = O.featurize(Named(S, names, names), 0.7, True)
-    Yarr = (rng.random((n, nt)) < 0.15).astype(float)
-    Yarr[:, 2] = 0; Yarr[8, 2] = 1; Yarr[11, 2] = 1
-    Yn = Named(Yarr, names, tn)
-    fold = rng.integers(0, k - 1, size=n); fold[8] = fold[11] = 1        # fold k-1 stays empty
-    want = np.zeros((n, nt))
-    for phi in range(k):
-        idx = [i for i in range(n) if fold[i] == phi]
-        if not idx:
-            continue
-        members = [names[i] for i in idx]
-        A, B = O.construct_queries(Yn, Xn, members)
-        yq = Yn.sub(members, tn)
-        yh = O.predict(A, B, yq); O.clean(yh, A, yq)
-        want[idx] = yh.array
-    got = c_oracle.predict_kfold(Xn.array, Yarr, fold, k, clean=True)
-    np.testing.assert_allclose(got, want, rtol=1e-12, atol=1e-15)
-    assert np.array_equal(got == -99, want == -99) and (got[8, 2] == -99) and (got[11, 2] == -99)
-    np.testing.assert_allclose(c_oracle.predict_kfold(Xn.array, Yarr, fold, k), want * (want != -99), rtol=1e-12, atol=1e-15)
+    for symmetric in (True, False):
+        if symmetric:
+            S = rng.random((n, n)); S = (S + S.T) / 2; np.fill_diagonal(S, 1.0)
+        else:
+            S = _iid_similarity(rng, n)
+        Xn = O.featurize(Named(S, names, names), 0.7, True)
+        Yarr = (rng.random((n, nt)) < 0.15).astype(float)
+        Yarr[:, 2] = 0; Yarr[8, 2] = 1; Yarr[11, 2] = 1
+        Yn = Named(Yarr, names, tn)
+        fold = rng.integers(0, k - 1, size=n); fold[8] = fold[11] = 1        # fold k-1 stays empty
+        want = np.zeros((n, nt))
+        for phi in range(k):
+            idx = [i for i in range(n) if fold[i] == phi]
+            if not idx:
+                continue
+            members = [names[i] for i in idx]
+            A, B = O.construct_queries(Yn, Xn, members)
+            yq = Yn.sub(members, tn)
+            yh = O.predict(A, B, yq); O.clean(yh, A, yq)
+            want[idx] = yh.array
+        got = c_oracle.predict_kfold(Xn.array, Yarr, fold, k, clean=True)
+        np.testing.assert_allclose(got, want, rtol=1e-12, atol=1e-15)
+        assert np.array_equal(got == -99, want == -99) and (got[8, 2] == -99) and (got[11, 2] == -99)
+        np.testing.assert_allclose(c_oracle.predict_kfold(Xn.array, Yarr, fold, k), want * (want != -99), rtol=1e-12, atol=1e-15)
+        if not symmetric:
+            _assert_orientation_matters(Xn.array, lambda Xt: c_oracle.predict_kfold(Xt, Yarr, fold, k, clean=True), want)
 
 
 def _helper_block():
